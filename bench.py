@@ -2,7 +2,7 @@
 """Benchmark of the hot path: stabilized frames/s = frames for which ``field = netG(window, False)`` AND
 ``warped = grid_sample(frame, field)`` completed (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 N=1 runs in this process.  N>1: either already under torch.distributed.run (RANK / WORLD_SIZE in the environment, one rank per
 GPU over RCCL), or -- when WORLD_SIZE is unset -- this process starts `python -m torch.distributed.run --nproc-per-node N` on
 itself BEFORE anything touches the GPU, relays the ranks' output and exits with their code (it never measures one GPU and
@@ -82,7 +82,28 @@ def parse():
     ap.add_argument("--force-collectives", action="store_true",
                     help="--gpus 1 only: initialise a ONE-rank RCCL group and run the training_ddp leg with its collectives forced "
                          "(first contact with RCCL on a single GPU; rccl_ranks = 1 in the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its LAST step to DIR (rank 0): field.npy (N,256,256,2) "
+                         "and warped.npy (N,3,256,256), float32; inputs are seeded, so two builds compare output for output (e.g. DIR = bench_outputs/<build>)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """Writes each (N, ...) tensor of ``arrays`` as d/<name>.npy in float32.  When all of them together exceed 64 MB, the same leading
+    frames of every array are kept (a fixed sample: frame i of one file belongs to frame i of the others).  Returns {name: shape}."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    per_frame = sum(4 * t[0].numel() for t in arrays.values())
+    n = min(min(t.shape[0] for t in arrays.values()), max(1, DUMP_LIMIT_BYTES // per_frame))
+    shapes = {}
+    for name, t in arrays.items():
+        v = t[:n].float().cpu().numpy()
+        np.save(os.path.join(d, name + ".npy"), v)
+        shapes[name] = list(v.shape)
+    return shapes
 
 
 # bench kernel name -> substrings of the rocprofv3 kernel names (tools/summarize_prof.py) that make it up
@@ -553,9 +574,13 @@ def main():
     x = torch.from_numpy(synth.noise_window(B, 31, 256, seed=123 + rank)).to(dev)
     frames = torch.from_numpy(synth.make_frames(B, 3, 256, 256, seed=321 + rank)).to(dev)
 
+    last = {}   # --dump-outputs: the field of the latest step (the warped frames are what step() returns)
+
     def step():
         with torch.no_grad():
             grid = net(x, False)
+            if a.dump_outputs:
+                last["field"] = grid
             return PF.grid_sample(frames, grid)
 
     def barrier():
@@ -616,6 +641,9 @@ def main():
         out = step_on(i)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if a.dump_outputs and rank == 0:   # now, before the legs below replace last["field"]
+        dumped = dump_outputs(a.dump_outputs, {"field": last["field"], "warped": out})
     barrier()
     # NOT the headline: the same step with the one dead layer of the inference forward pruned (UnetGenerator.prune_dead /
     # PWS_NETG_PRUNE_DEAD: stage 1's up2, whose output the reference reads only under `if is_training`, lib/networks_cascading.py:171,173,196).
@@ -715,6 +743,7 @@ def main():
                 "(pws_netg_opts.flags PWS_NETG_PRUNE_DEAD): its output x122 is read only under `if is_training` in the reference (lib/networks_cascading.py:171,173,196), "
                 "so the returned field is bit-identical; 92.33 instead of 94.48 GFLOP per frame"}} if pruned_fps else {}),
             "netg_frac_fp32_peak": round(fps / world * GFLOP_PER_FRAME_INFER / 1e3 / PEAK_FP32_TFLOPS, 4),
+            **({"dumped_outputs": {"dir": a.dump_outputs, "shapes": dumped, "what": "the last timed step's field and warped frames, float32"}} if dumped else {}),
         }
         if recs:
             agg = {}

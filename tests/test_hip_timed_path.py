@@ -306,6 +306,37 @@ def test_bench_watchdog_exits_non_zero(hip):
     assert line["value"] > 0 and "watchdog" in line["training_ddp"]["error"]
 
 
+def test_bench_dump_outputs_are_the_timed_steps_outputs(hip, tmp_path):
+    """`bench.py --dump-outputs DIR` writes the field and warped frames the timed path returned in its last step (float32): they are bench's
+    rank-0 inputs through the generator, within the parity bounds of the CPU path; `--steps` is the number of timed steps, `ms_per_step`
+    one step's time."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from oracle import torch_ref
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = str(tmp_path / "out")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-prof",
+                        "--no-extra", "--no-cpu-baseline", "--gs-batch", "8", "--dump-outputs", d], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    assert abs(line["ms_per_step"] - 1e3 * 8 / line["value"]) <= 1e-3 * line["ms_per_step"] + 1e-3, line
+    field, warped = np.load(os.path.join(d, "field.npy")), np.load(os.path.join(d, "warped.npy"))
+    assert field.dtype == np.float32 and warped.dtype == np.float32
+    assert field.shape == (8, 256, 256, 2) and warped.shape == (8, 3, 256, 256)
+    assert line["dumped_outputs"]["shapes"] == {"field": [8, 256, 256, 2], "warped": [8, 3, 256, 256]}
+    params = [torch.from_numpy(v) for _, v in synth.make_weights("W1", seed=123, ngf=64)]
+    x = torch.from_numpy(synth.noise_window(8, 31, 256, seed=123))
+    fr = torch.from_numpy(synth.make_frames(8, 3, 256, 256, seed=321))
+    with torch.no_grad():
+        ref_field = torch_ref.netg_forward(params, x, is_training=False)
+        ref_warp = torch.nn.functional.grid_sample(fr, ref_field, mode="bilinear", padding_mode="zeros", align_corners=False)
+    assert float(np.abs(field - ref_field.numpy()).max()) < FIELD_TOL
+    assert float(np.abs(warped - ref_warp.numpy()).max()) / 127.5 < WARP_TOL
+
+
 @pytest.mark.parametrize("math", ["fp32", "bf16"])
 def test_two_batches_in_flight_on_two_streams(hip, math):
     """bench.py --in-flight 2 (the headline's launch path since round 6): consecutive steps alternate over two streams without waiting for each
