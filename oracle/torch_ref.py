@@ -21,15 +21,23 @@ def _lrelu(x):
     return F.leaky_relu(x, 0.2)
 
 
-def netg_forward(params, x, is_training=True, align_corners=False):
-    """params: 92 tensors in state-dict order; x: N,31,256,256.  Returns like the reference's forward."""
+def netg_forward(params, x, is_training=True, align_corners=False, bn=None):
+    """params: 92 tensors in state-dict order; x: N,31,256,256.  Returns like the reference's forward.
+    bn: the use_BN=True variant in train() mode -- 46 (gamma, beta) pairs in layer order; every conv is followed by a BatchNorm2d
+    over the batch statistics (the running statistics are not tracked here)."""
     P = params
 
+    def norm(i, y):
+        if bn is None:
+            return y
+        gamma, beta = bn[i // 2]
+        return F.batch_norm(y, None, None, gamma, beta, training=True, eps=1e-5)
+
     def conv(i, t, s, p):
-        return F.conv2d(t, P[i], P[i + 1], stride=s, padding=p)
+        return norm(i, F.conv2d(t, P[i], P[i + 1], stride=s, padding=p))
 
     def convT(i, t, s, p):
-        return F.conv_transpose2d(t, P[i], P[i + 1], stride=s, padding=p)
+        return norm(i, F.conv_transpose2d(t, P[i], P[i + 1], stride=s, padding=p))
 
     def down(i, t):
         return _lrelu(conv(_DOWN1 + 2 * (i - 1), t, 2, 1))

@@ -700,6 +700,7 @@ static int theta_bwd1_slices(int n) {
 static size_t theta_bwd1_lds(int n, int nslices) { return (size_t)((n + nslices - 1) / nslices) * 6 * sizeof(float); }
 int theta_bwd_bn_lin(const float *dz2, const float *h, int n, int hidden, const float *w_lin, float *dw_lin, float *dh, hipStream_t st) {
     const int nslices = theta_bwd1_slices(n);
+    PWS_REQUIRE(theta_bwd1_lds(n, nslices) <= 64 * 1024, "pws_netg_backward (use_BN theta head): n = %d samples exceed the kernel's LDS staging", n);
     hipLaunchKernelGGL(theta_bwd1_kernel, dim3((unsigned)(((hidden + 255) / 256) * nslices)), dim3(256), theta_bwd1_lds(n, nslices), st, (const float *)nullptr, dz2, h,
                        hidden, w_lin, dw_lin, (float *)nullptr, (float *)nullptr, dh, 1, n, nslices);
     return check_launch("theta_bwd1_kernel<bn>");
