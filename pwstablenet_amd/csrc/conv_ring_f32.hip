@@ -45,9 +45,10 @@ struct RingfParams {
     int tiles_x, tiles_y;
     unsigned ncob, ncls, nunits;
     int gpp;              // K groups per plane = sum(src_c) / 16
+    int ablate;           // TIMING ONLY (PWS_OPT_EXPERIMENT 2200 + 16 v + mask, conv_ringf_try): 1 no matrix phase, 2 no DMA, 4 no stores
 };
 
-template <int MODE_, int TH_, int R_, int NT_ = 2>
+template <int MODE_, int TH_, int R_, int NT_ = 2, int MW_ = 8>
 struct RfCfg {
     static constexpr int MODE = MODE_, TH = TH_, TW = 32, R = R_;
     // NT: 32-channel output blocks per unit.  2: a matrix wave owns 64 output channels.  1: units of 32 output channels, twice as
@@ -58,11 +59,15 @@ struct RfCfg {
     static constexpr int TAPS = KS * KS;
     static constexpr int NPLANES = MODE == RF_K3S2 ? 4 : 1;   // input parity planes
     static constexpr int NCLS = MODE == RF_CT4 ? 4 : 1;       // output parity classes
-    static constexpr int MWAVES = 8, LWAVES = 4, THREADS = 64 * (MWAVES + LWAVES);
-    // tile = TH rows of 32 pixels of one sample; a matrix wave owns MT = TH / 8 rows (32-pixel operands) x 64 output channels:
+    // MW = 4: half a workgroup (half the tile's rows), two of them per CU -- each SIMD then carries two barrier domains, and one
+    // workgroup's matrix waves fill the pipe while the other's wait at a barrier or drain an epilogue (conv_ringf_try)
+    static constexpr int MWAVES = MW_, LWAVES = 4, THREADS = 64 * (MWAVES + LWAVES);
+    static constexpr int WPC = MWAVES == 8 ? 1 : 2;                                    // persistent workgroups per CU
+    static constexpr int MINW = (THREADS / 64 * WPC + 3) / 4;                         // waves per SIMD (register budget)
+    // tile = TH rows of 32 pixels of one sample; a matrix wave owns MT = TH / MW rows (32-pixel operands) x 32 NT output channels:
     // 16 x 32 tiles where the launch has enough of them for 256 persistent workgroups, 8 x 32 tiles otherwise
-    static_assert(TH == 16 || TH == 8, "tile");
-    static constexpr int MT = TH / 8;
+    static_assert((MWAVES == 8 && (TH == 16 || TH == 8)) || (MWAVES == 4 && (TH == 8 || TH == 4)), "tile");
+    static constexpr int MT = TH / MWAVES;
     static constexpr int IH = TH + KS - 1, IW = TW + KS - 1;
     static constexpr int CKG = 16;                                // input channels per K group
     static constexpr int ROWB = CKG * 4;                          // bytes per input row: one 64-byte L2 request
@@ -75,7 +80,7 @@ struct RfCfg {
     static constexpr int W_OFF = IN_WI * 1024;
     static constexpr int LDS_BYTES = R * GROUP_BYTES;
     static constexpr int MIX_IT = IN_WI % LWAVES == 0 ? -1 : IN_WI / LWAVES;
-    static_assert(LDS_BYTES <= 160 * 1024, "LDS");
+    static_assert(LDS_BYTES * WPC <= 160 * 1024, "LDS");
     static_assert(R >= 2 && R <= 4, "ring depth");
     static_assert((R - 2) * NL <= 63, "vmcnt is 6 bits");
 };
@@ -122,7 +127,7 @@ __device__ __forceinline__ RingfUnit ringf_unit(const RingfParams &p, unsigned u
 }
 
 template <class C>
-__global__ void __launch_bounds__(C::THREADS, 3) conv_ringf_kernel(const RingfParams p) {
+__global__ void __launch_bounds__(C::THREADS, C::MINW) conv_ringf_kernel(const RingfParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -238,17 +243,19 @@ __global__ void __launch_bounds__(C::THREADS, 3) conv_ringf_kernel(const RingfPa
                         }
                         const unsigned d_base = unif(dslot * (unsigned)C::GROUP_BYTES + (unsigned)(lw * 1024));
                         const unsigned d_smix = mix_in ? d_sin : d_sw;
-                        unsigned keep;
-                        asm volatile("s_nop 4\n\ts_mov_b32 %0, m0" : "=s"(keep));
+                        if (!(p.ablate & 2)) {
+                            unsigned keep;
+                            asm volatile("s_nop 4\n\ts_mov_b32 %0, m0" : "=s"(keep));
 #pragma unroll
-                        for (int it = 0; it < C::NL; ++it) {
-                            const bool in_ct = (it + 1) * C::LWAVES <= C::IN_WI, w_ct = it * C::LWAVES >= C::IN_WI;
-                            const unsigned dst = d_base + (unsigned)(it * C::LWAVES * 1024);
-                            if (in_ct) ringf_dma16_m0(dst, cv[it], d_rin, d_sin);
-                            else if (w_ct) ringf_dma16_m0(dst, cv[it], rsrc_w, d_sw);
-                            else ringf_dma16_m0(dst, cv[it], d_rmix, d_smix);
+                            for (int it = 0; it < C::NL; ++it) {
+                                const bool in_ct = (it + 1) * C::LWAVES <= C::IN_WI, w_ct = it * C::LWAVES >= C::IN_WI;
+                                const unsigned dst = d_base + (unsigned)(it * C::LWAVES * 1024);
+                                if (in_ct) ringf_dma16_m0(dst, cv[it], d_rin, d_sin);
+                                else if (w_ct) ringf_dma16_m0(dst, cv[it], rsrc_w, d_sw);
+                                else ringf_dma16_m0(dst, cv[it], d_rmix, d_smix);
+                            }
+                            asm volatile("s_mov_b32 m0, %0" ::"s"(keep));
                         }
-                        asm volatile("s_mov_b32 m0, %0" ::"s"(keep));
                         d_sin += (unsigned)(C::CKG * 4), d_sw += wstep;
                         ++issued;
                         dslot = dslot + 1 == (unsigned)C::R ? 0u : dslot + 1;
@@ -304,7 +311,7 @@ __global__ void __launch_bounds__(C::THREADS, 3) conv_ringf_kernel(const RingfPa
         if constexpr (C::MODE == RF_K3S2) tapmask = (cplane >> 1) ? ((cplane & 1) ? 0xfu : 0x5u) : ((cplane & 1) ? 0x3u : 0x1u);
         const unsigned gb = (unsigned)(cbuf * C::GROUP_BYTES);
 #pragma unroll
-        for (int tap = 0; tap < C::TAPS; ++tap) {
+        for (int tap = 0; tap < C::TAPS && !(p.ablate & 1); ++tap) {
             if constexpr (C::MODE == RF_K3S2) {
                 if (!((tapmask >> tap) & 1u)) continue;   // wave-uniform: 1, 2 or 4 taps per plane
             }
@@ -348,6 +355,7 @@ __global__ void __launch_bounds__(C::THREADS, 3) conv_ringf_kernel(const RingfPa
             const unsigned pxb = (unsigned)(SO * p.out_ld * 4);   // bytes between consecutive tile pixels in the output
 #pragma unroll
             for (int mt = 0; mt < C::MT; ++mt) {
+                if (p.ablate & 4) break;
                 const int y = CU.y0 * C::TH + wv * C::MT + mt;
                 const int oy = SO * y + (C::NCLS == 4 ? CU.py : 0);
                 const int ox0 = SO * (CU.x0 * C::TW + 4 * hi) + (C::NCLS == 4 ? CU.px : 0);
@@ -400,15 +408,22 @@ static int ringf_launch(RingfParams &rp, hipStream_t st) {
     int cin = 0;
     for (int s = 0; s < rp.nsrc; ++s) cin += rp.src_c[s];
     rp.gpp = cin / C::CKG;
-    const unsigned grid = rp.nunits < (unsigned)ncu ? rp.nunits : (unsigned)ncu;   // one persistent workgroup per CU
+    const unsigned slots = (unsigned)(ncu * C::WPC);
+    const unsigned grid = rp.nunits < slots ? rp.nunits : slots;   // persistent workgroups: C::WPC per CU
     hipLaunchKernelGGL((conv_ringf_kernel<C>), dim3(grid), dim3(C::THREADS), C::LDS_BYTES, st, rp);
     return check_launch("conv_ringf_kernel");
 }
 
 template <int MODE>
-static int ringf_launch_tile(int th, int nt, RingfParams &rp, hipStream_t st) {
+static int ringf_launch_tile(int th, int nt, bool half, RingfParams &rp, hipStream_t st) {
     constexpr int KS2 = MODE != RF_K3S1;
     if constexpr (MODE == RF_K3S2) {
+        if (half) {   // two workgroups per CU, LDS <= 80 KB each: the 64-channel units fit a ring of TWO groups only (the loader runs
+                      // one group ahead, vmcnt(0) before each barrier); the 32-channel units keep a ring of four
+            if (th == 8) return ringf_launch<RfCfg<MODE, 8, 2, 2, 4>>(rp, st);     // 2 x 36 KB (A/B only: v = 2)
+            if (nt == 2) return ringf_launch<RfCfg<MODE, 4, 2, 2, 4>>(rp, st);     // 2 x 28 KB = 56 KB
+            return ringf_launch<RfCfg<MODE, 4, 4, 1, 4>>(rp, st);                  // 4 x 20 KB = 80 KB
+        }
         if (th == 8 && nt == 1) return ringf_launch<RfCfg<MODE, 8, 4, 1>>(rp, st);
     }
     if (th == 16) return ringf_launch<RfCfg<MODE, 16, KS2 ? 3 : 2>>(rp, st);
@@ -460,11 +475,30 @@ int conv_ringf_try(int kind, const ConvKParams &kp, hipStream_t st, const ProfIn
     else if (mode == RF_K3S2 && per256_32 >= 256 && g_experiment != 26) th = 8, nt = 1;
     else return 1;
     if (mode == RF_CT4 && !forced) return 1;
+    // Stride-2 launches of 8 x 32 tiles (one unit per CU at the headline's shapes) run as HALF workgroups: 4 x 32 tiles, two
+    // workgroups per CU with a barrier domain each, so one fills the matrix pipe while the other waits at its barrier or drains its
+    // epilogue.  They leave a CU's LDS partly free (2 x 56 KB for 64-channel units; 2 x 80 KB for 32-channel units): in the bench's
+    // two batches in flight the other batch's short launches co-reside with them (profiles/r07_ringf_k3s2_ab.txt).  Same units of work per pixel and output channel, same K order: the bits do not change.  Measured
+    // (profiles/r07_ringf_k3s2_ab.txt, batch 8 / 16): 64 -> 128 @64^2 51.8 -> 47.7 us, 128 -> 256 @32^2 50.2 -> 48.8, 128 -> 128 @64^2
+    // 87.4 -> 83.5, 256 -> 256 @32^2 x 16 161.5 -> 154.2; 16 x 32 tiles gain nothing (64 -> 64 @128^2 ~86 us either way).
+    // Units of 32 output channels or 8 x 32 tiles instead of 16 x 32 (two units per workgroup) were slower on every launch.
+    // PWS_OPT_EXPERIMENT 2200 + 16 v + mask (2200..2247, this kernel's stride-2 kind only): v = 1 full workgroups everywhere,
+    // v = 2 half workgroups also for 16 x 32 tiles; mask = the timing-only ablations of RingfParams::ablate.  Output bits are the
+    // same for every v (tests/test_hip_ringf_variants.py).
+    // (PWS_OPT_EXPERIMENT ids read in this file: 22, 23, 24, 26, 27, 2200..2247)
+    bool half = mode == RF_K3S2 && th == 8;
+    if (mode == RF_K3S2 && g_experiment >= 2200 && g_experiment < 2248) {
+        const int v = (g_experiment - 2200) >> 4;
+        rp.ablate = (g_experiment - 2200) & 7;
+        if (v == 1) half = false;
+        else if (v == 2) half = true;
+    }
+    if (half) th /= 2;
     ProfScope prof(KID_CONV_RINGF, pi.flops, pi.bytes, st);
     switch (mode) {
-    case RF_K3S1: return ringf_launch_tile<RF_K3S1>(th, nt, rp, st);
-    case RF_CT4: return ringf_launch_tile<RF_CT4>(th, nt, rp, st);
-    default: return ringf_launch_tile<RF_K3S2>(th, nt, rp, st);
+    case RF_K3S1: return ringf_launch_tile<RF_K3S1>(th, nt, false, rp, st);
+    case RF_CT4: return ringf_launch_tile<RF_CT4>(th, nt, false, rp, st);
+    default: return ringf_launch_tile<RF_K3S2>(th, nt, half, rp, st);
     }
 }
 

@@ -47,7 +47,7 @@ def short(name):
     if m:
         a = [x.strip() for x in m.group(1).split(",")]
         mode = {"0": "k3s1", "1": "convT4", "2": "k3s2 planes"}.get(a[0], a[0])
-        return "conv_ringf_kernel<%s,tile %sx32,R%s>" % (mode, a[1], a[2])
+        return "conv_ringf_kernel<%s,tile %sx32,R%s%s>" % (mode, a[1], a[2], ",half workgroups" if len(a) > 4 and a[4] == "4" else "")
     return re.sub(r"\(.*", "", name).replace("pws::", "")[:100]
 
 
