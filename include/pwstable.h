@@ -40,6 +40,7 @@
  *   pws_upsample_bilinear_ac      UpsamplingBilinear2d(size=...)   main_new.py:706-710
  *   pws_upsample_grid_sample_fwd  the two above fused (720p path)  main_new.py:706-716
  *   pws_adam_step                 optim.Adam(...).step()           main_new.py:63,216
+ *   pws_field_homography          the automatic crop's per-frame findHomography + perspectiveTransform  main_new.py:550-603
  *   pws_pack_* / pws_netg_pack_weights   state_dict (OIHW / IOHW) -> kernel layout; main_new.py:60,471
  *
  * Layouts.  Frames / images: NCHW fp32 as in the reference.  Warp fields: N,H,W,2 fp32 (x then y,
@@ -384,6 +385,18 @@ int pws_area_half_u8(const unsigned char *in_hwc, unsigned char *out_hwc, int n,
  * (1080p, 2160p) -> OpenCV's integer-area path (int sum * float(1/area), round half to even); otherwise its area tables. */
 int pws_area_resize_u8(const unsigned char *in_hwc, unsigned char *out_hwc, int n, int h, int w, int oh, int ow, int swap_rb,
                        pws_stream_t stream);
+
+/* The automatic crop of the reference's video loop (main_new.py:484-606, a block it keeps inside a string literal), per frame
+ * (csrc/homography.hip): field[n,fh,fw,2] resized to the h0 x w0 source frame as pws_upsample_bilinear_ac does is sampled on the
+ * 20 x 20 lattice rows h0/2 + (a-10)*15, columns w0/2 + (b-10)*30 (p1, fp32); the homography M (m33 = 1) from p1 to the lattice's own
+ * position in [-1,1] (p2) minimising sum |p2 - pi(M [p1,1])|^2 over the 400 points is fitted in fp64 (Hartley-normalised DLT, then
+ * Gauss-Newton: cv2.findHomography's all-inlier result, unpinned: cv2 is not available), and the corners (-1,-1), (-1,.992),
+ * (.992,.992), (.992,-1) mapped through it (|w| <= FLT_EPSILON -> 0, as cv2.perspectiveTransform) give the frame's bounds in source
+ * pixels.  m_out[n,9] fp64 row-major; bounds_out[n,4] = top, bottom, left, right; pts_out[n,400,2] = p1 (may be NULL).  Samples
+ * without spread, a normal matrix that is not positive definite or a result that is not finite give NaN M and bounds.
+ * h0 >= 300 and w0 >= 600 (the lattice must fit); field and pts_out 8-byte aligned. */
+int pws_field_homography(const float *field, int n, int fh, int fw, int h0, int w0, double *m_out, float *bounds_out, float *pts_out,
+                         pws_stream_t stream);
 
 /* Adam (no weight decay / amsgrad) on a flat fp32 buffer, in place; step counts from 1. */
 int pws_adam_step(float *p, const float *g, float *m, float *v, size_t count, float lr, float beta1,

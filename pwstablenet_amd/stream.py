@@ -13,6 +13,8 @@ host<->device round trip per frame.  Here:
     and results go D2H on a third stream (hipMemcpyAsync through torch, one event per hand-off);
   * several GPUs take contiguous frame chunks with a 15-frame halo each (``distributed.shard_frames``): no collective.
 """
+import math
+
 import torch
 
 from . import functional as PF
@@ -62,6 +64,71 @@ def area_resize(frames_hwc, size, swap_rb=False):
     return out
 
 
+def _field_homography(field, h0, w0, m_out, bounds_out, pts_out=None):
+    A.check(A.lib().pws_field_homography(A.ptr(field), field.shape[0], field.shape[1], field.shape[2], h0, w0, A.ptr(m_out),
+                                         A.ptr(bounds_out), A.ptr(pts_out), A.current_stream()), "pws_field_homography")
+
+
+def _check_lattice(h0, w0):
+    if h0 < 300 or w0 < 600:
+        raise ValueError("automatic crop: the 20 x 20 sampling lattice needs a frame of at least 600 x 300 pixels, got %d x %d" % (w0, h0))
+
+
+def field_homography(field, frame_hw, return_points=False):
+    """The per-frame half of the reference's automatic crop (main_new.py:550-574) on the device: ``field`` (N, fh, fw, 2) as
+    ``netG(window, False)`` returns it, ``frame_hw`` = (H0, W0) of the source frames it warps.  The field resized to H0 x W0 as the warp
+    resizes it is sampled on a 20 x 20 lattice (p1), the homography M (m33 = 1) from p1 to the lattice's own positions in [-1, 1] is
+    fitted in fp64 (least squares on the reprojection error: cv2.findHomography's result when every sample is an inlier), and the
+    corners mapped through it give the frame's bounds in source pixels.  Returns M (N, 3, 3) float64 and bounds (N, 4) float32 = (top,
+    bottom, left, right) [and p1 (N, 400, 2) float32], all on the device; a frame without a well-defined fit has NaN M and bounds."""
+    A.require_cuda(field)
+    if field.dim() != 4 or field.shape[3] != 2:
+        raise ValueError("field_homography: field must be (N, fh, fw, 2), got %s" % (tuple(field.shape),))
+    h0, w0 = int(frame_hw[0]), int(frame_hw[1])
+    _check_lattice(h0, w0)
+    field = field.contiguous()
+    n = field.shape[0]
+    m = torch.empty((n, 3, 3), device=field.device, dtype=torch.float64)
+    bounds = torch.empty((n, 4), device=field.device, dtype=torch.float32)
+    pts = torch.empty((n, 400, 2), device=field.device, dtype=torch.float32) if return_points else None
+    _field_homography(field, h0, w0, m, bounds, pts)
+    return (m, bounds, pts) if return_points else (m, bounds)
+
+
+def auto_crop_window(bounds, frame_hw, output_hw=None, period=30):
+    """The reference's crop recurrence (main_new.py:575-603) over a clip's per-frame bounds (``field_homography``; (T, 4) top, bottom,
+    left, right in source pixels, a tensor on either side or an array): the window starts at the whole H0 x W0 frame, and each frame i
+    with period//2 < i < T - period//2 pulls every edge that lies outside the frame's bounds half way towards them, in float64.  Returns
+    (x_start, x_end, y_start, y_end), scaled to ``output_hw`` = (height, width) of the output frame when given, for run_video's ``crop``.
+    ValueError when a frame the recurrence reads has NaN bounds, or when the window is empty."""
+    if isinstance(bounds, torch.Tensor):
+        bounds = bounds.detach().to("cpu", torch.float64).tolist()
+    bounds = [[float(v) for v in row] for row in bounds]
+    if any(len(row) != 4 for row in bounds):
+        raise ValueError("auto_crop_window: bounds must be (T, 4): top, bottom, left, right")
+    h0, w0 = int(frame_hw[0]), int(frame_hw[1])
+    T, half, rate = len(bounds), int(period) // 2, 0.5
+    x0, x1, y0, y1 = 0.0, float(w0), 0.0, float(h0)
+    for i in range(half + 1, T - half):
+        top, bottom, left, right = bounds[i]
+        if not all(math.isfinite(v) for v in bounds[i]):
+            raise ValueError("auto_crop_window: frame %d has no homography (bounds %r)" % (i, bounds[i]))
+        if y0 < top:
+            y0 += (top - y0) * rate
+        if y1 > bottom:
+            y1 -= (y1 - bottom) * rate
+        if x0 < left:
+            x0 += (left - x0) * rate
+        if x1 > right:
+            x1 -= (x1 - right) * rate
+    if output_hw is not None:
+        sy, sx = int(output_hw[0]) / h0, int(output_hw[1]) / w0
+        x0, x1, y0, y1 = x0 * sx, x1 * sx, y0 * sy, y1 * sy
+    if not (int(x1) > int(x0) and int(y1) > int(y0)):
+        raise ValueError("auto_crop_window: the crop window x [%g, %g) y [%g, %g) is empty" % (x0, x1, y0, y1))
+    return x0, x1, y0, y1
+
+
 def _windows(gray_padded, start, count, period):
     """(count, period+1, 256, 256) windows: window b covers padded frames [start+b, start+b+period].  An OVERLAPPING VIEW of the
     plane buffer (sample stride = one plane): the generator's first layer reads it in place (pws_netg_opts.x_sample_stride); no
@@ -94,6 +161,15 @@ class VideoStabilizer:
         if need_r > 0:
             parts.append(gray[-1:].expand(need_r, -1, -1))
         return torch.cat(parts, 0) if len(parts) > 1 else gray
+
+    def _fields(self, gray, halo_left, halo_right, out):
+        """The generator half of run(): the fields of the out.shape[0] frames into ``out`` (T, 256, 256, 2), in the batches run()
+        forms (the same windows per generator call: the same fields bit for bit).  The copy also frees a graph's static output."""
+        gp = self._pad(gray.contiguous(), halo_left, halo_right).contiguous()
+        T = out.shape[0]
+        for s in range(0, T, self.batch):
+            e = min(T, s + self.batch)
+            out[s:e].copy_(self.net(_windows(gp, s, e - s, self.period), False))
 
     @torch.no_grad()
     def run(self, gray, frames, halo_left=0, halo_right=0, out=None):
@@ -180,6 +256,13 @@ class VideoStabilizer:
         in_flight = 2: consecutive chunks compute on two streams without waiting for each other (one chunk walks the generator's chain of
         small levels while the other's large layers fill the chip: DESIGN.md section 8); for the duration of the call the generator runs one
         queue per forward and, in graph mode, keeps one graph + arena per stream.  Same frames bit for bit as in_flight = 1.
+        crop = "auto": the reference's automatic crop (main_new.py:484-606), which cuts away the black wedges the warp's zero padding
+        leaves: pass 1 runs the generator once per frame, keeps the clip's fields on the device ((T, 256, 256, 2) fp32: 512 KB per frame,
+        on top of the window planes) and fits each frame's homography (``field_homography``) on the same stream; the host then runs the
+        window recurrence over the (T, 4) bounds (``auto_crop_window``, the call's one synchronisation); pass 2 uploads host-resident frames
+        again (device-resident ones are read in place) and runs only the warp, the output resize and the crop.  Same frames bit for bit as
+        crop=auto_crop_window(bounds, (H, W), output (height, width), period).  Needs the whole clip (no halos) and a source of at least
+        600 x 300.
         Returns (T, H, W, 3) -- or (T, H/2, W/2, 3) / (T, height, width, 3), or the crop window of it -- uint8 on the inputs' side."""
         half = self.period // 2
         if not (0 <= halo_left <= half and 0 <= halo_right <= half):
@@ -199,16 +282,31 @@ class VideoStabilizer:
                 raise ValueError("run_video: output_size %s must not exceed the %d x %d source (INTER_AREA down-scaling)" % (tuple(output_size), w, h))
         else:
             oh, ow = (h // 2, w // 2) if half_size_output else (h, w)
-        cy0, cy1, cx0, cx1 = 0, oh, 0, ow
-        if crop is not None:
-            if len(crop) not in (4, 5):
-                raise ValueError("crop must be (x_start, x_end, y_start, y_end[, threshold])")
-            th = int(crop[4]) if len(crop) == 5 else 0
-            cx0, cx1, cy0, cy1 = int(crop[0]) + th, int(crop[1]) - th, int(crop[2]) + th, int(crop[3]) - th
-            if not (0 <= cx0 < cx1 <= ow and 0 <= cy0 < cy1 <= oh):
-                raise ValueError("crop window x [%d, %d) y [%d, %d) does not lie inside the %d x %d output frame" % (cx0, cx1, cy0, cy1, ow, oh))
-        oshape = (T, cy1 - cy0, cx1 - cx0, 3)
-        out = torch.empty(oshape, dtype=torch.uint8, pin_memory=True) if on_host else torch.empty(oshape, dtype=torch.uint8, device=dev)
+        auto = isinstance(crop, str)
+        if auto:
+            if crop != "auto":
+                raise ValueError("crop must be None, \"auto\" or (x_start, x_end, y_start, y_end[, threshold])")
+            if halo_left or halo_right:
+                raise ValueError("run_video: crop=\"auto\" needs the whole clip (a shard cannot see the clip's crop recurrence): gather "
+                                 "the shards' field_homography bounds and pass crop=auto_crop_window(...)")
+            _check_lattice(h, w)
+
+        def crop_window(crop):
+            cy0, cy1, cx0, cx1 = 0, oh, 0, ow
+            if crop is not None:
+                if len(crop) not in (4, 5):
+                    raise ValueError("crop must be (x_start, x_end, y_start, y_end[, threshold])")
+                th = int(crop[4]) if len(crop) == 5 else 0
+                cx0, cx1, cy0, cy1 = int(crop[0]) + th, int(crop[1]) - th, int(crop[2]) + th, int(crop[3]) - th
+                if not (0 <= cx0 < cx1 <= ow and 0 <= cy0 < cy1 <= oh):
+                    raise ValueError("crop window x [%d, %d) y [%d, %d) does not lie inside the %d x %d output frame" % (cx0, cx1, cy0, cy1, ow, oh))
+            return cy0, cy1, cx0, cx1
+
+        def alloc_out():
+            oshape = (T, cy1 - cy0, cx1 - cx0, 3)
+            return torch.empty(oshape, dtype=torch.uint8, pin_memory=True) if on_host else torch.empty(oshape, dtype=torch.uint8, device=dev)
+        cy0, cy1, cx0, cx1 = crop_window(None if auto else crop)
+        out = None if auto and T > 0 else alloc_out()
         if T == 0:
             return out
         compute = torch.cuda.current_stream(dev)
@@ -230,6 +328,10 @@ class VideoStabilizer:
             for lane in lanes[1:]:
                 lane.wait_stream(compute)
         gray_all = torch.empty((n_all, 256, 256), device=dev, dtype=torch.float32)
+        if auto:
+            fields = torch.empty((T, 256, 256, 2), device=dev, dtype=torch.float32)
+            hom = torch.empty((T, 9), device=dev, dtype=torch.float64)
+            bounds = torch.empty((T, 4), device=dev, dtype=torch.float32)
         # chunk bounds in the index space of `frames`: the first / last chunk carry the halo frames with them
         chunks = [(s if s > halo_left else 0, min(halo_left + T, s + chunk) if s + chunk < halo_left + T else n_all)
                   for s in range(halo_left, halo_left + T, chunk)]
@@ -243,6 +345,25 @@ class VideoStabilizer:
                 ev = torch.cuda.Event()
                 ev.record(up)
             return buf, ev
+
+        def finish(warped, buf, s, e, lane):
+            """output resize + crop of the warped core frames s .. e-1 (output positions) on `lane`, and their way to `out`"""
+            if half_size_output:
+                warped = area_half(warped)
+            elif output_size is not None and (oh, ow) != (h, w):
+                warped = area_resize(warped, (ow, oh))
+            if crop is not None:
+                warped = warped[:, cy0:cy1, cx0:cx1, :].contiguous()   # packed on the device: only the window crosses PCIe
+            if on_host:
+                buf.record_stream(lane)
+                done = torch.cuda.Event()
+                done.record(lane)
+                with torch.cuda.stream(down):
+                    down.wait_event(done)
+                    out[s:e].copy_(warped, non_blocking=True)
+                warped.record_stream(down)
+            else:
+                out[s:e].copy_(warped)
         staged, uploaded = {}, 0
         try:
             for c, (s, e) in enumerate(chunks):
@@ -262,30 +383,42 @@ class VideoStabilizer:
                 cs, ce = max(s, halo_left), min(e, halo_left + T)
                 hl, hr = min(half, cs), min(half, n_all - ce)
                 with torch.cuda.stream(lane):
+                    if auto:   # pass 1: fields and per-frame bounds only (no halos here: core frames = output positions)
+                        self._fields(gray_all[cs - hl:ce + hr], hl, hr, fields[cs:ce])
+                        _field_homography(fields[cs:ce], h, w, hom[cs:ce], bounds[cs:ce])
+                        continue
                     warped = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr)
-                    if half_size_output:
-                        warped = area_half(warped)
-                    elif output_size is not None and (oh, ow) != (h, w):
-                        warped = area_resize(warped, (ow, oh))
-                    if crop is not None:
-                        warped = warped[:, cy0:cy1, cx0:cx1, :].contiguous()   # packed on the device: only the window crosses PCIe
-                    s, e = cs - halo_left, ce - halo_left   # position in the output
-                    if on_host:
-                        buf.record_stream(lane)
-                        done = torch.cuda.Event()
-                        done.record(lane)
-                        with torch.cuda.stream(down):
-                            down.wait_event(done)
-                            out[s:e].copy_(warped, non_blocking=True)
-                        warped.record_stream(down)
-                    else:
-                        out[s:e].copy_(warped)
+                    finish(warped, buf, cs - halo_left, ce - halo_left, lane)
         finally:
             if restore is not None:
                 for lane in lanes[1:]:
                     compute.wait_stream(lane)   # the caller's stream sees every chunk; gray_all and the outputs may be freed behind it
                 mod.two_queues = restore[3]
                 mod.enable_graph(restore[0], restore[1], per_stream=restore[2])
+        if auto:
+            crop = auto_crop_window(bounds, (h, w), (oh, ow), self.period)   # (the copy to the host waits for pass 1)
+            cy0, cy1, cx0, cx1 = crop_window(crop)
+            out = alloc_out()
+            # pass 2: warp + output resize + crop with the kept fields; chunk k+1 uploads while chunk k computes
+
+            def fetch(c):
+                s, e = chunks[c]
+                if not on_host:
+                    return frames[s:e], None
+                with torch.cuda.stream(up):
+                    buf = frames[s:e].to(dev, non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record(up)
+                return buf, ev
+            nxt = fetch(0)
+            for c, (s, e) in enumerate(chunks):
+                buf, ev = nxt
+                if c + 1 < len(chunks):
+                    nxt = fetch(c + 1)
+                if ev is not None:
+                    compute.wait_event(ev)
+                warped = PF.upsample_grid_sample_u8(buf.contiguous(), fields[s:e], swap_rb=self.swap_rb, align_corners=self.align_corners)
+                finish(warped, buf, s, e, compute)
         if on_host:
             down.synchronize()
         return out
