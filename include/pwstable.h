@@ -386,6 +386,22 @@ int pws_area_half_u8(const unsigned char *in_hwc, unsigned char *out_hwc, int n,
 int pws_area_resize_u8(const unsigned char *in_hwc, unsigned char *out_hwc, int n, int h, int w, int oh, int ow, int swap_rb,
                        pws_stream_t stream);
 
+/* 4:2:0 YUV frames as decoders hand them over: [n][h*3/2][w] uint8, the Y plane (h x w) then the chroma -- layout 0 NV12 (h/2 rows of w
+ * bytes, U and V interleaved), 1 I420 (the U plane h/2 x w/2, then the V plane).  BT.601 limited range, 8 bit.
+ * out[n,oh,ow] = pws_gray_area_u8 of the BGR frame cv2.cvtColor(frame, COLOR_YUV2BGR_NV12 / _I420) gives (OpenCV 4.x's fixed point,
+ * restated: csrc/frameio.hip), in one launch.  h and w even. */
+int pws_gray_area_yuv420_u8(const unsigned char *frames, float *out, int n, int h, int w, int oh, int ow, int normalize, int layout,
+                            pws_stream_t stream);
+/* INTER_AREA (pws_area_resize_u8's algorithms) of a 1- or 2-channel byte plane [n][h][w][c] -> [n][oh][ow][c]; in / out point at sample 0's
+ * plane, samples in_stride / out_stride bytes apart (the planes of packed YUV frames). */
+int pws_area_resize_plane_u8(const unsigned char *in, size_t in_stride, unsigned char *out, size_t out_stride, int n, int h, int w, int c,
+                             int oh, int ow, pws_stream_t stream);
+/* pws_upsample_grid_sample_u8 for packed 4:2:0 frames (layout as pws_gray_area_yuv420_u8), YUV in and out: each plane is warped by the
+ * field resized (align_corners=True) to the plane's own size, fp32 blend truncated; taps outside a plane read 16 (Y) / 128 (U, V), BT.601
+ * black.  h even, w % 4 == 0, frames and out 4-byte aligned.  3 bytes of frame traffic per pixel. */
+int pws_upsample_grid_sample_yuv420_u8(const unsigned char *frames, const float *field, unsigned char *out, int n, int h, int w, int fh,
+                                       int fw, int layout, int align_corners, pws_stream_t stream);
+
 /* The automatic crop of the reference's video loop (main_new.py:484-606, a block it keeps inside a string literal), per frame
  * (csrc/homography.hip): field[n,fh,fw,2] resized to the h0 x w0 source frame as pws_upsample_bilinear_ac does is sampled on the
  * 20 x 20 lattice rows h0/2 + (a-10)*15, columns w0/2 + (b-10)*30 (p1, fp32); the homography M (m33 = 1) from p1 to the lattice's own

@@ -157,6 +157,126 @@ __global__ void __launch_bounds__(256) area_tab_u8_kernel(const unsigned char *_
     o[0] = swap_rb ? r[2] : r[0], o[1] = r[1], o[2] = swap_rb ? r[0] : r[2];
 }
 
+
+// ---- 4:2:0 YUV frames ([n][h*3/2][w] uint8: Y plane, then NV12's interleaved UV rows or I420's U and V planes), as decoders hand them over.
+// Gray window planes: the gray of the BGR frame cv2.cvtColor(frame, COLOR_YUV2BGR_NV12 / _I420) would give, then the same INTER_AREA and
+// x / 255 * 2 - 1 as gray_area_u8_kernel, fused in one launch, so a YUV clip gets the fields of its BGR decode bit for bit.  Unpinned against
+// cv2 like the rest of this file: the conversion restates OpenCV 4.x's 8-bit BT.601 limited-range fixed point (imgproc color_yuv:
+// ITUR_BT_601_CY / CVR / CVG / CUG / CUB, shift 20), chroma taken from sample (x/2, y/2) without interpolation:
+//   y = max(0, Y - 16) * 1220542, u = U - 128, v = V - 128
+//   R = sat((y + 1673527 v + 2^19) >> 20), G = sat((y - 852492 v - 409993 u + 2^19) >> 20), B = sat((y + 2116026 u + 2^19) >> 20)
+__device__ __forceinline__ int sat_u8(int v) { return min(max(v, 0), 255); }
+template <int LAYOUT>   // 0 NV12, 1 I420
+__device__ __forceinline__ int gray_yuv420(const unsigned char *f, int H, int W, int x, int y) {
+    const int Y = f[(size_t)y * W + x];
+    const unsigned char *c = f + (size_t)H * W;
+    int U, V;
+    if (LAYOUT == 0) {
+        const unsigned char *p = c + (size_t)(y >> 1) * W + (x & ~1);
+        U = p[0], V = p[1];
+    } else {
+        const size_t o = (size_t)(y >> 1) * (W >> 1) + (x >> 1);
+        U = c[o], V = c[o + (size_t)(H >> 1) * (W >> 1)];
+    }
+    const int yy = max(0, Y - 16) * 1220542, u = U - 128, v = V - 128;
+    const int r = sat_u8((yy + 1673527 * v + (1 << 19)) >> 20);
+    const int g = sat_u8((yy - 852492 * v - 409993 * u + (1 << 19)) >> 20);
+    const int b = sat_u8((yy + 2116026 * u + (1 << 19)) >> 20);
+    return (b * 3735 + g * 19235 + r * 9798 + (1 << 14)) >> 15;   // gray_u8 above
+}
+
+// one lane per destination pixel, gray_area_u8_kernel's arithmetic in its order
+template <int LAYOUT>
+__global__ void __launch_bounds__(256) gray_area_yuv420_kernel(const unsigned char *__restrict__ frames, float *__restrict__ out, int H, int W,
+                                                               int OH, int OW, double sy, double sx, int normalize, size_t total) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int dx = (int)(i % OW), dy = (int)((i / OW) % OH);
+    const size_t n = i / ((size_t)OW * OH);
+    const AreaAxis tx = area_axis(dx, W, sx), ty = area_axis(dy, H, sy);
+    const unsigned char *f = frames + n * ((size_t)H * W * 3 / 2);
+    float sum = 0.f;
+    for (int j = 0; j < ty.n; ++j) {
+        int sj, sk;
+        float beta, alpha;
+        ty.tap(j, sj, beta);
+        float buf = 0.f;
+        for (int k = 0; k < tx.n; ++k) {
+            tx.tap(k, sk, alpha);
+            buf = buf + mul_rounded((float)gray_yuv420<LAYOUT>(f, H, W, sk, sj), alpha);
+        }
+        sum = j == 0 ? mul_rounded(beta, buf) : sum + mul_rounded(beta, buf);
+    }
+    const float g8 = fminf(fmaxf(rintf(sum), 0.f), 255.f);
+    out[i] = normalize ? g8 / 255 * 2 - 1 : g8;
+}
+
+// INTER_AREA of a C-channel byte plane (C = 1: Y, I420's U or V; C = 2: NV12's UV), the 3-channel kernels' algorithms above: 2 x 2 mean,
+// integer-ratio sum * float(1 / area), area tables.  in / out: the plane of sample 0; samples ist / ost bytes apart.  One lane per pixel.
+template <int C>
+__global__ void __launch_bounds__(256) area_half_plane_kernel(const unsigned char *__restrict__ in, size_t ist, unsigned char *__restrict__ out,
+                                                              size_t ost, int H, int W, size_t total) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int OW = W / 2, OH = H / 2;
+    const int ox = (int)(i % OW), oy = (int)((i / OW) % OH);
+    const size_t n = i / ((size_t)OW * OH);
+    const unsigned char *p = in + n * ist + ((size_t)2 * oy * W + 2 * ox) * C;
+    const unsigned char *q = p + (size_t)W * C;
+    unsigned char *o = out + n * ost + ((size_t)oy * OW + ox) * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) o[c] = (unsigned char)((p[c] + p[C + c] + q[c] + q[C + c] + 2) >> 2);
+}
+
+template <int C>
+__global__ void __launch_bounds__(256) area_int_plane_kernel(const unsigned char *__restrict__ in, size_t ist, unsigned char *__restrict__ out,
+                                                             size_t ost, int H, int W, int OH, int OW, int ky, int kx, float scale, size_t total) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int ox = (int)(i % OW), oy = (int)((i / OW) % OH);
+    const size_t n = i / ((size_t)OW * OH);
+    const unsigned char *p = in + n * ist + ((size_t)oy * ky * W + (size_t)ox * kx) * C;
+    int s[C] = {};
+    for (int j = 0; j < ky; ++j) {
+        const unsigned char *q = p + (size_t)j * W * C;
+        for (int k = 0; k < kx; ++k)
+#pragma unroll
+            for (int c = 0; c < C; ++c) s[c] += q[C * k + c];
+    }
+    unsigned char *o = out + n * ost + ((size_t)oy * OW + ox) * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) o[c] = (unsigned char)fminf(fmaxf(rintf(mul_rounded((float)s[c], scale)), 0.f), 255.f);
+}
+
+template <int C>
+__global__ void __launch_bounds__(256) area_tab_plane_kernel(const unsigned char *__restrict__ in, size_t ist, unsigned char *__restrict__ out,
+                                                             size_t ost, int H, int W, int OH, int OW, double sy, double sx, size_t total) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int dx = (int)(i % OW), dy = (int)((i / OW) % OH);
+    const size_t n = i / ((size_t)OW * OH);
+    const AreaAxis tx = area_axis(dx, W, sx), ty = area_axis(dy, H, sy);
+    const unsigned char *f = in + n * ist;
+    float sum[C] = {};
+    for (int j = 0; j < ty.n; ++j) {
+        int sj, sk;
+        float beta, alpha;
+        ty.tap(j, sj, beta);
+        const unsigned char *row = f + (size_t)sj * W * C;
+        float buf[C] = {};
+        for (int k = 0; k < tx.n; ++k) {
+            tx.tap(k, sk, alpha);
+#pragma unroll
+            for (int c = 0; c < C; ++c) buf[c] = buf[c] + mul_rounded((float)row[(size_t)sk * C + c], alpha);
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) sum[c] = j == 0 ? mul_rounded(beta, buf[c]) : sum[c] + mul_rounded(beta, buf[c]);
+    }
+    unsigned char *o = out + n * ost + ((size_t)dy * OW + dx) * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) o[c] = (unsigned char)fminf(fmaxf(rintf(sum[c]), 0.f), 255.f);
+}
+
 }  // namespace pws
 
 using namespace pws;
@@ -210,4 +330,54 @@ extern "C" int pws_area_resize_u8(const unsigned char *in_hwc, unsigned char *ou
     const double sy = 1.0 / ((double)oh / h), sx = 1.0 / ((double)ow / w);
     hipLaunchKernelGGL(area_tab_u8_kernel, dim3(nb), dim3(256), 0, as_stream(stream), in_hwc, out_hwc, h, w, oh, ow, sy, sx, swap_rb, total);
     return check_launch("area_tab_u8_kernel");
+}
+
+extern "C" int pws_gray_area_yuv420_u8(const unsigned char *frames, float *out, int n, int h, int w, int oh, int ow, int normalize, int layout,
+                                       pws_stream_t stream) {
+    PWS_REQUIRE(n >= 0 && h > 0 && w > 0 && oh > 0 && ow > 0 && oh <= h && ow <= w, "pws_gray_area_yuv420_u8: bad shape (down-scaling only)");
+    PWS_REQUIRE(h % 2 == 0 && w % 2 == 0, "pws_gray_area_yuv420_u8: h and w must be even (got %d x %d)", w, h);
+    PWS_REQUIRE(layout == 0 || layout == 1, "pws_gray_area_yuv420_u8: layout must be 0 (NV12) or 1 (I420), got %d", layout);
+    PWS_REQUIRE((double)h / oh <= AREA_MAX_TAPS - 2 && (double)w / ow <= AREA_MAX_TAPS - 2, "pws_gray_area_yuv420_u8: scale above %d",
+                AREA_MAX_TAPS - 2);
+    if (n == 0) return PWS_OK;
+    PWS_REQUIRE(frames && out, "pws_gray_area_yuv420_u8: NULL pointer");
+    const size_t total = (size_t)n * oh * ow;
+    const double sy = 1.0 / ((double)oh / h), sx = 1.0 / ((double)ow / w);
+    ProfScope prof(KID_OBJECTIVE, 16.0 * n * h * w, 1.5 * n * h * w + 4.0 * total, as_stream(stream));
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (layout == 0)
+        hipLaunchKernelGGL(gray_area_yuv420_kernel<0>, grid, dim3(256), 0, as_stream(stream), frames, out, h, w, oh, ow, sy, sx, normalize, total);
+    else
+        hipLaunchKernelGGL(gray_area_yuv420_kernel<1>, grid, dim3(256), 0, as_stream(stream), frames, out, h, w, oh, ow, sy, sx, normalize, total);
+    return check_launch("gray_area_yuv420_kernel");
+}
+
+extern "C" int pws_area_resize_plane_u8(const unsigned char *in, size_t in_stride, unsigned char *out, size_t out_stride, int n, int h, int w,
+                                        int c, int oh, int ow, pws_stream_t stream) {
+    PWS_REQUIRE(n >= 0 && h > 0 && w > 0 && oh > 0 && ow > 0 && oh <= h && ow <= w, "pws_area_resize_plane_u8: bad shape (down-scaling only)");
+    PWS_REQUIRE(c == 1 || c == 2, "pws_area_resize_plane_u8: 1 or 2 channels, got %d", c);
+    if (n == 0) return PWS_OK;
+    PWS_REQUIRE(in && out, "pws_area_resize_plane_u8: NULL pointer");
+    const size_t total = (size_t)n * oh * ow;
+    const dim3 grid((unsigned)((total + 255) / 256)), blk(256);
+    hipStream_t st = as_stream(stream);
+    ProfScope prof(KID_OBJECTIVE, (double)c * n * h * w, (double)c * ((double)n * h * w + (double)total), st);
+    if (h == 2 * oh && w == 2 * ow) {   // OpenCV's 2 x 2 SIMD path
+        if (c == 1) hipLaunchKernelGGL(area_half_plane_kernel<1>, grid, blk, 0, st, in, in_stride, out, out_stride, h, w, total);
+        else hipLaunchKernelGGL(area_half_plane_kernel<2>, grid, blk, 0, st, in, in_stride, out, out_stride, h, w, total);
+        return check_launch("area_half_plane_kernel");
+    }
+    if (h % oh == 0 && w % ow == 0) {
+        const int ky = h / oh, kx = w / ow;
+        const float scale = 1.f / (float)(kx * ky);
+        if (c == 1) hipLaunchKernelGGL(area_int_plane_kernel<1>, grid, blk, 0, st, in, in_stride, out, out_stride, h, w, oh, ow, ky, kx, scale, total);
+        else hipLaunchKernelGGL(area_int_plane_kernel<2>, grid, blk, 0, st, in, in_stride, out, out_stride, h, w, oh, ow, ky, kx, scale, total);
+        return check_launch("area_int_plane_kernel");
+    }
+    PWS_REQUIRE((double)h / oh <= AREA_MAX_TAPS - 2 && (double)w / ow <= AREA_MAX_TAPS - 2, "pws_area_resize_plane_u8: scale above %d",
+                AREA_MAX_TAPS - 2);
+    const double sy = 1.0 / ((double)oh / h), sx = 1.0 / ((double)ow / w);
+    if (c == 1) hipLaunchKernelGGL(area_tab_plane_kernel<1>, grid, blk, 0, st, in, in_stride, out, out_stride, h, w, oh, ow, sy, sx, total);
+    else hipLaunchKernelGGL(area_tab_plane_kernel<2>, grid, blk, 0, st, in, in_stride, out, out_stride, h, w, oh, ow, sy, sx, total);
+    return check_launch("area_tab_plane_kernel");
 }

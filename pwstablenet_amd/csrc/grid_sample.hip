@@ -997,3 +997,283 @@ extern "C" int pws_upsample_grid_sample_u8(const unsigned char *frame_hwc, const
 #undef PWS_U8_LAUNCH
     return check_launch("upsample_grid_sample_u8_kernel");
 }
+
+// ---------------------------------------------------------------------------------------------- fused 4:2:0 YUV path
+// The same warp for packed 4:2:0 frames as decoders hand them over ([n][h*3/2][w] uint8: the Y plane, then NV12's interleaved UV rows or
+// I420's U plane and V plane).  Each plane is warped by the field resized (align_corners=True) to the PLANE's own size, with the float
+// kernel's field interpolation, un-normalisation and 4-term blend order, truncated like astype(uint8).  Chroma samples are taken as centred
+// in their 2 x 2 luma block (the plane is warped on its own grid; MPEG-2 left siting is ignored: at most half a luma pixel).  A tap outside
+// the plane reads BT.601 black -- 16 in Y, 128 in U and V -- instead of zero (zero chroma would paint the border wedges green).
+// One launch covers every plane of every sample: the x dimension of the grid walks the Y plane's row groups, then the chroma row groups; a
+// wave owns 4 x 64 consecutive pixels of ONE plane row (Y: 256 luma pixels; chroma: 256 chroma pixels, U and V both), so row, sample,
+// plane, the field's row pair and its vertical weights are wave-uniform as in the BGR kernel above.  Per lane and tap row ONE aligned
+// 8-byte load + one v_alignbyte fetches a pixel's horizontal tap pair (2 bytes, or U V U V for NV12); the field's row pair is fetched once
+// per wave and handed round with ds_bpermute where the wave's pixels span few enough field columns (FMODE 2: one column per lane; 3: two);
+// float -> byte is one SDWA convert.
+namespace yuv {
+constexpr int PLANE_Y = 0, PLANE_NV12_UV = 1, PLANE_I420_UV = 2;
+struct Plane {      // one plane kind's geometry inside a frame (byte offsets from the frame's start)
+    int h, w;       // plane rows and pixels per row
+    unsigned off0, off1, pitch;   // first (and for I420 chroma: second) source plane, row pitch in bytes
+    float ry, rx, kx, kx1, ky, ky1;
+    unsigned nrg;   // row groups of 4 rows
+};
+}  // namespace yuv
+
+// the field at 4 consecutive pixels ox0 .. ox0+3 (clamped to the row) of plane row oy: the BGR kernel's arithmetic (its FMODE 0 and 2), plus
+// FMODE 3 (the chroma planes of 1280-wide frames span up to 103 field columns per wave)
+template <int FMODE>   // 0 four corners per pixel; 2 / 3 the wave's row pair, one / two columns per lane
+__device__ __forceinline__ void yuv_field4(const float *__restrict__ field, unsigned n, unsigned oy, int ox0, int wlast, int fh, int fw,
+                                           float ry, float rx, f32x2 gx[2], f32x2 gy[2]) {
+    const float sy = mul_rounded(ry, (float)oy);
+    const int y0 = __builtin_amdgcn_readfirstlane((int)sy), y1 = y0 + (y0 < fh - 1 ? 1 : 0);
+    const float ly = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, sy - (float)y0))), hy = 1.f - ly;
+    const float2 *f0 = reinterpret_cast<const float2 *>(field) + ((size_t)n * fh + y0) * fw;
+    const float2 *f1 = reinterpret_cast<const float2 *>(field) + ((size_t)n * fh + y1) * fw;
+    const f32x2 ly2 = pk_splat(ly), hy2 = pk_splat(hy), one2 = pk_splat(1.f);
+    const float xl = (float)wlast;   // pixels past the row's end (chroma rows of width 2 mod 4) take the last pixel's field: never stored
+    const float oxf = (float)ox0;
+    const f32x2 px[2] = {f32x2{fminf(oxf, xl), fminf(oxf + 1.f, xl)}, f32x2{fminf(oxf + 2.f, xl), fminf(oxf + 3.f, xl)}};
+    if constexpr (FMODE != 0) {
+        f32x2 sx[2], fl[2];
+        sx[0] = pk_mul_rounded(pk_splat(rx), px[0]), sx[1] = pk_mul_rounded(pk_splat(rx), px[1]);
+        fl[0] = pk_floor(sx[0]), fl[1] = pk_floor(sx[1]);
+        const unsigned cb = (unsigned)(int)fl[0].x;
+        {
+            // lane L holds field column c0 + L (FMODE 3: and c0 + 64 + L) of the row pair, clamped to the last column
+            const unsigned c0 = __builtin_amdgcn_readfirstlane(cb);
+            const unsigned lane = threadIdx.x & 63u, last = (unsigned)(fw - 1);
+            const float2 a0 = f0[min(c0 + lane, last)], a1 = f1[min(c0 + lane, last)];
+            float2 b0 = a0, b1 = a1;
+            if constexpr (FMODE == 3) b0 = f0[min(c0 + 64u + lane, last)], b1 = f1[min(c0 + 64u + lane, last)];
+            const int v[8] = {__builtin_bit_cast(int, a0.x), __builtin_bit_cast(int, a0.y), __builtin_bit_cast(int, a1.x), __builtin_bit_cast(int, a1.y),
+                              __builtin_bit_cast(int, b0.x), __builtin_bit_cast(int, b0.y), __builtin_bit_cast(int, b1.x), __builtin_bit_cast(int, b1.y)};
+            // value k (0: row 0 x, 1: row 0 y, 2: row 1 x, 3: row 1 y) of field column c0 + j (byte address 4 j)
+            auto take = [&](int addr, int k) {
+                const float lo = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(addr, v[k]));
+                if constexpr (FMODE == 3) {
+                    const float hi = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(addr, v[4 + k]));
+                    return addr >= 256 ? hi : lo;
+                }
+                return lo;
+            };
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const f32x2 lx = sx[q] - fl[q], hx = one2 - lx;
+                const int j0 = ((int)fl[q].x - (int)c0) * 4, j1 = ((int)fl[q].y - (int)c0) * 4;
+                gx[q] = pk_field_lerp(hy2, ly2, hx, lx, f32x2{take(j0, 0), take(j1, 0)}, f32x2{take(j0 + 4, 0), take(j1 + 4, 0)},
+                                      f32x2{take(j0, 2), take(j1, 2)}, f32x2{take(j0 + 4, 2), take(j1 + 4, 2)});
+                gy[q] = pk_field_lerp(hy2, ly2, hx, lx, f32x2{take(j0, 1), take(j1, 1)}, f32x2{take(j0 + 4, 1), take(j1 + 4, 1)},
+                                      f32x2{take(j0, 3), take(j1, 3)}, f32x2{take(j0 + 4, 3), take(j1 + 4, 3)});
+            }
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const f32x2 sx = pk_mul_rounded(pk_splat(rx), px[q]);
+            const f32x2 fl = pk_floor(sx), lx = sx - fl, hx = one2 - lx;
+            const unsigned xa = (unsigned)(int)fl.x, xb = (unsigned)(int)fl.y;
+            const unsigned xa1 = xa + ((int)xa < fw - 1 ? 1u : 0u), xb1 = xb + ((int)xb < fw - 1 ? 1u : 0u);
+            const float2 a0 = f0[xa], b0 = f0[xa1], c0 = f1[xa], d0 = f1[xa1];
+            const float2 a1 = f0[xb], b1 = f0[xb1], c1 = f1[xb], d1 = f1[xb1];
+            gx[q] = pk_field_lerp(hy2, ly2, hx, lx, f32x2{a0.x, a1.x}, f32x2{b0.x, b1.x}, f32x2{c0.x, c1.x}, f32x2{d0.x, d1.x});
+            gy[q] = pk_field_lerp(hy2, ly2, hx, lx, f32x2{a0.y, a1.y}, f32x2{b0.y, b1.y}, f32x2{c0.y, c1.y}, f32x2{d0.y, d1.y});
+        }
+    }
+}
+
+// One wave's row chunk of one plane kind.  B: bytes per pixel of a source plane (1; NV12 chroma 2); NP: source planes (I420 chroma 2).
+template <int KIND, int FMODE>
+__device__ __forceinline__ void yuv_warp_row(const unsigned char *__restrict__ frame, unsigned char *__restrict__ ofr, const float *__restrict__ field,
+                                             const yuv::Plane &P, unsigned n, unsigned oy, int ox0, int fh, int fw, unsigned fbytes, bool last_sample) {
+    constexpr int B = KIND == yuv::PLANE_NV12_UV ? 2 : 1, NP = KIND == yuv::PLANE_I420_UV ? 2 : 1;
+    constexpr float PAD = KIND == yuv::PLANE_Y ? 16.f : 128.f;   // BT.601 black
+    const int H = P.h, W = P.w;
+    if (FMODE < 2 && ox0 >= W) return;   // (FMODE 2 / 3: every lane fetches and serves field columns first)
+    f32x2 gx[2], gy[2];
+    yuv_field4<FMODE>(field, n, oy, ox0, W - 1, fh, fw, P.ry, P.rx, gx, gy);
+    if (ox0 >= W) return;
+    const f32x2 one2 = pk_splat(1.f);
+    unsigned off[2][4];   // byte offsets (from the frame's start, first source plane) of each pixel's tap pair in rows y0, y0 + 1
+    bool okl[4], okr[4], ok0[4], ok1[4], swp[4], out4[4];
+    f32x2 wa0[2], wb0[2], wa1[2], wb1[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const f32x2 ix = pk_fma(gx[q], pk_splat(P.kx), pk_splat(P.kx1)), iy = pk_fma(gy[q], pk_splat(P.ky), pk_splat(P.ky1));
+        const f32x2 fx = pk_floor(ix), fy = pk_floor(iy);
+        const f32x2 wx1 = ix - fx, wx0 = one2 - wx1, wy1 = iy - fy, wy0 = one2 - wy1;
+        wa0[q] = wx0 * wy0, wb0[q] = wx1 * wy0, wa1[q] = wx0 * wy1, wb1[q] = wx1 * wy1;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int i = 2 * q + e, x0 = (int)(e ? fx.y : fx.x), y0 = (int)(e ? fy.y : fy.x);
+            okl[i] = (unsigned)x0 < (unsigned)W, okr[i] = (unsigned)(x0 + 1) < (unsigned)W;
+            ok0[i] = (unsigned)y0 < (unsigned)H, ok1[i] = (unsigned)(y0 + 1) < (unsigned)H;
+            const int xs = med3_i32(x0, W - 2);
+            swp[i] = xs != x0;
+            out4[i] = !((okl[i] || okr[i]) && (ok0[i] || ok1[i]));   // x0 == -1: the right tap is the pair's left pixel; x0 == W - 1: the left tap is the pair's right one
+            const unsigned xb = (unsigned)xs * B;
+            off[0][i] = P.off0 + __umul24((unsigned)med3_i32(y0, H - 1), P.pitch) + xb;
+            off[1][i] = P.off0 + __umul24((unsigned)med3_i32(y0 + 1, H - 1), P.pitch) + xb;
+        }
+    }
+    // tap pairs: the aligned 8 bytes the pair starts in + v_alignbyte (from the frame's start, which is 4-byte aligned; the I420 V plane need
+    // not be).  Up to 6 bytes behind a pair are read and not used: only at the end of the last sample's last plane can they lie outside the
+    // caller's buffer, so a wave of the last sample in which some lane would read there takes exact 2- / 4-byte loads instead.
+    unsigned pr[NP][2][4];
+    bool exact = false;
+    if (last_sample) {
+        unsigned m = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) m = max(m, off[1][i] + (NP == 2 ? P.off1 - P.off0 : 0u));
+        exact = __builtin_amdgcn_ballot_w64((m & ~3u) + 8u > fbytes) != 0;
+    }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const unsigned shift = p ? P.off1 - P.off0 : 0u;
+        if (!exact) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const unsigned o = off[r][i] + shift;
+                    const uint2 t = *reinterpret_cast<const uint2 *>(frame + (o & ~3u));
+                    pr[p][r][i] = __builtin_amdgcn_alignbyte(t.y, t.x, o);
+                }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const unsigned o = off[r][i] + shift;
+                    pr[p][r][i] = B == 2 ? reinterpret_cast<const U8x4 *>(frame + o)->v : (unsigned)reinterpret_cast<const U8x2 *>(frame + o)->v;
+                }
+        }
+    }
+    // blend per output channel (Y: 1; NV12: U, V interleaved; I420: U plane, V plane), the BGR kernel's fma chain with black padding
+    constexpr int NCH = B * NP;
+    unsigned ow[NCH] = {};
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+        const int p = NP == 2 ? ch : 0, c = B == 2 ? ch : 0;   // source plane, byte inside a pixel (compile-time)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            float ux[2], uy[2], vx[2], vy[2];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int i = 2 * q + e;
+                const unsigned a = pr[p][0][i], b = pr[p][1][i];
+                const float al = (float)((a >> (8 * c)) & 0xffu), ar = (float)((a >> (8 * (B + c))) & 0xffu);
+                const float bl = (float)((b >> (8 * c)) & 0xffu), br = (float)((b >> (8 * (B + c))) & 0xffu);
+                const float l0 = swp[i] ? ar : al, r0 = swp[i] ? al : ar, l1 = swp[i] ? br : bl, r1 = swp[i] ? bl : br;
+                ux[e] = okl[i] && ok0[i] ? l0 : PAD, uy[e] = okr[i] && ok0[i] ? r0 : PAD;
+                vx[e] = okl[i] && ok1[i] ? l1 : PAD, vy[e] = okr[i] && ok1[i] ? r1 : PAD;
+            }
+            f32x2 r = pk_fma(f32x2{vy[0], vy[1]}, wb1[q], pk_fma(f32x2{vx[0], vx[1]}, wa1[q], pk_fma(f32x2{uy[0], uy[1]}, wb0[q],
+                                                                                                f32x2{ux[0], ux[1]} * wa0[q])));
+            // a pixel whose four taps all lie outside is black exactly (PAD times weights that sum to 1 - 1 ulp would truncate below it)
+            r.x = out4[2 * q] ? PAD : r.x, r.y = out4[2 * q + 1] ? PAD : r.y;
+            // output byte of pixel 2q + e: Y / I420 planes byte 2q + e of word 0; NV12 byte 2 (2q + e) + c of the 8 bytes
+            if constexpr (B == 2) {
+                cvt_u8_into((4 * q + c) & 3, ow[q], r.x), cvt_u8_into((4 * q + 2 + c) & 3, ow[q], r.y);
+            } else {
+                cvt_u8_into(2 * q, ow[ch], r.x), cvt_u8_into(2 * q + 1, ow[ch], r.y);
+            }
+        }
+    }
+    const bool full = ox0 + 4 <= W;   // chroma rows of width 2 mod 4: the row's last lane owns 2 pixels
+    const unsigned ob = P.off0 + oy * P.pitch + (unsigned)ox0 * B;
+    if constexpr (KIND == yuv::PLANE_Y) {
+        *reinterpret_cast<unsigned *>(ofr + ob) = ow[0];   // (4-byte aligned: w % 4 == 0)
+    } else if constexpr (KIND == yuv::PLANE_NV12_UV) {
+        unsigned *o = reinterpret_cast<unsigned *>(ofr + ob);   // (4-byte aligned: h * w and w are multiples of 4, 2 ox0 of 8)
+        o[0] = ow[0];
+        if (full) o[1] = ow[1];
+    } else {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            unsigned char *o = ofr + ob + (p ? P.off1 - P.off0 : 0u);   // (2-byte aligned only: the V plane starts at h w + h w / 4)
+            if (full) reinterpret_cast<U8x4 *>(o)->v = ow[p];
+            else reinterpret_cast<U8x2 *>(o)->v = (unsigned short)ow[p];
+        }
+    }
+}
+
+template <int LAYOUT, int FMY, int FMC>   // LAYOUT 0 NV12, 1 I420; FMY / FMC: field access mode of the Y / chroma planes
+__global__ void __launch_bounds__(256) upsample_grid_sample_yuv420_kernel(const unsigned char *__restrict__ input, const float *__restrict__ field,
+                                                                          unsigned char *__restrict__ out, yuv::Plane py, yuv::Plane pc, int fh,
+                                                                          int fw, unsigned fbytes) {
+    const unsigned rg = xcd_remap(blockIdx.x, gridDim.x);
+    const unsigned n = blockIdx.z;
+    const int ox0 = (int)(blockIdx.y * 256u + (threadIdx.x & 63u) * 4u);
+    const unsigned char *frame = input + (size_t)n * fbytes;
+    unsigned char *ofr = out + (size_t)n * fbytes;
+    const bool last = n + 1 == gridDim.z;
+    if (rg < py.nrg) {
+        const unsigned oy = __builtin_amdgcn_readfirstlane(rg * 4u + (threadIdx.x >> 6));
+        if (oy >= (unsigned)py.h || blockIdx.y * 256u >= (unsigned)py.w) return;
+        yuv_warp_row<yuv::PLANE_Y, FMY>(frame, ofr, field, py, n, oy, ox0, fh, fw, fbytes, last);
+    } else if (rg < py.nrg + pc.nrg) {
+        const unsigned oy = __builtin_amdgcn_readfirstlane((rg - py.nrg) * 4u + (threadIdx.x >> 6));
+        if (oy >= (unsigned)pc.h || blockIdx.y * 256u >= (unsigned)pc.w) return;
+        yuv_warp_row<LAYOUT == 0 ? yuv::PLANE_NV12_UV : yuv::PLANE_I420_UV, FMC>(frame, ofr, field, pc, n, oy, ox0, fh, fw, fbytes, last);
+    }
+}
+
+// field access mode for a plane of width w: 2 / 3 when a wave's 256 pixels touch at most 64 / 128 field columns, 1 when a lane's 4 touch
+// (the BGR kernel's rule, plus the two-column mode for the chroma planes and 854-wide frames), else 0
+static int yuv_fmode(float rx) {
+    if (255.f * rx + 3.f <= 63.f) return 2;
+    return 255.f * rx + 3.f <= 127.f ? 3 : 0;   // (the BGR kernel's FMODE 1, rx < 1/3, always meets one of these)
+}
+
+extern "C" int pws_upsample_grid_sample_yuv420_u8(const unsigned char *frames, const float *field, unsigned char *out, int n, int h, int w,
+                                                  int fh, int fw, int layout, int align_corners, pws_stream_t stream) {
+    PWS_REQUIRE(n >= 0 && h > 0 && w > 0 && fh > 0 && fw > 0, "pws_upsample_grid_sample_yuv420_u8: bad shape");
+    PWS_REQUIRE(layout == 0 || layout == 1, "pws_upsample_grid_sample_yuv420_u8: layout must be 0 (NV12) or 1 (I420), got %d", layout);
+    PWS_REQUIRE(h % 2 == 0 && w % 4 == 0 && h >= 2, "pws_upsample_grid_sample_yuv420_u8: h must be even and w a multiple of 4 (got %d x %d)", w, h);
+    if (n == 0) return PWS_OK;
+    PWS_REQUIRE(frames && field && out, "pws_upsample_grid_sample_yuv420_u8: NULL pointer");
+    PWS_REQUIRE(((reinterpret_cast<size_t>(frames) | reinterpret_cast<size_t>(out)) & 3) == 0,
+                "pws_upsample_grid_sample_yuv420_u8: frames and out must be 4-byte aligned");
+    PWS_REQUIRE((size_t)h * w < (1u << 29) && w < (1 << 23) && n < 65536, "pws_upsample_grid_sample_yuv420_u8: frame or batch too large");
+    const unsigned fbytes = (unsigned)((size_t)h * w * 3 / 2);
+    auto plane = [&](int ph, int pw, unsigned off0, unsigned off1, unsigned pitch) {
+        yuv::Plane p;
+        p.h = ph, p.w = pw, p.off0 = off0, p.off1 = off1, p.pitch = pitch;
+        p.ry = ph > 1 ? (float)(fh - 1) / (float)(ph - 1) : 0.f;
+        p.rx = pw > 1 ? (float)(fw - 1) / (float)(pw - 1) : 0.f;
+        p.kx = align_corners ? 0.5f * (float)(pw - 1) : 0.5f * (float)pw, p.kx1 = 0.5f * (float)(pw - 1);
+        p.ky = align_corners ? 0.5f * (float)(ph - 1) : 0.5f * (float)ph, p.ky1 = 0.5f * (float)(ph - 1);
+        p.nrg = (unsigned)((ph + 3) / 4);
+        return p;
+    };
+    const unsigned hw = (unsigned)(h * w), hc = (unsigned)(h / 2), wc = (unsigned)(w / 2);
+    const yuv::Plane py = plane(h, w, 0u, 0u, (unsigned)w);
+    const yuv::Plane pc = layout == 0 ? plane(h / 2, w / 2, hw, hw, (unsigned)w) : plane(h / 2, w / 2, hw, hw + hc * wc, wc);
+    const unsigned gx = (py.nrg + pc.nrg + 7u) & ~7u, cpr = (unsigned)((w + 255) / 256);   // (chroma rows need half the chunks: the rest return)
+    const int fmy = yuv_fmode(py.rx), fmc = yuv_fmode(pc.rx);
+    const size_t total = (size_t)n * h * w;
+    ProfScope prof(KID_UPSAMPLE_GRID_SAMPLE_U8, (double)total * 1.5 * (40.0 + 8.0), (double)total * 3.0 + 8.0 * (double)n * fh * fw,
+                   as_stream(stream));
+#define PWS_YUV_LAUNCH(L_, FY_, FC_)                                                                                                      \
+    hipLaunchKernelGGL((upsample_grid_sample_yuv420_kernel<L_, FY_, FC_>), dim3(gx, cpr, (unsigned)n), dim3(256), 0, as_stream(stream), frames, \
+                       field, out, py, pc, fh, fw, fbytes)
+#define PWS_YUV_FC(L_, FY_)                                                                                                               \
+    do {                                                                                                                                  \
+        if (fmc == 3) PWS_YUV_LAUNCH(L_, FY_, 3);                                                                                         \
+        else if (fmc == 2) PWS_YUV_LAUNCH(L_, FY_, 2);                                                                                    \
+        else PWS_YUV_LAUNCH(L_, FY_, 0);                                                                                                  \
+    } while (0)
+#define PWS_YUV_FY(L_)                                                                                                                    \
+    do {                                                                                                                                  \
+        if (fmy == 2) PWS_YUV_FC(L_, 2);                                                                                                  \
+        else if (fmy == 3) PWS_YUV_FC(L_, 3);                                                                                             \
+        else PWS_YUV_FC(L_, 0);                                                                                                           \
+    } while (0)
+    if (layout == 0) PWS_YUV_FY(0);
+    else PWS_YUV_FY(1);
+#undef PWS_YUV_FY
+#undef PWS_YUV_FC
+#undef PWS_YUV_LAUNCH
+    return check_launch("upsample_grid_sample_yuv420_kernel");
+}

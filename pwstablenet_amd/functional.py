@@ -159,6 +159,51 @@ def upsample_grid_sample_u8(frames_hwc, field, swap_rb=False, align_corners=None
     return out
 
 
+PIXEL_FORMATS = ("bgr24", "nv12", "i420")
+YUV420_LAYOUT = {"nv12": 0, "i420": 1}
+
+
+def yuv420_layout(pixel_format):
+    """0 (NV12) / 1 (I420) for a 4:2:0 pixel format; ValueError for anything else (P010, 4:2:2, 4:4:4, full range and BT.709 are not
+    supported)."""
+    if pixel_format not in YUV420_LAYOUT:
+        raise ValueError("pixel_format must be one of %s for 4:2:0 frames, got %r (8-bit BT.601 limited-range NV12 / I420 only)"
+                         % (tuple(YUV420_LAYOUT), pixel_format))
+    return YUV420_LAYOUT[pixel_format]
+
+
+def yuv420_shape(frames, pixel_format, w_multiple=4):
+    """(T, H, W) of packed 4:2:0 frames (T, H * 3 // 2, W) uint8; ValueError unless H and W are even and W a multiple of ``w_multiple``."""
+    yuv420_layout(pixel_format)
+    if frames.dim() != 3 or frames.dtype != torch.uint8:
+        raise ValueError("%s frames must be uint8 (T, H * 3 // 2, W), got %s %s" % (pixel_format, frames.dtype, tuple(frames.shape)))
+    t, ph, w = frames.shape
+    if ph % 3 != 0 or ph == 0:
+        raise ValueError("%s frames: packed height %d is not H * 3 // 2 of an even H" % (pixel_format, ph))
+    h = ph // 3 * 2
+    if w % 2 != 0 or w % w_multiple != 0:
+        raise ValueError("%s frames: width %d must be even and a multiple of %d" % (pixel_format, w, w_multiple))
+    return t, h, w
+
+
+def upsample_grid_sample_yuv420(frames, field, pixel_format, align_corners=None, out=None):
+    """upsample_grid_sample_u8 for packed 4:2:0 frames, YUV in and YUV out: ``frames`` (N, H * 3 // 2, W) uint8 in ``pixel_format``
+    "nv12" or "i420"; every plane is warped by ``field`` (N, fh, fw, 2) resized (align_corners=True) to the plane's own size, taps outside
+    a plane read BT.601 black (16 in Y, 128 in U and V), the fp32 blend is truncated.  H even, W % 4 == 0.  One kernel launch."""
+    A.require_cuda(field)
+    A.require_cuda(frames, dtype=torch.uint8)
+    layout = yuv420_layout(pixel_format)
+    n, h, w = yuv420_shape(frames, pixel_format)
+    if field.dim() != 4 or field.shape[0] != n or field.shape[3] != 2:
+        raise ValueError("upsample_grid_sample_yuv420: field must be (%d, fh, fw, 2), got %s" % (n, tuple(field.shape)))
+    frames, field = frames.contiguous(), field.contiguous()
+    if out is None:
+        out = torch.empty_like(frames)
+    A.check(A.lib().pws_upsample_grid_sample_yuv420_u8(A.ptr(frames), A.ptr(field), A.ptr(out), n, h, w, field.shape[1], field.shape[2], layout,
+                                                       _ac(align_corners), A.current_stream()), "pws_upsample_grid_sample_yuv420_u8")
+    return out
+
+
 def adam_step_(p, g, m, v, lr, beta1, beta2, eps, step):
     """In-place fused Adam on flat fp32 CUDA buffers."""
     A.require_cuda(p, g, m, v)

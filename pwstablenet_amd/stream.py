@@ -64,6 +64,70 @@ def area_resize(frames_hwc, size, swap_rb=False):
     return out
 
 
+def window_planes_yuv(frames, pixel_format, size=256, out=None):
+    """window_planes of the BGR frames ``cv2.cvtColor(frame, COLOR_YUV2BGR_NV12 / COLOR_YUV2BGR_I420)`` would give, straight from packed
+    4:2:0 frames (T, H * 3 // 2, W) uint8 in one launch (BT.601 limited range, OpenCV 4.x's 8-bit fixed point): the same planes bit for
+    bit, so a YUV clip gets the fields of its BGR decode.  H and W even.  -> (T, size, size) float32."""
+    A.require_cuda(frames, dtype=torch.uint8)
+    layout = PF.yuv420_layout(pixel_format)
+    t, h, w = PF.yuv420_shape(frames, pixel_format, w_multiple=2)
+    frames = frames.contiguous()
+    if out is None:
+        out = torch.empty((t, size, size), device=frames.device, dtype=torch.float32)
+    A.require_cuda(out)
+    if tuple(out.shape) != (t, size, size) or not out.is_contiguous():
+        raise ValueError("window_planes_yuv: out must be a contiguous (T, %d, %d) float32 tensor" % (size, size))
+    A.check(A.lib().pws_gray_area_yuv420_u8(A.ptr(frames), A.ptr(out), t, h, w, size, size, 1, layout, A.current_stream()),
+            "pws_gray_area_yuv420_u8")
+    return out
+
+
+def _yuv_planes(x, h, w, pixel_format):
+    """Views of the planes of packed 4:2:0 frames x (T, h * 3 // 2, w): [Y (T, h, w), UV (T, h/2, w)] for NV12, [Y, U (T, h/2, w/2),
+    V (T, h/2, w/2)] for I420."""
+    t = x.shape[0]
+    y = x[:, :h]
+    if pixel_format == "nv12":
+        return [y, x[:, h:]]
+    c = x.reshape(t, -1)[:, h * w:].reshape(t, 2, h // 2, w // 2)
+    return [y, c[:, 0], c[:, 1]]
+
+
+def area_resize_yuv(frames, pixel_format, size):
+    """area_resize for packed 4:2:0 frames, plane by plane: Y to (height, width), the chroma to (height/2, width/2) (NV12's interleaved UV
+    as a 2-channel image, I420's U and V as 1-channel images); ``size`` = (width, height), both even.  (T, H * 3 // 2, W) uint8 ->
+    (T, height * 3 // 2, width)."""
+    A.require_cuda(frames, dtype=torch.uint8)
+    PF.yuv420_layout(pixel_format)
+    t, h, w = PF.yuv420_shape(frames, pixel_format, w_multiple=2)
+    ow, oh = int(size[0]), int(size[1])
+    if ow % 2 or oh % 2 or not (0 < ow <= w and 0 < oh <= h):
+        raise ValueError("area_resize_yuv: output size %s must be even and within the %d x %d source" % (tuple(size), w, h))
+    frames = frames.contiguous()
+    out = torch.empty((t, oh * 3 // 2, ow), device=frames.device, dtype=torch.uint8)
+    fs, os_ = frames[0].numel(), out[0].numel()
+    geo = [(1, h, w, oh, ow)] + ([(2, h // 2, w // 2, oh // 2, ow // 2)] if pixel_format == "nv12" else [(1, h // 2, w // 2, oh // 2, ow // 2)] * 2)
+    for (c, ph, pw, qh, qw), src, dst in zip(geo, _yuv_planes(frames, h, w, pixel_format), _yuv_planes(out, oh, ow, pixel_format)):
+        A.check(A.lib().pws_area_resize_plane_u8(A.ptr(src), fs, A.ptr(dst), os_, t, ph, pw, c, qh, qw, A.current_stream()),
+                "pws_area_resize_plane_u8")
+    return out
+
+
+def _yuv_crop(x, h, w, pixel_format, cy0, cy1, cx0, cx1):
+    """The (even) window [cy0, cy1) x [cx0, cx1) of packed 4:2:0 frames, packed again on the device: Y [cy0:cy1, cx0:cx1], chroma
+    [cy0/2:cy1/2, cx0/2:cx1/2]."""
+    ch, cw = cy1 - cy0, cx1 - cx0
+    out = torch.empty((x.shape[0], ch * 3 // 2, cw), device=x.device, dtype=torch.uint8)
+    src, dst = _yuv_planes(x, h, w, pixel_format), _yuv_planes(out, ch, cw, pixel_format)
+    dst[0].copy_(src[0][:, cy0:cy1, cx0:cx1])
+    if pixel_format == "nv12":
+        dst[1].copy_(src[1][:, cy0 // 2:cy1 // 2, cx0:cx1])   # (U V interleaved: chroma columns cx0/2 .. are bytes cx0 ..)
+    else:
+        for k in (1, 2):
+            dst[k].copy_(src[k][:, cy0 // 2:cy1 // 2, cx0 // 2:cx1 // 2])
+    return out
+
+
 def _field_homography(field, h0, w0, m_out, bounds_out, pts_out=None):
     A.check(A.lib().pws_field_homography(A.ptr(field), field.shape[0], field.shape[1], field.shape[2], h0, w0, A.ptr(m_out),
                                          A.ptr(bounds_out), A.ptr(pts_out), A.current_stream()), "pws_field_homography")
@@ -172,13 +236,18 @@ class VideoStabilizer:
             out[s:e].copy_(self.net(_windows(gp, s, e - s, self.period), False))
 
     @torch.no_grad()
-    def run(self, gray, frames, halo_left=0, halo_right=0, out=None):
+    def run(self, gray, frames, halo_left=0, halo_right=0, out=None, pixel_format="bgr24"):
         """gray: (T + halo_left + halo_right, 256, 256) float32 in [-1,1] (``x/255*2-1`` as the reference, :650) for the T
         frames to stabilise plus whatever real neighbours exist on either side (up to period//2); frames: (T, C, H, W)
         float32 0..255, or (T, H, W, 3) uint8 as OpenCV delivers them (then the warp runs in the uint8 kernel: 4x less
         PCIe and HBM traffic per frame, ``self.swap_rb`` applies the reference's BGR->RGB).  Tensors may be on the device or in
-        (pinned) host memory.  Returns a tensor of the frames' shape and dtype on the inputs' side."""
+        (pinned) host memory.  Returns a tensor of the frames' shape and dtype on the inputs' side.
+        pixel_format = "nv12" / "i420": frames are packed 4:2:0 (T, H * 3 // 2, W) uint8 (H even, W % 4 == 0), warped plane by plane in
+        the fused YUV kernel (functional.upsample_grid_sample_yuv420: BT.601 black padding); ``self.swap_rb`` does not apply."""
         half = self.period // 2
+        yuv = pixel_format != "bgr24"
+        if yuv:
+            PF.yuv420_shape(frames, pixel_format)
         if not (0 <= halo_left <= half and 0 <= halo_right <= half):
             raise ValueError("halo must be within [0, %d]" % half)
         T = frames.shape[0]
@@ -216,7 +285,9 @@ class VideoStabilizer:
                 compute.wait_event(ev)
             win = _windows(gp, s, e - s, self.period)
             field = self.net(win, False)
-            if cur.dtype == torch.uint8:
+            if yuv:
+                warped = PF.upsample_grid_sample_yuv420(cur.contiguous(), field, pixel_format, align_corners=self.align_corners)
+            elif cur.dtype == torch.uint8:
                 warped = PF.upsample_grid_sample_u8(cur.contiguous(), field, swap_rb=self.swap_rb, align_corners=self.align_corners)
             else:
                 warped = PF.upsample_grid_sample(cur.contiguous(), field, align_corners=self.align_corners)
@@ -237,7 +308,7 @@ class VideoStabilizer:
 
     @torch.no_grad()
     def run_video(self, frames, chunk=32, half_size_output=False, frames_are_rgb=False, halo_left=0, halo_right=0, crop=None,
-                  output_size=None, in_flight=1):
+                  output_size=None, in_flight=1, pixel_format="bgr24"):
         """The whole device side of the reference's ``process()`` loop for one decoded clip: ``frames`` (T, H, W, 3) uint8 as
         cv2 delivers them, in (pinned) host memory or on the device.  Per chunk of ``chunk`` frames: H2D on a side stream,
         gray + INTER_AREA 256x256 window planes computed there from the uploaded frames (so nothing but the uint8 frames
@@ -263,7 +334,13 @@ class VideoStabilizer:
         again (device-resident ones are read in place) and runs only the warp, the output resize and the crop.  Same frames bit for bit as
         crop=auto_crop_window(bounds, (H, W), output (height, width), period).  Needs the whole clip (no halos) and a source of at least
         600 x 300.
-        Returns (T, H, W, 3) -- or (T, H/2, W/2, 3) / (T, height, width, 3), or the crop window of it -- uint8 on the inputs' side."""
+        pixel_format = "nv12" / "i420": ``frames`` are packed 4:2:0 (T, H * 3 // 2, W) uint8 as decoders hand them over (H even, W % 4 == 0),
+        YUV in and YUV out in the same layout: the window planes are those of the frames' BGR decode (window_planes_yuv: the same fields
+        bit for bit), every plane is warped by the field (functional.upsample_grid_sample_yuv420: BT.601 black padding) and resized plane by
+        plane (area_resize_yuv).  Output sizes and crop windows must be even; crop="auto" rounds the BGR path's window inward to even.
+        frames_are_rgb=True is an error there, and ``swap_rb`` is ignored.
+        Returns (T, H, W, 3) -- or (T, H/2, W/2, 3) / (T, height, width, 3), or the crop window of it -- uint8 on the inputs' side; for YUV
+        (T, oh * 3 // 2, ow) of the output (or crop window) size oh x ow."""
         half = self.period // 2
         if not (0 <= halo_left <= half and 0 <= halo_right <= half):
             raise ValueError("halo must be within [0, %d]" % half)
@@ -273,7 +350,13 @@ class VideoStabilizer:
             raise ValueError("frames holds %d frames, fewer than the halos %d + %d" % (n_all, halo_left, halo_right))
         on_host = not frames.is_cuda
         dev = self.device
-        h, w = frames.shape[1], frames.shape[2]
+        yuv = pixel_format != "bgr24"
+        if yuv:
+            _, h, w = PF.yuv420_shape(frames, pixel_format)
+            if frames_are_rgb:
+                raise ValueError("run_video: frames_are_rgb has no meaning for %s frames" % pixel_format)
+        else:
+            h, w = frames.shape[1], frames.shape[2]
         if output_size is not None and half_size_output:
             raise ValueError("run_video: give output_size or half_size_output, not both")
         if output_size is not None:
@@ -282,6 +365,8 @@ class VideoStabilizer:
                 raise ValueError("run_video: output_size %s must not exceed the %d x %d source (INTER_AREA down-scaling)" % (tuple(output_size), w, h))
         else:
             oh, ow = (h // 2, w // 2) if half_size_output else (h, w)
+        if yuv and (oh % 2 or ow % 2):
+            raise ValueError("run_video: the %s output size %d x %d must be even" % (pixel_format, ow, oh))
         auto = isinstance(crop, str)
         if auto:
             if crop != "auto":
@@ -300,10 +385,12 @@ class VideoStabilizer:
                 cx0, cx1, cy0, cy1 = int(crop[0]) + th, int(crop[1]) - th, int(crop[2]) + th, int(crop[3]) - th
                 if not (0 <= cx0 < cx1 <= ow and 0 <= cy0 < cy1 <= oh):
                     raise ValueError("crop window x [%d, %d) y [%d, %d) does not lie inside the %d x %d output frame" % (cx0, cx1, cy0, cy1, ow, oh))
+                if yuv and (cx0 | cx1 | cy0 | cy1) & 1:
+                    raise ValueError("crop window x [%d, %d) y [%d, %d) of %s frames must have even edges" % (cx0, cx1, cy0, cy1, pixel_format))
             return cy0, cy1, cx0, cx1
 
         def alloc_out():
-            oshape = (T, cy1 - cy0, cx1 - cx0, 3)
+            oshape = (T, (cy1 - cy0) * 3 // 2, cx1 - cx0) if yuv else (T, cy1 - cy0, cx1 - cx0, 3)
             return torch.empty(oshape, dtype=torch.uint8, pin_memory=True) if on_host else torch.empty(oshape, dtype=torch.uint8, device=dev)
         cy0, cy1, cx0, cx1 = crop_window(None if auto else crop)
         out = None if auto and T > 0 else alloc_out()
@@ -341,19 +428,28 @@ class VideoStabilizer:
             s, e = chunks[c]
             with torch.cuda.stream(up):
                 buf = frames[s:e].to(dev, non_blocking=True) if on_host else frames[s:e]
-                window_planes(buf, 256, frames_are_rgb, out=gray_all[s:e])
+                if yuv:
+                    window_planes_yuv(buf, pixel_format, 256, out=gray_all[s:e])
+                else:
+                    window_planes(buf, 256, frames_are_rgb, out=gray_all[s:e])
                 ev = torch.cuda.Event()
                 ev.record(up)
             return buf, ev
 
         def finish(warped, buf, s, e, lane):
             """output resize + crop of the warped core frames s .. e-1 (output positions) on `lane`, and their way to `out`"""
-            if half_size_output:
-                warped = area_half(warped)
-            elif output_size is not None and (oh, ow) != (h, w):
-                warped = area_resize(warped, (ow, oh))
-            if crop is not None:
-                warped = warped[:, cy0:cy1, cx0:cx1, :].contiguous()   # packed on the device: only the window crosses PCIe
+            if yuv:
+                if (oh, ow) != (h, w):
+                    warped = area_resize_yuv(warped, pixel_format, (ow, oh))
+                if crop is not None:
+                    warped = _yuv_crop(warped, oh, ow, pixel_format, cy0, cy1, cx0, cx1)   # packed on the device: only the window crosses PCIe
+            else:
+                if half_size_output:
+                    warped = area_half(warped)
+                elif output_size is not None and (oh, ow) != (h, w):
+                    warped = area_resize(warped, (ow, oh))
+                if crop is not None:
+                    warped = warped[:, cy0:cy1, cx0:cx1, :].contiguous()   # packed on the device: only the window crosses PCIe
             if on_host:
                 buf.record_stream(lane)
                 done = torch.cuda.Event()
@@ -387,7 +483,7 @@ class VideoStabilizer:
                         self._fields(gray_all[cs - hl:ce + hr], hl, hr, fields[cs:ce])
                         _field_homography(fields[cs:ce], h, w, hom[cs:ce], bounds[cs:ce])
                         continue
-                    warped = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr)
+                    warped = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr, pixel_format=pixel_format)
                     finish(warped, buf, cs - halo_left, ce - halo_left, lane)
         finally:
             if restore is not None:
@@ -397,6 +493,11 @@ class VideoStabilizer:
                 mod.enable_graph(restore[0], restore[1], per_stream=restore[2])
         if auto:
             crop = auto_crop_window(bounds, (h, w), (oh, ow), self.period)   # (the copy to the host waits for pass 1)
+            if yuv:   # the BGR path's window, rounded inward to even edges
+                x0, x1, y0, y1 = int(crop[0]), int(crop[1]), int(crop[2]), int(crop[3])
+                crop = (x0 + (x0 & 1), x1 - (x1 & 1), y0 + (y0 & 1), y1 - (y1 & 1))
+                if not (crop[1] > crop[0] and crop[3] > crop[2]):
+                    raise ValueError("run_video: the even crop window x [%d, %d) y [%d, %d) is empty" % crop)
             cy0, cy1, cx0, cx1 = crop_window(crop)
             out = alloc_out()
             # pass 2: warp + output resize + crop with the kept fields; chunk k+1 uploads while chunk k computes
@@ -417,7 +518,10 @@ class VideoStabilizer:
                     nxt = fetch(c + 1)
                 if ev is not None:
                     compute.wait_event(ev)
-                warped = PF.upsample_grid_sample_u8(buf.contiguous(), fields[s:e], swap_rb=self.swap_rb, align_corners=self.align_corners)
+                if yuv:
+                    warped = PF.upsample_grid_sample_yuv420(buf.contiguous(), fields[s:e], pixel_format, align_corners=self.align_corners)
+                else:
+                    warped = PF.upsample_grid_sample_u8(buf.contiguous(), fields[s:e], swap_rb=self.swap_rb, align_corners=self.align_corners)
                 finish(warped, buf, s, e, compute)
         if on_host:
             down.synchronize()
