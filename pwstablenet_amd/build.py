@@ -22,7 +22,7 @@ def source_hash():
     profiles/ carry it (`_meta.source_hash`), and bench.py only quotes counter-derived figures whose hash matches the build."""
     import hashlib
     h = hashlib.sha256()
-    files = sorted(SOURCES + ["common.h", "conv_common.h", "netg_pack.h"])
+    files = sorted(SOURCES + ["common.h", "conv_common.h", "experiments.h", "netg_pack.h"])
     for f in files + [os.path.join("..", "..", "include", "pwstable.h")]:
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(f.encode() + b"\0" + fh.read() + b"\0")
@@ -30,7 +30,7 @@ def source_hash():
 
 
 def _deps():
-    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "netg_pack.h"), os.path.join(HERE, "..", "include", "pwstable.h"), os.path.abspath(__file__)]
+    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "experiments.h"), os.path.join(CSRC, "netg_pack.h"), os.path.join(HERE, "..", "include", "pwstable.h"), os.path.abspath(__file__)]
     return max(os.path.getmtime(h) for h in hdrs)
 
 

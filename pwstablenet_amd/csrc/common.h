@@ -6,6 +6,7 @@
 #include <cstdio>
 
 #include "../../include/pwstable.h"
+#include "experiments.h"
 
 namespace pws {
 
@@ -90,7 +91,6 @@ struct DeterministicScope {
 extern bool g_two_queues;
 extern int g_math;  // PWS_OPT_MATH
 extern int g_store;  // PWS_OPT_STORE (effective only with PWS_MATH_BF16)
-extern int g_experiment;  // PWS_OPT_EXPERIMENT: selects measured kernel variants (tools/*_bench.py); 0 = product default
 extern bool g_prof_on;
 extern thread_local int g_prof_tag;  // the layer a launch belongs to, per calling thread
 bool prof_begin(int kernel_id, double flops, double bytes, hipStream_t st);  // false: nothing recorded (the stream is being captured)

@@ -611,8 +611,8 @@ static int launch_bf_io(ConvKParams &kp, hipStream_t st) {
     const dim3 grid = conv_grid(kp, C::BN);
 #ifdef PWS_INTERFERENCE_PROBE   // diagnostic build only (round 5: the six probe instantiations are no longer part of the shipped library; -DPWS_INTERFERENCE_PROBE brings them back for tools/probes/kernel_victim_probe.py)
     if constexpr (IO16 && C::KS == 3 && C::TH == 16 && C::TW == 16 && C::STRIDE == 1 && C::SUBPIX == 0) {   // the probe variants of this one tile (see conv_bf16_kernel)
-        switch (g_experiment) {
-#define PWS_BF_ABL_CASE(k) case 2100 + k: (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_bf16_kernel<C, IO16, k>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES); hipLaunchKernelGGL((conv_bf16_kernel<C, IO16, k>), grid, dim3(C::THREADS), C::LDS_BYTES, st, kp); return check_launch("conv_bf16_kernel");
+        switch (exp_mask(EXP_BF16_PROBE, 64)) {
+#define PWS_BF_ABL_CASE(k) case k: (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_bf16_kernel<C, IO16, k>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES); hipLaunchKernelGGL((conv_bf16_kernel<C, IO16, k>), grid, dim3(C::THREADS), C::LDS_BYTES, st, kp); return check_launch("conv_bf16_kernel");
             PWS_BF_ABL_CASE(1) PWS_BF_ABL_CASE(14) PWS_BF_ABL_CASE(16) PWS_BF_ABL_CASE(30) PWS_BF_ABL_CASE(32) PWS_BF_ABL_CASE(46)
         default: break;
         }
@@ -706,13 +706,12 @@ static const TileChoice kBCT4Deep[] = {bchoice<B_CT4_D8>(), bchoice<B_CT4_D4>(),
 static const TileChoice kBSP3Deep[] = {bchoice<B_SP3_D8>(), bchoice<B_SP3_D4>(), bchoice<B_SP3_D2>()};
 
 // the deep tile of this launch, or nullptr: the map is exactly 8 x 8 / 4 x 4 / 2 x 2, the batch fills the tile's samples, and K is
-// long enough for the K split to give every CU work (PWS_OPT_EXPERIMENT 95: never, 96: whenever the map fits)
+// long enough for the K split to give every CU work (PWS_OPT_EXPERIMENT 96: whenever the map fits)
 static const TileChoice *deep_tile(const TileChoice *deep, const ConvKParams &kp, int cin_total) {
-    if (g_experiment == 95) return nullptr;
     const int idx = (kp.LH == 8 && kp.LW == 8) ? 0 : ((kp.LH == 4 && kp.LW == 4) ? 1 : ((kp.LH == 2 && kp.LW == 2) ? 2 : -1));
     if (idx < 0) return nullptr;
     const TileChoice &c = deep[idx];
-    if (g_experiment == 96) return &c;
+    if (exp_is(EXP_DEEP_TILE_ALWAYS)) return &c;
     // measured at batch 64 (tools/conv_bench.py, bf16 storage): 8 x 8: 512 -> 512 3x3 51.5 -> 43.7 us; 4 x 4: transposed 1024 -> 512 47.7 ->
     // 43.9 us but 3x3 512 -> 512 26.4 -> 27.2 us; 2 x 2: 16.7 -> 21.0 us -- the deep launches are bound by their chunk-serial K loop and
     // the K-split reduce, not by weight re-reads: only the two winning cases are taken

@@ -112,7 +112,7 @@ __device__ __forceinline__ void conv_block_coords(const ConvKParams &p, bool sub
     }
 }
 static inline dim3 conv_grid(ConvKParams &kp, int bn) {
-    kp.cls_inner = kp.nclasses == 4 && kp.ntiles % 8 == 0 && g_experiment != 9 ? 1 : 0;
+    kp.cls_inner = kp.nclasses == 4 && kp.ntiles % 8 == 0 ? 1 : 0;
     const unsigned gy = (unsigned)((kp.cout + bn - 1) / bn);
     return kp.cls_inner ? dim3(kp.ntiles * 4, gy, (unsigned)kp.ksplit) : dim3(kp.ntiles, gy, (unsigned)(kp.nclasses * kp.ksplit));
 }

@@ -288,7 +288,7 @@ __global__ void __launch_bounds__(FT_THREADS, 3) conv_first_kernel(const FirstPa
 // to 32 channels with 16-byte aligned rows, whole 8 x 32 tiles, an even cout / out_ld, enough units for half the chip
 // (PWS_OPT_EXPERIMENT 25: never; 29: also for the tests' small launches).  Returns 1 when not covered.
 int conv_first_try(const ConvKParams &kp, hipStream_t st, const ProfInfo &pi) {
-    if (kp.io_bf16 || kp.ndst != 0 || kp.nsrc != 1 || g_experiment == 25) return 1;
+    if (kp.io_bf16 || kp.ndst != 0 || kp.nsrc != 1 || exp_is(EXP_FIRST_MFMA)) return 1;
     if (kp.src_c[0] > FT_CP || kp.cin_pad != FT_CP || kp.W % FT_TW != 0 || kp.H % FT_TH != 0 || kp.cout % 4 != 0 || kp.out_ld % 2 != 0) return 1;
     const size_t sstride = kp.src_ld[0] ? (size_t)kp.src_ld[0] : (size_t)kp.src_c[0] * kp.H * kp.W;
     if ((reinterpret_cast<size_t>(kp.src_ptr[0]) & 15) || sstride % 4 != 0 || (reinterpret_cast<size_t>(kp.out) & 7) ||
@@ -304,7 +304,7 @@ int conv_first_try(const ConvKParams &kp, hipStream_t st, const ProfInfo &pi) {
     p.tiles_x = kp.W / FT_TW, p.tiles_y = kp.H / FT_TH;
     p.ncob = (unsigned)((kp.cout + 63) / 64);
     p.nunits = (unsigned)(p.tiles_x * p.tiles_y) * (unsigned)kp.N * p.ncob;
-    p.ablate = g_experiment >= 1100 && g_experiment < 1116 ? g_experiment - 1100 : 0;
+    p.ablate = exp_mask(EXP_FIRST_ABLATE, 16);
     static PerDeviceInt ncu_dev;
     int &ncu = ncu_dev.cur();
     if (ncu == 0) {
@@ -312,7 +312,7 @@ int conv_first_try(const ConvKParams &kp, hipStream_t st, const ProfInfo &pi) {
         hipDeviceProp_t prop;
         ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
     }
-    if (p.nunits < (unsigned)(ncu / 2) && g_experiment != 29) return 1;
+    if (p.nunits < (unsigned)(ncu / 2) && !exp_is(EXP_FIRST_SMALL)) return 1;
     static PerDeviceFlag attr_set_dev;
     bool &attr_set = attr_set_dev.cur();   // hipFuncSetAttribute acts on the CURRENT device's function object
     if (!attr_set) {
@@ -324,7 +324,7 @@ int conv_first_try(const ConvKParams &kp, hipStream_t st, const ProfInfo &pi) {
         attr_set = true;
     }
     const unsigned grid = p.nunits < (unsigned)ncu ? p.nunits : (unsigned)ncu;   // one persistent workgroup per CU
-    if (g_experiment == 1200) {   // measurement aid (tools/first_ablate.sh): the shader clock the chip holds inside this kernel
+    if (exp_is(EXP_FIRST_CLOCK)) {   // measurement aid (tools/first_ablate.sh): the shader clock the chip holds inside this kernel
         static unsigned long long *clk = nullptr;
         if (!clk && hipHostMalloc(&clk, 2 * 1024 * sizeof(unsigned long long)) != hipSuccess) return PWS_EHIP;
         p.clk = clk;

@@ -351,7 +351,7 @@ __global__ void __launch_bounds__(W5_THREADS, 2) wino5_first_kernel(const Wino5P
 // 16-byte aligned rows, exactly 64 output channels, whole 8 x 16 units, transformed weights given (pws_conv_args.w_wring), enough units for
 // the chip (PWS_OPT_EXPERIMENT 26: never; 30: also for the tests' small launches).  Returns 1 when not covered (conv_first_kernel is next).
 int wino5_first_try(const ConvKParams &kp, const float *u, hipStream_t st, const ProfInfo &pi) {
-    if (!u || kp.io_bf16 || kp.ndst != 0 || kp.nsrc != 1 || g_experiment == 26 || g_experiment == 25) return 1;
+    if (!u || kp.io_bf16 || kp.ndst != 0 || kp.nsrc != 1 || exp_is(EXP_FIRST_NO_WINO) || exp_is(EXP_FIRST_MFMA)) return 1;
     if (kp.src_c[0] > 32 || kp.cin_pad != 32 || kp.cout != 64 || kp.W % (2 * W5_TC) != 0 || kp.H % (2 * W5_TR) != 0 || kp.out_ld % 4 != 0) return 1;
     const size_t sstride = kp.src_ld[0] ? (size_t)kp.src_ld[0] : (size_t)kp.src_c[0] * kp.H * kp.W;
     if ((reinterpret_cast<size_t>(kp.src_ptr[0]) & 15) || sstride % 4 != 0 || (reinterpret_cast<size_t>(kp.out) & 15) ||
@@ -363,7 +363,7 @@ int wino5_first_try(const ConvKParams &kp, const float *u, hipStream_t st, const
     p.u = u, p.bias = kp.bias, p.act = kp.act, p.out = static_cast<float *>(kp.out), p.out_ld = kp.out_ld;
     p.tiles_x = kp.W / (2 * W5_TC), p.tiles_y = kp.H / (2 * W5_TR);
     p.nunits = (unsigned)(p.tiles_x * p.tiles_y) * (unsigned)kp.N;
-    p.ablate = g_experiment >= 1300 && g_experiment < 1364 ? g_experiment - 1300 : 0;
+    p.ablate = exp_mask(EXP_WINO5_ABLATE, 64);
     static PerDeviceInt ncu_dev;
     int &ncu = ncu_dev.cur();
     if (ncu == 0) {
@@ -371,7 +371,7 @@ int wino5_first_try(const ConvKParams &kp, const float *u, hipStream_t st, const
         hipDeviceProp_t prop;
         ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
     }
-    if (p.nunits < (unsigned)(2 * ncu) && g_experiment != 30) return 1;   // a unit is short (8 k-steps): the pipeline wants a few per workgroup
+    if (p.nunits < (unsigned)(2 * ncu) && !exp_is(EXP_WINO5_SMALL)) return 1;   // a unit is short (8 k-steps): the pipeline wants a few per workgroup
     static PerDeviceFlag attr_set_dev;
     bool &attr_set = attr_set_dev.cur();   // hipFuncSetAttribute acts on the CURRENT device's function object
     if (!attr_set) {

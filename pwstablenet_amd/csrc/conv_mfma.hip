@@ -367,7 +367,7 @@ int conv_bf16_dgrad(int kind, ConvKParams &kp, int cout_f, float *ws, size_t ws_
 // direct fp32 kernel (conv_mfma_kernel), so that the whole-network error can be attributed family by family.  Bits: 1 = first layer (no
 // F(2x2,5x5), no planar-LDS kernel), 2 = the 3x3 stride-1 Winograd kernels, 4 = the transposed layers' F(2x2,2x2), 8 = conv_ringf_kernel,
 // 16 = conv_skinny_kernel.  Measurement only: nothing in the product sets it.
-static inline bool ledger_direct(int bit) { return g_experiment >= 3000 && g_experiment < 3032 && ((g_experiment - 3000) & bit) != 0; }
+static inline bool ledger_direct(int bit) { return (exp_mask(EXP_PARITY_LEDGER, 32) & bit) != 0; }
 int conv_ringf_try(int kind, const ConvKParams &kp, hipStream_t st, const ProfInfo &pi);   // conv_ring_f32.hip; 1 = not covered
 int conv_first_try(const ConvKParams &kp, hipStream_t st, const ProfInfo &pi);             // conv_first.hip; 1 = not covered
 int wino5_first_try(const ConvKParams &kp, const float *u, hipStream_t st, const ProfInfo &pi);   // conv_first_wino.hip; 1 = not covered

@@ -80,9 +80,9 @@ struct RingParams {
 #ifdef PWS_RING_TIMERS
     unsigned long long *timers;   // [workgroup][matrix wave][8]
 #endif
-    int ablate;           // measurement only (PWS_OPT_EXPERIMENT 41..48): 1 = the DMA pieces fetch nothing after the first groups,
+    int ablate;           // measurement only (EXP_RING_ABLATE + mask): 1 = the DMA pieces fetch nothing after the first groups,
                           // 8 = weight pieces only for a workgroup's first unit (what resident weights would save: 5.5 % at 64 -> 64 @256^2),
-                          // 2 = no matrix phase, 4 = no epilogue -- results are meaningless, only the timing is read
+                          // 2 = no matrix phase, 4 = no epilogue, 16 = no act' loads -- results are meaningless, only the timing is read
 };
 
 // MT_: 32-pixel operand rows per matrix wave.  2: eight matrix waves (two per SIMD), each 64 pixels x 64 channels -- every matrix instruction
@@ -909,7 +909,7 @@ static int ring_launch_tile(int pix, int tw, RingParams &rp, hipStream_t st) {
         return 1;
     }
     if constexpr (MODE == RM_K3S1 || MODE == RM_CT4 || MODE == RM_K4S2)
-        if (tw == 32 && g_experiment != 105 && !(g_experiment == 106 && DG) && !(g_experiment == 107 && !DG)) return ring_launch<RgCfg<MODE, 16, 32, 1, MODE == RM_K3S1 ? 2 : 3, 4>, DG, SG>(rp, st);   // (A/B: 105 = the 8-wave kernel, 106 / 107 = for the data gradients / the forwards only)
+        if (tw == 32 && !exp_is(EXP_RING_8WAVE)) return ring_launch<RgCfg<MODE, 16, 32, 1, MODE == RM_K3S1 ? 2 : 3, 4>, DG, SG>(rp, st);   // (EXP_RING_8WAVE: the 8-wave kernel)
     if (tw == 32) return ring_launch<RgCfg<MODE, 16, 32, 1, MODE == RM_K3S1 ? 2 : 3>, DG, SG>(rp, st);
     if (tw == 16) return ring_launch<RgCfg<MODE, 16, 16, 2, 2>, DG, SG>(rp, st);
     if constexpr (MODE != RM_K3S1) return ring_launch<RgCfg<MODE, 8, 8, 8, 2>, DG, SG>(rp, st);
@@ -920,9 +920,9 @@ static int ring_launch_tile(int pix, int tw, RingParams &rp, hipStream_t st) {
 // is covered: bf16 storage with 16-byte epilogue stores, every source a multiple of 32 channels, a logical map of at least
 // 16 x 32 pixels and enough units to give every CU one.  Returns 1 when not covered (the caller runs conv_bf16_kernel).
 int conv_ring_try(int kind, bool dgrad, const ConvKParams &kp, hipStream_t st, const ProfInfo &pi) {
-    if (!kp.io_bf16 || !kp.epi16 || g_experiment == 20) return 1;
+    if (!kp.io_bf16 || !kp.epi16 || exp_is(EXP_RING_OFF)) return 1;
 #ifdef PWS_INTERFERENCE_PROBE
-    if (g_experiment >= 2100 && g_experiment < 2140) return 1;   // (2100 ..: the probe variants of conv_bf16_kernel)
+    if (exp_in(EXP_BF16_PROBE, 64)) return 1;   // (the probe variants of conv_bf16_kernel)
 #endif
     for (int s = 0; s < kp.nsrc; ++s)
         if (kp.src_c[s] % 32 != 0 || kp.src_ld[s] % 8 != 0 || (reinterpret_cast<size_t>(kp.src_ptr[s]) & 15)) return 1;
@@ -934,8 +934,8 @@ int conv_ring_try(int kind, bool dgrad, const ConvKParams &kp, hipStream_t st, c
     else if (kind == PWS_CONV_K5S1 && !dgrad) mode = RM_K5, planes = 25;
     else return 1;
     // the first layer (round 6): ONE source of 32 channels (the NHWC-32 copy of the window), ONE 64-channel output block -- what makes its weights resident;
-    // 8 x 32 tiles (PWS_OPT_EXPERIMENT 189: never -- conv_bf16_k5_kernel as in rounds 1-5)
-    if (mode == RM_K5 && (g_experiment == 189 || kp.nsrc != 1 || kp.src_c[0] != 32 || kp.cout > 64 || kp.kpad_bf != 32 || kp.LW % 32 != 0 || kp.LH % 8 != 0)) return 1;
+    // 8 x 32 tiles
+    if (mode == RM_K5 && (kp.nsrc != 1 || kp.src_c[0] != 32 || kp.cout > 64 || kp.kpad_bf != 32 || kp.LW % 32 != 0 || kp.LH % 8 != 0)) return 1;
     const size_t sample_bytes = (size_t)kp.H * kp.W * 2;
     for (int s = 0; s < kp.nsrc; ++s)
         if (sample_bytes * kp.src_ld[s] >= (1u << 31)) return 1;
@@ -958,16 +958,16 @@ int conv_ring_try(int kind, bool dgrad, const ConvKParams &kp, hipStream_t st, c
         rp.timers = e ? reinterpret_cast<unsigned long long *>(strtoull(e, nullptr, 0)) : nullptr;
     }
 #endif
-    rp.ablate = g_experiment >= 41 && g_experiment <= 48 ? g_experiment - 40 : (g_experiment == 49 ? 16 : 0);   // (49 = mask 16: no act' loads)   // (48 = mask 8: weight pieces only for a workgroup's first unit)
+    rp.ablate = exp_mask(EXP_RING_ABLATE, 32);
     // Unit size and tile shape: whole tiles only.  512-pixel units when they give every CU (most of) one; else 256, else 128 -- a smaller unit stages
     // the same weight rows for fewer pixels, so it is taken only where the large one would leave the chip idle.  Below `min_small` units of 128 pixels
-    // the launch is the split-K / one-shot kernels' (PWS_OPT_EXPERIMENT 181 .. 184: min_small 64 / 96 / 192 / 256; 185: no small units, rounds 2-5; 186 / 187: units of 256 / 128 pixels whatever the count).
+    // the launch is the split-K / one-shot kernels' (PWS_OPT_EXPERIMENT 186 / 187: units of 256 / 128 pixels whatever the count).
     const long per_px = (long)((kp.cout + 63) / 64) * ((mode == RM_CT4 || mode == RM_SP3) ? 4 : 1);
     const long px = (long)kp.LW * kp.LH * kp.N;
     int pix = 0, tw = 0;
     if (mode == RM_K5) {
         pix = 256, tw = 32;
-        if (px / 256 < 192 && g_experiment != 21) return 1;
+        if (px / 256 < 192 && !exp_is(EXP_RING_SMALL)) return 1;
     } else {
         int tw512 = 0;
         if (kp.LW % 32 == 0 && kp.LH % 16 == 0) tw512 = 32;
@@ -979,24 +979,22 @@ int conv_ring_try(int kind, bool dgrad, const ConvKParams &kp, hipStream_t st, c
         int tw128 = 0;
         if (kp.LW % 8 == 0 && kp.LH % 8 == 0 && kp.N % 2 == 0) tw128 = 8;
         else if (kp.LW % 4 == 0 && kp.LH % 4 == 0 && kp.N % 8 == 0) tw128 = 4;
-        const bool small_ok = g_experiment != 185;
         // (measured, tools/probes/r6c / r6d: batch-8 inference 6471 -> 6600 f/s with 64 instead of 128 -- its alternatives are launch-latency-bound split-K
         //  pairs; the batch-64 training step 25.88 -> 25.94 ms -- there the alternative is a conv_bf16_kernel launch that fills the chip: by batch)
-        const long min_dflt = kp.N <= 16 ? 64 : 128;
-        const long min_small = g_experiment == 181 ? 64 : (g_experiment == 182 ? 96 : (g_experiment == 183 ? 192 : (g_experiment == 184 ? 256 : min_dflt)));
-        const int force_pix = g_experiment == 186 ? 256 : (g_experiment == 187 ? 128 : 0);   // tests: that unit size or nothing
+        const long min_small = kp.N <= 16 ? 64 : 128;
+        const int force_pix = exp_is(EXP_RING_UNIT256) ? 256 : (exp_is(EXP_RING_UNIT128) ? 128 : 0);   // tests: that unit size or nothing
         if (force_pix == 256 && tw256) pix = 256, tw = tw256;
         else if (force_pix == 128 && tw128) pix = 128, tw = tw128;
         else if (force_pix) return 1;
-        else if (tw512 && (px / 512 * per_px >= 192 || g_experiment == 21)) pix = 512, tw = tw512;
-        else if (small_ok && tw256 && px / 256 * per_px >= 192) pix = 256, tw = tw256;
-        else if (small_ok && tw128 && px / 128 * per_px >= min_small) pix = 128, tw = tw128;
+        else if (tw512 && (px / 512 * per_px >= 192 || exp_is(EXP_RING_SMALL))) pix = 512, tw = tw512;
+        else if (tw256 && px / 256 * per_px >= 192) pix = 256, tw = tw256;
+        else if (tw128 && px / 128 * per_px >= min_small) pix = 128, tw = tw128;
         else return 1;   // too few units for 256 persistent workgroups: the split-K kernels do better
     }
     if (kp.cout > (pix == 512 && tw == 16 && mode == RM_K3S1 ? 512 : 1024)) return 1;   // the bias vector's LDS slot (RgCfg::BIAS_FLOATS)
     if (px / pix * per_px >= (1l << 28)) return 1;   // 32-bit unit arithmetic in the kernel
     // the sign-bit variant of the data-gradient epilogue: when EVERY destination with an act' has its sign bits (PWS_OPT_EXPERIMENT 12: never)
-    bool sg = dgrad && g_experiment != 12, any_act = false;
+    bool sg = dgrad && !exp_is(EXP_NO_SIGN_BITS), any_act = false;
     for (int s = 0; s < kp.ndst; ++s)
         if (kp.dst_act[s] != PWS_ACT_NONE) any_act = true, sg = sg && kp.dst_sign[s] != nullptr;
     sg = sg && any_act;

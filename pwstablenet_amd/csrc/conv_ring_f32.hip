@@ -45,7 +45,7 @@ struct RingfParams {
     int tiles_x, tiles_y;
     unsigned ncob, ncls, nunits;
     int gpp;              // K groups per plane = sum(src_c) / 16
-    int ablate;           // TIMING ONLY (PWS_OPT_EXPERIMENT 2200 + 16 v + mask, conv_ringf_try): 1 no matrix phase, 2 no DMA, 4 no stores
+    int ablate;           // TIMING ONLY (EXP_RINGF_VARIANT + 16 v + mask, conv_ringf_try): 1 no matrix phase, 2 no DMA, 4 no stores
 };
 
 template <int MODE_, int TH_, int R_, int NT_ = 2, int MW_ = 8>
@@ -435,7 +435,7 @@ static int ringf_launch_tile(int th, int nt, bool half, RingfParams &rp, hipStre
 // occupy the chip.  `prefer_other`: the caller has a faster specialised kernel for this launch when the map is large (Winograd for
 // the 3x3 kind).  Returns 1 when not covered.
 int conv_ringf_try(int kind, const ConvKParams &kp, hipStream_t st, const ProfInfo &pi) {
-    if (kp.io_bf16 || kp.ndst != 0 || g_experiment == 22) return 1;
+    if (kp.io_bf16 || kp.ndst != 0 || exp_is(EXP_RINGF_OFF)) return 1;
     for (int s = 0; s < kp.nsrc; ++s)
         if (kp.src_ld[s] == 0 || kp.src_c[s] % 16 != 0 || kp.src_ld[s] % 4 != 0 || (reinterpret_cast<size_t>(kp.src_ptr[s]) & 15)) return 1;
     if (kp.LW % 32 != 0 || kp.LH % 8 != 0 || kp.cout % 4 != 0) return 1;
@@ -463,16 +463,16 @@ int conv_ringf_try(int kind, const ConvKParams &kp, hipStream_t st, const ProfIn
     // the 8 x 32-tile variant and the transposed kind stay available to the tests (PWS_OPT_EXPERIMENT 23 / 24).
     const long per256_32 = (long)kp.LW * kp.LH * kp.N / 256 * ((kp.cout + 31) / 32);   // ... with 32 output channels each
     int th, nt = 2;
-    const bool forced = g_experiment == 23 || g_experiment == 24;
+    const bool forced = exp_is(EXP_RINGF_8X32) || exp_is(EXP_RINGF_16X32);
     // (stride-2 kind: from one 16 x 32 unit per CU upwards -- 64 -> 64 @256^2 x 8 = 256 units: 113 vs 136 us of conv_mfma_kernel; with
     //  fewer units than CUs the persistent kernel loses: 128 -> 128 @128^2 x 8 = 128 units 188 vs 109 us)
-    if (g_experiment == 27 && mode == RF_K3S2) th = 8, nt = 1;   // (the 32-channel units forced for the tests' small launches)
-    else if (kp.LH % 16 == 0 && (per256 / 2 >= (mode == RF_K3S2 ? 256 : 512) || g_experiment == 24)) th = 16;
+    if (exp_is(EXP_RINGF_32CH) && mode == RF_K3S2) th = 8, nt = 1;   // (the 32-channel units forced for the tests' small launches)
+    else if (kp.LH % 16 == 0 && (per256 / 2 >= (mode == RF_K3S2 ? 256 : 512) || exp_is(EXP_RINGF_16X32))) th = 16;
     // (stride-2 kind with one 8 x 32 unit per CU, measured after the loader's offsets moved into registers: 128 -> 128 @128^2 x 8
     //  91 vs 98 us, 64 -> 128 @128^2 52 vs 60 us of conv_mfma_kernel; half a chip of units loses: 256 -> 256 @64^2 158 vs 98 us)
     else if (forced || (mode == RF_K3S2 && per256 >= 256)) th = 8;
     // (units of 32 output channels where 64-channel units fill only half the chip: 256 -> 256 @64^2 x 8 = 256 such units)
-    else if (mode == RF_K3S2 && per256_32 >= 256 && g_experiment != 26) th = 8, nt = 1;
+    else if (mode == RF_K3S2 && per256_32 >= 256) th = 8, nt = 1;
     else return 1;
     if (mode == RF_CT4 && !forced) return 1;
     // Stride-2 launches of 8 x 32 tiles (one unit per CU at the headline's shapes) run as HALF workgroups: 4 x 32 tiles, two
@@ -482,14 +482,13 @@ int conv_ringf_try(int kind, const ConvKParams &kp, hipStream_t st, const ProfIn
     // (profiles/r07_ringf_k3s2_ab.txt, batch 8 / 16): 64 -> 128 @64^2 51.8 -> 47.7 us, 128 -> 256 @32^2 50.2 -> 48.8, 128 -> 128 @64^2
     // 87.4 -> 83.5, 256 -> 256 @32^2 x 16 161.5 -> 154.2; 16 x 32 tiles gain nothing (64 -> 64 @128^2 ~86 us either way).
     // Units of 32 output channels or 8 x 32 tiles instead of 16 x 32 (two units per workgroup) were slower on every launch.
-    // PWS_OPT_EXPERIMENT 2200 + 16 v + mask (2200..2247, this kernel's stride-2 kind only): v = 1 full workgroups everywhere,
+    // EXP_RINGF_VARIANT + 16 v + mask (this kernel's stride-2 kind only): v = 1 full workgroups everywhere,
     // v = 2 half workgroups also for 16 x 32 tiles; mask = the timing-only ablations of RingfParams::ablate.  Output bits are the
     // same for every v (tests/test_hip_ringf_variants.py).
-    // (PWS_OPT_EXPERIMENT ids read in this file: 22, 23, 24, 26, 27, 2200..2247)
     bool half = mode == RF_K3S2 && th == 8;
-    if (mode == RF_K3S2 && g_experiment >= 2200 && g_experiment < 2248) {
-        const int v = (g_experiment - 2200) >> 4;
-        rp.ablate = (g_experiment - 2200) & 7;
+    if (mode == RF_K3S2 && exp_in(EXP_RINGF_VARIANT, 48)) {
+        const int v = exp_mask(EXP_RINGF_VARIANT, 48) >> 4;
+        rp.ablate = exp_mask(EXP_RINGF_VARIANT, 48) & 7;
         if (v == 1) half = false;
         else if (v == 2) half = true;
     }

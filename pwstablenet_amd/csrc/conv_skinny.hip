@@ -217,7 +217,7 @@ static int skinny_launch(const SkParams &p, unsigned grid, int lds_bytes, hipStr
 // covered: NHWC fp32 sources in multiples of 16 channels, at most 128 output pixels per parity class, cout a multiple of 4, and a
 // workspace for the K split.  Returns 1 when not covered (the caller runs conv_mfma_kernel's small tiles).
 int conv_skinny_try(int kind, ConvKParams &kp, float *final_out, float *ws, size_t ws_floats, hipStream_t st, const ProfInfo &pi) {
-    if (kp.io_bf16 || kp.ndst != 0 || g_experiment == 70) return 1;
+    if (kp.io_bf16 || kp.ndst != 0 || exp_is(EXP_SKINNY_OFF)) return 1;
     int mode;
     if (kind == PWS_CONV_K3S1 || kind == PWS_CONVT_K3S1) mode = SK_K3S1;
     else if (kind == PWS_CONV_K3S2) mode = SK_K3S2;
@@ -260,7 +260,7 @@ int conv_skinny_try(int kind, ConvKParams &kp, float *final_out, float *ws, size
     p.out = p.ksplit > 1 ? ws : final_out;
     const unsigned grid = (unsigned)(blocks1 * p.ksplit);
     const int lds_bytes = p.cps * ntaps * 4096;
-    if (g_experiment == 71) return PWS_OK;   // TIMING ONLY: the launch is skipped (what the deep levels cost end to end)
+    if (exp_is(EXP_SKINNY_SKIP)) return PWS_OK;   // TIMING ONLY: the launch is skipped (what the deep levels cost end to end)
     ProfScope prof(KID_CONV_SKINNY, pi.flops, pi.bytes, st);   // covers the split-K reduce as well
     int rc;
     if (M <= 16) rc = skinny_launch<1, 1, 1>(p, grid, lds_bytes, st);

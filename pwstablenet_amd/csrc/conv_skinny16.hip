@@ -214,7 +214,7 @@ static int skinny16_launch(const Sk16Params &p, unsigned grid, int lds_bytes, hi
 // layer's cout).  Returns 1 when not covered (the caller runs conv_bf16_kernel's small tiles).  PWS_OPT_EXPERIMENT 71 switches it off.
 int conv_skinny16_try(int kind, bool dgrad, ConvKParams &kp, int kchan, float *final_out, float *ws, size_t ws_floats, hipStream_t st,
                       const ProfInfo &pi) {
-    if (!kp.io_bf16 || g_experiment == 71 || !ws) return 1;
+    if (!kp.io_bf16 || exp_is(EXP_SKINNY16_OFF) || !ws) return 1;
     Sk16Params p{};
     if (kind == PWS_CONV_K3S1 || kind == PWS_CONVT_K3S1) p.ks = 3, p.stride = 1, p.pad = 1, p.subpix = 0;
     else if (kind == PWS_CONV_K3S2 && !dgrad) p.ks = 3, p.stride = 2, p.pad = 1, p.subpix = 0;
@@ -227,7 +227,7 @@ int conv_skinny16_try(int kind, bool dgrad, ConvKParams &kp, int kchan, float *f
     // Measured at batch 64 (tools/layer_profile.py --batch 64 --math bf16 --train): 64 .. 256 pixels per class 16 - 30 us against 21 - 35 us
     // of conv_bf16_kernel, 1024 pixels +-10 % either way, 4096 pixels 2 - 3.5x SLOWER (an A operand gathered per tap and lane re-reads
     // the input nine times, and every 128-pixel block fetches the layer's weights again): small M only (PWS_OPT_EXPERIMENT 72: up to 4096)
-    const long mmax = g_experiment == 72 ? 4096 : (g_experiment >= 730 && g_experiment <= 739 ? (64L << (g_experiment - 730)) : 256);
+    const long mmax = exp_is(EXP_SKINNY16_4096) ? 4096 : 256;
     if (M < 1 || M > mmax || kp.cout % 4 != 0 || kchan % 32 != 0) return 1;
     int cin = 0;
     for (int s = 0; s < kp.nsrc; ++s) {

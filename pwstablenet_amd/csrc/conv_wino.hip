@@ -45,7 +45,7 @@ struct WinoParams {
     int out_ld, act;
     int tiles_x, tiles_y;
     unsigned ntiles;
-    int ablate;  // measurement knob (env PWS_WINO_ABLATE, tools/conv_bench.py): 1 skip epilogue, 2 skip transform,
+    int ablate;  // measurement knob (EXP_WINO_ABLATE + mask, tools/conv_bench.py): 1 skip epilogue, 2 skip transform,
                  // 4 skip MFMA, 8 skip U loads -- results are then wrong on purpose; 0 in normal operation
 };
 
@@ -397,8 +397,7 @@ int wino_k3s1_launch(const pws_conv_args *a, const ProfHint &ph, hipStream_t st)
     }
     p.N = a->n, p.H = a->h, p.W = a->w, p.cin_pad = (cin + 15) / 16 * 16, p.cout = a->cout;
     p.uw = a->w_wino, p.bias = a->bias, p.out = a->out, p.out_ld = a->out_ld, p.act = a->act;
-    static const int ablate = getenv("PWS_WINO_ABLATE") ? atoi(getenv("PWS_WINO_ABLATE")) : 0;
-    p.ablate = ablate;
+    p.ablate = exp_mask(EXP_WINO_ABLATE, 16);
     return a->kind == PWS_CONVT_K4S2 ? wino_launch<1>(p, a->cout, ph, st) : wino_launch<0>(p, a->cout, ph, st);
 }
 

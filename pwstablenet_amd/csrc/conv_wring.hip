@@ -58,7 +58,7 @@ struct WringParams {
     int nchunks;              // sum(src_c) / 16
     int ksplit, cps;          // K split: a unit covers the cps = nchunks / ksplit chunks [ks * cps, (ks + 1) * cps) and writes its raw sums to
     size_t split_stride;      // out + ks * split_stride (dense [pixel][cout]); splitk_reduce_kernel adds them, bias + activation there
-    int ablate;               // measurement only (PWS_OPT_EXPERIMENT 51..57, or 1000 + mask): 1 = DMA pieces fetch nothing after the
+    int ablate;               // measurement only (EXP_WRING_ABLATE + mask): 1 = DMA pieces fetch nothing after the
                               // first slot, 2 = no matrix phase, 4 = no epilogue stores, 8 = no A-operand reads, 16 = no B-operand
                               // reads, 32 = no barrier / DMA wait, 64 = no DMA instructions -- results are meaningless, only the
                               // timing is read
@@ -568,10 +568,10 @@ static int wring_launch(const WringParams &p, unsigned grid, hipStream_t st) {
 // (partial sums in a->ws, added by splitk_reduce_kernel).
 // Returns 1 when not covered (the caller goes on to the first-generation Winograd kernel / the direct kernels).
 int wring_try(const pws_conv_args *a, const ProfHint &ph, hipStream_t st) {
-    if (!a->w_wring || g_experiment == 50) return 1;
+    if (!a->w_wring || exp_is(EXP_WRING_OFF)) return 1;
     const bool ct4 = a->kind == PWS_CONVT_K4S2;
     if (!ct4 && a->kind != PWS_CONV_K3S1 && a->kind != PWS_CONVT_K3S1) return 1;
-    const bool g16 = a->w == 16 && a->n % 2 == 0 && g_experiment != 61;
+    const bool g16 = a->w == 16 && a->n % 2 == 0;
     if (a->h % WR_TH != 0 || (!g16 && a->w % WR_TW != 0) || a->cout % 32 != 0 || a->out_ld % 2 != 0 || (reinterpret_cast<size_t>(a->out) & 7)) return 1;
     int cin = 0;
     for (int s = 0; s < a->nsrc; ++s) {
@@ -601,11 +601,11 @@ int wring_try(const pws_conv_args *a, const ProfHint &ph, hipStream_t st) {
     unsigned units1 = tiles * p.ncob * p.ncls;
     p.nchunks = cin / 16;
     // K split over units when there are fewer units than CUs: the smallest divisor of the chunk count that fills the chip (at most 8
-    // splits, at least 4 chunks per unit), partial sums through the caller's workspace (PWS_OPT_EXPERIMENT 62: never split)
+    // splits, at least 4 chunks per unit), partial sums through the caller's workspace
     const size_t out_floats = (size_t)a->n * (ct4 ? 4 : 1) * a->h * a->w * a->cout;
     auto split_for = [&](unsigned units) {   // 1 = none needed / none possible
         int ks = 1;
-        if (units < (unsigned)ncu && a->ws && g_experiment != 62) {
+        if (units < (unsigned)ncu && a->ws) {
             for (int k = 2; k <= 8; ++k) {
                 if (p.nchunks % k != 0 || p.nchunks / k < 4 || (size_t)k * out_floats * 4 > a->ws_bytes) continue;
                 ks = k;
@@ -618,24 +618,23 @@ int wring_try(const pws_conv_args *a, const ProfHint &ph, hipStream_t st) {
     // DMA per matrix instruction) or a deeper K split of the two-class units.  Measured at batch 8 (tools/layer_profile.py): the split
     // wins where MODE 2 would have to split as well (1024 -> 256 @16^2: 115 -> 101 us) or where its units keep >= 32 chunks
     // (1024 -> 128 @32^2: 187 -> 178 us); MODE 2 without any split wins over a split to 16 chunks (512 -> 128 @32^2: 100 vs 103 us).
-    // (PWS_OPT_EXPERIMENT 59 forces MODE 2, 60 forbids it, 63 = the rule before: MODE 2 whenever the two-class units do not fill the chip)
+    // (PWS_OPT_EXPERIMENT 59 forces MODE 2)
     bool mode2 = false;
     if (ct4 && units1 < (unsigned)ncu) {
         const int k1 = split_for(units1), k2 = split_for(units1 * 2);
         const bool split1_fills = units1 * (unsigned)k1 >= (unsigned)ncu;
-        mode2 = g_experiment == 63 || !(split1_fills && (k2 > 1 || p.nchunks / k1 >= 32));
+        mode2 = !(split1_fills && (k2 > 1 || p.nchunks / k1 >= 32));
     }
-    if (g_experiment == 60) mode2 = false;
-    if (ct4 && g_experiment == 59) mode2 = true;
+    if (ct4 && exp_is(EXP_WRING_MODE2)) mode2 = true;
     if (mode2) p.ncls = 4, units1 *= 2;
     const int ksplit = split_for(units1);
     p.ksplit = ksplit, p.cps = p.nchunks / ksplit, p.split_stride = out_floats;
     p.nunits = units1 * (unsigned)ksplit;
     if (ksplit > 1) p.out = static_cast<float *>(a->ws);
-    p.ablate = g_experiment >= 51 && g_experiment <= 57 ? g_experiment - 50 : (g_experiment >= 1000 && g_experiment < 2024 ? g_experiment - 1000 : 0);
+    p.ablate = exp_mask(EXP_WRING_ABLATE, 1024);
     // a unit is cps x 8 192 (9 216) matrix cycles: fewer units than CUs leave CUs idle for the whole launch, and a non-integer
     // number of rounds costs its tail -- taken from 3/4 of the chip upwards (PWS_OPT_EXPERIMENT 58 / 59 force it for the tests)
-    if (p.nunits < (unsigned)(ncu * 3 / 4) && g_experiment != 58 && g_experiment != 59) return 1;
+    if (p.nunits < (unsigned)(ncu * 3 / 4) && !exp_is(EXP_WRING_FORCE) && !exp_is(EXP_WRING_MODE2)) return 1;
     ProfScope prof(ct4 ? KID_CONV_WRING_CT4 : KID_CONV_WRING, ph.flops, ph.bytes, st);   // covers the split-K reduce as well
     const unsigned grid = p.nunits < (unsigned)ncu ? p.nunits : (unsigned)ncu;   // one persistent workgroup per CU
     int rc;

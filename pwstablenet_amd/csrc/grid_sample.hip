@@ -801,12 +801,11 @@ extern "C" int pws_grid_sample_fwd(const float *input, const float *grid, float 
         const size_t groups = total / 4;
         const unsigned nb = (unsigned)((groups + 255) / 256);
         // streaming hints once the launch no longer fits the 256 MB Infinity Cache (see the kernel's comment)
-        // (experiments 2..4 are this file's A/B switches: 2 / 3 = never non-temporal; every OTHER value -- other kernels' A/B numbers -- keeps the product rule)
-        const bool nt = g_experiment == 1 || (!(g_experiment >= 2 && g_experiment <= 4) && (double)total * (8.0 + 8.0 * c) > 256e6);
-        if (g_experiment == 5 && nt)   // row window + wave shuffle (A/B only, tools/gs_shuffle_ab.py)
+        const bool nt = !exp_is(EXP_GS_BWD_GENERAL) && !exp_is(EXP_U8_CVT_SHIFT) && (double)total * (8.0 + 8.0 * c) > 256e6;
+        if (exp_is(EXP_GS_ROWWIN) && nt)   // row window + wave shuffle (A/B only, tools/gs_shuffle_ab.py)
             hipLaunchKernelGGL((grid_sample_fwd2_kernel<4, true, true>), dim3(nb), dim3(256), 0, as_stream(stream), input, grid, out, c, h,
                                w, howo, groups, nb, align_corners);
-        else if (g_experiment == 5)
+        else if (exp_is(EXP_GS_ROWWIN))
             hipLaunchKernelGGL((grid_sample_fwd2_kernel<4, false, true>), dim3(nb), dim3(256), 0, as_stream(stream), input, grid, out, c, h,
                                w, howo, groups, nb, align_corners);
         else if (nt)
@@ -850,7 +849,7 @@ extern "C" int pws_grid_sample_bwd(const float *gout, const float *input, const 
     ProfScope prof(KID_GRID_SAMPLE_BWD, (double)total * (20.0 + 16.0 * c),
                    (double)total * (8.0 + 4.0 * c + (ggrid ? 8.0 : 0.0)) + (ginput ? 8.0 : 4.0) * c * (double)n * h * w,
                    as_stream(stream));
-    if (!ginput && (ho * wo) % 4 == 0 && w >= 2 && aligned16(grid) && aligned16(gout) && aligned16(ggrid) && g_experiment != 2) {
+    if (!ginput && (ho * wo) % 4 == 0 && w >= 2 && aligned16(grid) && aligned16(gout) && aligned16(ggrid) && !exp_is(EXP_GS_BWD_GENERAL)) {
         // the field gradient alone: 4 pixels per lane, vector loads, paired gathers (see the kernel)
         const size_t groups = total / 4;
         const unsigned nbg = (unsigned)((groups + 255) / 256);
@@ -933,7 +932,7 @@ extern "C" int pws_upsample_grid_sample_fwd(const float *input, const float *fie
     if (w % 4 == 0 && aligned16(out)) {
         const size_t groups = total / 4;
         const unsigned nb = (unsigned)((groups + 255) / 256);
-        const bool nt = g_experiment == 1 || (!(g_experiment >= 2 && g_experiment <= 5) && (double)total * 8.0 * c > 256e6);
+        const bool nt = !exp_is(EXP_GS_BWD_GENERAL) && !exp_is(EXP_U8_CVT_SHIFT) && !exp_is(EXP_GS_ROWWIN) && (double)total * 8.0 * c > 256e6;
         if (3.f * rx < 0.999f && nt)
             hipLaunchKernelGGL((upsample_grid_sample_fwd_kernel<4, true, true>), dim3(nb), dim3(256), 0, as_stream(stream), input,
                                field, out, c, h, w, fh, fw, ry, rx, groups, nb, align_corners);
@@ -970,13 +969,13 @@ extern "C" int pws_upsample_grid_sample_u8(const unsigned char *frame_hwc, const
     // (Rounds 2-5 kept a row-window + wave-shuffle variant here, north_star's "wavefront shuffles for the bilinear gather": 16 -> 2 memory
     // instructions per lane bought nothing, 33.6 vs 27.2 us on a pure translation -- the kernel is bound by its vector instructions;
     // docs/ROUNDS.md.  The float kernel's variant stays: grid_sample_fwd2_kernel<.., ROWWIN>, tools/gs_shuffle_ab.py.)
-    const bool pku8 = g_experiment != 4;
+    const bool pku8 = !exp_is(EXP_U8_CVT_SHIFT);
     const float kx = align_corners ? 0.5f * (float)(w - 1) : 0.5f * (float)w, kx1 = 0.5f * (float)(w - 1);
     const float ky = align_corners ? 0.5f * (float)(h - 1) : 0.5f * (float)h, ky1 = 0.5f * (float)(h - 1);
     const bool narrow = 3.f * rx < 0.999f;
     // field access (the kernel's FMODE): 3 * rx < 1 -> a lane's 4 pixels touch <= 3 field columns; 255 * rx + 3 <= 63 -> a wave's 256 pixels touch
     // <= 63: the wave fetches them once (1280 from 256 columns: rx = 0.199).  PWS_OPT_EXPERIMENT 49: per-lane windows (A/B)
-    const int fmode = !narrow ? 0 : (255.f * rx + 3.f <= 63.f && g_experiment != 49 ? 2 : 1);
+    const int fmode = !narrow ? 0 : (255.f * rx + 3.f <= 63.f && !exp_is(EXP_GS_U8_LANE_WINDOWS) ? 2 : 1);
 #define PWS_U8_LAUNCH_F(FMODE_, SWAP_, PK_)                                                                                             \
     hipLaunchKernelGGL((upsample_grid_sample_u8_kernel<FMODE_, SWAP_, PK_>), dim3(gx, cpr, (unsigned)n), dim3(256), 0, as_stream(stream), \
                        frame_hwc, field, out_hwc, h, w, fh, fw, ry, rx, nrg, kx, kx1, ky, ky1)

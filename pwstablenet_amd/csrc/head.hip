@@ -716,17 +716,17 @@ extern "C" int pws_field_head_fwd_s(const float *x, int ld, int n, int h, int w,
         ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
     }
     unsigned pgrid = ntiles;
-    if (g_experiment != 92 && ntiles > (unsigned)(ncu * 3)) {   // equal shares: k tiles per workgroup, as few workgroups as that takes
+    if (!exp_is(EXP_HEAD_ONE_TILE) && ntiles > (unsigned)(ncu * 3)) {   // equal shares: k tiles per workgroup, as few workgroups as that takes
         const unsigned k = (ntiles + (unsigned)(ncu * 3) - 1) / (unsigned)(ncu * 3);
         pgrid = ((ntiles + k - 1) / k + kXcds - 1) / kXcds * kXcds;
     }
     const bool v2_16 = store == PWS_STORE_BF16 && ld % 8 == 0, v2_32 = store != PWS_STORE_BF16;
-    if (c == 64 && (v2_16 || v2_32) && g_experiment != 90 && g_experiment != 35 && w >= F2_TW && h >= F2_TH && (long long)h * w * ld * 4 < (1ll << 30)) {
+    if (c == 64 && (v2_16 || v2_32) && !exp_is(EXP_HEAD_VALU) && !exp_is(EXP_HEAD_V1) && w >= F2_TW && h >= F2_TH && (long long)h * w * ld * 4 < (1ll << 30)) {
         // the second cut (16 x 32 tiles; PWS_OPT_EXPERIMENT 35: the first cut below)
         const int tx2 = (w + F2_TW - 1) / F2_TW, ty2 = (h + F2_TH - 1) / F2_TH;
         const unsigned nt2 = (unsigned)tx2 * ty2 * n;
         unsigned pg2 = nt2;
-        if (g_experiment != 92 && nt2 > (unsigned)(ncu * 3)) {
+        if (!exp_is(EXP_HEAD_ONE_TILE) && nt2 > (unsigned)(ncu * 3)) {
             const unsigned k = (nt2 + (unsigned)(ncu * 3) - 1) / (unsigned)(ncu * 3);
             pg2 = ((nt2 + k - 1) / k + kXcds - 1) / kXcds * kXcds;
         }
@@ -736,13 +736,13 @@ extern "C" int pws_field_head_fwd_s(const float *x, int ld, int n, int h, int w,
         else
             hipLaunchKernelGGL((field_head_v2_kernel<true, 2>), dim3(pg2), dim3(256), 0, as_stream(stream), x, ld, n, h, w, w_out, b_out, theta, align_corners, resid,
                                grid, tx2, ty2, nt2, 0);
-    } else if (store == PWS_STORE_BF16 && c == 64 && ld % 8 == 0 && g_experiment != 90)   // the matrix-core kernel (see its comment)
+    } else if (store == PWS_STORE_BF16 && c == 64 && ld % 8 == 0 && !exp_is(EXP_HEAD_VALU))   // the matrix-core kernel (see its comment)
         hipLaunchKernelGGL(field_head16_mfma_kernel, dim3(pgrid), dim3(256), 0, as_stream(stream), reinterpret_cast<const __bf16 *>(x), ld, n, h, w,
                            w_out, b_out, theta, align_corners, resid, grid, tiles_x, tiles_y, ntiles, 0);
     else if (store == PWS_STORE_BF16)
         hipLaunchKernelGGL(field_head_kernel<true>, dim3(ntiles), dim3(256), 0, as_stream(stream), x, ld, n, h, w, c, w_out, b_out,
                            theta, align_corners, resid, grid, tiles_x, tiles_y, ntiles, 0);
-    else if (c == 64 && g_experiment != 90)
+    else if (c == 64 && !exp_is(EXP_HEAD_VALU))
         hipLaunchKernelGGL(field_head32_mfma_kernel, dim3(pgrid), dim3(256), 0, as_stream(stream), x, ld, n, h, w, w_out, b_out, theta, align_corners,
                            resid, grid, tiles_x, tiles_y, ntiles, 0);
     else

@@ -634,7 +634,7 @@ int field_bwd_dx_dw(const float *x, int ld, const float *gz, int n, int h, int w
                 "pws_field_head_bwd: dx_act needs bf16 storage, dx, PWS_ACT_LRELU / PWS_ACT_RELU and ld %% 8 == 0");
     const size_t total = (size_t)n * h * w;
     if (io16 && dx && dw_out && c == 64 && ld % 8 == 0 && dx_ld % 8 == 0 && (reinterpret_cast<size_t>(x) & 15) == 0 &&
-        (reinterpret_cast<size_t>(dx) & 15) == 0 && g_experiment != 91) {
+        (reinterpret_cast<size_t>(dx) & 15) == 0 && !exp_is(EXP_HEAD_BWD_VALU)) {
         // dx and dW_out from one read of the activation, on the matrix cores (field_bwd16_mfma_kernel)
         const int tiles_x = (w + FQ_T - 1) / FQ_T, tiles_y = (h + FQ_T - 1) / FQ_T;
         const long ntiles = (long)tiles_x * tiles_y * n;

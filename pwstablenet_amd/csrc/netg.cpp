@@ -385,7 +385,7 @@ class Exec {
         // (The arena holds the bytes in every training layout -- the workspace size does not depend on the storage mode.)
         if (wants_sign(act, l.cout, ow)) {
             unsigned char *sg = reinterpret_cast<unsigned char *>(alloc(((size_t)n_ * oh * ow * (l.cout / 8) + 3) / 4));
-            if (io16_ && g_experiment != 12) o.seg[0].sign = sg;
+            if (io16_ && !exp_is(EXP_NO_SIGN_BITS)) o.seg[0].sign = sg;
         }
         return run_conv(layer, x, act, o, 1, nchw_src, nchw_c);
     }
@@ -409,7 +409,7 @@ class Exec {
         t.ptr = alloc((size_t)ngroups * n_ * h * w * c);
         if (wants_sign(act, c, w)) {
             unsigned char *sg = reinterpret_cast<unsigned char *>(alloc(((size_t)ngroups * n_ * h * w * (c / 8) + 3) / 4));
-            if (io16_ && g_experiment != 12) t.sign = sg;
+            if (io16_ && !exp_is(EXP_NO_SIGN_BITS)) t.sign = sg;
         }
         return t;
     }
@@ -639,8 +639,7 @@ static void forward_lockstep(Exec &E, const Tn &in, const float *x, int n, int i
         Tn skip = s == 3 && l == 2 ? enc(2, 2) : enc(l, s);                          // x32 == x22
         return Exec::cat(E.group(Vl[l], s - 1), skip);
     };
-    // ---- encoders.  sched (PWS_OPT_EXPERIMENT 150 + v, measured in tools/lockstep_sched.sh): how queue 1 follows queue 0
-    const int sched = g_experiment >= 150 && g_experiment < 160 ? g_experiment - 150 : 0;
+    // ---- encoders
     auto db1 = [&](const Tn &x11) {   // down_bottom1 (:178 == :200): once, into group 1 of E2
         Tn c = E.conv(L_DB1_CS, x11, PWS_ACT_LRELU);
         E.conv_groups(L_DB1_CS + 1, c, PWS_ACT_LRELU, 1, Ek[2], 1);
@@ -653,42 +652,17 @@ static void forward_lockstep(Exec &E, const Tn &in, const float *x, int n, int i
     auto enc1 = [&](int k, const Tn &x11) { E.conv_groups(L_DOWN1 + (k - 2), k == 2 ? x11 : enc(k - 1, 1), PWS_ACT_LRELU, 1, Ek[k], 0); };
     E.use(0);
     Tn x11 = E.conv(L_TRANSFER, in, PWS_ACT_LRELU, x, input_nc);
-    hipEvent_t lvl[9] = {};
-    if (sched == 4) {   // an event behind every level of stage 1: queue 1 follows level by level
-        lvl[1] = E.mark(0);
-        for (int k = 2; k <= 8; ++k) enc1(k, x11), lvl[k] = E.mark(0);
-        E.use(1);
-        E.wait(1, lvl[1]);
-        db1(x11);
-        E.wait(1, lvl[2]);
-        level3();
-    } else if (sched == 2) {   // the large early layers of stages 2 / 3 on queue 0 itself, queue 1 gets the merged levels only
-        enc1(2, x11);
-        db1(x11);
-        level3();
-        for (int k = 3; k <= 5; ++k) enc1(k, x11);
-        E.order(0, 1);
-        for (int k = 6; k <= 8; ++k) enc1(k, x11);
-        E.order(0, 1);
-        E.use(1);
-    } else if (sched == 1) {   // queue 1 starts behind the whole stage-1 encoder
-        for (int k = 2; k <= 8; ++k) enc1(k, x11);
-        E.order(0, 1);
-        E.use(1);
-        db1(x11);
-        level3();
-    } else {   // 0 / 3: queue 1 starts behind x14 (its large layers beside the deeper levels of stage 1), the merged levels behind x18
-        const int first = sched == 5 ? 3 : (sched == 6 ? 5 : 4);   // (5 / 6: behind x13 / x15 instead -- fp32 1815 / 1826 against 1840 f/s, bf16 6238 / 6150 against 6252)
-        for (int k = 2; k <= first; ++k) enc1(k, x11);
-        E.order(0, 1);
-        E.use(1);
-        db1(x11);
-        level3();
-        E.use(0);
-        for (int k = first + 1; k <= 8; ++k) enc1(k, x11);
-        E.order(0, 1);
-        E.use(1);
-    }
+    // queue 1 starts behind x14 (its large layers beside the deeper levels of stage 1), the merged levels behind x18.  (Measured against
+    // queue 1 behind x13 / x15: fp32 1815 / 1826 against 1840 f/s, bf16 6238 / 6150 against 6252.)
+    for (int k = 2; k <= 4; ++k) enc1(k, x11);
+    E.order(0, 1);
+    E.use(1);
+    db1(x11);
+    level3();
+    E.use(0);
+    for (int k = 5; k <= 8; ++k) enc1(k, x11);
+    E.order(0, 1);
+    E.use(1);
     if (is_training) {
         E.use(0);
         E.theta(enc(8, 1), 0, th1);
@@ -696,11 +670,9 @@ static void forward_lockstep(Exec &E, const Tn &in, const float *x, int n, int i
     }
     for (int k = 4; k <= 8; ++k) {   // levels 4 .. 8, merged, on queue 1
         const int db = k - 1;   // down_bottom index
-        if (sched == 4) E.wait(1, lvl[k - 1]);
         E.conv_groups(L_DB1_CS + 2 * (db - 1), enc(k - 1, 1), PWS_ACT_LRELU, 2, Ck[k], 0);
         E.conv_groups(L_DB1_CS + 2 * (db - 1) + 1, Exec::cat(enc(k - 1, 2), E.group(Ck[k], 0)), PWS_ACT_LRELU, 2, Ek[k], 1);
     }
-    if (sched == 4) E.wait(1, lvl[8]);   // (the bottom of stage 1: x_up of the deepest decoder level)
     // (the theta heads of stages 2 / 3 -- 30 us of GEMV launches the field heads need at the very end -- are issued on queue 1 BEHIND the deep
     //  decoder levels, where that queue has nothing else to do: in front of them they sat on the critical path)
     // ---- stage 1 decoder (reference :166-174) on queue 0
@@ -721,15 +693,9 @@ static void forward_lockstep(Exec &E, const Tn &in, const float *x, int n, int i
         E.conv_groups(L_UB7_MP + 2 * (7 - l) + 1, dec(l + 1, 1), PWS_ACT_RELU, 2, Gl[l], 0);
         E.conv_groups(L_UB7_MP + 2 * (7 - l), Exec::cat(E.group(Gl[l], 0), dec(l + 1, 2)), PWS_ACT_RELU, 2, Vl[l], 1);
     };
-    if (sched == 3) {   // everything of the decoders on queue 0
-        E.order(1, 0);
-        E.use(0);
-        for (int l = 7; l >= 5; --l) merged_level(l);
-    } else {
-        E.use(1);
-        for (int l = 7; l >= 5; --l) merged_level(l);
-        E.order(1, 0);
-    }
+    E.use(1);
+    for (int l = 7; l >= 5; --l) merged_level(l);
+    E.order(1, 0);
     E.use(1);
     if (is_training) E.theta(enc(8, 2), 1, th2);
     E.theta(enc(8, 3), 2, th3);
@@ -761,7 +727,7 @@ static void forward_graph(Exec &E, const float *x, int n, int input_nc, int g, i
 
     Tn in{};
     in.nseg = 1, in.h = S, in.w = S, in.seg[0] = Seg{nullptr, input_nc, 0};
-    if (!E.bn_on() && g_experiment != 15) {   // (15: the per-stage schedule below, A/B; the BatchNorm path keeps it: statistics are per call)
+    if (!E.bn_on() && !exp_is(EXP_NETG_PER_STAGE)) {   // (15: the per-stage schedule below, A/B; the BatchNorm path keeps it: statistics are per call)
         forward_lockstep(E, in, x, n, input_nc, g, is_training, ac, grids, resid, th1, th2, th3);
         return;
     }
@@ -810,9 +776,8 @@ static void forward_graph(Exec &E, const float *x, int n, int input_nc, int g, i
     Tn x255 = E.up_bottom(5, x166, x266, &x25);
     hipEvent_t dec2_deep = E.mark(0);
     // ---- stage 3 decoder (reference :212-219), deep levels: on queue 1 behind the stage-3 encoder, beside the LARGE levels of the stage-2
-    // decoder on queue 0 (nine latency-bound launches on <= 8 x 8 maps under three chip-filling ones); PWS_OPT_EXPERIMENT 14: on queue 0
-    // after the whole stage-2 decoder, as before
-    const bool deep_on_q1 = g_experiment != 14 && !E.bn_on();
+    // decoder on queue 0 (nine latency-bound launches on <= 8 x 8 maps under three chip-filling ones)
+    const bool deep_on_q1 = !E.bn_on();
     Tn x377{}, x366{}, x355{};
     hipEvent_t dec3_deep = nullptr;
     if (deep_on_q1) {
@@ -934,10 +899,10 @@ static int run_backward(const float *packed, const float *packed_dgrad, const fl
     // Weight gradients are leaves of the backward graph (only the optimizer reads them): they run on the side queue, each behind an
     // event recorded where its dy is final, while this queue goes on with the data-gradient chain -- whose deep levels are ~100
     // latency-bound launches that then sit beside chip-filling weight-gradient kernels instead of between them.  The queues join at
-    // the end of the call.  (PWS_OPT_EXPERIMENT 16 or two_queues == 0: one queue, as before.)
+    // the end of the call.  (two_queues == 0: one queue.)
     hipStream_t wst = st;
     SideStream *wside = nullptr;
-    if (mode.two_queues && g_experiment != 16) {
+    if (mode.two_queues) {
         wside = &side_stream();
         if (hipStream_t q = wside->pick(st)) wst = q, wside->begin(st);
         else wside = nullptr;
@@ -967,7 +932,7 @@ static int run_backward(const float *packed, const float *packed_dgrad, const fl
     // (pws_dst.act_y) instead of by a separate pass over the buffer.  A dry sweep finds, per tensor, the tape position of that
     // last writer (same control flow as the real sweep below) and the op that produced the tensor.
     std::unordered_map<const float *, size_t> last_writer, producer;
-    const bool fuse_act = E.io16() && !bn && mode.math == PWS_MATH_BF16 && g_experiment != 11;
+    const bool fuse_act = E.io16() && !bn && mode.math == PWS_MATH_BF16;
     if (fuse_act) {
         std::unordered_map<const float *, bool> wr;
         bool hd[3] = {false, false, false};
@@ -1308,7 +1273,7 @@ extern "C" int pws_netg_pack_weights_train(const float *const *params, float *pa
         const PackLayer &p = f.layer[i];
         const Layer &l = L[i];
         const bool has_dg = l.dg_off != (size_t)-1;
-        bool ok = math == PWS_MATH_BF16 && g_experiment != 120 && pack_tiled(p.kind) && l.wb_off != (size_t)-1 && p.cout % 64 == 0 && p.cin_pad % 32 == 0;
+        bool ok = math == PWS_MATH_BF16 && !exp_is(EXP_NO_PACK_ONE_PASS) && pack_tiled(p.kind) && l.wb_off != (size_t)-1 && p.cout % 64 == 0 && p.cin_pad % 32 == 0;
         if (ok && has_dg) ok = l.dgb_off != (size_t)-1 && p.cin % 64 == 0;   // (cout % 64 == 0 covers the data-gradient copy's k padding)
         // every source of the layer must be a multiple of 32 channels, or the bf16 kernels decline and fall back to the fp32 copies:
         // sources are sums of ngf multiples, ngf % 32 == 0 settles it

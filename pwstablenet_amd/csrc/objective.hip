@@ -304,7 +304,7 @@ __global__ void __launch_bounds__(256) temporal_l1_kernel(const float *__restric
     for (unsigned b = blockIdx.x; b < nblocks; b += gridDim.x) {   // (forward: capped grid, see warp_norm_fwd_kernel)
         const unsigned blk = xcd_remap(b, nblocks);
         size_t p = (size_t)blk * 256 + threadIdx.x;
-        if (BWD && g_pair == 2) {
+        if (BWD && g_pair == 2) {   // (g_pair == 2: the measured, rejected vertical merge -- no launch passes it; kept so that the product kernel stays as it is)
             // a workgroup = 128 columns x 2 rows, a wave = 32 columns x 2 rows (lanes l and l + 32 are vertical neighbours)
             const unsigned tiles_x = (unsigned)W / 128u, per_sample = tiles_x * ((unsigned)H / 2u);
             const unsigned ns = blk / per_sample, tb = blk % per_sample;
@@ -490,83 +490,6 @@ __global__ void __launch_bounds__(256) temporal_l1_bwd_tiled_kernel(const float 
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     if (xq + i < W) gfake1[o + i] = g1[ch][i];
-            }
-        }
-    }
-    if (in_lds) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < bw * bh; i += 256) {
-            const size_t q = (size_t)(y_lo + i / bw) * W + (x_lo + i % bw);
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                const float v = box[ch][i];
-                if (v != 0.f) atomicAdd(gfake2 + ((size_t)n * 3 + ch) * HW + q, v);
-            }
-        }
-    }
-}
-
-// The lean form of the tiled variant: 16 x 16 pixels per workgroup, ONE pixel per lane (few registers, a 7 KB box: many workgroups per
-// CU).  PWS_OPT_EXPERIMENT 99 (A/B, tools/temporal_ab.py).
-constexpr int kT16Box = 24 * 24;
-__global__ void __launch_bounds__(256) temporal_l1_bwd_tile16_kernel(const float *__restrict__ fake1, const float *__restrict__ fake2,
-                                                                     const float *__restrict__ theta, float c, const float *__restrict__ scale,
-                                                                     float *__restrict__ gfake1, float *__restrict__ gfake2, int H, int W, int tiles_x,
-                                                                     int tiles_y) {
-    __shared__ float box[3][kT16Box];
-    const int tile = blockIdx.x % (tiles_x * tiles_y), n = blockIdx.x / (tiles_x * tiles_y);
-    const int px0 = (tile % tiles_x) * 16, py0 = (tile / tiles_x) * 16;
-    const int HW = H * W;
-    if (scale) c *= *scale;
-    const float *th = theta + (size_t)n * 6;
-    float ixmin = 3.0e38f, ixmax = -3.0e38f, iymin = 3.0e38f, iymax = -3.0e38f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int cx = min(px0 + ((k & 1) ? 15 : 0), W - 1), cy = min(py0 + ((k & 2) ? 15 : 0), H - 1);
-        const float bx = base_o(cx, W), by = base_o(cy, H);
-        const float ix = unnorm_o(th[0] * bx + th[1] * by + th[2], W), iy = unnorm_o(th[3] * bx + th[4] * by + th[5], H);
-        ixmin = fminf(ixmin, ix), ixmax = fmaxf(ixmax, ix), iymin = fminf(iymin, iy), iymax = fmaxf(iymax, iy);
-    }
-    const bool finite = ixmin > -1.0e9f && ixmax < 1.0e9f && iymin > -1.0e9f && iymax < 1.0e9f;
-    const int x_lo = finite ? min(max((int)floorf(ixmin) - 1, 0), W - 1) : 0, x_hi = finite ? min(max((int)floorf(ixmax) + 2, 0), W - 1) : W - 1;
-    const int y_lo = finite ? min(max((int)floorf(iymin) - 1, 0), H - 1) : 0, y_hi = finite ? min(max((int)floorf(iymax) + 2, 0), H - 1) : H - 1;
-    const int bw = x_hi - x_lo + 1, bh = y_hi - y_lo + 1;
-    const bool in_lds = finite && bw * bh <= kT16Box;   // block-uniform
-    if (in_lds) {
-        for (int i = threadIdx.x; i < bw * bh; i += 256) box[0][i] = 0.f, box[1][i] = 0.f, box[2][i] = 0.f;
-        __syncthreads();
-    }
-    const int y_ = py0 + (int)(threadIdx.x >> 4), x_ = px0 + (int)(threadIdx.x & 15);
-    if (y_ < H && x_ < W) {
-        const float bx = base_o(x_, W), by = base_o(y_, H);
-        const Taps4 t = make_taps4(th[0] * bx + th[1] * by + th[2], th[3] * bx + th[4] * by + th[5], H, W);
-        int c00 = 0, c01 = 0, c10 = 0, c11 = 0;
-        if (in_lds) {
-            const int r0 = t.o00 / W, q0 = t.o00 - r0 * W, r1 = t.o11 / W, q1 = t.o11 - r1 * W;
-            const int a0 = min(max(r0 - y_lo, 0), bh - 1), a1 = min(max(r1 - y_lo, 0), bh - 1);
-            const int b0 = min(max(q0 - x_lo, 0), bw - 1), b1 = min(max(q1 - x_lo, 0), bw - 1);
-            c00 = a0 * bw + b0, c01 = a0 * bw + b1, c10 = a1 * bw + b0, c11 = a1 * bw + b1;
-        }
-        const int hw = y_ * W + x_;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            const size_t pl = ((size_t)n * 3 + ch) * HW;
-            const float *ip = fake2 + pl;
-            const float o21 = ip[t.o00] * t.w00 + ip[t.o01] * t.w01 + ip[t.o10] * t.w10 + ip[t.o11] * t.w11;
-            const float sg = c * sgn(o21 - fake1[pl + hw]);
-            gfake1[pl + hw] -= sg;
-            if (sg == 0.f) continue;
-            if (in_lds) {
-                if (t.w00 != 0.f) atomicAdd(&box[ch][c00], sg * t.w00);
-                if (t.w01 != 0.f) atomicAdd(&box[ch][c01], sg * t.w01);
-                if (t.w10 != 0.f) atomicAdd(&box[ch][c10], sg * t.w10);
-                if (t.w11 != 0.f) atomicAdd(&box[ch][c11], sg * t.w11);
-            } else {
-                float *gp = gfake2 + pl;
-                if (t.w00 != 0.f) atomicAdd(gp + t.o00, sg * t.w00);
-                if (t.w01 != 0.f) atomicAdd(gp + t.o01, sg * t.w01);
-                if (t.w10 != 0.f) atomicAdd(gp + t.o10, sg * t.w10);
-                if (t.w11 != 0.f) atomicAdd(gp + t.o11, sg * t.w11);
             }
         }
     }
@@ -973,8 +896,7 @@ extern "C" int pws_warp_norm_bwd(const float *src, size_t src_nstride, const flo
     const unsigned nb = (unsigned)((total + 255) / 256);
     ProfScope prof(KID_OBJECTIVE, 150.0 * total, (double)total * (8.0 + 12.0 + 8.0 + (target ? 12.0 : 0.0) + (gextra ? 12.0 : 0.0)),
                    as_stream(stream));
-    if (((size_t)h * w) % 4 == 0 && w >= 2 && al16(grid) && al16(ggrid) && (!gextra || al16(gextra)) && (!target || (al16(target) && tgt_nstride % 4 == 0)) &&
-        g_experiment != 94) {   // 4 pixels per lane (94: one pixel per lane, A/B and tests)
+    if (((size_t)h * w) % 4 == 0 && w >= 2 && al16(grid) && al16(ggrid) && (!gextra || al16(gextra)) && (!target || (al16(target) && tgt_nstride % 4 == 0))) {   // 4 pixels per lane
         const size_t groups = total / 4;
         const unsigned nb4 = (unsigned)((groups + 255) / 256);
         hipLaunchKernelGGL(warp_norm_bwd4_kernel, dim3(nb4), dim3(256), 0, as_stream(stream), src, src_nstride, grid, target, tgt_nstride, c_l1, scale,
@@ -1010,24 +932,18 @@ extern "C" int pws_temporal_l1_bwd(const float *fake1, const float *fake2, const
     // Measured (tools/temporal_ab.py, random frames): 108 / 416 us per launch at 32 / 128 samples for one lane per pixel with 12 memory
     // atomics, 156 / 598 us for the tiles with the scatter in LDS -- the L2 retires fp32 atomics at ~230 G/s, the tiled kernel's two
     // barriers, box zeroing / flush and 186 registers cost more than the atomics it saves.  NOT taken (PWS_OPT_EXPERIMENT 98 takes it).
-    if (g_experiment == 99) {
-        const int tx = (w + 15) / 16, ty = (h + 15) / 16;
-        hipLaunchKernelGGL(temporal_l1_bwd_tile16_kernel, dim3((unsigned)(n * tx * ty)), dim3(256), 0, as_stream(stream), fake1, fake2, theta, c, scale,
-                           gfake1, gfake2, h, w, tx, ty);
-        return check_launch("temporal_l1_bwd_tile16_kernel");
-    }
-    if (g_experiment == 98) {
+    if (exp_is(EXP_TL1_TILED)) {
         const int tx = (w + kTT - 1) / kTT, ty = (h + kTT - 1) / kTT;
         hipLaunchKernelGGL(temporal_l1_bwd_tiled_kernel, dim3((unsigned)(n * tx * ty)), dim3(256), 0, as_stream(stream), fake1, fake2, theta, c, scale,
                            gfake1, gfake2, h, w, tx, ty);
         return check_launch("temporal_l1_bwd_tiled_kernel");
     }
     // neighbouring lanes merge the atomics of the taps they share -- only when a wave never straddles two samples (h * w % 64 == 0: the
-    // hand-over compares plane-relative offsets, and two samples have different theta) (PWS_OPT_EXPERIMENT 93: never; 101: vertical neighbours as well -- a wave as
-    // 32 columns x 2 rows: 1.5 instead of 2 atomics per pixel and plane, measured SLOWER, 91 vs 72 us: the narrower rows and the extra shuffles cost more)
+    // hand-over compares plane-relative offsets, and two samples have different theta).  (Merging vertical neighbours as well -- a wave as
+    // 32 columns x 2 rows: 1.5 instead of 2 atomics per pixel and plane -- measured SLOWER, 91 vs 72 us: the narrower rows and the extra shuffles cost more: g_pair == 2, which no launch passes any more.)
     hipLaunchKernelGGL(temporal_l1_kernel<true>, dim3(nb), dim3(256), 0, as_stream(stream), fake1, fake2, theta,
                        (double *)nullptr, c, scale, gfake1, gfake2, h, w, total, nb, (float *)nullptr,
-                       (total % 256 != 0 || ((size_t)h * w) % 64 != 0 || g_experiment == 93) ? 0 : ((w % 128 == 0 && h % 2 == 0 && g_experiment == 101) ? 2 : 1));
+                       (total % 256 != 0 || ((size_t)h * w) % 64 != 0) ? 0 : 1);
     return check_launch("temporal_l1_kernel<bwd>");
 }
 
@@ -1085,7 +1001,7 @@ extern "C" int pws_field_smoothness(const float *grid, double *slots_dx, double 
     const size_t total = (size_t)m * h * w;
     const unsigned nb = (unsigned)((total + 255) / 256);
     ProfScope prof(KID_OBJECTIVE, 10.0 * total, 8.0 * total, as_stream(stream));
-    if (w % 4 == 0 && al16(grid) && g_experiment != 110) {   // (110: one pixel per lane, A/B and tests)
+    if (w % 4 == 0 && al16(grid) && !exp_is(EXP_SMOOTH_ONE_PIXEL)) {   // (110: one pixel per lane, A/B and tests)
         const size_t groups = total / 4;
         const unsigned nb4 = (unsigned)((groups + 255) / 256);
         hipLaunchKernelGGL(field_smoothness4_kernel, dim3(nb4 > kLossGrid ? kLossGrid : nb4), dim3(256), 0, as_stream(stream), grid, slots_dx, slots_dy, h, w, groups, nb4);
@@ -1122,7 +1038,7 @@ extern "C" int pws_shape_loss_fwd(const float *resid, double *slots, int m, int 
     PWS_REQUIRE(resid && slots, "pws_shape_loss_fwd: NULL pointer");
     const int threads = ((bs * bs + 63) / 64) * 64;
     ProfScope prof(KID_OBJECTIVE, 120.0 * m * size * size, 8.0 * m * size * size, as_stream(stream));
-    if (bs == 16 && al16(resid) && g_experiment != 97) {   // one wave per block (97: the general kernel, A/B and tests)
+    if (bs == 16 && al16(resid) && !exp_is(EXP_SHAPE_GENERAL)) {   // one wave per block (97: the general kernel, A/B and tests)
         const unsigned nb = (unsigned)(m * block * block);
         hipLaunchKernelGGL(shape_loss16_kernel<false>, dim3((nb + 3) / 4 > kLossGrid ? kLossGrid : (nb + 3) / 4), dim3(256), 0, as_stream(stream), resid, slots, 0.0, (const float *)nullptr,
                            (float *)nullptr, size, block, nb, gi[0], gi[1], gi[2]);
@@ -1143,7 +1059,7 @@ extern "C" int pws_shape_loss_bwd(const float *resid, double c, const float *sca
     PWS_REQUIRE(resid && gresid, "pws_shape_loss_bwd: NULL pointer");
     const int threads = ((bs * bs + 63) / 64) * 64;
     ProfScope prof(KID_OBJECTIVE, 240.0 * m * size * size, 16.0 * m * size * size, as_stream(stream));
-    if (bs == 16 && al16(resid) && al16(gresid) && g_experiment != 97) {
+    if (bs == 16 && al16(resid) && al16(gresid) && !exp_is(EXP_SHAPE_GENERAL)) {
         const unsigned nb = (unsigned)(m * block * block);
         hipLaunchKernelGGL(shape_loss16_kernel<true>, dim3((nb + 3) / 4), dim3(256), 0, as_stream(stream), resid, (double *)nullptr, c, scale, gresid, size,
                            block, nb, gi[0], gi[1], gi[2]);

@@ -431,7 +431,7 @@ static int launch_wb(WgradBfParams &p, int nclasses, hipStream_t st) {
     // The deep levels (few tiles, 2.4-16.8 MB of weights): every pixel split ends with 64 x 64 x taps atomics on the SAME addresses, so with 1-2 tiles
     // per workgroup the launch is the atomics (down_bottom6.conv_same at batch 64: 64 tiles over 32 splits = 18.9 M atomics for 0.6 M weights, 73 us at
     // 65 TFLOP/s).  At least `mint` tiles per workgroup (PWS_OPT_EXPERIMENT 190 + k: mint = k, 190 = no floor as in rounds 1-5).
-    const long mint = g_experiment >= 190 && g_experiment < 200 ? g_experiment - 190 : 6;   // (tools/probes/r6e_wgrad.sh: 256 -> 256 @8x8 x 64: 71 / 45 / 39 / 41 us at 0 / 4 / 6 / 8)
+    const long mint = exp_in(EXP_WGRAD_MIN_TILES, 10) ? exp_mask(EXP_WGRAD_MIN_TILES, 10) : 6;   // (tools/probes/r6e_wgrad.sh: 256 -> 256 @8x8 x 64: 71 / 45 / 39 / 41 us at 0 / 4 / 6 / 8)
     if (mint > 0 && ps > p.ntiles / mint) ps = p.ntiles / mint;
     if (ps > p.ntiles) ps = p.ntiles;
     if (ps < 1 || t_deterministic) ps = 1;   // deterministic: one adding workgroup per (channel block, class, tap group)
@@ -509,7 +509,7 @@ int wgrad_bf16_launch(const pws_conv_bwd_weight_args *a, hipStream_t st) { retur
 // declined); 1 = not covered (tile shapes that would straddle the pairs, fp32 storage): the caller launches the pairs one after the other.
 // PWS_OPT_EXPERIMENT 188: never (A/B).
 int wgrad_bf16_launch_pair(const pws_conv_bwd_weight_args *a, hipStream_t st) {
-    if (g_experiment == 188 || a->store != PWS_STORE_BF16 || !a->gout2) return 1;
+    if (exp_is(EXP_WGRAD_NO_MERGE) || a->store != PWS_STORE_BF16 || !a->gout2) return 1;
     for (int s = 0; s < a->nsrc; ++s)
         if (!a->src2_ptr[s] || (reinterpret_cast<size_t>(a->src2_ptr[s]) & 15)) return 1;
     return wgrad_bf16_launch_impl(a, st, true);
@@ -558,9 +558,8 @@ static int wgrad_bf16_launch_impl(const pws_conv_bwd_weight_args *a, hipStream_t
     case PWS_CONV_K3S2:
         p.OH = p.LH = (a->h - 1) / 2 + 1, p.OW = p.LW = (a->w - 1) / 2 + 1;
         c = &pick(kWbK3S2, 3, p.LH, p.LW, a->n);
-        // >= 128 output channels on maps that whole 8 x 8 tiles cover: 64 x 128 channels per (8-wave) workgroup.  PWS_OPT_EXPERIMENT 83
-        // keeps the 64 x 64 workgroups (A/B)
-        if (c == &kWbK3S2[0] && a->cout % 128 == 0 && p.io_bf16 && g_experiment != 83) c = &kWbK3S2W;
+        // >= 128 output channels on maps that whole 8 x 8 tiles cover: 64 x 128 channels per (8-wave) workgroup
+        if (c == &kWbK3S2[0] && a->cout % 128 == 0 && p.io_bf16) c = &kWbK3S2W;
         break;
     case PWS_CONVT_K4S2:
         p.LH = a->h, p.LW = a->w, p.OH = 2 * a->h, p.OW = 2 * a->w, nclasses = 4, k2 = 4;

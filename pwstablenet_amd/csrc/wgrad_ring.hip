@@ -477,7 +477,7 @@ static int wrg_launch(WgradRingParams &p, int nclasses, hipStream_t st) {
     if (ps > p.ntiles) ps = p.ntiles;
     if (ps < 1 || t_deterministic) ps = 1;
     p.xcd_groups = 0;
-    if (C::WIDE && ps >= 8 && g_experiment != 84) {
+    if (C::WIDE && ps >= 8) {
         // the workgroups that walk the same tiles next to each other on one XCD: a multiple of 8 pixel splits, 1-D grid (kernel head)
         ps = ps / 8 * 8;
         p.xcd_groups = (int)ps;
@@ -495,7 +495,6 @@ static int wgrad_ring_try_impl(const pws_conv_bwd_weight_args *a, int cin, hipSt
 int wgrad_ring_try(const pws_conv_bwd_weight_args *a, int cin, hipStream_t st) { return wgrad_ring_try_impl(a, cin, st, false); }
 // both operand pairs of a->gout2 in one launch (conv2d_bwd_weight_impl); 1 = not covered (the caller then launches them one after the other)
 int wgrad_ring_try_pair(const pws_conv_bwd_weight_args *a, hipStream_t st) {
-    if (g_experiment == 89) return 1;   // A/B: never merge
     int cin = 0;
     for (int s = 0; s < a->nsrc; ++s) {
         if (a->src[s].channels % 32 != 0 || a->src[s].ld % 8 != 0 || (reinterpret_cast<size_t>(a->src2_ptr[s]) & 15)) return 1;
@@ -505,13 +504,13 @@ int wgrad_ring_try_pair(const pws_conv_bwd_weight_args *a, hipStream_t st) {
     return wgrad_ring_try_impl(a, cin, st, true);
 }
 static int wgrad_ring_try_impl(const pws_conv_bwd_weight_args *a, int cin, hipStream_t st, bool pair) {
-    if (a->store != PWS_STORE_BF16 || g_experiment == 80) return 1;   // 80: never (A/B, tests)
+    if (a->store != PWS_STORE_BF16 || exp_is(EXP_WGRAD_RING_OFF)) return 1;
     if (a->kind != PWS_CONV_K3S1 && a->kind != PWS_CONVT_K3S1 && a->kind != PWS_CONVT_K4S2 && a->kind != PWS_CONV_K5S1 && a->kind != PWS_CONV_K3S2) return 1;
     const bool first = a->kind == PWS_CONV_K5S1;   // the first layer: one source of 32 (31 + padding) channels
     if (first && (cin != 32 || a->nsrc != 1)) return 1;
     const bool ct4 = a->kind == PWS_CONVT_K4S2;
-    const bool s2 = a->kind == PWS_CONV_K3S2;      // round 4: tiles of 4 x 16 output pixels (PWS_OPT_EXPERIMENT 87: never)
-    if (s2 && (g_experiment == 87 || a->h % 8 != 0 || a->w % 32 != 0 || cin < 64)) return 1;
+    const bool s2 = a->kind == PWS_CONV_K3S2;      // round 4: tiles of 4 x 16 output pixels
+    if (s2 && (a->h % 8 != 0 || a->w % 32 != 0 || cin < 64)) return 1;
     if (!s2 && ((!first && cin < 64) || a->h % (ct4 ? 8 : 16) != 0 || a->w % 16 != 0)) return 1;
     if (a->cout < 32) return 1;
     // Measured (tools/wgrad_ring_bench.sh, batch 64, bf16 storage): the first layer (5x5, 32 -> 64 @256^2) 480 us against 1110 us;
@@ -521,17 +520,14 @@ static int wgrad_ring_try_impl(const pws_conv_bwd_weight_args *a, int cin, hipSt
     // Both kernels stage ~1.07 GB per launch at ~3 TB/s: the tile stream, not the matrix pipe, sets the pace of either.
     // The transposed kind as class pairs (SUBPIX 2): 780 / 416 / 421 / 217 us on the four decoder shapes against 807 / 436 / 423 / 207 us
     // of wgrad_bf16_kernel (one class per workgroup, SUBPIX 1: 910 / 488 / 485 / 248): 54 KB staged per 2 x 1024 matrix cycles is
-    // more than the LDS-DMA delivers -- not taken either (81 takes the pairs, 82 the single classes).
+    // more than the LDS-DMA delivers -- not taken either (81 takes the pairs).
     // Round 4: the class pairs on 128 x 64-channel workgroups (WrgCfg<..., WIDE>: dy staged once for twice the matrix work, 0.75 operand
-    // fragments per matrix instruction, the workgroups that share tiles grouped on one XCD) -- taken for cin % 128 == 0;
-    // PWS_OPT_EXPERIMENT 85: never (the previous selection).
-    // (86: every covered launch as 81, but the 64 x 64 pairs)
-    const bool wide = ct4 && cin % 128 == 0 && g_experiment != 85 && g_experiment != 86;   // (1300 + mask: timing-only ablations of the wide kernel)
-    const bool force = g_experiment == 81 || g_experiment == 86;
+    // fragments per matrix instruction, the workgroups that share tiles grouped on one XCD) -- taken for cin % 128 == 0.
+    const bool wide = ct4 && cin % 128 == 0;
+    const bool force = exp_is(EXP_WGRAD_RING_FORCE);
     // Round 6: the 64-channel 3x3 layers too (after round 5's loader rewrite the ring wins there: 64 -> 64 @256^2 x 64 377 -> 348 us, @128^2 135 -> 104 us,
-    // tools/probes/r6l_wgrad64.sh; PWS_OPT_EXPERIMENT 176: from 128 channels as in rounds 2-5)
-    const int ring_min_cin = g_experiment == 176 ? 128 : 64;
-    if (!first && !s2 && ((ct4 && !wide) || cin < ring_min_cin) && !force && g_experiment != 82) return 1;
+    // tools/probes/r6l_wgrad64.sh)
+    if (!first && !s2 && ((ct4 && !wide) || cin < 64) && !force) return 1;
     for (int s = 0; s < a->nsrc; ++s)
         if ((size_t)a->h * a->w * a->src[s].ld * 2 >= (1u << 31) || (reinterpret_cast<size_t>(a->src[s].ptr) & 15) || a->src[s].ld % 8 != 0) return 1;
     const int oh = ct4 ? 2 * a->h : (s2 ? a->h / 2 : a->h), ow = ct4 ? 2 * a->w : (s2 ? a->w / 2 : a->w);
@@ -555,27 +551,22 @@ static int wgrad_ring_try_impl(const pws_conv_bwd_weight_args *a, int cin, hipSt
     const double out_pix = (double)p.N * oh * ow;
     ProfScope prof(KID_WGRAD_RING, 2.0 * out_pix * a->cout * cin * k2,
                    4.0 * ((double)p.N * a->h * a->w * cin + out_pix * a->cout + k2 * cin * a->cout * (nclasses == 4 ? 4 : 1)), st);
-    if (ct4 && g_experiment == 82) return (a->h % 16 == 0) ? wrg_launch<WrgCfg<2, 0, 1>>(p, nclasses, st) : 1;   // one class per workgroup (A/B)
     if (ct4 && wide) {
-        switch (g_experiment) {   // 1300 + mask: timing-only ablations
-        case 1301: return wrg_launch<WrgCfg<2, 0, 2, false, true, 1>>(p, nclasses, st);
-        case 1302: return wrg_launch<WrgCfg<2, 0, 2, false, true, 2>>(p, nclasses, st);
-        case 1303: return wrg_launch<WrgCfg<2, 0, 2, false, true, 3>>(p, nclasses, st);
-        case 1304: return wrg_launch<WrgCfg<2, 0, 2, false, true, 4>>(p, nclasses, st);
-        case 1305: return wrg_launch<WrgCfg<2, 0, 2, false, true, 5>>(p, nclasses, st);
-        case 1307: return wrg_launch<WrgCfg<2, 0, 2, false, true, 7>>(p, nclasses, st);
-        case 1308: return wrg_launch<WrgCfg<2, 0, 2, false, true, 8>>(p, nclasses, st);
-        case 1315: return wrg_launch<WrgCfg<2, 0, 2, false, true, 15>>(p, nclasses, st);
-        // (4 x 16 tiles in a ring of 4 -- 120 instead of 76 KB in flight -- measured SLOWER on all six decoder shapes, 5-11 %: tools/wgrad_ring_ab2.sh)
-        case 88: return wrg_launch<WrgCfg<2, 0, 2, false, true, 0, false, 4, 4>>(p, nclasses, st);
+        switch (exp_mask(EXP_WGRAD_WIDE_ABLATE, 16)) {   // timing-only ablations
+        case 1: return wrg_launch<WrgCfg<2, 0, 2, false, true, 1>>(p, nclasses, st);
+        case 2: return wrg_launch<WrgCfg<2, 0, 2, false, true, 2>>(p, nclasses, st);
+        case 3: return wrg_launch<WrgCfg<2, 0, 2, false, true, 3>>(p, nclasses, st);
+        case 4: return wrg_launch<WrgCfg<2, 0, 2, false, true, 4>>(p, nclasses, st);
+        case 5: return wrg_launch<WrgCfg<2, 0, 2, false, true, 5>>(p, nclasses, st);
+        case 7: return wrg_launch<WrgCfg<2, 0, 2, false, true, 7>>(p, nclasses, st);
+        case 8: return wrg_launch<WrgCfg<2, 0, 2, false, true, 8>>(p, nclasses, st);
+        case 15: return wrg_launch<WrgCfg<2, 0, 2, false, true, 15>>(p, nclasses, st);
         default: return wrg_launch<WrgCfg<2, 0, 2, false, true>>(p, nclasses, st);
         }
     }
     if (ct4) return wrg_launch<WrgCfg<2, 0, 2>>(p, nclasses, st);
     if (first) return wrg_launch<WrgCfg<5, 2, 0, true>>(p, nclasses, st);
     if (s2) return wrg_launch<WrgCfg<3, 1, 0, false, false, 0, true>>(p, nclasses, st);
-    // (8 x 16 tiles in a ring of 4: within +-3 % of the 16 x 16 tiles in a ring of 2 on five layer shapes, tools/wgrad_ring_ab2.sh: kept for A/B)
-    if (g_experiment == 88) return wrg_launch<WrgCfg<3, 1, 0, false, false, 0, false, 8, 4>>(p, nclasses, st);
     return wrg_launch<WrgCfg<3, 1, 0>>(p, nclasses, st);
 }
 

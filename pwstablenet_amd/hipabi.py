@@ -4,6 +4,7 @@ This is the ONLY way the Python host reaches the kernels, and it passes raw devi
 the current HIP stream -- exactly what any other host language would pass.  There is no CPU fallback:
 if the library is missing or the call fails, a RuntimeError is raised.
 """
+import contextlib
 import ctypes
 import os
 
@@ -21,6 +22,59 @@ ABI_VERSION = 5
 NETG_DETERMINISTIC = 1
 NETG_PRUNE_DEAD = 2
 OPT_EXPERIMENT = 100   # measured kernel variants (tools, per-path tests); 0 = product default
+
+
+class Exp:
+    """PWS_OPT_EXPERIMENT ids, mirrored by hand from enum Exp in csrc/experiments.h (which says what each one selects)."""
+    GS_BWD_GENERAL = 2
+    U8_CVT_SHIFT = 4
+    GS_ROWWIN = 5
+    NO_SIGN_BITS = 12
+    NETG_PER_STAGE = 15
+    RING_OFF = 20
+    RING_SMALL = 21
+    RINGF_OFF = 22
+    RINGF_8X32 = 23
+    RINGF_16X32 = 24
+    FIRST_MFMA = 25
+    FIRST_NO_WINO = 26
+    RINGF_32CH = 27
+    FIRST_SMALL = 29
+    WINO5_SMALL = 30
+    HEAD_V1 = 35
+    GS_U8_LANE_WINDOWS = 49
+    WRING_OFF = 50
+    WRING_FORCE = 58
+    WRING_MODE2 = 59
+    SKINNY_OFF = 70
+    SKINNY16_OFF = 71
+    SKINNY16_4096 = 72
+    SKINNY_SKIP = 73
+    WGRAD_RING_OFF = 80
+    WGRAD_RING_FORCE = 81
+    HEAD_VALU = 90
+    HEAD_BWD_VALU = 91
+    HEAD_ONE_TILE = 92
+    DEEP_TILE_ALWAYS = 96
+    SHAPE_GENERAL = 97
+    TL1_TILED = 98
+    RING_8WAVE = 105
+    SMOOTH_ONE_PIXEL = 110
+    NO_PACK_ONE_PASS = 120
+    RING_UNIT256 = 186
+    RING_UNIT128 = 187
+    WGRAD_NO_MERGE = 188
+    WGRAD_MIN_TILES = 190
+    FIRST_ABLATE = 1100
+    FIRST_CLOCK = 1200
+    WINO5_ABLATE = 1300
+    WGRAD_WIDE_ABLATE = 1400
+    RING_ABLATE = 1500
+    WINO_ABLATE = 1600
+    BF16_PROBE = 2100
+    RINGF_VARIANT = 2200
+    PARITY_LEDGER = 3000
+    WRING_ABLATE = 4000
 OBJ_SLOTS = 64
 CONV_K3S1, CONV_K3S2, CONV_K5S1, CONVT_K3S1, CONVT_K4S2, CONV_K2S1P0, CONV_K1, CONV_K3S1_OUT = range(8)
 
@@ -201,6 +255,18 @@ def lib():
             raise RuntimeError("pwstablenet_amd: ABI version mismatch (%d)" % L.pws_version())
         _lib = L
     return _lib
+
+
+@contextlib.contextmanager
+def experiment(exp):
+    """Runs the body with PWS_OPT_EXPERIMENT = exp (an Exp id, or 0 for the product), then restores the previous value."""
+    L = lib()
+    prev = L.pws_get_option(OPT_EXPERIMENT)
+    check(L.pws_set_option(OPT_EXPERIMENT, exp), "pws_set_option(PWS_OPT_EXPERIMENT, %d)" % exp)
+    try:
+        yield
+    finally:
+        L.pws_set_option(OPT_EXPERIMENT, prev)
 
 
 def check(rc, what=""):

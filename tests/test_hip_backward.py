@@ -13,6 +13,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 import torch.nn.functional as F  # noqa: E402
+from pwstablenet_amd.hipabi import Exp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -183,14 +184,14 @@ def l2_warp_loss(grids, frames, target, gs):
 # levels), 22 = conv_ringf_kernel off).  A tensor passes if it is within `tol` of the float64 step (relative to the tensor's
 # largest gradient) OR at most 3x as far from it as torch's own fp32 step is ON THE SAME TENSOR -- and never beyond `cap`.
 _GRAD_TOL = {   # (loss_kind, kind) -> {experiment: (tol, cap)}
-    ("field", "W1"): {0: (1e-3, 3e-3), 70: (5e-4, 2e-3), 22: (1e-3, 3e-3)},
-    ("field", "W2"): {0: (2e-3, 3e-2), 70: (2e-3, 3e-2), 22: (2e-3, 3e-2)},   # cap: the float64 step itself takes other ReLU branches (W2 saturates)
-    ("warp", "W1"): {0: (1e-2, 4e-2), 70: (1e-2, 4e-2), 22: (1e-2, 4e-2)},
-    ("warp", "W2"): {0: (1e-2, 4e-2), 70: (1e-2, 4e-2), 22: (1e-2, 4e-2)},
+    ("field", "W1"): {0: (1e-3, 3e-3), Exp.SKINNY_OFF: (5e-4, 2e-3), Exp.RINGF_OFF: (1e-3, 3e-3)},
+    ("field", "W2"): {0: (2e-3, 3e-2), Exp.SKINNY_OFF: (2e-3, 3e-2), Exp.RINGF_OFF: (2e-3, 3e-2)},   # cap: the float64 step itself takes other ReLU branches (W2 saturates)
+    ("warp", "W1"): {0: (1e-2, 4e-2), Exp.SKINNY_OFF: (1e-2, 4e-2), Exp.RINGF_OFF: (1e-2, 4e-2)},
+    ("warp", "W2"): {0: (1e-2, 4e-2), Exp.SKINNY_OFF: (1e-2, 4e-2), Exp.RINGF_OFF: (1e-2, 4e-2)},
 }
 
 
-@pytest.mark.parametrize("experiment", [0, 70, 22])
+@pytest.mark.parametrize("experiment", [0, Exp.SKINNY_OFF, Exp.RINGF_OFF])
 @pytest.mark.parametrize("kind", ["W1", "W2"])
 @pytest.mark.parametrize("loss_kind", ["field", "warp"])
 def test_netg_backward_vs_torch_cpu_autograd(hip, cpu_grad_ref, kind, loss_kind, experiment):
@@ -206,16 +207,12 @@ def test_netg_backward_vs_torch_cpu_autograd(hip, cpu_grad_ref, kind, loss_kind,
     from pwstablenet_amd import functional as PF
     tol, cap = _GRAD_TOL[(loss_kind, kind)][experiment]
     weights, xw, frames, target, tfield, loss_fn, closs, cgrads, dgrads = cpu_grad_ref(kind, loss_kind)
-    L = hip.lib()
-    L.pws_set_option(hip.OPT_EXPERIMENT, experiment)
-    try:
+    with hip.experiment(experiment):
         net = make_net(kind, 16)
         grids, resid = net(xw.cuda())
         loss = loss_fn(grids, resid, frames.cuda(), target.cuda(), tfield.cuda(), PF.grid_sample)
         loss.backward()
         torch.cuda.synchronize()
-    finally:
-        L.pws_set_option(hip.OPT_EXPERIMENT, 0)
     assert abs(loss.item() - closs) < 1e-5 * max(1.0, abs(closs))
     rows, bad = [], []
     for (name, _), p, ref, ref64 in zip(weights, net.module._ordered_params(), cgrads, dgrads):

@@ -18,6 +18,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 import torch.nn.functional as F  # noqa: E402
+from pwstablenet_amd.hipabi import Exp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -295,12 +296,9 @@ def test_field_head_backward_bf16_storage_and_fused_activation_gradient(hip, act
     ref32 = run(L.pws_field_head_bwd_s, A.STORE_FP32)
     # c == 64 takes the fused matrix-core kernel (dx and dW from one read of x; gz and W_out enter the products as bf16);
     # PWS_OPT_EXPERIMENT 91 keeps the VALU kernels (fp32 products), which every other channel count runs anyway
-    L.pws_set_option(A.OPT_EXPERIMENT, 91)
-    try:
+    with A.experiment(Exp.HEAD_BWD_VALU):
         plain = run(L.pws_field_head_bwd_s, A.STORE_BF16)
         fused = run(L.pws_field_head_bwd_act, A.STORE_BF16, getattr(A, act)) if act != "ACT_NONE" else None
-    finally:
-        L.pws_set_option(A.OPT_EXPERIMENT, 0)
     assert torch.equal(plain[0], ref32[0].bfloat16().float())       # same fp32 sums, one rounding
     for a_, b_ in zip(ref32[1:], plain[1:]):
         np.testing.assert_allclose(b_.cpu().numpy(), a_.cpu().numpy(), rtol=1e-4, atol=1e-5 * float(a_.abs().max()))
@@ -360,9 +358,7 @@ DEEP_CASES = [
 def test_bf16_deep_map_tiles(hip, kname, shape, src_c, cout):
     """The 256-pixel tiles of the deep maps (8 x 8 x 4 samples, 4 x 4 x 16, 2 x 2 x 64; PWS_OPT_EXPERIMENT 96 takes them whenever the
     map fits, whatever the batch and K): forward (fp32 and bf16 storage, with and without K split), data gradient, fused act'."""
-    L = hip.lib()
-    L.pws_set_option(100, 96)
-    try:
+    with hip.experiment(Exp.DEEP_TILE_ALWAYS):
         if kname != "CONV_K3S2":
             test_bf16_storage_conv_forward(hip, kname, shape, src_c, cout)
             test_bf16_conv_forward(hip, kname, shape, src_c, cout, 1)
@@ -370,8 +366,6 @@ def test_bf16_deep_map_tiles(hip, kname, shape, src_c, cout):
             for store in (False, True):
                 test_bf16_conv_data_gradient(hip, kname, shape, src_c, cout, store)
             test_bf16_data_gradient_with_fused_activation_gradient(hip, kname, shape, src_c, cout, "ACT_LRELU")
-    finally:
-        L.pws_set_option(100, 0)
 
 
 @pytest.mark.parametrize("shape", [(3, 37, 45), (2, 64, 64), (1, 16, 16)])
@@ -395,20 +389,17 @@ def test_field_head_forward_bf16_storage_matrix_core_kernel(hip, shape):
     A.check(L.pws_pack_conv_weight(A.ptr(d_wo), A.ptr(po), A.CONV_K3S1_OUT, c, 2, st), "pack")
     d_x = nhwc(x).cuda().bfloat16()
     got = {}
-    try:
-        for exp in (0, 90):
-            L.pws_set_option(100, exp)
+    for exp in (0, Exp.HEAD_VALU):
+        with A.experiment(exp):
             res = torch.full((n, h, w, 2), float("nan"), device="cuda")
             grid = torch.full((n, h, w, 2), float("nan"), device="cuda")
             A.check(L.pws_field_head_fwd_s(A.ptr(d_x), c, n, h, w, c, A.ptr(po), A.ptr(d_bo), A.ptr(d_th), 0, A.ptr(res), A.ptr(grid),
                                            A.STORE_BF16, st), "field")
             got[exp] = (res.cpu().numpy(), grid.cpu().numpy())
-    finally:
-        L.pws_set_option(100, 0)
-    for exp in (0, 90):
+    for exp in (0, Exp.HEAD_VALU):
         np.testing.assert_allclose(got[exp][0], ref_res.numpy(), rtol=0, atol=5e-6)   # measured 3.0e-6 (fp32 sums of 576 terms, tanh twice)
         np.testing.assert_allclose(got[exp][1], ref_grid.numpy(), rtol=0, atol=6e-6)
-    assert not np.array_equal(got[0][0], got[90][0]) or n * h * w < 512   # two different kernels ran
+    assert not np.array_equal(got[0][0], got[Exp.HEAD_VALU][0]) or n * h * w < 512   # two different kernels ran
 
 
 @pytest.mark.parametrize("store", ["bf16", "fp32"])
@@ -433,17 +424,14 @@ def test_field_head_persistent_walk_equals_one_tile_per_workgroup(hip, oracle, s
     A.check(L.pws_pack_conv_weight(A.ptr(d_wo), A.ptr(po), A.CONV_K3S1_OUT, c, 2, st), "pack")
     d_x = nhwc(torch.from_numpy(x)).cuda().to(torch.bfloat16 if store == "bf16" else torch.float32)
     got = {}
-    try:
-        for exp in (0, 92):
-            L.pws_set_option(A.OPT_EXPERIMENT, exp)
+    for exp in (0, Exp.HEAD_ONE_TILE):
+        with A.experiment(exp):
             res = torch.full((n, h, w, 2), float("nan"), device="cuda")
             grid = torch.full((n, h, w, 2), float("nan"), device="cuda")
             A.check(L.pws_field_head_fwd_s(A.ptr(d_x), c, n, h, w, c, A.ptr(po), A.ptr(d_bo), A.ptr(d_th), 0, A.ptr(res), A.ptr(grid),
                                            A.STORE_BF16 if store == "bf16" else A.STORE_FP32, st), "field")
             got[exp] = (res.cpu().numpy(), grid.cpu().numpy())
-    finally:
-        L.pws_set_option(A.OPT_EXPERIMENT, 0)
-    assert np.array_equal(got[0][0], got[92][0]) and np.array_equal(got[0][1], got[92][1])
+    assert np.array_equal(got[0][0], got[Exp.HEAD_ONE_TILE][0]) and np.array_equal(got[0][1], got[Exp.HEAD_ONE_TILE][1])
     np.testing.assert_allclose(got[0][0], ref_res, rtol=0, atol=2e-5)
     np.testing.assert_allclose(got[0][1], ref_grid, rtol=0, atol=5e-5)
 
@@ -465,9 +453,8 @@ def test_field_head_second_cut_gives_the_bits_of_the_first(hip, store, shape):
     bout = torch.randn(2, device="cuda", generator=g) * 0.1
     theta = torch.randn((n, 6), device="cuda", generator=g) * 0.1
     out = {}
-    try:
-        for e in (0, 35):
-            L.pws_set_option(A.OPT_EXPERIMENT, e)
+    for e in (0, Exp.HEAD_V1):
+        with A.experiment(e):
             res = torch.full((n, h, w, 2), float("nan"), device="cuda")
             grid = torch.full((n, h, w, 2), float("nan"), device="cuda")
             A.check(L.pws_field_head_fwd_s(ctypes.c_void_p(x.data_ptr()), c, n, h, w, c, A.ptr(wout), A.ptr(bout), A.ptr(theta), 0, A.ptr(res), A.ptr(grid),
@@ -476,9 +463,7 @@ def test_field_head_second_cut_gives_the_bits_of_the_first(hip, store, shape):
             A.check(L.pws_field_head_fwd_s(ctypes.c_void_p(x.data_ptr()), c, n, h, w, c, A.ptr(wout), None, None, 1, None, A.ptr(only),
                                            A.STORE_BF16 if store == "bf16" else A.STORE_FP32, st), "field head")
             out[e] = (res.clone(), grid.clone(), only.clone())
-    finally:
-        L.pws_set_option(A.OPT_EXPERIMENT, 0)
-    for a, b in zip(out[0], out[35]):
+    for a, b in zip(out[0], out[Exp.HEAD_V1]):
         assert not torch.isnan(a).any() and torch.equal(a, b)
 
 
@@ -504,17 +489,14 @@ def test_field_head_c64_with_padded_rows_through_the_c_abi(hip, oracle, store, l
     A.check(L.pws_pack_conv_weight(A.ptr(d_wo), A.ptr(po), A.CONV_K3S1_OUT, c, 2, st), "pack")
     wide = torch.full((n, h, w, ld), float("nan"), device="cuda", dtype=torch.bfloat16 if store == "bf16" else torch.float32)
     wide[..., :c] = nhwc(torch.from_numpy(x)).cuda().to(wide.dtype)
-    try:
-        for exp in (0, 90):
-            L.pws_set_option(A.OPT_EXPERIMENT, exp)
+    for exp in (0, Exp.HEAD_VALU):
+        with A.experiment(exp):
             res = torch.full((n, h, w, 2), float("nan"), device="cuda")
             grid = torch.full((n, h, w, 2), float("nan"), device="cuda")
             A.check(L.pws_field_head_fwd_s(A.ptr(wide), ld, n, h, w, c, A.ptr(po), A.ptr(d_bo), A.ptr(d_th), 0, A.ptr(res), A.ptr(grid),
                                            A.STORE_BF16 if store == "bf16" else A.STORE_FP32, st), "field")
             np.testing.assert_allclose(res.cpu().numpy(), ref_res, rtol=0, atol=2e-5, err_msg="experiment %d" % exp)
             np.testing.assert_allclose(grid.cpu().numpy(), ref_grid, rtol=0, atol=5e-5, err_msg="experiment %d" % exp)
-    finally:
-        L.pws_set_option(A.OPT_EXPERIMENT, 0)
     # the ABI refuses what its 16-byte operand loads cannot take, instead of reading misaligned
     bad = wide.view(-1)[1:]   # one element (2 or 4 bytes) past a 16-byte boundary
     assert L.pws_field_head_fwd_s(A.ptr(bad), ld, n, h - 1, w, c, A.ptr(po), A.ptr(d_bo), A.ptr(d_th), 0, A.ptr(res), A.ptr(grid),
@@ -605,20 +587,16 @@ def test_bf16_one_shot_kernel_forward(hip, kname, shape, src_c, cout):
     72) and switched off (71 -> conv_bf16_kernel): both against PyTorch-CPU on the same rounded operands.  Its data-gradient kinds run
     in test_bf16_conv_data_gradient (the small-map cases with bf16 storage and a workspace)."""
     A = hip
-    L = A.lib()
     x, wt, b, _ = make_case(kname, shape, src_c, cout, "sk16")
     xr, wr = bf16r(x), bf16r(wt)
     want = nhwc(torch_layer(kname, xr, wr, b, 1)).numpy()
     got = {}
-    try:
-        for e, name in ((72, "conv_skinny16_kernel"), (71, "conv_bf16_kernel")):
-            L.pws_set_option(100, e)
+    for e, name in ((Exp.SKINNY16_4096, "conv_skinny16_kernel"), (Exp.SKINNY16_OFF, "conv_bf16_kernel")):
+        with A.experiment(e):
             got[e] = hip_fwd(A, kname, xr, wt, b, 1, src_c, cout, 64, store=True, expect=name).numpy()
             assert not np.isnan(got[e]).any()
             assert relerr(got[e], want) < STORE_TOL, (name, relerr(got[e], want))
-    finally:
-        L.pws_set_option(100, 0)
-    assert relerr(got[72], got[71]) < STORE_TOL   # same products; fp32 summation order and the bf16 rounding of the result
+    assert relerr(got[Exp.SKINNY16_4096], got[Exp.SKINNY16_OFF]) < STORE_TOL   # same products; fp32 summation order and the bf16 rounding of the result
 
 
 @pytest.mark.parametrize("kname,shape,src_c,cout", [
@@ -670,26 +648,25 @@ def test_bf16_weight_gradient_ring(hip, kname, shape, src_c, cout):
     want_db = dy.double().sum(dim=(0, 2, 3)).numpy()
     got = {}
     try:
-        for force, name in ((81, "wgrad_ring_kernel"), (80, "wgrad_bf16_kernel")):
-            L.pws_set_option(100, force)
-            dwp = torch.zeros(L.pws_packed_weight_floats(kind, cin, cout), device="cuda")
-            wa.gout, wa.gout_ld, wa.dw_packed = d_dy.data_ptr(), cout, dwp.data_ptr()
-            db = torch.full((cout,), 0.25, device="cuda")
-            wa.dbias = db.data_ptr()
-            L.pws_prof_enable(1)
-            A.check(L.pws_conv2d_bwd_weight(ctypes.byref(wa), st), "bwd_weight bf16")
-            L.pws_prof_enable(0)
-            assert [r[0] for r in A.prof_collect()] == [name]
-            dw = torch.empty(tuple(wt.shape), device="cuda")
-            A.check(L.pws_unpack_conv_weight(A.ptr(dwp), A.ptr(dw), kind, cin, cout, st), "unpack")
-            got[force] = dw.cpu().numpy()
-            err = relerr(got[force], wg.grad.numpy())
-            assert err < 1e-4, (name, err)
-            np.testing.assert_allclose(db.cpu().numpy() - 0.25, want_db, rtol=0, atol=2e-5 * np.abs(dy.numpy()).sum(axis=(0, 2, 3)).max())
+        for force, name in ((Exp.WGRAD_RING_FORCE, "wgrad_ring_kernel"), (Exp.WGRAD_RING_OFF, "wgrad_bf16_kernel")):
+            with A.experiment(force):
+                dwp = torch.zeros(L.pws_packed_weight_floats(kind, cin, cout), device="cuda")
+                wa.gout, wa.gout_ld, wa.dw_packed = d_dy.data_ptr(), cout, dwp.data_ptr()
+                db = torch.full((cout,), 0.25, device="cuda")
+                wa.dbias = db.data_ptr()
+                L.pws_prof_enable(1)
+                A.check(L.pws_conv2d_bwd_weight(ctypes.byref(wa), st), "bwd_weight bf16")
+                L.pws_prof_enable(0)
+                assert [r[0] for r in A.prof_collect()] == [name]
+                dw = torch.empty(tuple(wt.shape), device="cuda")
+                A.check(L.pws_unpack_conv_weight(A.ptr(dwp), A.ptr(dw), kind, cin, cout, st), "unpack")
+                got[force] = dw.cpu().numpy()
+                err = relerr(got[force], wg.grad.numpy())
+                assert err < 1e-4, (name, err)
+                np.testing.assert_allclose(db.cpu().numpy() - 0.25, want_db, rtol=0, atol=2e-5 * np.abs(dy.numpy()).sum(axis=(0, 2, 3)).max())
     finally:
         L.pws_prof_enable(0)
-        L.pws_set_option(100, 0)
-    assert relerr(got[81], got[80]) < 2e-5   # same products, fp32 summation order only
+    assert relerr(got[Exp.WGRAD_RING_FORCE], got[Exp.WGRAD_RING_OFF]) < 2e-5   # same products, fp32 summation order only
 
 
 # ---------------------------------------------------------------------------------------------- whole generator
@@ -813,19 +790,15 @@ def test_netg_bf16_training_step_gradients_vs_fp32(hip, store):
     l16, g16 = step("bf16")
     hip.lib().pws_prof_enable(0)
     if store == "bf16":   # the sign-bit epilogues (PWS_OPT_EXPERIMENT 12: off) change which bytes are read, not one result
-        hip.lib().pws_set_option(hip.OPT_EXPERIMENT, 12)
-        try:
+        with hip.experiment(Exp.NO_SIGN_BITS):
             l12, g12 = step("bf16")
-        finally:
-            hip.lib().pws_set_option(hip.OPT_EXPERIMENT, 0)
         if not getattr(net.module, "deterministic", False):
             net.module.deterministic = True   # (atomics' arrival order moves the weight gradients' last bits otherwise)
             try:
                 ld0, gd0 = step("bf16")
-                hip.lib().pws_set_option(hip.OPT_EXPERIMENT, 12)
-                ld12, gd12 = step("bf16")
+                with hip.experiment(Exp.NO_SIGN_BITS):
+                    ld12, gd12 = step("bf16")
             finally:
-                hip.lib().pws_set_option(hip.OPT_EXPERIMENT, 0)
                 net.module.deterministic = False
             assert ld0 == ld12 and all(torch.equal(a, b) for a, b in zip(gd0, gd12))
     names = [r[0] for r in hip.prof_collect()]
@@ -863,8 +836,7 @@ def test_one_pass_training_pack_gives_the_bits_of_the_four_pass_pack(hip, ngf):
     L = hip.lib()
 
     def step(exp):
-        L.pws_set_option(hip.OPT_EXPERIMENT, exp)
-        try:
+        with hip.experiment(exp):
             m = net.module
             m._packed = torch.full((L.pws_netg_packed_floats(31, ngf),), float("nan"), device="cuda")
             m._packed_dgrad = torch.full((L.pws_netg_packed_dgrad_floats(31, ngf),), float("nan"), device="cuda")
@@ -877,11 +849,9 @@ def test_one_pass_training_pack_gives_the_bits_of_the_four_pass_pack(hip, ngf):
             L.pws_prof_enable(0)
             names = [r[0] for r in hip.prof_collect()]
             return [g.detach().clone() for g in grids], loss.item(), [p.grad.clone() for p in net.parameters()], names
-        finally:
-            L.pws_set_option(hip.OPT_EXPERIMENT, 0)
 
     g1, l1, d1, _ = step(0)
-    g0, l0, d0, _ = step(120)
+    g0, l0, d0, _ = step(Exp.NO_PACK_ONE_PASS)
     assert np.isfinite(l1) and l1 == l0
     assert all(torch.equal(a, b) for a, b in zip(g1, g0))
     assert all(torch.equal(a, b) for a, b in zip(d1, d0))
@@ -971,13 +941,10 @@ def test_forward_sign_bits_equal_the_sign_of_the_stored_output(hip, kname, shape
     a.store, a.math, a.w_bf16 = A.STORE_BF16, A.MATH_BF16, wb.data_ptr()
     a.w_packed, a.bias, a.out, a.out_ld, a.ws, a.ws_bytes = wp.data_ptr(), d_b.data_ptr(), out.data_ptr(), cout, ws.data_ptr(), ws.numel()
     a.out_sign, a.out_sign_ld = sign.data_ptr(), sld
-    L.pws_set_option(A.OPT_EXPERIMENT, 21 if expect == "conv_ring_kernel" else 0)   # (21: the ring kernel also for launches of few units)
-    try:
+    with A.experiment(Exp.RING_SMALL if expect == "conv_ring_kernel" else 0):   # (the ring kernel also for launches of few units)
         L.pws_prof_enable(1)
         A.check(L.pws_conv2d_fwd(ctypes.byref(a), st), "conv with sign bits")
         L.pws_prof_enable(0)
-    finally:
-        L.pws_set_option(A.OPT_EXPERIMENT, 0)
     assert [r[0] for r in A.prof_collect()] == [expect]
     torch.cuda.synchronize()
     assert not torch.isnan(out.float()).any()
@@ -1016,7 +983,6 @@ def test_data_gradient_with_sign_bits_is_bit_identical_to_reading_the_forward_te
     wsb = torch.empty(64 << 20, device="cuda", dtype=torch.uint8)
 
     def run(with_sign, exp):
-        L.pws_set_option(A.OPT_EXPERIMENT, exp)
         da = A.PwsConvBwdDataArgs()
         da.kind, da.n, da.h, da.w, da.cout = kind, n, h, w, cout
         da.gout, da.gout_ld, da.w_dgrad, da.ndst = d_dy.data_ptr(), cout, wdg.data_ptr(), len(src_c)
@@ -1032,17 +998,15 @@ def test_data_gradient_with_sign_bits_is_bit_identical_to_reading_the_forward_te
                 da.dst[i].act_y, da.dst[i].act_y_ld, da.dst[i].act = ys[i].data_ptr(), c, getattr(A, act)
                 if with_sign:
                     da.dst[i].act_sign, da.dst[i].act_sign_ld = signs[i].data_ptr(), c // 8
-        try:
+        with A.experiment(exp):
             L.pws_prof_enable(1)
             A.check(L.pws_conv2d_bwd_data(ctypes.byref(da), st), "bwd_data")
             L.pws_prof_enable(0)
-        finally:
-            L.pws_set_option(A.OPT_EXPERIMENT, 0)
         ran.append([r[0] for r in A.prof_collect()])
         torch.cuda.synchronize()
         return [o.float().cpu() for o in outs]
     ran = []
-    ref, got, off = run(False, 0), run(True, 0), run(True, 12)
+    ref, got, off = run(False, 0), run(True, 0), run(True, Exp.NO_SIGN_BITS)
     assert ran[0] == ran[1] == ran[2] and (ran[0] == ["conv_ring_kernel"]) == (shape[1] >= 128), ran
     for r_, g_, o_ in zip(ref, got, off):
         assert not torch.isnan(r_).any()
@@ -1050,7 +1014,7 @@ def test_data_gradient_with_sign_bits_is_bit_identical_to_reading_the_forward_te
     if ran[0] == ["conv_ring_kernel"]:
         # round 4: on 32-wide tiles the kinds without a tap mask run FOUR matrix waves of 4 tile rows (RgCfg<..., MT = 4>); PWS_OPT_EXPERIMENT 105
         # = the eight-wave kernel.  Same products, another fp32 summation order, one rounding to bf16
-        for exp, with_sign in ((105, True), (105, False)):
+        for exp, with_sign in ((Exp.RING_8WAVE, True), (Exp.RING_8WAVE, False)):
             eight = run(with_sign, exp)
             assert ran[-1] == ["conv_ring_kernel"]
             for r_, e_ in zip(ref, eight):
@@ -1079,17 +1043,17 @@ def test_nchw_to_nhwc_pad_and_first_layer_bf16(hip):
 
 
 @pytest.mark.parametrize("kname,shape,src_c,cout,force", [
-    ("CONVT_K4S2", (2, 16, 32), [128], 64, 81),        # class pairs on 128 x 64-channel workgroups: both operand pairs in one ring launch
-    ("CONV_K3S1", (3, 16, 32), [64, 64], 96, 81),      # 3x3 on the ring, virtual concat, cout 96
-    ("CONV_K3S2", (2, 32, 64), [64], 64, 81),          # stride-2 kind on the ring (ring of 3: the tile walk crosses from pair 1 to pair 2)
-    ("CONV_K5S1", (2, 32, 48), [32], 64, 81),          # the first layer's shape on the ring
+    ("CONVT_K4S2", (2, 16, 32), [128], 64, Exp.WGRAD_RING_FORCE),        # class pairs on 128 x 64-channel workgroups: both operand pairs in one ring launch
+    ("CONV_K3S1", (3, 16, 32), [64, 64], 96, Exp.WGRAD_RING_FORCE),      # 3x3 on the ring, virtual concat, cout 96
+    ("CONV_K3S2", (2, 32, 64), [64], 64, Exp.WGRAD_RING_FORCE),          # stride-2 kind on the ring (ring of 3: the tile walk crosses from pair 1 to pair 2)
+    ("CONV_K5S1", (2, 32, 48), [32], 64, Exp.WGRAD_RING_FORCE),          # the first layer's shape on the ring
     ("CONV_K3S1", (2, 16, 16), [32], 32, 0),           # not covered by the ring (32 input channels), 16 x 16 tiles: two launches inside the call
-    ("CONVT_K4S2", (2, 8, 8), [64], 32, 80),           # ring switched off, 8 x 8 tiles: ONE launch of wgrad_bf16_kernel over both pairs (round 6)
+    ("CONVT_K4S2", (2, 8, 8), [64], 32, Exp.WGRAD_RING_OFF),           # ring switched off, 8 x 8 tiles: ONE launch of wgrad_bf16_kernel over both pairs (round 6)
     ("CONV_K3S1", (3, 8, 8), [64, 32], 72, 0),         # the same on the 3x3 kind, virtual concat, cout ending inside a block
     ("CONVT_K4S2", (4, 4, 4), [64], 64, 0),            # 4 x 4 maps: tiles of 4 samples, a pair of 4 + 4 samples = two whole tiles
     ("CONVT_K3S1", (16, 2, 2), [64, 32], 64, 0),       # 2 x 2 maps: tiles of 16 samples
     ("CONVT_K4S2", (6, 4, 4), [64], 64, 0),            # 6 samples in tiles of 4: a tile would straddle the pairs -> two launches
-    ("CONV_K3S1", (2, 8, 8), [64], 64, 188),           # merged launch switched off: two launches inside the call
+    ("CONV_K3S1", (2, 8, 8), [64], 64, Exp.WGRAD_NO_MERGE),           # merged launch switched off: two launches inside the call
 ])
 def test_bf16_weight_gradient_of_a_layer_used_twice(hip, kname, shape, src_c, cout, force):
     """pws_conv_bwd_weight_args.gout2 / src2_ptr (round 4): stages 2 and 3 of the generator run the same modules, so a shared layer's weight
@@ -1150,14 +1114,13 @@ def test_bf16_weight_gradient_of_a_layer_used_twice(hip, kname, shape, src_c, co
         A.check(L.pws_unpack_conv_weight(A.ptr(dwp), A.ptr(dw), kind, cin, cout, st), "unpack")
         return dw.cpu().numpy(), db.cpu().numpy(), names
     try:
-        L.pws_set_option(100, force)
-        both, db_both, names = run([args(pairs[0], pairs[1])])
-        two, db_two, _ = run([args(pairs[0]), args(pairs[1])])
+        with A.experiment(force):
+            both, db_both, names = run([args(pairs[0], pairs[1])])
+            two, db_two, _ = run([args(pairs[0]), args(pairs[1])])
     finally:
         L.pws_prof_enable(0)
-        L.pws_set_option(100, 0)
-    two_launches = force == 188 or (kname, shape) in (("CONVT_K4S2", (6, 4, 4)), ("CONV_K3S1", (2, 16, 16)))
-    assert names == (["wgrad_ring_kernel"] if force == 81 else ["wgrad_bf16_kernel"] * (2 if two_launches else 1)), names
+    two_launches = force == Exp.WGRAD_NO_MERGE or (kname, shape) in (("CONVT_K4S2", (6, 4, 4)), ("CONV_K3S1", (2, 16, 16)))
+    assert names == (["wgrad_ring_kernel"] if force == Exp.WGRAD_RING_FORCE else ["wgrad_bf16_kernel"] * (2 if two_launches else 1)), names
     assert relerr(both, want_dw) < 1e-4 and relerr(both, two) < 2e-5
     tol = 2e-5 * (np.abs(pairs[0][1].numpy()).sum(axis=(0, 2, 3)).max() + np.abs(pairs[1][1].numpy()).sum(axis=(0, 2, 3)).max())
     np.testing.assert_allclose(db_both, want_db, rtol=0, atol=tol)

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
+from pwstablenet_amd.hipabi import Exp  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 from pwstablenet_amd import synth  # noqa: E402
@@ -98,9 +99,6 @@ def test_grid_sample_row_window_shuffle_variant_is_bit_identical(hip, shape, n):
     for name, th in thetas.items():
         grid = F.affine_grid(th.unsqueeze(0).repeat(n, 1, 1), (n, 3, h, w), align_corners=False).cuda()
         want = PF.grid_sample(img, grid)
-        hip.lib().pws_set_option(hip.OPT_EXPERIMENT, 5)
-        try:
+        with hip.experiment(Exp.GS_ROWWIN):
             got = PF.grid_sample(img, grid)
-        finally:
-            hip.lib().pws_set_option(hip.OPT_EXPERIMENT, 0)
         assert torch.equal(got, want), name

@@ -16,6 +16,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 import torch.nn.functional as F  # noqa: E402
+from pwstablenet_amd.hipabi import Exp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -328,7 +329,6 @@ def test_field_head_bf16_vs_float64(hip, n, h, w, c, ac, which, valu, act):
     enter the products as bf16) and the VALU kernels (PWS_OPT_EXPERIMENT 91; every other c takes them anyway: fp32 products), each with
     pws_field_head_bwd_act -- dx (accumulated) times act'(x), with some x exactly +-0 (act'(0) is the negative branch)."""
     A = hip
-    L = A.lib()
     rs = np.random.RandomState(zlib.crc32(repr(("field16", n, h, w, c, ac, which, valu, act)).encode()))
     x, w_out, b_out, theta, gg, gr = _field_inputs(rs, n, h, w, c, which)
     x = x.bfloat16().float()
@@ -344,12 +344,9 @@ def test_field_head_bf16_vs_float64(hip, n, h, w, c, ac, which, valu, act):
     dx_old = (torch.randn((n, h, w, c)) * 0.5 * float(gx64.abs().max())).bfloat16().float()
     dx_init = _strided(dx_old, dx_ld, -7.0, torch.bfloat16)
     want_dx = (gx64 + dx_old.double()) * mask
-    L.pws_set_option(A.OPT_EXPERIMENT, 91 if valu else 0)
-    try:
+    with A.experiment(Exp.HEAD_BWD_VALU if valu else 0):
         out = _run_field(A, x_dev, ld, c, w_out, b_out, theta, ac, gg, gr, A.STORE_BF16, dx_ld, dx_init, 1, True,
                          dx_act=None if act == "ACT_NONE" else getattr(A, act))
-    finally:
-        L.pws_set_option(A.OPT_EXPERIMENT, 0)
     resid, grid, dx, gw, gb, gt, pre_w = out
     got = dx.cpu().float()
     assert bool((got[..., c:] == -7.0).all()), "dx padding channels written"

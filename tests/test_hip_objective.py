@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from pwstablenet_amd import synth
+from pwstablenet_amd.hipabi import Exp
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -166,13 +167,10 @@ def test_feature_and_smoothness_vs_reference_functions(hip, ref):
     np.testing.assert_allclose((s[1] / (m * 256 * 255 * 2) + s[2] / (m * 255 * 256 * 2)) / 2, delta.item(), rtol=1e-5)
     # (round 4) four pixels per lane (field_smoothness4_kernel); PWS_OPT_EXPERIMENT 110 = the one-pixel kernel: the same sums up to the fp32 partial sums
     # of a lane's eight terms; a field whose width is not a multiple of 4 takes the one-pixel kernel by itself
-    L.pws_set_option(100, 110)
-    try:
+    with hip.experiment(Exp.SMOOTH_ONE_PIXEL):
         slots1 = _slots("cuda", 3)
         q1 = [ctypes.c_void_p(slots1.data_ptr() + k * 64 * 8) for k in range(3)]
         hip.check(L.pws_field_smoothness(hip.ptr(g), q1[1], q1[2], m, 256, 256, st()), "smooth1")
-    finally:
-        L.pws_set_option(100, 0)
     s1 = slots1.sum(1).cpu().numpy()
     np.testing.assert_allclose(s[1:3], s1[1:3], rtol=1e-7)
     g_odd = g[:, :250, :254].contiguous()   # 254 columns
@@ -225,13 +223,10 @@ def test_shape_loss_fwd_bwd_vs_reference_function(hip, ref, size, block):
     if block == 16:
         # 16 x 16 blocks run one WAVE per block (shape_loss16_kernel); PWS_OPT_EXPERIMENT 97 takes the general one-workgroup-per-block
         # kernel: same doubles up to the summation order
-        try:
-            L.pws_set_option(100, 97)
+        with hip.experiment(Exp.SHAPE_GENERAL):
             slots2, gr2 = _slots("cuda"), torch.empty_like(d)
             hip.check(L.pws_shape_loss_fwd(hip.ptr(d), hip.ptr(slots2), 3, size, block, st()), "shape")
             hip.check(L.pws_shape_loss_bwd(hip.ptr(d), 0.5, None, hip.ptr(gr2), 3, size, block, st()), "shapeb")
-        finally:
-            L.pws_set_option(100, 0)
         np.testing.assert_allclose(slots2.sum().item(), slots.sum().item(), rtol=1e-12)
         np.testing.assert_allclose(gr2.cpu().numpy(), gr.cpu().numpy(), atol=1e-7)
 
@@ -433,11 +428,8 @@ def test_temporal_l1_backward_without_atomics_equals_the_scatter(hip, kind):
         torch.cuda.synchronize()
         return g1, g2
     a1, a2 = run(False)     # one lane per pixel, atomics to memory (the product)
-    try:
-        L.pws_set_option(100, 98)   # tiles with the scatter in LDS (temporal_l1_bwd_tiled_kernel: measured slower, kept for the A/B)
+    with hip.experiment(Exp.TL1_TILED):  # tiles with the scatter in LDS (temporal_l1_bwd_tiled_kernel: measured slower, kept for the A/B)
         p1, p2 = run(False)
-    finally:
-        L.pws_set_option(100, 0)
     assert torch.equal(a1, p1)
     assert float((a2 - p2).abs().max()) <= 2e-5 * max(1.0, float(a2.abs().max())), float((a2 - p2).abs().max())
     d1, d2 = run(True)

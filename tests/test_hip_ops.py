@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
+from pwstablenet_amd.hipabi import Exp  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 from pwstablenet_amd import synth  # noqa: E402
@@ -172,7 +173,7 @@ RINGF_CASES = [
 ]
 
 
-@pytest.mark.parametrize("force", [23, 24, 27])
+@pytest.mark.parametrize("force", [Exp.RINGF_8X32, Exp.RINGF_16X32, Exp.RINGF_32CH])
 @pytest.mark.parametrize("kname,shape,src_c,cout", RINGF_CASES)
 @pytest.mark.parametrize("act", [1, 2])
 def test_fp32_ring_kernel_vs_oracle(hip, oracle, kname, shape, src_c, cout, act, force):
@@ -181,7 +182,7 @@ def test_fp32_ring_kernel_vs_oracle(hip, oracle, kname, shape, src_c, cout, act,
     3x3 s2 as parity planes, transposed 4x4 s2 as parity classes, virtual concats, cout ending inside a 64-channel block."""
     A = hip
     L = A.lib()
-    if force == 27 and kname != "CONV_K3S2":
+    if force == Exp.RINGF_32CH and kname != "CONV_K3S2":
         pytest.skip("32-channel units exist for the stride-2 kind only")
     kind = getattr(A, kname)
     n, h, w = shape
@@ -201,19 +202,18 @@ def test_fp32_ring_kernel_vs_oracle(hip, oracle, kname, shape, src_c, cout, act,
         c0 += c
     got = {}
     try:
-        for exp in (force, 22):
-            assert L.pws_set_option(100, exp) == 0
-            L.pws_prof_enable(1)
-            got[exp] = run_conv(A, kind, srcs, wt, b, act, cout, ws_mb=64)
-            L.pws_prof_enable(0)
-            names = [r[0] for r in A.prof_collect()]
-            assert (names == ["conv_ringf_kernel"]) == (exp != 22), (exp, names)
+        for exp in (force, Exp.RINGF_OFF):
+            with A.experiment(exp):
+                L.pws_prof_enable(1)
+                got[exp] = run_conv(A, kind, srcs, wt, b, act, cout, ws_mb=64)
+                L.pws_prof_enable(0)
+                names = [r[0] for r in A.prof_collect()]
+                assert (names == ["conv_ringf_kernel"]) == (exp != Exp.RINGF_OFF), (exp, names)
     finally:
         L.pws_prof_enable(0)
-        L.pws_set_option(100, 0)
     assert not np.isnan(got[force]).any()
     np.testing.assert_allclose(nchw(got[force]), ref, rtol=0, atol=5e-5)
-    np.testing.assert_allclose(got[force], got[22], rtol=0, atol=5e-5)
+    np.testing.assert_allclose(got[force], got[Exp.RINGF_OFF], rtol=0, atol=5e-5)
 
 
 @pytest.mark.parametrize("kname,shape,src_c,cout", [
@@ -289,21 +289,21 @@ def test_conv_winograd_ring_vs_oracle(hip, oracle, kname, shape, src_c, cout):
     ring_name = "wino_ring_kernel<convT4,F(2x2,2x2)>" if k == 4 else "wino_ring_kernel<F(2x2,3x3)>"
     got = {}
     try:
-        for force in (58, 59, 50) if k == 4 else (58, 50):   # 59: one parity class per unit (the variant for launches of few units)
-            L.pws_set_option(100, force)
-            L.pws_prof_enable(1)
-            got[force] = run_conv(A, kind, srcs, wt, b, 1, cout, wino=True, ws_mb=64)
-            L.pws_prof_enable(0)
-            names = [r[0] for r in A.prof_collect()]
-            assert (ring_name in names) == (force != 50), names
+        # 59: one parity class per unit (the variant for launches of few units)
+        for force in (Exp.WRING_FORCE, Exp.WRING_MODE2, Exp.WRING_OFF) if k == 4 else (Exp.WRING_FORCE, Exp.WRING_OFF):
+            with A.experiment(force):
+                L.pws_prof_enable(1)
+                got[force] = run_conv(A, kind, srcs, wt, b, 1, cout, wino=True, ws_mb=64)
+                L.pws_prof_enable(0)
+                names = [r[0] for r in A.prof_collect()]
+                assert (ring_name in names) == (force != Exp.WRING_OFF), names
     finally:
         L.pws_prof_enable(0)
-        L.pws_set_option(100, 0)
-    assert not np.isnan(got[58]).any()
-    np.testing.assert_allclose(nchw(got[58]), ref, rtol=0, atol=5e-5)
-    np.testing.assert_allclose(got[58], got[50], rtol=0, atol=5e-5)
+    assert not np.isnan(got[Exp.WRING_FORCE]).any()
+    np.testing.assert_allclose(nchw(got[Exp.WRING_FORCE]), ref, rtol=0, atol=5e-5)
+    np.testing.assert_allclose(got[Exp.WRING_FORCE], got[Exp.WRING_OFF], rtol=0, atol=5e-5)
     if 59 in got:
-        np.testing.assert_allclose(nchw(got[59]), ref, rtol=0, atol=5e-5)
+        np.testing.assert_allclose(nchw(got[Exp.WRING_MODE2]), ref, rtol=0, atol=5e-5)
 
 
 @pytest.mark.parametrize("kname,shape,src_c,cout", [
@@ -339,19 +339,18 @@ def test_conv_skinny_vs_oracle(hip, oracle, kname, shape, src_c, cout):
         c0 += c
     got = {}
     try:
-        for force in (0, 70):
-            L.pws_set_option(100, force)
-            L.pws_prof_enable(1)
-            got[force] = run_conv(A, kind, srcs, wt, b, 1, cout, ws_mb=64)
-            L.pws_prof_enable(0)
-            names = [r[0] for r in A.prof_collect()]
-            assert ("conv_skinny_kernel" in names) == (force == 0), names
+        for force in (0, Exp.SKINNY_OFF):
+            with A.experiment(force):
+                L.pws_prof_enable(1)
+                got[force] = run_conv(A, kind, srcs, wt, b, 1, cout, ws_mb=64)
+                L.pws_prof_enable(0)
+                names = [r[0] for r in A.prof_collect()]
+                assert ("conv_skinny_kernel" in names) == (force == 0), names
     finally:
         L.pws_prof_enable(0)
-        L.pws_set_option(100, 0)
     assert not np.isnan(got[0]).any()
     np.testing.assert_allclose(nchw(got[0]), ref, rtol=0, atol=5e-5)
-    np.testing.assert_allclose(got[0], got[70], rtol=0, atol=5e-5)
+    np.testing.assert_allclose(got[0], got[Exp.SKINNY_OFF], rtol=0, atol=5e-5)
 
 
 def test_conv_first_layer_nchw_31ch(hip, oracle):
@@ -394,20 +393,19 @@ def test_first_layer_planar_kernel_vs_oracle(hip, oracle, shape, cin, cout, plan
     ref = oracle.conv2d(np.ascontiguousarray(x), wt, b, 1, 2, {1: oracle.ACT_LRELU, 2: oracle.ACT_RELU}[act])
     got = {}
     try:
-        for exp in ((29 if forced else 0), 25):
-            assert L.pws_set_option(100, exp) == 0
-            L.pws_prof_enable(1)
-            got[exp] = run_conv(A, A.CONV_K5S1, None, wt, b, act, cout, nchw_src=xfull, nchw_channels=cin if planes else None)
-            L.pws_prof_enable(0)
-            names = [r[0] for r in A.prof_collect()]
-            assert names == (["conv_mfma_kernel<k5s1,16x16>"] if exp == 25 else ["conv_first_kernel"]), (exp, names)
+        for exp in ((Exp.FIRST_SMALL if forced else 0), Exp.FIRST_MFMA):
+            with A.experiment(exp):
+                L.pws_prof_enable(1)
+                got[exp] = run_conv(A, A.CONV_K5S1, None, wt, b, act, cout, nchw_src=xfull, nchw_channels=cin if planes else None)
+                L.pws_prof_enable(0)
+                names = [r[0] for r in A.prof_collect()]
+                assert names == (["conv_mfma_kernel<k5s1,16x16>"] if exp == Exp.FIRST_MFMA else ["conv_first_kernel"]), (exp, names)
     finally:
         L.pws_prof_enable(0)
-        L.pws_set_option(100, 0)
-    new = got[29 if forced else 0]
+    new = got[Exp.FIRST_SMALL if forced else 0]
     assert not np.isnan(new).any(), "kernel left output elements unwritten"
     np.testing.assert_allclose(nchw(new), ref, rtol=0, atol=5e-5)
-    np.testing.assert_allclose(new, got[25], rtol=0, atol=5e-5)
+    np.testing.assert_allclose(new, got[Exp.FIRST_MFMA], rtol=0, atol=5e-5)
 
 
 WINO5_CASES = [   # (n, h, w), cin, planes per sample in memory (None = dense), forced (PWS_OPT_EXPERIMENT 30: launches of fewer than 2 units per CU)
@@ -438,24 +436,23 @@ def test_first_layer_winograd_kernel_vs_oracle(hip, oracle, shape, cin, planes, 
     ref = oracle.conv2d(np.ascontiguousarray(x), wt, b, 1, 2, {1: oracle.ACT_LRELU, 2: oracle.ACT_RELU}[act]) if small else None
     got = {}
     try:
-        for exp in ((30 if forced else 0), 26):
-            assert L.pws_set_option(100, exp) == 0
-            L.pws_prof_enable(1)
-            got[exp] = run_conv(A, A.CONV_K5S1, None, wt, b, act, 64, nchw_src=xfull, nchw_channels=cin if planes else None, wino=True)
-            L.pws_prof_enable(0)
-            names = [r[0] for r in A.prof_collect()]
-            if exp != 26:
-                assert names == ["wino5_first_kernel"], (exp, names)
-            else:
-                assert names[0] in ("conv_first_kernel", "conv_mfma_kernel<k5s1,16x16>"), names
+        for exp in ((Exp.WINO5_SMALL if forced else 0), Exp.FIRST_NO_WINO):
+            with A.experiment(exp):
+                L.pws_prof_enable(1)
+                got[exp] = run_conv(A, A.CONV_K5S1, None, wt, b, act, 64, nchw_src=xfull, nchw_channels=cin if planes else None, wino=True)
+                L.pws_prof_enable(0)
+                names = [r[0] for r in A.prof_collect()]
+                if exp != Exp.FIRST_NO_WINO:
+                    assert names == ["wino5_first_kernel"], (exp, names)
+                else:
+                    assert names[0] in ("conv_first_kernel", "conv_mfma_kernel<k5s1,16x16>"), names
     finally:
         L.pws_prof_enable(0)
-        L.pws_set_option(100, 0)
-    new = got[30 if forced else 0]
+    new = got[Exp.WINO5_SMALL if forced else 0]
     assert not np.isnan(new).any(), "kernel left output elements unwritten"
     if ref is not None:
         np.testing.assert_allclose(nchw(new), ref, rtol=0, atol=5e-5)
-    np.testing.assert_allclose(new, got[26], rtol=0, atol=5e-5)
+    np.testing.assert_allclose(new, got[Exp.FIRST_NO_WINO], rtol=0, atol=5e-5)
 
 
 def test_conv_empty_batch_and_bad_args(hip):
@@ -536,20 +533,19 @@ def test_grid_sample_field_gradient_kernel(hip, oracle, shape, ac):
     L, st = A.lib(), A.current_stream()
     d_img, d_grid, d_gout = dev(img), dev(grid), dev(gout)
     got = {}
-    for exp in (0, 2):
-        assert L.pws_set_option(100, exp) == 0
-        gg = torch.full_like(d_grid, float("nan"))
-        L.pws_prof_enable(1)
-        A.check(L.pws_grid_sample_bwd(A.ptr(d_gout), A.ptr(d_img), A.ptr(d_grid), None, A.ptr(gg), n, c, h, w, ho, wo, ac, st), "bwd")
-        L.pws_prof_enable(0)
-        assert [r[0] for r in A.prof_collect()] == ["grid_sample_bwd_kernel"]
-        torch.cuda.synchronize()
-        got[exp] = gg.cpu().numpy()
-    L.pws_set_option(100, 0)
+    for exp in (0, Exp.GS_BWD_GENERAL):
+        with A.experiment(exp):
+            gg = torch.full_like(d_grid, float("nan"))
+            L.pws_prof_enable(1)
+            A.check(L.pws_grid_sample_bwd(A.ptr(d_gout), A.ptr(d_img), A.ptr(d_grid), None, A.ptr(gg), n, c, h, w, ho, wo, ac, st), "bwd")
+            L.pws_prof_enable(0)
+            assert [r[0] for r in A.prof_collect()] == ["grid_sample_bwd_kernel"]
+            torch.cuda.synchronize()
+            got[exp] = gg.cpu().numpy()
     assert not np.isnan(got[0]).any()
     scale = np.abs(rgg).max()
     assert np.abs(got[0] - rgg).max() < 2e-5 * scale + 1e-3, np.abs(got[0] - rgg).max() / scale
-    assert np.abs(got[0] - got[2]).max() < 2e-5 * scale + 1e-3
+    assert np.abs(got[0] - got[Exp.GS_BWD_GENERAL]).max() < 2e-5 * scale + 1e-3
 
 
 def test_grid_sample_linearity_full_size(hip):

@@ -13,6 +13,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 import torch.nn.functional as F  # noqa: E402
+from pwstablenet_amd.hipabi import Exp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -45,32 +46,30 @@ BWD = [
 # units of 512.  PWS_OPT_EXPERIMENT 186 / 187 force that unit size; shapes chosen so that exactly that tile shape applies (several tiles per map,
 # cout ending inside a 64-channel block, virtual concats).
 FWD_SMALL = [
-    ("CONV_K3S1", (1, 16, 32), [32], 64, 186), ("CONVT_K3S1", (3, 16, 16), [64], 128, 186), ("CONVT_K4S2", (1, 16, 16), [64, 32], 72, 186),
-    ("CONV_K3S2", (1, 32, 64), [32, 32], 64, 186),
-    ("CONV_K3S1", (4, 8, 8), [64], 64, 186), ("CONV_K3S1", (8, 8, 24), [32], 40, 186), ("CONVT_K4S2", (4, 8, 8), [32, 32], 96, 186),
-    ("CONV_K3S2", (4, 16, 16), [64], 64, 186),
-    ("CONV_K3S1", (2, 8, 8), [64, 32], 64, 187), ("CONVT_K3S1", (6, 8, 16), [32], 72, 187), ("CONVT_K4S2", (2, 8, 8), [64], 64, 187),
-    ("CONV_K3S2", (2, 16, 16), [32, 32], 128, 187),
-    ("CONV_K3S1", (8, 4, 4), [64], 64, 187), ("CONVT_K3S1", (16, 4, 12), [32], 64, 187), ("CONVT_K4S2", (8, 4, 4), [32, 64], 64, 187),
-    ("CONV_K3S2", (8, 8, 8), [64], 96, 187),
+    ("CONV_K3S1", (1, 16, 32), [32], 64, Exp.RING_UNIT256), ("CONVT_K3S1", (3, 16, 16), [64], 128, Exp.RING_UNIT256), ("CONVT_K4S2", (1, 16, 16), [64, 32], 72, Exp.RING_UNIT256),
+    ("CONV_K3S2", (1, 32, 64), [32, 32], 64, Exp.RING_UNIT256),
+    ("CONV_K3S1", (4, 8, 8), [64], 64, Exp.RING_UNIT256), ("CONV_K3S1", (8, 8, 24), [32], 40, Exp.RING_UNIT256), ("CONVT_K4S2", (4, 8, 8), [32, 32], 96, Exp.RING_UNIT256),
+    ("CONV_K3S2", (4, 16, 16), [64], 64, Exp.RING_UNIT256),
+    ("CONV_K3S1", (2, 8, 8), [64, 32], 64, Exp.RING_UNIT128), ("CONVT_K3S1", (6, 8, 16), [32], 72, Exp.RING_UNIT128), ("CONVT_K4S2", (2, 8, 8), [64], 64, Exp.RING_UNIT128),
+    ("CONV_K3S2", (2, 16, 16), [32, 32], 128, Exp.RING_UNIT128),
+    ("CONV_K3S1", (8, 4, 4), [64], 64, Exp.RING_UNIT128), ("CONVT_K3S1", (16, 4, 12), [32], 64, Exp.RING_UNIT128), ("CONVT_K4S2", (8, 4, 4), [32, 64], 64, Exp.RING_UNIT128),
+    ("CONV_K3S2", (8, 8, 8), [64], 96, Exp.RING_UNIT128),
 ]
 BWD_SMALL = [
-    ("CONV_K3S1", (1, 16, 32), [64], 64, 186), ("CONVT_K3S1", (3, 16, 16), [32, 64, 32], 64, 186), ("CONV_K3S2", (1, 32, 64), [32, 32], 64, 186),
-    ("CONVT_K4S2", (1, 16, 16), [64, 64], 32, 186),
-    ("CONV_K3S1", (4, 8, 8), [64], 96, 186), ("CONV_K3S2", (4, 16, 16), [64], 32, 186), ("CONVT_K4S2", (4, 8, 8), [32, 64], 64, 186),
-    ("CONV_K3S1", (2, 8, 8), [64, 32], 64, 187), ("CONV_K3S2", (2, 16, 16), [32, 32], 64, 187), ("CONVT_K4S2", (2, 8, 8), [64], 64, 187),
-    ("CONV_K3S1", (8, 4, 4), [64], 64, 187), ("CONV_K3S2", (8, 8, 8), [128], 96, 187), ("CONVT_K4S2", (8, 4, 4), [32, 64], 64, 187),
+    ("CONV_K3S1", (1, 16, 32), [64], 64, Exp.RING_UNIT256), ("CONVT_K3S1", (3, 16, 16), [32, 64, 32], 64, Exp.RING_UNIT256), ("CONV_K3S2", (1, 32, 64), [32, 32], 64, Exp.RING_UNIT256),
+    ("CONVT_K4S2", (1, 16, 16), [64, 64], 32, Exp.RING_UNIT256),
+    ("CONV_K3S1", (4, 8, 8), [64], 96, Exp.RING_UNIT256), ("CONV_K3S2", (4, 16, 16), [64], 32, Exp.RING_UNIT256), ("CONVT_K4S2", (4, 8, 8), [32, 64], 64, Exp.RING_UNIT256),
+    ("CONV_K3S1", (2, 8, 8), [64, 32], 64, Exp.RING_UNIT128), ("CONV_K3S2", (2, 16, 16), [32, 32], 64, Exp.RING_UNIT128), ("CONVT_K4S2", (2, 8, 8), [64], 64, Exp.RING_UNIT128),
+    ("CONV_K3S1", (8, 4, 4), [64], 64, Exp.RING_UNIT128), ("CONV_K3S2", (8, 8, 8), [128], 96, Exp.RING_UNIT128), ("CONVT_K4S2", (8, 4, 4), [32, 64], 64, Exp.RING_UNIT128),
 ]
 
 
 @pytest.fixture()
 def force(hip):
-    L = hip.lib()
-
-    def set_(v):
-        assert L.pws_set_option(100, v) == 0
-    yield set_
-    set_(0)
+    def set_(v):   # the experiment id for the rest of the test
+        hip.check(hip.lib().pws_set_option(hip.OPT_EXPERIMENT, v), "pws_set_option")
+    with hip.experiment(0):
+        yield set_
 
 
 def _fwd(A, kname, x, wt, b, act, src_c, cout):
@@ -110,7 +109,7 @@ def _fwd(A, kname, x, wt, b, act, src_c, cout):
 
 
 @pytest.mark.parametrize("act", [1, 2])
-@pytest.mark.parametrize("kname,shape,src_c,cout,unit", [c + (21,) for c in FWD] + FWD_SMALL)
+@pytest.mark.parametrize("kname,shape,src_c,cout,unit", [c + (Exp.RING_SMALL,) for c in FWD] + FWD_SMALL)
 def test_ring_forward(hip, force, kname, shape, src_c, cout, unit, act):
     x, wt, b, _ = make_case(kname, shape, src_c, cout, "ring")
     xr, wr = bf16r(x), bf16r(wt)
@@ -118,9 +117,9 @@ def test_ring_forward(hip, force, kname, shape, src_c, cout, unit, act):
     force(unit)
     got, names = _fwd(hip, kname, xr, wt, b, act, src_c, cout)
     assert names == ["conv_ring_kernel"], names
-    force(20)
+    force(Exp.RING_OFF)
     old, names = _fwd(hip, kname, xr, wt, b, act, src_c, cout)
-    assert names == ["conv_bf16_kernel"] or (unit != 21 and "conv_ring_kernel" not in names), names   # (the smallest maps are the one-shot kernel's)
+    assert names == ["conv_bf16_kernel"] or (unit != Exp.RING_SMALL and "conv_ring_kernel" not in names), names   # (the smallest maps are the one-shot kernel's)
     got, old = got.numpy(), old.numpy()
     assert not np.isnan(got).any()
     e_ref, e_old = relerr(got, want), relerr(got, old)
@@ -162,7 +161,7 @@ def _bwd(A, kname, d_dy, wt, shape, src_c, cout, ys, act, stale):
 
 
 @pytest.mark.parametrize("act", [0, 1, 2])
-@pytest.mark.parametrize("kname,shape,src_c,cout,unit", [c + (21,) for c in BWD] + BWD_SMALL)
+@pytest.mark.parametrize("kname,shape,src_c,cout,unit", [c + (Exp.RING_SMALL,) for c in BWD] + BWD_SMALL)
 def test_ring_data_gradient(hip, force, kname, shape, src_c, cout, unit, act):
     x, wt, b, rs = make_case(kname, shape, src_c, cout, "ringd")
     n, cin, h, w = x.shape
@@ -180,9 +179,9 @@ def test_ring_data_gradient(hip, force, kname, shape, src_c, cout, unit, act):
     force(unit)
     got, names = _bwd(hip, kname, d_dy, wt, shape, src_c, cout, ys, act, stale)
     assert names == ["conv_ring_kernel"], names
-    force(20)
+    force(Exp.RING_OFF)
     old, names = _bwd(hip, kname, d_dy, wt, shape, src_c, cout, ys, act, stale)
-    assert names == ["conv_bf16_kernel"] or (unit != 21 and "conv_ring_kernel" not in names), names
+    assert names == ["conv_bf16_kernel"] or (unit != Exp.RING_SMALL and "conv_ring_kernel" not in names), names
     slope = {0: 1.0, 1: 0.2, 2: 0.0}[act]
     c0 = 0
     for i, c in enumerate(src_c):
@@ -212,7 +211,7 @@ def test_ring_whole_generator_matches_first_generation_kernels(hip, force):
     x = torch.from_numpy(synth.make_window(8, 31, 256, seed=11)).cuda()
     tgt = torch.from_numpy(np.random.RandomState(5).standard_normal((8, 256, 256, 2)).astype(np.float32) * 0.1).cuda()
     res = {}
-    for tag, exp in (("ring", 0), ("v1", 20)):
+    for tag, exp in (("ring", 0), ("v1", Exp.RING_OFF)):
         force(exp)
         net.zero_grad(set_to_none=True)
         hip.lib().pws_prof_enable(1)

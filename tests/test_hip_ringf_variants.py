@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
+from pwstablenet_amd.hipabi import Exp  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 # (N, H, W, cin, cout) of the input; the launch picks 16 x 32 tiles, 8 x 32 tiles, or 8 x 32 tiles of 32 output channels
@@ -32,14 +33,13 @@ def run_k3s2(A, n, h, w, cin, cout, exp):
     a.src[0].ptr, a.src[0].channels, a.src[0].ld = x.data_ptr(), cin, cin
     a.w_packed, a.bias, a.out, a.out_ld, a.ws, a.ws_bytes = wp.data_ptr(), b.data_ptr(), out.data_ptr(), cout, ws.data_ptr(), ws.numel()
     try:
-        assert L.pws_set_option(100, exp) == 0
-        L.pws_prof_enable(1)
-        A.check(L.pws_conv2d_fwd(ctypes.byref(a), st), "conv")
-        L.pws_prof_enable(0)
-        names = [r[0] for r in A.prof_collect()]
+        with A.experiment(exp):
+            L.pws_prof_enable(1)
+            A.check(L.pws_conv2d_fwd(ctypes.byref(a), st), "conv")
+            L.pws_prof_enable(0)
+            names = [r[0] for r in A.prof_collect()]
     finally:
         L.pws_prof_enable(0)
-        L.pws_set_option(100, 0)
     torch.cuda.synchronize()
     return out.cpu().numpy(), names
 
@@ -49,7 +49,7 @@ def test_k3s2_workgroup_variants_bit_identical(hip, case):
     ref, names = run_k3s2(hip, *case, 0)
     assert names == ["conv_ringf_kernel"], names
     assert not np.isnan(ref).any()
-    for exp in (2216, 2232):
+    for exp in (Exp.RINGF_VARIANT + 16, Exp.RINGF_VARIANT + 32):
         got, names = run_k3s2(hip, *case, exp)
         assert names == ["conv_ringf_kernel"], (exp, names)
         assert got.tobytes() == ref.tobytes(), (exp, float(np.abs(got - ref).max()))

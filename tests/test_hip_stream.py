@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
+from pwstablenet_amd.hipabi import Exp  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 from pwstablenet_amd import synth  # noqa: E402
@@ -82,18 +83,12 @@ def test_u8_hwc_fused_warp(hip, shape, swap):
     assert got.dtype == torch.uint8 and got.shape == u8.shape
     # float -> byte through v_cvt_pk_u8_f32 (product) and through (int) + clamp + shift (PWS_OPT_EXPERIMENT 4): the instruction truncates
     # and saturates like astype(uint8) of a value in [0, 255] -- byte-identical
-    hip.lib().pws_set_option(hip.OPT_EXPERIMENT, 4)
-    try:
+    with hip.experiment(Exp.U8_CVT_SHIFT):
         taps = PF.upsample_grid_sample_u8(d_u8, d_field, swap_rb=swap).cpu()
-    finally:
-        hip.lib().pws_set_option(hip.OPT_EXPERIMENT, 0)
     assert torch.equal(got, taps)
     # per-lane field windows (PWS_OPT_EXPERIMENT 49) instead of the wave's shared row pair: the same field values, the same bytes
-    hip.lib().pws_set_option(hip.OPT_EXPERIMENT, 49)
-    try:
+    with hip.experiment(Exp.GS_U8_LANE_WINDOWS):
         lanes = PF.upsample_grid_sample_u8(d_u8, d_field, swap_rb=swap).cpu()
-    finally:
-        hip.lib().pws_set_option(hip.OPT_EXPERIMENT, 0)
     assert torch.equal(got, lanes)
     # (a) the float HIP path + truncation: same taps and weights; the 4-term blend may be contracted into FMAs differently
     # by the compiler in the two kernels, so a value within 1e-3 of an integer may truncate to the neighbour

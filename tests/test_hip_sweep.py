@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+from pwstablenet_amd.hipabi import Exp
 
 pytestmark = pytest.mark.gpu
 
@@ -133,16 +134,13 @@ def test_bf16_storage_dispatch_sweep(hip, kname, shape, src_c, cout):
         return dw
 
     res = {}
-    try:
-        # product dispatch; first-generation conv kernel; ring kernel for every launch it covers (not only the long ones); no one-shot
-        # kernel; no ring weight gradient; ring weight gradient for every launch it covers
-        # (round 6) 186 / 187: the ring kernel's units of 256 / 128 pixels wherever a tile shape of that size divides the map (else the launch falls through
-        # to the other kernels, which is the dispatch being swept too); 188: a shared layer's operand pairs as two weight-gradient launches
-        for e in (0, 20, 21, 186, 187, 71, 80, 81):
-            L.pws_set_option(100, e)
-            res[e] = (forward(), dgrad(), wgrad()) if e in (0, 20) else (forward(), dgrad(), None) if e in (21, 186, 187, 71) else (None, None, wgrad())
-    finally:
-        L.pws_set_option(100, 0)
+    # product dispatch; first-generation conv kernel; ring kernel for every launch it covers (not only the long ones); no one-shot
+    # kernel; no ring weight gradient; ring weight gradient for every launch it covers
+    # (round 6) 186 / 187: the ring kernel's units of 256 / 128 pixels wherever a tile shape of that size divides the map (else the launch falls through
+    # to the other kernels, which is the dispatch being swept too); 188: a shared layer's operand pairs as two weight-gradient launches
+    for e in (0, Exp.RING_OFF, Exp.RING_SMALL, Exp.RING_UNIT256, Exp.RING_UNIT128, Exp.SKINNY16_OFF, Exp.WGRAD_RING_OFF, Exp.WGRAD_RING_FORCE):
+        with A.experiment(e):
+            res[e] = (forward(), dgrad(), wgrad()) if e in (0, Exp.RING_OFF) else (forward(), dgrad(), None) if e in (Exp.RING_SMALL, Exp.RING_UNIT256, Exp.RING_UNIT128, Exp.SKINNY16_OFF) else (None, None, wgrad())
     torch.cuda.synchronize()
     for e, (fy, fdx, fdw) in res.items():
         if fy is not None:
@@ -221,15 +219,12 @@ def test_fp32_dispatch_sweep(hip, kname, shape, src_c, cout):
     ws = torch.empty(64 << 20, dtype=torch.uint8, device="cuda")
     a.w_packed, a.bias, a.out_ld, a.ws, a.ws_bytes = wp.data_ptr(), d_b.data_ptr(), cout, ws.data_ptr(), ws.numel()
     res = {}
-    try:
-        for e in (0, 50, 70, 22, 23):
-            L.pws_set_option(100, e)
+    for e in (0, Exp.WRING_OFF, Exp.SKINNY_OFF, Exp.RINGF_OFF, Exp.RINGF_8X32):
+        with A.experiment(e):
             out = torch.full((n, oh, ow, cout), float("nan"), device="cuda")
             a.out = out.data_ptr()
             A.check(L.pws_conv2d_fwd(ctypes.byref(a), st), "fwd fp32")
             res[e] = out
-    finally:
-        L.pws_set_option(100, 0)
     torch.cuda.synchronize()
     for e, out in res.items():
         assert not torch.isnan(out).any(), e

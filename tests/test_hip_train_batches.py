@@ -34,6 +34,7 @@ torch = pytest.importorskip("torch")
 import torch.nn.functional as F  # noqa: E402
 
 from pwstablenet_amd import spec, synth  # noqa: E402
+from pwstablenet_amd.hipabi import Exp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -802,7 +803,6 @@ def test_deep_weight_gradient_deterministic_and_without_tile_floor(hip, entry):
     deterministic mode (one adding workgroup per address: ps = 1) is bit-identical run to run and within the bound of float64;
     PWS_OPT_EXPERIMENT 190 (no tiles-per-workgroup floor: the other side of the round-6 floor of 6) is within the same bound."""
     A = hip
-    L = A.lib()
     pas, li, kernel, n, pair, math, store = entry
     ly = _get_layer(A, li, math)
     seed = zlib.crc32(repr(entry).encode())
@@ -810,11 +810,8 @@ def test_deep_weight_gradient_deterministic_and_without_tile_floor(hip, entry):
     ew, eb, dws = check_wgrad(A, ly, n, kernel, pair, seed, deterministic=True, repeat=2)
     assert torch.equal(dws[0][0], dws[1][0]) and torch.equal(dws[0][1], dws[1][1]), "deterministic runs differ"
     assert ew <= tol and eb <= tol, ("deterministic", entry, ew, eb)
-    try:
-        L.pws_set_option(A.OPT_EXPERIMENT, 190)
+    with A.experiment(Exp.WGRAD_MIN_TILES):
         ew2, eb2, _ = check_wgrad(A, ly, n, kernel, pair, seed)
-    finally:
-        L.pws_set_option(A.OPT_EXPERIMENT, 0)
     print("%s: deterministic %.3g / %.3g, no floor %.3g / %.3g (bound %.3g)" % (_entry_id(entry), ew, eb, ew2, eb2, tol))
     assert ew2 <= tol and eb2 <= tol, ("experiment 190", entry, ew2, eb2)
 

@@ -17,7 +17,7 @@ net.load_state_dict({"module." + k: torch.from_numpy(v) for k, v in synth.make_w
 net = net.cuda()
 x = torch.from_numpy(synth.noise_window(8, 31, 256, 123)).cuda()
 for e in [int(v) for v in sys.argv[1:]] or [0]:
-    A.lib().pws_set_option(100, e)
+    A.lib().pws_set_option(A.OPT_EXPERIMENT, e)
     net.module.enable_graph(False)
     net.module.set_math("bf16")
     net.module.enable_graph(True)
@@ -31,4 +31,4 @@ for e in [int(v) for v in sys.argv[1:]] or [0]:
         torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / 100
     print("exp %4d: %.3f ms per batch of 8 = %.0f frames/s" % (e, dt * 1e3, 8 / dt))
-A.lib().pws_set_option(100, 0)
+A.lib().pws_set_option(A.OPT_EXPERIMENT, 0)

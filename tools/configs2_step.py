@@ -22,7 +22,7 @@ def main():
     ap.add_argument("--math", default="bf16")
     ap.add_argument("--per-rep", action="store_true", help="sync after every step and print when the host was done issuing / when the device was done")
     a = ap.parse_args()
-    A.lib().pws_set_option(100, int(os.environ.get("PWS_EXPERIMENT", "0")))
+    A.lib().pws_set_option(A.OPT_EXPERIMENT, int(os.environ.get("PWS_EXPERIMENT", "0")))
     with contextlib.redirect_stdout(sys.stderr):
         net = define_G(31, 2, 64, "normal", 0.02)
     net.load_state_dict({"module." + k: torch.from_numpy(v) for k, v in synth.make_weights("W1", seed=123, ngf=64)})

@@ -13,7 +13,7 @@ from pwstablenet_amd import hipabi as A  # noqa: E402
 def bench_dgrad(kname, n, h, w, cin, cout):
     """Data gradient of the layer (forward input n x h x w x cin, forward cout) with bf16 math and storage, one destination."""
     L, st = A.lib(), A.current_stream()
-    L.pws_set_option(100, int(os.environ.get("PWS_EXPERIMENT", "0")))
+    L.pws_set_option(A.OPT_EXPERIMENT, int(os.environ.get("PWS_EXPERIMENT", "0")))
     kind = getattr(A, kname)
     k = {"CONV_K3S1": 3, "CONV_K3S2": 3, "CONVT_K3S1": 3, "CONVT_K4S2": 4}[kname]
     wt = torch.randn((cout, cin, k, k) if not kname.startswith("CONVT") else (cin, cout, k, k), device="cuda") / (cin * k) ** 0.5
@@ -52,7 +52,7 @@ def bench_dgrad(kname, n, h, w, cin, cout):
 
 def bench(kname, n, h, w, cin, cout, wino, bf16=False):
     L, st = A.lib(), A.current_stream()
-    L.pws_set_option(100, int(os.environ.get("PWS_EXPERIMENT", "0")))
+    L.pws_set_option(A.OPT_EXPERIMENT, int(os.environ.get("PWS_EXPERIMENT", "0")))
     kind = getattr(A, kname)
     k = {"CONV_K3S1": 3, "CONV_K3S2": 3, "CONVT_K3S1": 3, "CONVT_K4S2": 4, "CONV_K5S1": 5}[kname]
     wt = torch.randn((cout, cin, k, k) if not kname.startswith("CONVT") else (cin, cout, k, k), device="cuda") / (cin * k) ** 0.5
@@ -151,7 +151,7 @@ def bench(kname, n, h, w, cin, cout, wino, bf16=False):
 def bench_first(n=8, h=256, w=256, cin=31, cout=64):
     """The generator's first layer on the NCHW window (conv_first_kernel; PWS_EXPERIMENT 25 = conv_mfma_kernel<k5s1, NCHW>)."""
     L, st = A.lib(), A.current_stream()
-    L.pws_set_option(100, int(os.environ.get("PWS_EXPERIMENT", "0")))
+    L.pws_set_option(A.OPT_EXPERIMENT, int(os.environ.get("PWS_EXPERIMENT", "0")))
     wt = torch.randn((cout, cin, 5, 5), device="cuda") / (cin * 25) ** 0.5
     wp = torch.empty(L.pws_packed_weight_floats(A.CONV_K5S1, cin, cout), device="cuda")
     A.check(L.pws_pack_conv_weight(A.ptr(wt), A.ptr(wp), A.CONV_K5S1, cin, cout, st), "pack")
@@ -183,7 +183,7 @@ def bench_first(n=8, h=256, w=256, cin=31, cout=64):
     ms = sorted(x_[4] for x_ in r)[len(r) // 2]
     print("first layer n=%d %dx%d %d->%d exp=%s %-30s: %8.1f us  %6.1f TFLOP/s (algorithmic)" % (
         n, h, w, cin, cout, os.environ.get("PWS_EXPERIMENT", "0"), r[0][0], ms * 1e3, r[0][2] / (ms * 1e-3) / 1e12))
-    L.pws_set_option(100, 0)
+    L.pws_set_option(A.OPT_EXPERIMENT, 0)
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """fp32 inference (batch 8, graph + two queues, as bench.py's headline leg) under PWS_EXPERIMENT values:
-    python tools/fp32_infer_ab.py 0 26 ..."""
+    python tools/fp32_infer_ab.py 0 22 ..."""
 import os
 import sys
 import time
@@ -18,7 +18,7 @@ net = net.cuda()
 x = torch.from_numpy(synth.noise_window(8, 31, 256, 123)).cuda()
 for rep in range(2):
     for e in [int(v) for v in sys.argv[1:]] or [0]:
-        A.lib().pws_set_option(100, e)
+        A.lib().pws_set_option(A.OPT_EXPERIMENT, e)
         net.module.enable_graph(False)
         net.module.enable_graph(True)
         with torch.no_grad():
@@ -31,4 +31,4 @@ for rep in range(2):
             torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / 100
         print("exp %4d: %.3f ms per batch of 8 = %.0f frames/s" % (e, dt * 1e3, 8 / dt))
-A.lib().pws_set_option(100, 0)
+A.lib().pws_set_option(A.OPT_EXPERIMENT, 0)

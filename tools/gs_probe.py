@@ -12,7 +12,7 @@ from pwstablenet_amd import hipabi as A  # noqa: E402
 
 v = int(os.environ.get("PWS_GS_VARIANT", "2"))
 case = os.environ.get("PWS_GS_CASE", "gs256")
-A.lib().pws_set_option(100, v)
+A.lib().pws_set_option(A.OPT_EXPERIMENT, v)
 torch.manual_seed(0)
 if case in ("gs256", "gs720"):
     shape = (256, 3, 256, 256) if case == "gs256" else (16, 3, 720, 1280)

@@ -23,7 +23,7 @@ for GB in (64, 256):
               (4.0 / 256) * (torch.sin(3 * ramp).view(1, 256, 1, 1) * torch.cos(2 * ramp).view(1, 1, 256, 1))}
     for name, grid in fields.items():
         res, outs = {}, {}
-        for exp, tag in ((0, "paired gathers"), (5, "row window + shuffle")):
+        for exp, tag in ((0, "paired gathers"), (A.Exp.GS_ROWWIN, "row window + shuffle")):
             L.pws_set_option(A.OPT_EXPERIMENT, exp)
             with torch.no_grad():
                 for _ in range(3):

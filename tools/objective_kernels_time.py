@@ -13,7 +13,7 @@ from pwstablenet_amd import hipabi as A  # noqa: E402
 m = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 n, h, w, nf = m // 2, 256, 256, 400
 L = A.lib()
-L.pws_set_option(100, int(os.environ.get("PWS_EXPERIMENT", "0")))
+L.pws_set_option(A.OPT_EXPERIMENT, int(os.environ.get("PWS_EXPERIMENT", "0")))
 g = torch.Generator(device="cuda").manual_seed(3)
 base = torch.stack(torch.meshgrid(torch.linspace(-1, 1, 256, device="cuda"), torch.linspace(-1, 1, 256, device="cuda"), indexing="ij")[::-1], -1)
 grid = (base[None] + 0.05 * torch.randn(m, h, w, 2, device="cuda", generator=g)).contiguous()

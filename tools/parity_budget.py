@@ -52,8 +52,7 @@ def main():
         print("%-86s %12s %12s %14s" % ("path", "field err", "warped err", "warped - product"))
         base = None
         for mask, what in FAMILIES:
-            L.pws_set_option(A.OPT_EXPERIMENT, 3000 + mask if mask else 0)
-            try:
+            with A.experiment(A.Exp.PARITY_LEDGER + mask if mask else 0):
                 net = define_G(31, 2, 64, "normal", 0.02)
                 net.load_state_dict({"module." + k: torch.from_numpy(v) for k, v in weights})
                 net = net.cuda()
@@ -64,8 +63,6 @@ def main():
                     w = PF.grid_sample(fr.cuda(), f)
                 ferr = float((f.cpu() - field).abs().max())
                 werr = float((w.cpu() - warped).abs().max()) / 127.5
-            finally:
-                L.pws_set_option(A.OPT_EXPERIMENT, 0)
             if base is None:
                 base = werr
             print("%-86s %12.3e %12.3e %+14.3e" % (what, ferr, werr, werr - base), flush=True)

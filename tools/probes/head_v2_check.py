@@ -12,7 +12,7 @@ for store in ("fp32", "bf16"):
         wout = torch.randn((9, c, 2), device="cuda", generator=g) * 0.05
         bout = torch.randn(2, device="cuda", generator=g) * 0.1
         out = {}
-        for e in (0, 35):
+        for e in (0, A.Exp.HEAD_V1):
             L.pws_set_option(A.OPT_EXPERIMENT, e)
             res = torch.full((n, h, w, 2), float("nan"), device="cuda")
             A.check(L.pws_field_head_fwd_s(ctypes.c_void_p(x.data_ptr()), c, n, h, w, c, A.ptr(wout), A.ptr(bout), None, 0, A.ptr(res), None,

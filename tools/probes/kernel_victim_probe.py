@@ -20,7 +20,7 @@ from pwstablenet_amd import synth  # noqa: E402
 secs = float(sys.argv[1]) if len(sys.argv) > 1 else 4.0
 amath = sys.argv[2] if len(sys.argv) > 2 else "bf16"
 L = A.lib()
-L.pws_set_option(100, int(os.environ.get("PWS_EXPERIMENT", "0")))
+L.pws_set_option(A.OPT_EXPERIMENT, int(os.environ.get("PWS_EXPERIMENT", "0")))
 m, n, h, w = 4, 2, 256, 256
 g = torch.Generator(device="cuda").manual_seed(3)
 base = torch.stack(torch.meshgrid(torch.linspace(-1, 1, 256, device="cuda"), torch.linspace(-1, 1, 256, device="cuda"), indexing="ij")[::-1], -1)

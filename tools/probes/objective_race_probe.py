@@ -19,7 +19,7 @@ from pwstablenet_amd import synth  # noqa: E402
 from pwstablenet_amd.objective import StabObjective, u8_normalize  # noqa: E402
 
 from pwstablenet_amd import hipabi as A  # noqa: E402
-A.lib().pws_set_option(100, int(os.environ.get("PWS_EXPERIMENT", "0")))
+A.lib().pws_set_option(A.OPT_EXPERIMENT, int(os.environ.get("PWS_EXPERIMENT", "0")))
 if os.environ.get("PROBE_TWO_QUEUES") is not None:
     A.lib().pws_set_option(A.OPT_TWO_QUEUES, int(os.environ["PROBE_TWO_QUEUES"]))
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 300

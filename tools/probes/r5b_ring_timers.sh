@@ -12,7 +12,7 @@ for shape in "CONVT_K4S2 64 128 128 256 64" "CONVT_K4S2 64 64 64 512 128" "CONV_
 done
 ) > gpurun_out/r5b/timers.txt 2>&1
 (
-for e in 0 41 42 44 43 45 46 47 0; do
+for e in 0 1501 1502 1504 1503 1505 1506 1507 0; do
   export PWS_EXPERIMENT=$e
   python tools/conv_bench.py CONVT_K4S2 64 128 128 256 64 bf16
   python tools/conv_bench.py CONVT_K4S2 64 128 128 256 64 bf16 dgrad

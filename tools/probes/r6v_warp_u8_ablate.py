@@ -10,7 +10,7 @@ th=torch.tensor([1,0,0,0,1,0],device=dev,dtype=torch.float32).repeat(B,1)
 ramp=torch.linspace(0,6.28,256,device=dev)
 field=PF.affine_grid(th+0.02*torch.randn_like(th),(B,3,256,256))+(4.0/256)*(torch.sin(3*ramp).view(1,256,1,1)*torch.cos(2*ramp).view(1,1,256,1))
 L=A.lib()
-for exp in (0,49,4,0):
+for exp in (0, A.Exp.GS_U8_LANE_WINDOWS, A.Exp.U8_CVT_SHIFT, 0):
     L.pws_set_option(A.OPT_EXPERIMENT, exp)
     with torch.no_grad():
         for i in range(8): PF.upsample_grid_sample_u8(rot[i%4],field,swap_rb=True)

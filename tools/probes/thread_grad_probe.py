@@ -92,7 +92,7 @@ def tagged(fn, tag):
 rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 12
 math = sys.argv[2] if len(sys.argv) > 2 else "bf16"
 variant = sys.argv[3] if len(sys.argv) > 3 else "all"
-A.lib().pws_set_option(100, int(os.environ.get("PWS_EXPERIMENT", "0")))
+A.lib().pws_set_option(A.OPT_EXPERIMENT, int(os.environ.get("PWS_EXPERIMENT", "0")))
 _tq = False if os.environ.get("PROBE_CU_MASK") == "1" else None
 works = [T._train_work("W1", 11, math, 2, two_queues=_tq), T._train_work("W2", 12, math, 2, two_queues=_tq)]
 infer_net = T.make_net("W1", 5)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of the bf16 conv kernels on the configs[2] layer shapes (batch 64 = 32 item pairs x 2 forwards), bf16 storage, inputs rotated
-# through 3 buffers.  PWS_EXPERIMENT: 20 = first-generation conv_bf16_kernel, 0 = ring kernel (product), 31 / 32 = ring depth variants.
+# through 3 buffers.  PWS_EXPERIMENT: 20 = first-generation conv_bf16_kernel, 0 = ring kernel (product).
 export CONV_BENCH_STORE16=1 CONV_BENCH_ROTATE=3
 EXPS="${EXPS:-20 0}"
 for e in $EXPS; do

@@ -34,7 +34,7 @@ with torch.no_grad():
 L = A.lib()
 for name, field in fields.items():
     res = {}
-    for exp, tag in ((0, "product"), (4, "clamp + shift")):
+    for exp, tag in ((0, "product"), (A.Exp.U8_CVT_SHIFT, "clamp + shift")):
         L.pws_set_option(A.OPT_EXPERIMENT, exp)
         with torch.no_grad():
             for i in range(8):

@@ -14,7 +14,7 @@ from pwstablenet_amd import hipabi as A  # noqa: E402
 def main():
     kname, n, h, w, cin, cout = sys.argv[1], *map(int, sys.argv[2:7])
     L, st = A.lib(), A.current_stream()
-    L.pws_set_option(100, int(os.environ.get("PWS_EXPERIMENT", "0")))
+    L.pws_set_option(A.OPT_EXPERIMENT, int(os.environ.get("PWS_EXPERIMENT", "0")))
     kind = getattr(A, kname)
     k = {"CONV_K3S1": 3, "CONV_K3S2": 3, "CONVT_K3S1": 3, "CONVT_K4S2": 4, "CONV_K5S1": 5}[kname]
     oh, ow = (h, w) if "S1" in kname else ((h // 2, w // 2) if kname == "CONV_K3S2" else (2 * h, 2 * w))

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Ring weight-gradient kernel (PWS_EXPERIMENT 0; 82 = transposed kind with one class per workgroup) vs wgrad_bf16_kernel (80) on the
+# Ring weight-gradient kernel (PWS_EXPERIMENT 0) vs wgrad_bf16_kernel (80) on the
 # layers that dominate the configs[2] step (batch 64)
 for e in ${WGR_EXPS:-0 80}; do
   export PWS_EXPERIMENT=$e

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Winograd ring kernel (PWS_EXPERIMENT 0) vs the kernels that run without it (50) on the generator's conv_same and transposed
-# layers (batch 8).  WRING_EXPS selects other variants (timing-only ablations: 1000 + mask, see WringParams.ablate).
+# layers (batch 8).  WRING_EXPS selects other variants (timing-only ablations: 4000 + mask, see WringParams.ablate).
 export CONV_BENCH_ROTATE=3
 for e in ${WRING_EXPS:-0 50}; do
   export PWS_EXPERIMENT=$e
