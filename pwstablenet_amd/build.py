@@ -11,9 +11,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libpwstable_hip.so")
-SOURCES = ["abi.cpp", "netg.cpp", "netg_pack.hip", "pack.hip", "conv_mfma.hip", "conv_bf16.hip", "conv_ring.hip", "conv_ring_f32.hip", "conv_first.hip", "conv_first_wino.hip", "conv_wgrad.hip", "wgrad_bf16.hip", "wgrad_ring.hip", "conv_wino.hip", "conv_wring.hip", "conv_skinny.hip", "conv_skinny16.hip", "head.hip", "head_bwd.hip", "grid_sample.hip",
+SOURCES = ["abi.cpp", "netg_layers.cpp", "netg_forward.cpp", "netg_backward.cpp", "netg_pack.hip", "pack.hip", "conv_mfma.hip", "conv_bf16.hip", "conv_ring.hip", "conv_ring_f32.hip", "conv_first.hip", "conv_first_wino.hip", "conv_wgrad.hip", "wgrad_bf16.hip", "wgrad_ring.hip", "conv_wino.hip", "conv_wring.hip", "conv_skinny.hip", "conv_skinny16.hip", "head.hip", "head_bwd.hip", "grid_sample.hip",
            "adam.hip", "objective.hip", "pool.hip", "frameio.hip", "bnorm.hip", "homography.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+HEADERS = ["common.h", "conv_common.h", "experiments.h", "netg_pack.h", "netg_layers.h", "netg_exec.h", os.path.join("..", "..", "include", "pwstable.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 
@@ -22,16 +23,14 @@ def source_hash():
     profiles/ carry it (`_meta.source_hash`), and bench.py only quotes counter-derived figures whose hash matches the build."""
     import hashlib
     h = hashlib.sha256()
-    files = sorted(SOURCES + ["common.h", "conv_common.h", "experiments.h", "netg_pack.h"])
-    for f in files + [os.path.join("..", "..", "include", "pwstable.h")]:
+    for f in sorted(SOURCES + HEADERS[:-1]) + HEADERS[-1:]:
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(f.encode() + b"\0" + fh.read() + b"\0")
     return h.hexdigest()[:16]
 
 
 def _deps():
-    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "experiments.h"), os.path.join(CSRC, "netg_pack.h"), os.path.join(HERE, "..", "include", "pwstable.h"), os.path.abspath(__file__)]
-    return max(os.path.getmtime(h) for h in hdrs)
+    return max(os.path.getmtime(h) for h in [os.path.join(CSRC, h) for h in HEADERS] + [os.path.abspath(__file__)])
 
 
 def _resources(stderr_text):

@@ -111,7 +111,7 @@ int nchw_to_nhwc_pad_strided(const float *x, size_t sample_stride, float *out, i
 struct ProfHint {
     double flops, bytes;
 };
-// use_BN training path: pieces of the two heads sequenced by netg.cpp (head.hip / head_bwd.hip)
+// use_BN training path: pieces of the two heads sequenced by netg_exec.h / netg_backward.cpp (head.hip / head_bwd.hip)
 int theta_z1(const float *x, int n, int c, int hidden, const float *w_flat, const float *b_flat, float *ws, float *z1, hipStream_t st);
 int theta_z2(const float *h, int n, int hidden, const float *w_lin, const float *b_lin, float *z2, hipStream_t st);
 int field_head_raw(const float *x, int ld, int n, int h, int w, int c, const float *w_out, const float *b_out, float *z, hipStream_t st);

@@ -19,8 +19,8 @@ enum Exp : int {
     EXP_GS_BWD_GENERAL = 2,        // grid_sample.hip REFERENCE: the general backward kernel for the field-only gradient; never non-temporal
     EXP_U8_CVT_SHIFT = 4,          // grid_sample.hip REFERENCE: uint8 warp, float -> byte by (int) + clamp + shift; never non-temporal
     EXP_GS_ROWWIN = 5,             // grid_sample.hip REFERENCE: grid_sample_fwd2_kernel's row window + wave shuffle
-    EXP_NO_SIGN_BITS = 12,         // netg.cpp, conv_ring.hip REFERENCE: sign-bit epilogues off
-    EXP_NETG_PER_STAGE = 15,       // netg.cpp REFERENCE: the per-stage forward schedule instead of the lockstep one
+    EXP_NO_SIGN_BITS = 12,         // netg_exec.h, conv_ring.hip REFERENCE: sign-bit epilogues off
+    EXP_NETG_PER_STAGE = 15,       // netg_forward.cpp REFERENCE: the per-stage forward schedule instead of the lockstep one
     EXP_RING_OFF = 20,             // conv_ring.hip REFERENCE: conv_bf16_kernel instead of the bf16 ring kernel
     EXP_RING_SMALL = 21,           // conv_ring.hip FORCE: the ring kernel also for launches too small to fill the chip
     EXP_RINGF_OFF = 22,            // conv_ring_f32.hip REFERENCE: conv_mfma_kernel instead of the fp32 ring kernel
@@ -50,7 +50,7 @@ enum Exp : int {
     EXP_TL1_TILED = 98,            // objective.hip REFERENCE: temporal_l1_bwd_tiled_kernel
     EXP_RING_8WAVE = 105,          // conv_ring.hip REFERENCE: the eight-wave kernel on 32-wide tiles
     EXP_SMOOTH_ONE_PIXEL = 110,    // objective.hip REFERENCE: field smoothness with one pixel per lane
-    EXP_NO_PACK_ONE_PASS = 120,    // netg.cpp REFERENCE: no one-pass bf16 weight packing
+    EXP_NO_PACK_ONE_PASS = 120,    // netg_layers.cpp REFERENCE: no one-pass bf16 weight packing
     EXP_RING_UNIT256 = 186,        // conv_ring.hip FORCE: units of 256 pixels
     EXP_RING_UNIT128 = 187,        // conv_ring.hip FORCE: units of 128 pixels
     EXP_WGRAD_NO_MERGE = 188,      // wgrad_bf16.hip REFERENCE: a shared layer's operand pairs as two launches

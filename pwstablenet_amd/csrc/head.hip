@@ -577,7 +577,7 @@ __global__ void __launch_bounds__(256) field_head32_mfma_kernel(const float *__r
     }
 }
 
-// ---- use_BN training-mode pieces of the two heads (netg.cpp sequences them with pws_bn_train_fwd in between)
+// ---- use_BN training-mode pieces of the two heads (netg_exec.h sequences them with pws_bn_train_fwd in between)
 // z1[n][j] = sum over K slices of the hidden pre-activations + b1[j]   (theta_hidden_kernel's partials)
 __global__ void __launch_bounds__(256) theta_sum_kernel(const float *__restrict__ partial, int nslices, int n, int hidden,
                                                         const float *__restrict__ b_flat, float *__restrict__ z1) {
@@ -631,7 +631,7 @@ static int theta_slices(int k1) {
     return (k1 + kchunk - 1) / kchunk;
 }
 
-// ---- host helpers of the use_BN training path (declared in common.h, called by netg.cpp; not part of the C ABI)
+// ---- host helpers of the use_BN training path (declared in common.h, called by netg_exec.h and netg_backward.cpp; not part of the C ABI)
 namespace pws {
 int theta_z1(const float *x, int n, int c, int hidden, const float *w_flat, const float *b_flat, float *ws, float *z1, hipStream_t st) {
     const int k1 = 4 * c, kchunk = 64, nslices = theta_slices(k1);

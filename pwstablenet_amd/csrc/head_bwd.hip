@@ -603,7 +603,7 @@ extern "C" int pws_field_head_bwd(const float *x, int ld, int n, int h, int w, i
                                 db_out, dtheta, ws, PWS_STORE_FP32, stream);
 }
 
-// The field head's backward in two halves (netg.cpp puts the BatchNorm backward of the `out` layer between them when use_BN):
+// The field head's backward in two halves (netg_backward.cpp puts the BatchNorm backward of the `out` layer between them when use_BN):
 // gz: gz = d loss / d (input of tanh(tanh(.))), dtheta, [db_out];  dx_dw: data and weight gradient of the 3x3 conv from gz.
 namespace pws {
 int field_bwd_gz(const float *resid, const float *g_grid, const float *g_resid, int n, int h, int w, int ac, float *gz, float *db_out,

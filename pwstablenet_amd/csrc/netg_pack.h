@@ -1,4 +1,4 @@
-// Argument blocks of the whole-generator pack / unpack kernels (netg_pack.hip), filled by netg.cpp from its layer table.
+// Argument blocks of the whole-generator pack / unpack kernels (netg_pack.hip), filled by netg_layers.cpp from its layer table.
 #pragma once
 #include "common.h"
 

@@ -319,7 +319,7 @@ __global__ void __launch_bounds__(256) unpack_all_kernel(const UnpackAllArgs a, 
 
 // ---- one pass for a bf16 training step: torch tensor tile -> LDS -> bf16 forward layout [plane][cout][cin_pad] AND bf16 data-gradient
 // layout [plane][cin][cout] (both k-contiguous, as bf16_all_kernel writes them), + the bias.  Only for layers whose padded extents are
-// the real ones (netg.cpp: cout % 64 == 0, cin_pad % 32 == 0; with a data-gradient copy cin % 64 == 0 too), so the tiles cover every
+// the real ones (netg_layers.cpp: cout % 64 == 0, cin_pad % 32 == 0; with a data-gradient copy cin % 64 == 0 too), so the tiles cover every
 // element of both destinations and nothing is left to zero-fill.  Per step and generator: 194 MB read + 2 x 97 MB written, against
 // 194 + 194 (pack) + 194 + 97 (bf16) + 194 + 194 (data-gradient pack) + 194 + 97 (bf16) with the four launches it replaces.
 __global__ void __launch_bounds__(256) pack16_all_kernel(const Pack16Args a, float *__restrict__ packed, float *__restrict__ packed_dgrad) {

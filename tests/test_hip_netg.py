@@ -173,7 +173,7 @@ def test_use_bn_eval_inference_vs_reference_golden(hip):
 @pytest.mark.parametrize("math", ["fp32", "bf16"])
 def test_lockstep_schedule_equals_the_per_stage_schedule(hip, math):
     """Round 4: stages 2 and 3 run in lockstep -- the 23 layers they share go out as ONE launch of batch 2n on sample-group views of
-    shared buffers (csrc/netg.cpp forward_lockstep; reference lib/networks_cascading.py:178-219 runs them one after the other).
+    shared buffers (csrc/netg_forward.cpp forward_lockstep; reference lib/networks_cascading.py:178-219 runs them one after the other).
     PWS_OPT_EXPERIMENT 15 keeps the per-stage schedule: same layers on the same inputs, so the six training fields and the inference
     field agree to rounding (a launch of twice the batch may split K differently: fp32 summation order), and so does one backward
     (the tape holds one op per stage in either schedule)."""

@@ -1,5 +1,5 @@
 """include/pwstable.h:9-14 promises "re-entrant per stream and per thread" with ONE side queue per device shared by the host
-threads (csrc/netg.cpp: shared_side_queue / SideStream::pick).  The reference's ``nn.DataParallel`` runs one Python thread per
+threads (csrc/netg_exec.h: shared_side_queue / SideStream::pick).  The reference's ``nn.DataParallel`` runs one Python thread per
 replica inside ``forward`` (lib/networks_cascading.py:51-52), so this is a path its users take.
 
 Two host threads, each on its own torch stream, run concurrently -- eager inference, hipGraph capture + replay, and one whole

@@ -42,7 +42,7 @@ NGF, NB, S = 64, 64, 256            # the product's width, the step's batch (32 
 SPECS = spec.layer_specs(31, 2, NGF)
 HEADS = (15, 44, 45)                 # out (field head), flatten, linear (theta head): kernels of their own (tests/test_hip_heads.py)
 WGRAD_KERNELS = ("wgrad_mfma_kernel", "wgrad_bf16_kernel", "wgrad_ring_kernel")
-RING_LAYERS = {0, 11, 12, 13, 14, 16, 18, 20, 22, 36, 37, 38, 39, 40, 41, 42, 43}   # netg.cpp build_layers(ring = true)
+RING_LAYERS = {0, 11, 12, 13, 14, 16, 18, 20, 22, 36, 37, 38, 39, 40, 41, 42, 43}   # netg_layers.cpp build_layers(ring = true)
 
 # bounds (relative to max |float64 reference| of the whole tensor).  fp32 math: exact-fp32 products; the error is the rounding of the
 # fp32 sums (chains of cin * taps terms per output, in the orders of tiles, K splits and Winograd transforms), far below the
@@ -65,7 +65,7 @@ def _kname(ls):
 
 def _layer(li):
     """(kname, input side, [source channels], [producer act of each source], cout, act of the output) of layer li as the executor
-    runs it (netg.cpp forward_lockstep: x_sk, conv_same outputs, d_s(l) = cat(v_sl, x_sl))."""
+    runs it (netg_forward.cpp forward_lockstep: x_sk, conv_same outputs, d_s(l) = cat(v_sl, x_sl))."""
     g = NGF
     enc_c = [0, g, g, 2 * g, 4 * g, 4 * g, 4 * g, 4 * g, 4 * g]
     dec_c = [0, g, g, 2 * g, 4 * g, 4 * g, 4 * g, 4 * g]
@@ -590,7 +590,7 @@ def check_fwd(A, ly, n, kernel, seed):
     a.math, a.store = (A.MATH_BF16, A.STORE_BF16) if bf else (A.MATH_FP32, A.STORE_FP32)
     if bf:
         a.w_bf16 = ly.wb.data_ptr()
-        if oh >= 32:                                # netg.cpp wants_sign: the executor keeps the sign bits of this output
+        if oh >= 32:                                # netg_exec.h wants_sign: the executor keeps the sign bits of this output
             sign = torch.zeros((n * oh * oh, ly.cout // 8), device="cuda", dtype=torch.uint8)
             a.out_sign, a.out_sign_ld = sign.data_ptr(), ly.cout // 8
     else:
