@@ -394,6 +394,24 @@ int pws_area_resize_plane_u8(const unsigned char *in, size_t in_stride, unsigned
 int pws_upsample_grid_sample_yuv420_u8(const unsigned char *frames, const float *field, unsigned char *out, int n, int h, int w, int fh,
                                        int fw, int layout, int align_corners, pws_stream_t stream);
 
+/* 10-bit 4:2:0 frames [n][h*3/2][w] of little-endian 16-bit words in the 8-bit formats' plane order; layout 0 P010 (the Y plane, then h/2 rows
+ * of interleaved U V; the sample in the HIGH 10 bits, word = v10 << 6; the low 6 bits of input words are ignored, output words have them
+ * zero), 1 I010 / yuv420p10le (Y, U and V planes; the sample in the LOW 10 bits; input words above 1023 are clamped).  BT.601 limited range.
+ * out[n,oh,ow] = pws_gray_area_yuv420_u8 of the frames' 8-bit reduction v8 = min(255, (v10 + 2) >> 2), fused into the loads: the planes of
+ * the NV12 / I420 clip of the reduced samples bit for bit.  h and w even. */
+int pws_gray_area_yuv420_u16(const unsigned short *frames, float *out, int n, int h, int w, int oh, int ow, int normalize, int layout,
+                             pws_stream_t stream);
+/* INTER_AREA of a 1- or 2-channel plane of 10-bit samples [n][h][w][c] -> [n][oh][ow][c] on the 10-bit values (cv::resize's dispatch for
+ * 16-bit unsigned: 2 x 2 mean, integer-ratio block sum * float(1 / area), area tables), saturated to 0..1023 and stored in the layout's
+ * placement; in / out point at sample 0's plane, samples in_stride / out_stride 16-bit WORDS apart (the planes of packed frames). */
+int pws_area_resize_plane_u16(const unsigned short *in, size_t in_stride, unsigned short *out, size_t out_stride, int n, int h, int w, int c,
+                              int oh, int ow, int layout, pws_stream_t stream);
+/* pws_upsample_grid_sample_yuv420_u8 for 10-bit frames (layout as pws_gray_area_yuv420_u16), YUV in and out: each plane is warped by the
+ * field resized (align_corners=True) to the plane's own size, fp32 blend of the 10-bit values truncated and clamped to 0..1023; taps outside
+ * a plane read 64 (Y) / 512 (U, V), BT.601 black.  h even, w % 4 == 0, frames and out 8-byte aligned.  6 bytes of frame traffic per pixel. */
+int pws_upsample_grid_sample_yuv420_u16(const unsigned short *frames, const float *field, unsigned short *out, int n, int h, int w, int fh,
+                                        int fw, int layout, int align_corners, pws_stream_t stream);
+
 /* The automatic crop of the reference's video loop (main_new.py:484-606, a block it keeps inside a string literal), per frame
  * (csrc/homography.hip): field[n,fh,fw,2] resized to the h0 x w0 source frame as pws_upsample_bilinear_ac does is sampled on the
  * 20 x 20 lattice rows h0/2 + (a-10)*15, columns w0/2 + (b-10)*30 (p1, fp32); the homography M (m33 = 1) from p1 to the lattice's own

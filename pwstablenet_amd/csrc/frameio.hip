@@ -277,6 +277,132 @@ __global__ void __launch_bounds__(256) area_tab_plane_kernel(const unsigned char
     for (int c = 0; c < C; ++c) o[c] = (unsigned char)fminf(fmaxf(rintf(sum[c]), 0.f), 255.f);
 }
 
+// ---- 10-bit 4:2:0 frames ([n][h*3/2][w] little-endian 16-bit words, the 8-bit formats' plane order): LAYOUT 0 P010 (the sample in the HIGH 10 bits
+// of its word, word = v10 << 6, as hardware decoders deliver it; the low 6 bits of an input word are ignored), 1 I010 / yuv420p10le (the sample in the
+// LOW 10 bits; words above 1023 are clamped).  BT.601 limited range like the 8-bit path.
+template <int LAYOUT>
+__device__ __forceinline__ int sample10(unsigned short word) { return LAYOUT == 0 ? word >> 6 : min((int)word, 1023); }
+template <int LAYOUT>
+__device__ __forceinline__ unsigned short place10(int v10) { return (unsigned short)(LAYOUT == 0 ? v10 << 6 : v10); }
+// the 8-bit reduction the generator sees (it was trained on 8-bit gray): round to nearest, saturate
+template <int LAYOUT>
+__device__ __forceinline__ int reduce8(unsigned short word) { return min(255, (sample10<LAYOUT>(word) + 2) >> 2); }
+
+// gray_yuv420 above on the reduced samples, the reduction fused into the loads (no 8-bit copy of the frames)
+template <int LAYOUT>   // 0 P010 (NV12's plane order), 1 I010 (I420's)
+__device__ __forceinline__ int gray_yuv420_u16(const unsigned short *f, int H, int W, int x, int y) {
+    const int Y = reduce8<LAYOUT>(f[(size_t)y * W + x]);
+    const unsigned short *c = f + (size_t)H * W;
+    int U, V;
+    if (LAYOUT == 0) {
+        const unsigned short *p = c + (size_t)(y >> 1) * W + (x & ~1);
+        U = reduce8<LAYOUT>(p[0]), V = reduce8<LAYOUT>(p[1]);
+    } else {
+        const size_t o = (size_t)(y >> 1) * (W >> 1) + (x >> 1);
+        U = reduce8<LAYOUT>(c[o]), V = reduce8<LAYOUT>(c[o + (size_t)(H >> 1) * (W >> 1)]);
+    }
+    const int yy = max(0, Y - 16) * 1220542, u = U - 128, v = V - 128;
+    const int r = sat_u8((yy + 1673527 * v + (1 << 19)) >> 20);
+    const int g = sat_u8((yy - 852492 * v - 409993 * u + (1 << 19)) >> 20);
+    const int b = sat_u8((yy + 2116026 * u + (1 << 19)) >> 20);
+    return (b * 3735 + g * 19235 + r * 9798 + (1 << 14)) >> 15;
+}
+
+// one lane per destination pixel, gray_area_yuv420_kernel's arithmetic in its order: the planes of the NV12 / I420 clip of the reduced samples bit for bit
+template <int LAYOUT>
+__global__ void __launch_bounds__(256) gray_area_yuv420_u16_kernel(const unsigned short *__restrict__ frames, float *__restrict__ out, int H, int W,
+                                                                   int OH, int OW, double sy, double sx, int normalize, size_t total) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int dx = (int)(i % OW), dy = (int)((i / OW) % OH);
+    const size_t n = i / ((size_t)OW * OH);
+    const AreaAxis tx = area_axis(dx, W, sx), ty = area_axis(dy, H, sy);
+    const unsigned short *f = frames + n * ((size_t)H * W * 3 / 2);
+    float sum = 0.f;
+    for (int j = 0; j < ty.n; ++j) {
+        int sj, sk;
+        float beta, alpha;
+        ty.tap(j, sj, beta);
+        float buf = 0.f;
+        for (int k = 0; k < tx.n; ++k) {
+            tx.tap(k, sk, alpha);
+            buf = buf + mul_rounded((float)gray_yuv420_u16<LAYOUT>(f, H, W, sk, sj), alpha);
+        }
+        sum = j == 0 ? mul_rounded(beta, buf) : sum + mul_rounded(beta, buf);
+    }
+    const float g8 = fminf(fmaxf(rintf(sum), 0.f), 255.f);
+    out[i] = normalize ? g8 / 255 * 2 - 1 : g8;
+}
+
+// INTER_AREA of a C-channel plane of 10-bit samples (C = 1: Y, I010's U or V; C = 2: P010's UV), cv::resize's dispatch for 16-bit unsigned on the
+// 10-bit VALUES: 2 x 2 mean (ResizeAreaFastVec_SIMD_16u), integer ratios the block sum * float(1 / area) (resizeAreaFast_<ushort, float>: the float
+// sum of a block of 10-bit values is exact), else the area tables; saturate to 0..1023, stored in the layout's placement.  in / out: the plane of
+// sample 0; samples ist / ost WORDS apart.  One lane per pixel.
+template <int C, int LAYOUT>
+__global__ void __launch_bounds__(256) area_half_plane_u16_kernel(const unsigned short *__restrict__ in, size_t ist, unsigned short *__restrict__ out,
+                                                                  size_t ost, int H, int W, size_t total) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int OW = W / 2, OH = H / 2;
+    const int ox = (int)(i % OW), oy = (int)((i / OW) % OH);
+    const size_t n = i / ((size_t)OW * OH);
+    const unsigned short *p = in + n * ist + ((size_t)2 * oy * W + 2 * ox) * C;
+    const unsigned short *q = p + (size_t)W * C;
+    unsigned short *o = out + n * ost + ((size_t)oy * OW + ox) * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+        o[c] = place10<LAYOUT>((sample10<LAYOUT>(p[c]) + sample10<LAYOUT>(p[C + c]) + sample10<LAYOUT>(q[c]) + sample10<LAYOUT>(q[C + c]) + 2) >> 2);
+}
+
+template <int C, int LAYOUT>
+__global__ void __launch_bounds__(256) area_int_plane_u16_kernel(const unsigned short *__restrict__ in, size_t ist, unsigned short *__restrict__ out,
+                                                                 size_t ost, int H, int W, int OH, int OW, int ky, int kx, float scale, size_t total) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int ox = (int)(i % OW), oy = (int)((i / OW) % OH);
+    const size_t n = i / ((size_t)OW * OH);
+    const unsigned short *p = in + n * ist + ((size_t)oy * ky * W + (size_t)ox * kx) * C;
+    int s[C] = {};
+    for (int j = 0; j < ky; ++j) {
+        const unsigned short *q = p + (size_t)j * W * C;
+        for (int k = 0; k < kx; ++k)
+#pragma unroll
+            for (int c = 0; c < C; ++c) s[c] += sample10<LAYOUT>(q[C * k + c]);
+    }
+    unsigned short *o = out + n * ost + ((size_t)oy * OW + ox) * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) o[c] = place10<LAYOUT>((int)fminf(fmaxf(rintf(mul_rounded((float)s[c], scale)), 0.f), 1023.f));
+}
+
+template <int C, int LAYOUT>
+__global__ void __launch_bounds__(256) area_tab_plane_u16_kernel(const unsigned short *__restrict__ in, size_t ist, unsigned short *__restrict__ out,
+                                                                 size_t ost, int H, int W, int OH, int OW, double sy, double sx, size_t total) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int dx = (int)(i % OW), dy = (int)((i / OW) % OH);
+    const size_t n = i / ((size_t)OW * OH);
+    const AreaAxis tx = area_axis(dx, W, sx), ty = area_axis(dy, H, sy);
+    const unsigned short *f = in + n * ist;
+    float sum[C] = {};
+    for (int j = 0; j < ty.n; ++j) {
+        int sj, sk;
+        float beta, alpha;
+        ty.tap(j, sj, beta);
+        const unsigned short *row = f + (size_t)sj * W * C;
+        float buf[C] = {};
+        for (int k = 0; k < tx.n; ++k) {
+            tx.tap(k, sk, alpha);
+#pragma unroll
+            for (int c = 0; c < C; ++c) buf[c] = buf[c] + mul_rounded((float)sample10<LAYOUT>(row[(size_t)sk * C + c]), alpha);
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) sum[c] = j == 0 ? mul_rounded(beta, buf[c]) : sum[c] + mul_rounded(beta, buf[c]);
+    }
+    unsigned short *o = out + n * ost + ((size_t)dy * OW + dx) * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) o[c] = place10<LAYOUT>((int)fminf(fmaxf(rintf(sum[c]), 0.f), 1023.f));
+}
+
 }  // namespace pws
 
 using namespace pws;
@@ -380,4 +506,64 @@ extern "C" int pws_area_resize_plane_u8(const unsigned char *in, size_t in_strid
     if (c == 1) hipLaunchKernelGGL(area_tab_plane_kernel<1>, grid, blk, 0, st, in, in_stride, out, out_stride, h, w, oh, ow, sy, sx, total);
     else hipLaunchKernelGGL(area_tab_plane_kernel<2>, grid, blk, 0, st, in, in_stride, out, out_stride, h, w, oh, ow, sy, sx, total);
     return check_launch("area_tab_plane_kernel");
+}
+
+extern "C" int pws_gray_area_yuv420_u16(const unsigned short *frames, float *out, int n, int h, int w, int oh, int ow, int normalize, int layout,
+                                        pws_stream_t stream) {
+    PWS_REQUIRE(n >= 0 && h > 0 && w > 0 && oh > 0 && ow > 0 && oh <= h && ow <= w, "pws_gray_area_yuv420_u16: bad shape (down-scaling only)");
+    PWS_REQUIRE(h % 2 == 0 && w % 2 == 0, "pws_gray_area_yuv420_u16: h and w must be even (got %d x %d)", w, h);
+    PWS_REQUIRE(layout == 0 || layout == 1, "pws_gray_area_yuv420_u16: layout must be 0 (P010) or 1 (I010), got %d", layout);
+    PWS_REQUIRE((double)h / oh <= AREA_MAX_TAPS - 2 && (double)w / ow <= AREA_MAX_TAPS - 2, "pws_gray_area_yuv420_u16: scale above %d",
+                AREA_MAX_TAPS - 2);
+    if (n == 0) return PWS_OK;
+    PWS_REQUIRE(frames && out, "pws_gray_area_yuv420_u16: NULL pointer");
+    PWS_REQUIRE((reinterpret_cast<size_t>(frames) & 1) == 0, "pws_gray_area_yuv420_u16: frames must be 2-byte aligned");
+    const size_t total = (size_t)n * oh * ow;
+    const double sy = 1.0 / ((double)oh / h), sx = 1.0 / ((double)ow / w);
+    // (frame I/O has no kernel id of its own: the 16-bit entries are booked under KID_OBJECTIVE like their 8-bit neighbours, on purpose)
+    ProfScope prof(KID_OBJECTIVE, 19.0 * n * h * w, 3.0 * n * h * w + 4.0 * total, as_stream(stream));
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (layout == 0)
+        hipLaunchKernelGGL(gray_area_yuv420_u16_kernel<0>, grid, dim3(256), 0, as_stream(stream), frames, out, h, w, oh, ow, sy, sx, normalize, total);
+    else
+        hipLaunchKernelGGL(gray_area_yuv420_u16_kernel<1>, grid, dim3(256), 0, as_stream(stream), frames, out, h, w, oh, ow, sy, sx, normalize, total);
+    return check_launch("gray_area_yuv420_u16_kernel");
+}
+
+extern "C" int pws_area_resize_plane_u16(const unsigned short *in, size_t in_stride, unsigned short *out, size_t out_stride, int n, int h, int w,
+                                         int c, int oh, int ow, int layout, pws_stream_t stream) {
+    PWS_REQUIRE(n >= 0 && h > 0 && w > 0 && oh > 0 && ow > 0 && oh <= h && ow <= w, "pws_area_resize_plane_u16: bad shape (down-scaling only)");
+    PWS_REQUIRE(c == 1 || c == 2, "pws_area_resize_plane_u16: 1 or 2 channels, got %d", c);
+    PWS_REQUIRE(layout == 0 || layout == 1, "pws_area_resize_plane_u16: layout must be 0 (P010) or 1 (I010), got %d", layout);
+    if (n == 0) return PWS_OK;
+    PWS_REQUIRE(in && out, "pws_area_resize_plane_u16: NULL pointer");
+    PWS_REQUIRE(((reinterpret_cast<size_t>(in) | reinterpret_cast<size_t>(out)) & 1) == 0, "pws_area_resize_plane_u16: in and out must be 2-byte aligned");
+    const size_t total = (size_t)n * oh * ow;
+    const dim3 grid((unsigned)((total + 255) / 256)), blk(256);
+    hipStream_t st = as_stream(stream);
+    ProfScope prof(KID_OBJECTIVE, (double)c * n * h * w, 2.0 * c * ((double)n * h * w + (double)total), st);
+#define PWS_AREA16(KERNEL_, ...)                                                                                       \
+    do {                                                                                                               \
+        if (c == 1 && layout == 0) hipLaunchKernelGGL((KERNEL_<1, 0>), grid, blk, 0, st, in, in_stride, out, out_stride, __VA_ARGS__);      \
+        else if (c == 1) hipLaunchKernelGGL((KERNEL_<1, 1>), grid, blk, 0, st, in, in_stride, out, out_stride, __VA_ARGS__);                \
+        else if (layout == 0) hipLaunchKernelGGL((KERNEL_<2, 0>), grid, blk, 0, st, in, in_stride, out, out_stride, __VA_ARGS__);           \
+        else hipLaunchKernelGGL((KERNEL_<2, 1>), grid, blk, 0, st, in, in_stride, out, out_stride, __VA_ARGS__);                            \
+    } while (0)
+    if (h == 2 * oh && w == 2 * ow) {   // OpenCV's 2 x 2 SIMD path
+        PWS_AREA16(area_half_plane_u16_kernel, h, w, total);
+        return check_launch("area_half_plane_u16_kernel");
+    }
+    if (h % oh == 0 && w % ow == 0) {
+        const int ky = h / oh, kx = w / ow;
+        const float scale = 1.f / (float)(kx * ky);
+        PWS_REQUIRE((size_t)kx * ky <= 16384, "pws_area_resize_plane_u16: block of %d x %d too large", kx, ky);   // (the float sum stays exact)
+        PWS_AREA16(area_int_plane_u16_kernel, h, w, oh, ow, ky, kx, scale, total);
+        return check_launch("area_int_plane_u16_kernel");
+    }
+    PWS_REQUIRE((double)h / oh <= AREA_MAX_TAPS - 2 && (double)w / ow <= AREA_MAX_TAPS - 2, "pws_area_resize_plane_u16: scale above %d",
+                AREA_MAX_TAPS - 2);
+    const double sy = 1.0 / ((double)oh / h), sx = 1.0 / ((double)ow / w);
+    PWS_AREA16(area_tab_plane_u16_kernel, h, w, oh, ow, sy, sx, total);
+#undef PWS_AREA16
+    return check_launch("area_tab_plane_u16_kernel");
 }

@@ -1276,3 +1276,221 @@ extern "C" int pws_upsample_grid_sample_yuv420_u8(const unsigned char *frames, c
 #undef PWS_YUV_LAUNCH
     return check_launch("upsample_grid_sample_yuv420_kernel");
 }
+
+// ---------------------------------------------------------------------------------------------- fused 10-bit 4:2:0 path (P010 / I010)
+// The YUV warp above for 16-bit frames ([n][h*3/2][w] little-endian words in the 8-bit formats' plane order): LAYOUT 0 P010 (sample = word >> 6,
+// stored << 6 with zero low bits), 1 I010 (sample = min(word, 1023)).  The blend runs in fp32 on the 10-bit values with the same field
+// interpolation, un-normalisation and 4-term order, is truncated and clamped to 0..1023; taps outside a plane read BT.601 black at 10 bits,
+// 64 in Y and 512 in U and V.  Twice the bytes of the 8-bit kernel on the SAME count of vector memory instructions per lane (counted in the
+// gfx950 code), the count that bounds the 8-bit kernels (profiles/r06_warp_u8_rewrite.txt) and this one: measured
+// 1.09x (P010 / NV12) and 1.10x (I010 / I420) for 8 frames of 1280x720, profiles/yuv16_stream_bench.json.  A lane owns 4 pixels of one plane row; per tap row and pixel ONE 8-byte load fetches the horizontal tap pair (4 bytes
+// behind v_alignbyte for the 2-byte planes -- pair offsets are even, so the rotation is 0 or 2 bytes; P010's U V U V pair is the 8 bytes
+// themselves); the field's row pair comes through yuv_field4 as above; a Y lane writes its 4 samples in one aligned 8-byte store, an I010
+// chroma lane 8 bytes per plane, a P010 chroma lane its 4 U V pairs in one 16-byte store.
+namespace yuv {
+struct __attribute__((packed, aligned(2))) U16x2 {   // two samples at 2-byte alignment (the exact loads at the end of the last sample)
+    unsigned v;
+};
+struct __attribute__((aligned(8))) U32x4 {           // 16 bytes at 8-byte alignment (P010 chroma rows: the pitch is 2 w bytes, a multiple of 8)
+    unsigned x, y, z, w;
+};
+// 8 bytes at dword alignment (the tap pairs' loads, the I010 chroma store): uint2 would promise 8.  A vector type, not a struct: a struct's
+// store is two member stores to the compiler, which it then shares between the `full` branches instead of pairing them into one dwordx2.
+typedef unsigned U32x2 __attribute__((ext_vector_type(2), aligned(4)));
+template <int LAYOUT>
+__device__ __forceinline__ float sample10f(unsigned word, int half) {   // the 10-bit sample in 16-bit half `half` of a 32-bit word, as float
+    const unsigned v = LAYOUT == 0 ? (word >> (16 * half + 6)) & 0x3ffu : min((word >> (16 * half)) & 0xffffu, 1023u);
+    return (float)v;
+}
+template <int LAYOUT>
+__device__ __forceinline__ unsigned place10(float blend) {   // truncate (the blend is >= 0), clamp to 10 bits, the layout's placement
+    const unsigned v = min((unsigned)blend, 1023u);
+    return LAYOUT == 0 ? v << 6 : v;
+}
+}  // namespace yuv
+
+// One wave's row chunk of one plane kind.  B: bytes per pixel of a source plane (2; P010 chroma 4); NP: source planes (I010 chroma 2).
+template <int KIND, int FMODE, int LAYOUT>
+__device__ __forceinline__ void yuv16_warp_row(const unsigned char *__restrict__ frame, unsigned char *__restrict__ ofr, const float *__restrict__ field,
+                                               const yuv::Plane &P, unsigned n, unsigned oy, int ox0, int fh, int fw, unsigned fbytes, bool last_sample) {
+    constexpr int B = KIND == yuv::PLANE_NV12_UV ? 4 : 2, NP = KIND == yuv::PLANE_I420_UV ? 2 : 1;
+    constexpr float PAD = KIND == yuv::PLANE_Y ? 64.f : 512.f;   // BT.601 black at 10 bits
+    const int H = P.h, W = P.w;
+    if (FMODE < 2 && ox0 >= W) return;   // (FMODE 2 / 3: every lane fetches and serves field columns first)
+    f32x2 gx[2], gy[2];
+    yuv_field4<FMODE>(field, n, oy, ox0, W - 1, fh, fw, P.ry, P.rx, gx, gy);
+    if (ox0 >= W) return;
+    const f32x2 one2 = pk_splat(1.f);
+    unsigned off[2][4];   // byte offsets (from the frame's start, first source plane) of each pixel's tap pair in rows y0, y0 + 1
+    bool okl[4], okr[4], ok0[4], ok1[4], swp[4], out4[4];
+    f32x2 wa0[2], wb0[2], wa1[2], wb1[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const f32x2 ix = pk_fma(gx[q], pk_splat(P.kx), pk_splat(P.kx1)), iy = pk_fma(gy[q], pk_splat(P.ky), pk_splat(P.ky1));
+        const f32x2 fx = pk_floor(ix), fy = pk_floor(iy);
+        const f32x2 wx1 = ix - fx, wx0 = one2 - wx1, wy1 = iy - fy, wy0 = one2 - wy1;
+        wa0[q] = wx0 * wy0, wb0[q] = wx1 * wy0, wa1[q] = wx0 * wy1, wb1[q] = wx1 * wy1;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int i = 2 * q + e, x0 = (int)(e ? fx.y : fx.x), y0 = (int)(e ? fy.y : fy.x);
+            okl[i] = (unsigned)x0 < (unsigned)W, okr[i] = (unsigned)(x0 + 1) < (unsigned)W;
+            ok0[i] = (unsigned)y0 < (unsigned)H, ok1[i] = (unsigned)(y0 + 1) < (unsigned)H;
+            const int xs = med3_i32(x0, W - 2);
+            swp[i] = xs != x0;
+            out4[i] = !((okl[i] || okr[i]) && (ok0[i] || ok1[i]));   // x0 == -1: the right tap is the pair's left pixel; x0 == W - 1: the left tap is the pair's right one
+            const unsigned xb = (unsigned)xs * B;
+            off[0][i] = P.off0 + __umul24((unsigned)med3_i32(y0, H - 1), P.pitch) + xb;
+            off[1][i] = P.off0 + __umul24((unsigned)med3_i32(y0 + 1, H - 1), P.pitch) + xb;
+        }
+    }
+    // tap pairs.  2-byte planes: the 8 bytes the pair's dword starts + v_alignbyte (up to 4 bytes behind the pair are read and not used: only at
+    // the end of the last sample's last plane can they lie outside the caller's buffer, and a wave of the last sample in which some lane would
+    // read there takes exact 4-byte loads instead).  P010 chroma: the pair IS 8 bytes at a 4-byte aligned offset, nothing is read beyond it.
+    unsigned pl[NP][2][4], ph[NP][2][4];   // B == 2: pl = left | right << 16.  B == 4: pl = left U | V << 16, ph = right U | V << 16
+    bool exact = false;
+    if (B == 2 && last_sample) {
+        unsigned m = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) m = max(m, off[1][i] + (NP == 2 ? P.off1 - P.off0 : 0u));
+        exact = __builtin_amdgcn_ballot_w64((m & ~3u) + 8u > fbytes) != 0;
+    }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const unsigned shift = p ? P.off1 - P.off0 : 0u;
+        if (!exact) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const unsigned o = off[r][i] + shift;
+                    const yuv::U32x2 t = *reinterpret_cast<const yuv::U32x2 *>(frame + (o & ~3u));
+                    if constexpr (B == 4) pl[p][r][i] = t.x, ph[p][r][i] = t.y;
+                    else pl[p][r][i] = __builtin_amdgcn_alignbyte(t.y, t.x, o), ph[p][r][i] = 0u;
+                }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) pl[p][r][i] = reinterpret_cast<const yuv::U16x2 *>(frame + off[r][i] + shift)->v, ph[p][r][i] = 0u;
+        }
+    }
+    // blend per output channel (Y: 1; P010: U, V interleaved; I010: U plane, V plane), the 8-bit kernel's fma chain with black padding
+    constexpr int NCH = (B == 4 ? 2 : 1) * NP;
+    unsigned res[NCH][4];
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+        const int p = NP == 2 ? ch : 0, c = B == 4 ? ch : 0;   // source plane, 16-bit half inside a P010 chroma pixel (compile-time)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            float ux[2], uy[2], vx[2], vy[2];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int i = 2 * q + e;
+                const float al = yuv::sample10f<LAYOUT>(pl[p][0][i], c), ar = B == 4 ? yuv::sample10f<LAYOUT>(ph[p][0][i], c) : yuv::sample10f<LAYOUT>(pl[p][0][i], 1);
+                const float bl = yuv::sample10f<LAYOUT>(pl[p][1][i], c), br = B == 4 ? yuv::sample10f<LAYOUT>(ph[p][1][i], c) : yuv::sample10f<LAYOUT>(pl[p][1][i], 1);
+                const float l0 = swp[i] ? ar : al, r0 = swp[i] ? al : ar, l1 = swp[i] ? br : bl, r1 = swp[i] ? bl : br;
+                ux[e] = okl[i] && ok0[i] ? l0 : PAD, uy[e] = okr[i] && ok0[i] ? r0 : PAD;
+                vx[e] = okl[i] && ok1[i] ? l1 : PAD, vy[e] = okr[i] && ok1[i] ? r1 : PAD;
+            }
+            f32x2 r = pk_fma(f32x2{vy[0], vy[1]}, wb1[q], pk_fma(f32x2{vx[0], vx[1]}, wa1[q], pk_fma(f32x2{uy[0], uy[1]}, wb0[q],
+                                                                                                f32x2{ux[0], ux[1]} * wa0[q])));
+            // a pixel whose four taps all lie outside is black exactly (PAD times weights that sum to 1 - 1 ulp would truncate below it)
+            r.x = out4[2 * q] ? PAD : r.x, r.y = out4[2 * q + 1] ? PAD : r.y;
+            res[ch][2 * q] = yuv::place10<LAYOUT>(r.x), res[ch][2 * q + 1] = yuv::place10<LAYOUT>(r.y);
+        }
+    }
+    const bool full = ox0 + 4 <= W;   // chroma rows of width 2 mod 4: the row's last lane owns 2 pixels
+    const unsigned ob = P.off0 + oy * P.pitch + (unsigned)ox0 * B;
+    if constexpr (KIND == yuv::PLANE_Y) {
+        *reinterpret_cast<uint2 *>(ofr + ob) = uint2{res[0][0] | res[0][1] << 16, res[0][2] | res[0][3] << 16};   // (8-byte aligned: w % 4 == 0)
+    } else if constexpr (KIND == yuv::PLANE_NV12_UV) {
+        const unsigned w0 = res[0][0] | res[1][0] << 16, w1 = res[0][1] | res[1][1] << 16;
+        if (full) *reinterpret_cast<yuv::U32x4 *>(ofr + ob) = yuv::U32x4{w0, w1, res[0][2] | res[1][2] << 16, res[0][3] | res[1][3] << 16};
+        else *reinterpret_cast<yuv::U32x2 *>(ofr + ob) = yuv::U32x2{w0, w1};
+    } else {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            unsigned char *o = ofr + ob + (p ? P.off1 - P.off0 : 0u);   // (4-byte aligned: the chroma planes' pitch and size are multiples of 4 bytes)
+            const unsigned w0 = res[p][0] | res[p][1] << 16;
+            if (full) *reinterpret_cast<yuv::U32x2 *>(o) = yuv::U32x2{w0, res[p][2] | res[p][3] << 16};   // (one 8-byte store at dword alignment, like the tap loads)
+            else *reinterpret_cast<unsigned *>(o) = w0;
+        }
+    }
+}
+
+template <int LAYOUT, int FMY, int FMC>   // LAYOUT 0 P010, 1 I010; FMY / FMC: field access mode of the Y / chroma planes
+__global__ void __launch_bounds__(256) upsample_grid_sample_yuv420_u16_kernel(const unsigned char *__restrict__ input, const float *__restrict__ field,
+                                                                              unsigned char *__restrict__ out, yuv::Plane py, yuv::Plane pc, int fh,
+                                                                              int fw, unsigned fbytes) {
+    const unsigned rg = xcd_remap(blockIdx.x, gridDim.x);
+    const unsigned n = blockIdx.z;
+    const int ox0 = (int)(blockIdx.y * 256u + (threadIdx.x & 63u) * 4u);
+    const unsigned char *frame = input + (size_t)n * fbytes;
+    unsigned char *ofr = out + (size_t)n * fbytes;
+    const bool last = n + 1 == gridDim.z;
+    if (rg < py.nrg) {
+        const unsigned oy = __builtin_amdgcn_readfirstlane(rg * 4u + (threadIdx.x >> 6));
+        if (oy >= (unsigned)py.h || blockIdx.y * 256u >= (unsigned)py.w) return;
+        yuv16_warp_row<yuv::PLANE_Y, FMY, LAYOUT>(frame, ofr, field, py, n, oy, ox0, fh, fw, fbytes, last);
+    } else if (rg < py.nrg + pc.nrg) {
+        const unsigned oy = __builtin_amdgcn_readfirstlane((rg - py.nrg) * 4u + (threadIdx.x >> 6));
+        if (oy >= (unsigned)pc.h || blockIdx.y * 256u >= (unsigned)pc.w) return;
+        yuv16_warp_row<LAYOUT == 0 ? yuv::PLANE_NV12_UV : yuv::PLANE_I420_UV, FMC, LAYOUT>(frame, ofr, field, pc, n, oy, ox0, fh, fw, fbytes, last);
+    }
+}
+
+extern "C" int pws_upsample_grid_sample_yuv420_u16(const unsigned short *frames, const float *field, unsigned short *out, int n, int h, int w,
+                                                   int fh, int fw, int layout, int align_corners, pws_stream_t stream) {
+    PWS_REQUIRE(n >= 0 && h > 0 && w > 0 && fh > 0 && fw > 0, "pws_upsample_grid_sample_yuv420_u16: bad shape");
+    PWS_REQUIRE(layout == 0 || layout == 1, "pws_upsample_grid_sample_yuv420_u16: layout must be 0 (P010) or 1 (I010), got %d", layout);
+    PWS_REQUIRE(h % 2 == 0 && w % 4 == 0 && h >= 2, "pws_upsample_grid_sample_yuv420_u16: h must be even and w a multiple of 4 (got %d x %d)", w, h);
+    if (n == 0) return PWS_OK;
+    PWS_REQUIRE(frames && field && out, "pws_upsample_grid_sample_yuv420_u16: NULL pointer");
+    PWS_REQUIRE(((reinterpret_cast<size_t>(frames) | reinterpret_cast<size_t>(out)) & 7) == 0,
+                "pws_upsample_grid_sample_yuv420_u16: frames and out must be 8-byte aligned");
+    PWS_REQUIRE((size_t)h * w < (1u << 28) && w < (1 << 22) && n < 65536, "pws_upsample_grid_sample_yuv420_u16: frame or batch too large");
+    const unsigned fbytes = (unsigned)((size_t)h * w * 3);   // (a multiple of 8: every sample starts 8-byte aligned)
+    auto plane = [&](int ph, int pw, unsigned off0, unsigned off1, unsigned pitch) {
+        yuv::Plane p;
+        p.h = ph, p.w = pw, p.off0 = off0, p.off1 = off1, p.pitch = pitch;
+        p.ry = ph > 1 ? (float)(fh - 1) / (float)(ph - 1) : 0.f;
+        p.rx = pw > 1 ? (float)(fw - 1) / (float)(pw - 1) : 0.f;
+        p.kx = align_corners ? 0.5f * (float)(pw - 1) : 0.5f * (float)pw, p.kx1 = 0.5f * (float)(pw - 1);
+        p.ky = align_corners ? 0.5f * (float)(ph - 1) : 0.5f * (float)ph, p.ky1 = 0.5f * (float)(ph - 1);
+        p.nrg = (unsigned)((ph + 3) / 4);
+        return p;
+    };
+    const unsigned hw2 = 2u * (unsigned)(h * w), hc = (unsigned)(h / 2), wc = (unsigned)(w / 2);   // byte offsets and pitches
+    const yuv::Plane py = plane(h, w, 0u, 0u, 2u * (unsigned)w);
+    const yuv::Plane pc = layout == 0 ? plane(h / 2, w / 2, hw2, hw2, 2u * (unsigned)w) : plane(h / 2, w / 2, hw2, hw2 + 2u * hc * wc, 2u * wc);
+    const unsigned gx = (py.nrg + pc.nrg + 7u) & ~7u, cpr = (unsigned)((w + 255) / 256);   // (chroma rows need half the chunks: the rest return)
+    const int fmy = yuv_fmode(py.rx), fmc = yuv_fmode(pc.rx);
+    const size_t total = (size_t)n * h * w;
+    // (booked under the 8-bit integer warps' id on purpose, like the NV12 / I420 launch above: one row "fused byte warp" in the per-kernel
+    // stats, told apart by the bytes booked per launch -- 6 per pixel here against 3; a clip has one depth, so a run does not mix them)
+    ProfScope prof(KID_UPSAMPLE_GRID_SAMPLE_U8, (double)total * 1.5 * (40.0 + 8.0), (double)total * 6.0 + 8.0 * (double)n * fh * fw,
+                   as_stream(stream));
+    const unsigned char *src = reinterpret_cast<const unsigned char *>(frames);
+    unsigned char *dst = reinterpret_cast<unsigned char *>(out);
+#define PWS_YUV16_LAUNCH(L_, FY_, FC_)                                                                                                    \
+    hipLaunchKernelGGL((upsample_grid_sample_yuv420_u16_kernel<L_, FY_, FC_>), dim3(gx, cpr, (unsigned)n), dim3(256), 0, as_stream(stream), src, \
+                       field, dst, py, pc, fh, fw, fbytes)
+#define PWS_YUV16_FC(L_, FY_)                                                                                                             \
+    do {                                                                                                                                  \
+        if (fmc == 3) PWS_YUV16_LAUNCH(L_, FY_, 3);                                                                                       \
+        else if (fmc == 2) PWS_YUV16_LAUNCH(L_, FY_, 2);                                                                                  \
+        else PWS_YUV16_LAUNCH(L_, FY_, 0);                                                                                                \
+    } while (0)
+#define PWS_YUV16_FY(L_)                                                                                                                  \
+    do {                                                                                                                                  \
+        if (fmy == 2) PWS_YUV16_FC(L_, 2);                                                                                                \
+        else if (fmy == 3) PWS_YUV16_FC(L_, 3);                                                                                           \
+        else PWS_YUV16_FC(L_, 0);                                                                                                         \
+    } while (0)
+    if (layout == 0) PWS_YUV16_FY(0);
+    else PWS_YUV16_FY(1);
+#undef PWS_YUV16_FY
+#undef PWS_YUV16_FC
+#undef PWS_YUV16_LAUNCH
+    return check_launch("upsample_grid_sample_yuv420_u16_kernel");
+}

@@ -164,8 +164,9 @@ YUV420_LAYOUT = {"nv12": 0, "i420": 1}
 
 
 def yuv420_layout(pixel_format):
-    """0 (NV12) / 1 (I420) for a 4:2:0 pixel format; ValueError for anything else (P010, 4:2:2, 4:4:4, full range and BT.709 are not
-    supported)."""
+    """0 (NV12) / 1 (I420) for an 8-bit 4:2:0 pixel format; ValueError for anything else (4:2:2, 4:4:4, full range and BT.709 are not
+    supported; the 10-bit formats P010 / I010 have functions of their own: ``yuv420_16_layout``, ``yuv420_16_shape``,
+    ``upsample_grid_sample_yuv420_16``)."""
     if pixel_format not in YUV420_LAYOUT:
         raise ValueError("pixel_format must be one of %s for 4:2:0 frames, got %r (8-bit BT.601 limited-range NV12 / I420 only)"
                          % (tuple(YUV420_LAYOUT), pixel_format))
@@ -201,6 +202,53 @@ def upsample_grid_sample_yuv420(frames, field, pixel_format, align_corners=None,
         out = torch.empty_like(frames)
     A.check(A.lib().pws_upsample_grid_sample_yuv420_u8(A.ptr(frames), A.ptr(field), A.ptr(out), n, h, w, field.shape[1], field.shape[2], layout,
                                                        _ac(align_corners), A.current_stream()), "pws_upsample_grid_sample_yuv420_u8")
+    return out
+
+
+PIXEL_FORMATS_16 = ("p010", "i010")
+YUV420_16_LAYOUT = {"p010": 0, "i010": 1}
+
+
+def yuv420_16_layout(pixel_format):
+    """0 (P010: NV12's plane order, the 10-bit sample in the high bits of each 16-bit word) / 1 (I010, ffmpeg's yuv420p10le: I420's plane
+    order, the sample in the low 10 bits) for a 10-bit 4:2:0 pixel format; ValueError for anything else."""
+    if pixel_format not in YUV420_16_LAYOUT:
+        raise ValueError("pixel_format must be one of %s for 10-bit 4:2:0 frames, got %r (BT.601 limited-range P010 / I010 only)"
+                         % (tuple(YUV420_16_LAYOUT), pixel_format))
+    return YUV420_16_LAYOUT[pixel_format]
+
+
+def yuv420_16_shape(frames, pixel_format, w_multiple=4):
+    """(T, H, W) of packed 10-bit 4:2:0 frames (T, H * 3 // 2, W) uint16; ValueError unless H and W are even and W a multiple of
+    ``w_multiple``."""
+    yuv420_16_layout(pixel_format)
+    if frames.dim() != 3 or frames.dtype != torch.uint16:
+        raise ValueError("%s frames must be uint16 (T, H * 3 // 2, W), got %s %s" % (pixel_format, frames.dtype, tuple(frames.shape)))
+    t, ph, w = frames.shape
+    if ph % 3 != 0 or ph == 0:
+        raise ValueError("%s frames: packed height %d is not H * 3 // 2 of an even H" % (pixel_format, ph))
+    h = ph // 3 * 2
+    if w % 2 != 0 or w % w_multiple != 0:
+        raise ValueError("%s frames: width %d must be even and a multiple of %d" % (pixel_format, w, w_multiple))
+    return t, h, w
+
+
+def upsample_grid_sample_yuv420_16(frames, field, pixel_format, align_corners=None, out=None):
+    """upsample_grid_sample_yuv420 for 10-bit frames, YUV in and YUV out: ``frames`` (N, H * 3 // 2, W) uint16 in ``pixel_format`` "p010"
+    (sample = word >> 6; output words have zero low bits) or "i010" (sample = min(word, 1023)); every plane is warped by ``field``
+    (N, fh, fw, 2) resized (align_corners=True) to the plane's own size, bilinear in fp32 on the 10-bit values, taps outside a plane read
+    BT.601 black (64 in Y, 512 in U and V), the blend is truncated and clamped to 0..1023.  H even, W % 4 == 0.  One kernel launch."""
+    layout = yuv420_16_layout(pixel_format)
+    n, h, w = yuv420_16_shape(frames, pixel_format)   # (a tensor that is not uint16 is a ValueError, like a bad shape)
+    A.require_cuda(field)
+    A.require_cuda(frames, dtype=torch.uint16)
+    if field.dim() != 4 or field.shape[0] != n or field.shape[3] != 2:
+        raise ValueError("upsample_grid_sample_yuv420_16: field must be (%d, fh, fw, 2), got %s" % (n, tuple(field.shape)))
+    frames, field = frames.contiguous(), field.contiguous()
+    if out is None:
+        out = torch.empty_like(frames)
+    A.check(A.lib().pws_upsample_grid_sample_yuv420_u16(A.ptr(frames), A.ptr(field), A.ptr(out), n, h, w, field.shape[1], field.shape[2], layout,
+                                                        _ac(align_corners), A.current_stream()), "pws_upsample_grid_sample_yuv420_u16")
     return out
 
 

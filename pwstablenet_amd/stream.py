@@ -84,10 +84,10 @@ def window_planes_yuv(frames, pixel_format, size=256, out=None):
 
 def _yuv_planes(x, h, w, pixel_format):
     """Views of the planes of packed 4:2:0 frames x (T, h * 3 // 2, w): [Y (T, h, w), UV (T, h/2, w)] for NV12, [Y, U (T, h/2, w/2),
-    V (T, h/2, w/2)] for I420."""
+    V (T, h/2, w/2)] for I420; P010 as NV12 and I010 as I420, in 16-bit words."""
     t = x.shape[0]
     y = x[:, :h]
-    if pixel_format == "nv12":
+    if pixel_format in ("nv12", "p010"):
         return [y, x[:, h:]]
     c = x.reshape(t, -1)[:, h * w:].reshape(t, 2, h // 2, w // 2)
     return [y, c[:, 0], c[:, 1]]
@@ -113,15 +113,54 @@ def area_resize_yuv(frames, pixel_format, size):
     return out
 
 
+def window_planes_yuv16(frames, pixel_format, size=256, out=None):
+    """window_planes_yuv for 10-bit frames (T, H * 3 // 2, W) uint16, "p010" or "i010": the generator was trained on 8-bit gray, so the plane
+    of a 10-bit frame is by definition the plane of its 8-bit reduction ``v8 = min(255, (v10 + 2) >> 2)``, fused into the kernel's loads (no
+    8-bit copy of the frames): a P010 / I010 clip gets the fields of the NV12 / I420 clip of its reduced samples bit for bit.  H and W even.
+    -> (T, size, size) float32."""
+    layout = PF.yuv420_16_layout(pixel_format)
+    t, h, w = PF.yuv420_16_shape(frames, pixel_format, w_multiple=2)
+    A.require_cuda(frames, dtype=torch.uint16)
+    frames = frames.contiguous()
+    if out is None:
+        out = torch.empty((t, size, size), device=frames.device, dtype=torch.float32)
+    A.require_cuda(out)
+    if tuple(out.shape) != (t, size, size) or not out.is_contiguous():
+        raise ValueError("window_planes_yuv16: out must be a contiguous (T, %d, %d) float32 tensor" % (size, size))
+    A.check(A.lib().pws_gray_area_yuv420_u16(A.ptr(frames), A.ptr(out), t, h, w, size, size, 1, layout, A.current_stream()),
+            "pws_gray_area_yuv420_u16")
+    return out
+
+
+def area_resize_yuv16(frames, pixel_format, size):
+    """area_resize_yuv for 10-bit frames, INTER_AREA plane by plane on the 10-bit values (P010's interleaved UV as a 2-channel image),
+    clamped to 0..1023 and stored in the format's placement; ``size`` = (width, height), both even.  (T, H * 3 // 2, W) uint16 ->
+    (T, height * 3 // 2, width)."""
+    layout = PF.yuv420_16_layout(pixel_format)
+    t, h, w = PF.yuv420_16_shape(frames, pixel_format, w_multiple=2)
+    A.require_cuda(frames, dtype=torch.uint16)
+    ow, oh = int(size[0]), int(size[1])
+    if ow % 2 or oh % 2 or not (0 < ow <= w and 0 < oh <= h):
+        raise ValueError("area_resize_yuv16: output size %s must be even and within the %d x %d source" % (tuple(size), w, h))
+    frames = frames.contiguous()
+    out = torch.empty((t, oh * 3 // 2, ow), device=frames.device, dtype=torch.uint16)
+    fs, os_ = frames[0].numel(), out[0].numel()   # (in 16-bit words)
+    geo = [(1, h, w, oh, ow)] + ([(2, h // 2, w // 2, oh // 2, ow // 2)] if layout == 0 else [(1, h // 2, w // 2, oh // 2, ow // 2)] * 2)
+    for (c, ph, pw, qh, qw), src, dst in zip(geo, _yuv_planes(frames, h, w, pixel_format), _yuv_planes(out, oh, ow, pixel_format)):
+        A.check(A.lib().pws_area_resize_plane_u16(A.ptr(src), fs, A.ptr(dst), os_, t, ph, pw, c, qh, qw, layout, A.current_stream()),
+                "pws_area_resize_plane_u16")
+    return out
+
+
 def _yuv_crop(x, h, w, pixel_format, cy0, cy1, cx0, cx1):
     """The (even) window [cy0, cy1) x [cx0, cx1) of packed 4:2:0 frames, packed again on the device: Y [cy0:cy1, cx0:cx1], chroma
     [cy0/2:cy1/2, cx0/2:cx1/2]."""
     ch, cw = cy1 - cy0, cx1 - cx0
-    out = torch.empty((x.shape[0], ch * 3 // 2, cw), device=x.device, dtype=torch.uint8)
+    out = torch.empty((x.shape[0], ch * 3 // 2, cw), device=x.device, dtype=x.dtype)
     src, dst = _yuv_planes(x, h, w, pixel_format), _yuv_planes(out, ch, cw, pixel_format)
     dst[0].copy_(src[0][:, cy0:cy1, cx0:cx1])
-    if pixel_format == "nv12":
-        dst[1].copy_(src[1][:, cy0 // 2:cy1 // 2, cx0:cx1])   # (U V interleaved: chroma columns cx0/2 .. are bytes cx0 ..)
+    if pixel_format in ("nv12", "p010"):
+        dst[1].copy_(src[1][:, cy0 // 2:cy1 // 2, cx0:cx1])   # (U V interleaved: chroma columns cx0/2 .. are samples cx0 ..)
     else:
         for k in (1, 2):
             dst[k].copy_(src[k][:, cy0 // 2:cy1 // 2, cx0 // 2:cx1 // 2])
@@ -243,11 +282,17 @@ class VideoStabilizer:
         PCIe and HBM traffic per frame, ``self.swap_rb`` applies the reference's BGR->RGB).  Tensors may be on the device or in
         (pinned) host memory.  Returns a tensor of the frames' shape and dtype on the inputs' side.
         pixel_format = "nv12" / "i420": frames are packed 4:2:0 (T, H * 3 // 2, W) uint8 (H even, W % 4 == 0), warped plane by plane in
-        the fused YUV kernel (functional.upsample_grid_sample_yuv420: BT.601 black padding); ``self.swap_rb`` does not apply."""
+        the fused YUV kernel (functional.upsample_grid_sample_yuv420: BT.601 black padding); ``self.swap_rb`` does not apply.
+        pixel_format = "p010" / "i010": the same for 10-bit frames (T, H * 3 // 2, W) uint16 (functional.upsample_grid_sample_yuv420_16)."""
         half = self.period // 2
         yuv = pixel_format != "bgr24"
-        if yuv:
+        yuv16 = pixel_format in PF.PIXEL_FORMATS_16
+        if yuv16:
+            PF.yuv420_16_shape(frames, pixel_format)
+        elif yuv:
             PF.yuv420_shape(frames, pixel_format)
+        elif frames.dtype == torch.uint16:
+            raise ValueError("run: uint16 frames need pixel_format \"p010\" or \"i010\", got %r" % (pixel_format,))
         if not (0 <= halo_left <= half and 0 <= halo_right <= half):
             raise ValueError("halo must be within [0, %d]" % half)
         T = frames.shape[0]
@@ -285,7 +330,9 @@ class VideoStabilizer:
                 compute.wait_event(ev)
             win = _windows(gp, s, e - s, self.period)
             field = self.net(win, False)
-            if yuv:
+            if yuv16:
+                warped = PF.upsample_grid_sample_yuv420_16(cur.contiguous(), field, pixel_format, align_corners=self.align_corners)
+            elif yuv:
                 warped = PF.upsample_grid_sample_yuv420(cur.contiguous(), field, pixel_format, align_corners=self.align_corners)
             elif cur.dtype == torch.uint8:
                 warped = PF.upsample_grid_sample_u8(cur.contiguous(), field, swap_rb=self.swap_rb, align_corners=self.align_corners)
@@ -339,6 +386,12 @@ class VideoStabilizer:
         bit for bit), every plane is warped by the field (functional.upsample_grid_sample_yuv420: BT.601 black padding) and resized plane by
         plane (area_resize_yuv).  Output sizes and crop windows must be even; crop="auto" rounds the BGR path's window inward to even.
         frames_are_rgb=True is an error there, and ``swap_rb`` is ignored.
+        pixel_format = "p010" / "i010": 10-bit 4:2:0 frames (T, H * 3 // 2, W) uint16, BT.601 limited range, in NV12's / I420's plane order
+        (P010: the sample in the high 10 bits of each word, as hardware decoders deliver it; I010 = yuv420p10le: in the low 10 bits), uint16
+        out in the same layout.  The window planes are those of the frames' 8-bit reduction (window_planes_yuv16: the fields of the NV12 /
+        I420 clip of the reduced samples bit for bit), the warp and the output resize work on the 10-bit values
+        (functional.upsample_grid_sample_yuv420_16: black is 64 / 512; area_resize_yuv16); everything else as for NV12 / I420.  A tensor
+        whose dtype does not belong to the pixel format is a ValueError.
         Returns (T, H, W, 3) -- or (T, H/2, W/2, 3) / (T, height, width, 3), or the crop window of it -- uint8 on the inputs' side; for YUV
         (T, oh * 3 // 2, ow) of the output (or crop window) size oh x ow."""
         half = self.period // 2
@@ -351,11 +404,14 @@ class VideoStabilizer:
         on_host = not frames.is_cuda
         dev = self.device
         yuv = pixel_format != "bgr24"
+        yuv16 = pixel_format in PF.PIXEL_FORMATS_16
         if yuv:
-            _, h, w = PF.yuv420_shape(frames, pixel_format)
+            _, h, w = PF.yuv420_16_shape(frames, pixel_format) if yuv16 else PF.yuv420_shape(frames, pixel_format)
             if frames_are_rgb:
                 raise ValueError("run_video: frames_are_rgb has no meaning for %s frames" % pixel_format)
         else:
+            if frames.dtype == torch.uint16:
+                raise ValueError("run_video: uint16 frames need pixel_format \"p010\" or \"i010\", got %r" % (pixel_format,))
             h, w = frames.shape[1], frames.shape[2]
         if output_size is not None and half_size_output:
             raise ValueError("run_video: give output_size or half_size_output, not both")
@@ -391,7 +447,7 @@ class VideoStabilizer:
 
         def alloc_out():
             oshape = (T, (cy1 - cy0) * 3 // 2, cx1 - cx0) if yuv else (T, cy1 - cy0, cx1 - cx0, 3)
-            return torch.empty(oshape, dtype=torch.uint8, pin_memory=True) if on_host else torch.empty(oshape, dtype=torch.uint8, device=dev)
+            return torch.empty(oshape, dtype=frames.dtype, pin_memory=True) if on_host else torch.empty(oshape, dtype=frames.dtype, device=dev)
         cy0, cy1, cx0, cx1 = crop_window(None if auto else crop)
         out = None if auto and T > 0 else alloc_out()
         if T == 0:
@@ -428,7 +484,9 @@ class VideoStabilizer:
             s, e = chunks[c]
             with torch.cuda.stream(up):
                 buf = frames[s:e].to(dev, non_blocking=True) if on_host else frames[s:e]
-                if yuv:
+                if yuv16:
+                    window_planes_yuv16(buf, pixel_format, 256, out=gray_all[s:e])
+                elif yuv:
                     window_planes_yuv(buf, pixel_format, 256, out=gray_all[s:e])
                 else:
                     window_planes(buf, 256, frames_are_rgb, out=gray_all[s:e])
@@ -440,7 +498,7 @@ class VideoStabilizer:
             """output resize + crop of the warped core frames s .. e-1 (output positions) on `lane`, and their way to `out`"""
             if yuv:
                 if (oh, ow) != (h, w):
-                    warped = area_resize_yuv(warped, pixel_format, (ow, oh))
+                    warped = (area_resize_yuv16 if yuv16 else area_resize_yuv)(warped, pixel_format, (ow, oh))
                 if crop is not None:
                     warped = _yuv_crop(warped, oh, ow, pixel_format, cy0, cy1, cx0, cx1)   # packed on the device: only the window crosses PCIe
             else:
@@ -518,7 +576,9 @@ class VideoStabilizer:
                     nxt = fetch(c + 1)
                 if ev is not None:
                     compute.wait_event(ev)
-                if yuv:
+                if yuv16:
+                    warped = PF.upsample_grid_sample_yuv420_16(buf.contiguous(), fields[s:e], pixel_format, align_corners=self.align_corners)
+                elif yuv:
                     warped = PF.upsample_grid_sample_yuv420(buf.contiguous(), fields[s:e], pixel_format, align_corners=self.align_corners)
                 else:
                     warped = PF.upsample_grid_sample_u8(buf.contiguous(), fields[s:e], swap_rb=self.swap_rb, align_corners=self.align_corners)
