@@ -41,6 +41,7 @@
  *   pws_upsample_grid_sample_fwd  the two above fused (720p path)  main_new.py:706-716
  *   pws_adam_step                 optim.Adam(...).step()           main_new.py:63,216
  *   pws_field_homography          the automatic crop's per-frame findHomography + perspectiveTransform  main_new.py:550-603
+ *   pws_scene_change              the window's end clamp, applied at hard cuts too (cut score)          main_new.py:627-633
  *   pws_pack_* / pws_netg_pack_weights   state_dict (OIHW / IOHW) -> kernel layout; main_new.py:60,471
  *
  * Layouts.  Frames / images: NCHW fp32 as in the reference.  Warp fields: N,H,W,2 fp32 (x then y,
@@ -423,6 +424,16 @@ int pws_upsample_grid_sample_yuv420_u16(const unsigned short *frames, const floa
  * h0 >= 300 and w0 >= 600 (the lattice must fit); field and pts_out 8-byte aligned. */
 int pws_field_homography(const float *field, int n, int fh, int fw, int h0, int w0, double *m_out, float *bounds_out, float *pts_out,
                          pws_stream_t stream);
+
+/* Scene-cut score for edited footage (csrc/scene.hip).  The reference clamps a frame's 31-plane window at the clip's first and last frame
+ * only (main_new.py:627-633); the streaming stabiliser applies the same clamp at every hard cut, which it finds from the L1 distance of
+ * block-wise histograms of consecutive window planes (motion-tolerant, unlike a pixel difference).
+ * planes: (n, h, w) fp32 contiguous, nominally in [-1, 1] (window_planes).  h % 4 == 0, w % 4 == 0.
+ * hist: (n, 16, 32) uint32 -- block (by*4+bx) of the 4 x 4 grid of (h/4) x (w/4) blocks, 32 bins: the bin of a sample v is 0 if
+ *       !(x >= 0) with x = (v + 1.0f) * 16.0f in fp32 (NaN, anything below -1), else min(31, (int)x).
+ * sad:  (n) uint32 -- sad[0] = 0, sad[t] = sum over the 512 counters |hist[t] - hist[t-1]|.
+ * Integer arithmetic after the bin: exact, the same bits on every run.  planes and sad 4-byte aligned, hist 8-byte aligned. */
+int pws_scene_change(const float *planes, int n, int h, int w, unsigned *hist, unsigned *sad, pws_stream_t stream);
 
 /* Adam (no weight decay / amsgrad) on a flat fp32 buffer, in place; step counts from 1. */
 int pws_adam_step(float *p, const float *g, float *m, float *v, size_t count, float lr, float beta1,

@@ -14,6 +14,7 @@ host<->device round trip per frame.  Here:
   * several GPUs take contiguous frame chunks with a 15-frame halo each (``distributed.shard_frames``): no collective.
 """
 import math
+import time
 
 import torch
 
@@ -198,12 +199,68 @@ def field_homography(field, frame_hw, return_points=False):
     return (m, bounds, pts) if return_points else (m, bounds)
 
 
-def auto_crop_window(bounds, frame_hw, output_hw=None, period=30):
+def scene_scores(planes, return_counts=False):
+    """The cut score of consecutive window planes (csrc/scene.hip): ``planes`` (T, h, w) float32 on the device, contiguous, h and w
+    multiples of 4 (``window_planes``: 256 x 256).  Every plane is summarised by the 32-bin histograms of its 4 x 4 blocks (512 counters; the
+    bin of a sample v is ``min(31, int((v + 1) * 16))``, 0 below -1 and for NaN); ``score[t] = sum |hist[t] - hist[t-1]| / (2 h w)`` lies in
+    [0, 1] (0: the same block histograms, which a shaky shot nearly keeps; 1: no sample of any block kept its bin), ``score[0] = 0``.  The
+    counters are exact integers and the division is torch's on them: the same bits on every run.  Returns (T,) float32 on the device
+    [, hist (T, 16, 32) int32, sad (T,) int32].  A tensor that is not contiguous float32 (T, h, w) is a ValueError."""
+    if not isinstance(planes, torch.Tensor) or planes.dim() != 3 or planes.dtype != torch.float32 or not planes.is_contiguous():
+        raise ValueError("scene_scores: planes must be a contiguous (T, h, w) float32 tensor")
+    A.require_cuda(planes)
+    t, h, w = planes.shape
+    hist = torch.empty((t, 16, 32), device=planes.device, dtype=torch.int32)
+    sad = torch.empty((t,), device=planes.device, dtype=torch.int32)
+    A.check(A.lib().pws_scene_change(A.ptr(planes), t, h, w, A.ptr(hist), A.ptr(sad), A.current_stream()), "pws_scene_change")
+    scores = sad.to(torch.float32) / float(2 * h * w)
+    return (scores, hist, sad) if return_counts else scores
+
+
+def find_scene_cuts(scores, threshold=0.25, min_scene=16):
+    """The cut rule over a clip's ``scene_scores`` (a tensor on either side, an array or a sequence; host arithmetic): the sorted indices t,
+    1 <= t < T, at which a new scene starts.  t is a cut if ``score[t] > threshold`` and t lies at least ``min_scene`` frames after the
+    previous accepted cut (or after frame 0); a candidate closer than that is dropped and does not restart the count (a photo flash gives two
+    high scores a frame or two apart, and one cut at most).  The rule is causal -- nothing after t is read -- so run_video can apply it
+    chunk by chunk while the clip is still uploading."""
+    if isinstance(scores, torch.Tensor):
+        scores = scores.detach().to("cpu", torch.float32).tolist()
+    cuts, last = [], 0
+    for t, v in enumerate(scores):
+        if t >= 1 and float(v) > threshold and t - last >= min_scene:
+            cuts.append(t)
+            last = t
+    return cuts
+
+
+def _check_cuts(cuts, n, what):
+    """scene_cuts as a list of ints: sorted, unique, within 1 .. n-1 (ValueError otherwise)."""
+    if isinstance(cuts, torch.Tensor):
+        cuts = cuts.tolist()
+    try:
+        cuts = [int(c) for c in cuts]
+    except (TypeError, ValueError):
+        raise ValueError("%s: scene_cuts must be a sequence of frame indices" % what) from None
+    if any(not 1 <= c < n for c in cuts) or any(c2 <= c1 for c1, c2 in zip(cuts, cuts[1:])):
+        raise ValueError("%s: scene_cuts must be sorted, unique and within 1 .. %d, got %r" % (what, n - 1, cuts))
+    return cuts
+
+
+def _scenes(n, cuts):
+    """The scenes [a, b) that the cuts split 0 .. n into."""
+    edges = [0] + list(cuts) + [n]
+    return list(zip(edges[:-1], edges[1:]))
+
+
+def auto_crop_window(bounds, frame_hw, output_hw=None, period=30, scene_cuts=None):
     """The reference's crop recurrence (main_new.py:575-603) over a clip's per-frame bounds (``field_homography``; (T, 4) top, bottom,
     left, right in source pixels, a tensor on either side or an array): the window starts at the whole H0 x W0 frame, and each frame i
     with period//2 < i < T - period//2 pulls every edge that lies outside the frame's bounds half way towards them, in float64.  Returns
     (x_start, x_end, y_start, y_end), scaled to ``output_hw`` = (height, width) of the output frame when given, for run_video's ``crop``.
-    ValueError when a frame the recurrence reads has NaN bounds, or when the window is empty."""
+    ValueError when a frame the recurrence reads has NaN bounds, or when the window is empty.
+    scene_cuts (sorted indices at which a new scene starts): the reference's end rule holds per scene -- frame i of scene [a, b) is read only
+    if a + period//2 < i < b - period//2, since the frames next to a cut see a clamped window as those at the clip's ends do -- and the one
+    window is carried from scene to scene (one output size serves the whole clip)."""
     if isinstance(bounds, torch.Tensor):
         bounds = bounds.detach().to("cpu", torch.float64).tolist()
     bounds = [[float(v) for v in row] for row in bounds]
@@ -212,7 +269,8 @@ def auto_crop_window(bounds, frame_hw, output_hw=None, period=30):
     h0, w0 = int(frame_hw[0]), int(frame_hw[1])
     T, half, rate = len(bounds), int(period) // 2, 0.5
     x0, x1, y0, y1 = 0.0, float(w0), 0.0, float(h0)
-    for i in range(half + 1, T - half):
+    scenes = _scenes(T, _check_cuts(scene_cuts, T, "auto_crop_window")) if scene_cuts is not None and len(scene_cuts) else [(0, T)]
+    for i in (i for a, b in scenes for i in range(a + half + 1, b - half)):
         top, bottom, left, right = bounds[i]
         if not all(math.isfinite(v) for v in bounds[i]):
             raise ValueError("auto_crop_window: frame %d has no homography (bounds %r)" % (i, bounds[i]))
@@ -252,6 +310,8 @@ class VideoStabilizer:
         # True for checkpoints trained under the reference's pinned torch 0.4)
         self.align_corners = bool(getattr(getattr(netG, "module", netG), "align_corners", False))
         self._lanes = []   # compute streams of run_video(in_flight > 1)
+        self.scene_cuts = []   # the cuts the last run_video used (frames' index space)
+        self.scene_wait_s = 0.0   # host time the last run_video(scene_cuts="auto") spent waiting for scores
 
     def _pad(self, gray, halo_left, halo_right):
         """Replicates the first / last available frame so that every frame owns a full window (reference :627-633)."""
@@ -265,17 +325,45 @@ class VideoStabilizer:
             parts.append(gray[-1:].expand(need_r, -1, -1))
         return torch.cat(parts, 0) if len(parts) > 1 else gray
 
-    def _fields(self, gray, halo_left, halo_right, out):
+    def _layout(self, gray, halo_left, halo_right, T, scene_cuts=None):
+        """The padded plane buffer and the generator batches of run(): [(s, e, start)] -- frames s .. e-1 (output positions) form one call
+        whose windows begin at padded plane start, start + 1, ...
+        With scene cuts (indices into ``gray``, halos included) plane j of the window of gray frame g in scene [a, b) is
+        gray[clamp(g - half + j, a, b - 1)]: the buffer holds, scene after scene, [first frame x need_l, scene, last frame x need_r] (a
+        frame's window starts 2 * half planes further on for each earlier scene), and the batches restart at every scene's first frame,
+        because a strided view cannot span a cut: a scene sees the generator calls that a clip made of it alone would see.  Scenes that lie
+        wholly inside a halo hold no frame to stabilise and are left out."""
+        if not scene_cuts:
+            gp = self._pad(gray, halo_left, halo_right).contiguous()
+            return gp, [(s, min(T, s + self.batch), s) for s in range(0, T, self.batch)]
+        half, n = self.period // 2, gray.shape[0]
+        parts, batches, pos = [], [], 0
+        for a, b in _scenes(n, scene_cuts):
+            ca, cb = max(a, halo_left), min(b, halo_left + T)   # the scene's frames to stabilise
+            if ca >= cb:
+                continue
+            need_l = half if a > 0 else max(0, half - halo_left)
+            need_r = half if b < n else max(0, half - halo_right)
+            if need_l:
+                parts.append(gray[a:a + 1].expand(need_l, -1, -1))
+            parts.append(gray[a:b])
+            if need_r:
+                parts.append(gray[b - 1:b].expand(need_r, -1, -1))
+            first = pos + need_l - half - a   # the window of gray frame g starts at padded plane first + g
+            for s in range(ca, cb, self.batch):
+                batches.append((s - halo_left, min(cb, s + self.batch) - halo_left, first + s))
+            pos += need_l + (b - a) + need_r
+        return torch.cat(parts, 0), batches
+
+    def _fields(self, gray, halo_left, halo_right, out, scene_cuts=None):
         """The generator half of run(): the fields of the out.shape[0] frames into ``out`` (T, 256, 256, 2), in the batches run()
         forms (the same windows per generator call: the same fields bit for bit).  The copy also frees a graph's static output."""
-        gp = self._pad(gray.contiguous(), halo_left, halo_right).contiguous()
-        T = out.shape[0]
-        for s in range(0, T, self.batch):
-            e = min(T, s + self.batch)
-            out[s:e].copy_(self.net(_windows(gp, s, e - s, self.period), False))
+        gp, batches = self._layout(gray.contiguous(), halo_left, halo_right, out.shape[0], scene_cuts)
+        for s, e, start in batches:
+            out[s:e].copy_(self.net(_windows(gp, start, e - s, self.period), False))
 
     @torch.no_grad()
-    def run(self, gray, frames, halo_left=0, halo_right=0, out=None, pixel_format="bgr24"):
+    def run(self, gray, frames, halo_left=0, halo_right=0, out=None, pixel_format="bgr24", scene_cuts=None):
         """gray: (T + halo_left + halo_right, 256, 256) float32 in [-1,1] (``x/255*2-1`` as the reference, :650) for the T
         frames to stabilise plus whatever real neighbours exist on either side (up to period//2); frames: (T, C, H, W)
         float32 0..255, or (T, H, W, 3) uint8 as OpenCV delivers them (then the warp runs in the uint8 kernel: 4x less
@@ -283,7 +371,10 @@ class VideoStabilizer:
         (pinned) host memory.  Returns a tensor of the frames' shape and dtype on the inputs' side.
         pixel_format = "nv12" / "i420": frames are packed 4:2:0 (T, H * 3 // 2, W) uint8 (H even, W % 4 == 0), warped plane by plane in
         the fused YUV kernel (functional.upsample_grid_sample_yuv420: BT.601 black padding); ``self.swap_rb`` does not apply.
-        pixel_format = "p010" / "i010": the same for 10-bit frames (T, H * 3 // 2, W) uint16 (functional.upsample_grid_sample_yuv420_16)."""
+        pixel_format = "p010" / "i010": the same for 10-bit frames (T, H * 3 // 2, W) uint16 (functional.upsample_grid_sample_yuv420_16).
+        scene_cuts: sorted indices into ``gray`` (halo frames count; 1 .. len - 1) at which a new scene starts.  Windows end at them as they
+        end at the clip's ends -- the scene's first / last frame is repeated (_layout) -- and the batches restart at every scene, so a scene
+        is stabilised exactly as the clip of that scene alone would be.  None or empty: one scene."""
         half = self.period // 2
         yuv = pixel_format != "bgr24"
         yuv16 = pixel_format in PF.PIXEL_FORMATS_16
@@ -300,17 +391,18 @@ class VideoStabilizer:
             raise ValueError("gray has %d frames, expected %d + %d + %d" % (gray.shape[0], T, halo_left, halo_right))
         on_host = not frames.is_cuda
         dev = self.device
+        cuts = _check_cuts(scene_cuts, gray.shape[0], "run") if scene_cuts is not None else None
         gray_d = gray.to(dev, non_blocking=True) if not gray.is_cuda else gray  # 256 KB per frame: copied once
-        gp = self._pad(gray_d.contiguous(), halo_left, halo_right).contiguous()
         if out is None:
             out = torch.empty_like(frames, pin_memory=on_host) if on_host else torch.empty_like(frames)
         if T == 0:
             return out
+        gp, batches = self._layout(gray_d.contiguous(), halo_left, halo_right, T, cuts)
         compute = torch.cuda.current_stream(dev)
         h2d, d2h = (torch.cuda.Stream(dev), torch.cuda.Stream(dev)) if on_host else (None, None)
 
-        def fetch(s):
-            e = min(T, s + self.batch)
+        def fetch(k):
+            s, e, _ = batches[k]
             if not on_host:
                 return frames[s:e], None
             with torch.cuda.stream(h2d):
@@ -321,14 +413,13 @@ class VideoStabilizer:
 
         nxt = fetch(0)
         pending = []
-        for s in range(0, T, self.batch):
-            e = min(T, s + self.batch)
+        for k, (s, e, start) in enumerate(batches):
             cur, ev = nxt
-            if e < T:
-                nxt = fetch(e)  # overlaps with this batch's compute
+            if k + 1 < len(batches):
+                nxt = fetch(k + 1)  # overlaps with this batch's compute
             if ev is not None:
                 compute.wait_event(ev)
-            win = _windows(gp, s, e - s, self.period)
+            win = _windows(gp, start, e - s, self.period)
             field = self.net(win, False)
             if yuv16:
                 warped = PF.upsample_grid_sample_yuv420_16(cur.contiguous(), field, pixel_format, align_corners=self.align_corners)
@@ -355,7 +446,7 @@ class VideoStabilizer:
 
     @torch.no_grad()
     def run_video(self, frames, chunk=32, half_size_output=False, frames_are_rgb=False, halo_left=0, halo_right=0, crop=None,
-                  output_size=None, in_flight=1, pixel_format="bgr24"):
+                  output_size=None, in_flight=1, pixel_format="bgr24", scene_cuts=None, scene_threshold=0.25, scene_min_len=16):
         """The whole device side of the reference's ``process()`` loop for one decoded clip: ``frames`` (T, H, W, 3) uint8 as
         cv2 delivers them, in (pinned) host memory or on the device.  Per chunk of ``chunk`` frames: H2D on a side stream,
         gray + INTER_AREA 256x256 window planes computed there from the uploaded frames (so nothing but the uint8 frames
@@ -392,6 +483,17 @@ class VideoStabilizer:
         I420 clip of the reduced samples bit for bit), the warp and the output resize work on the 10-bit values
         (functional.upsample_grid_sample_yuv420_16: black is 64 / 512; area_resize_yuv16); everything else as for NV12 / I420.  A tensor
         whose dtype does not belong to the pixel format is a ValueError.
+        scene_cuts: edited footage.  A sorted sequence of indices into ``frames`` (halo frames count; 1 .. len - 1) at which a new scene starts
+        (a hard cut), or "auto" to find them.  Windows end at a cut as they end at the clip's ends (the scene's first / last frame repeated)
+        and the generator batches restart there (run()), so every scene is stabilised as a clip of its own, inside the one chunk pipeline;
+        crop="auto" applies the reference's end rule per scene and carries its one window across the cuts (auto_crop_window).  "auto": the
+        upload stream also runs ``scene_scores`` over each chunk's planes (plus the previous chunk's last one) and copies the scores to
+        pinned host memory; before a chunk is issued the host waits for the upload that holds the last plane its windows reach -- one wait
+        per chunk on the UPLOAD stream, never on a compute lane -- and extends the cut list with ``find_scene_cuts``' causal rule
+        (scene_threshold, scene_min_len).  Only hard cuts are found: a dissolve or a fade stays one scene, as today.  A shard (non-zero
+        halo) that detects on its own slice has no history before its halo and may place scene_min_len differently from the whole clip:
+        sharded hosts compute ``scene_scores`` per shard, gather, call ``find_scene_cuts`` once and pass explicit lists.  The cuts used are
+        left in ``self.scene_cuts``.  None (the default): one scene, every path as without the argument.
         Returns (T, H, W, 3) -- or (T, H/2, W/2, 3) / (T, height, width, 3), or the crop window of it -- uint8 on the inputs' side; for YUV
         (T, oh * 3 // 2, ow) of the output (or crop window) size oh x ow."""
         half = self.period // 2
@@ -431,6 +533,11 @@ class VideoStabilizer:
                 raise ValueError("run_video: crop=\"auto\" needs the whole clip (a shard cannot see the clip's crop recurrence): gather "
                                  "the shards' field_homography bounds and pass crop=auto_crop_window(...)")
             _check_lattice(h, w)
+        detect = isinstance(scene_cuts, str)
+        if detect and scene_cuts != "auto":
+            raise ValueError("scene_cuts must be None, \"auto\" or a sorted sequence of frame indices, got %r" % (scene_cuts,))
+        cuts = [] if detect or scene_cuts is None else _check_cuts(scene_cuts, n_all, "run_video")
+        self.scene_cuts = cuts
 
         def crop_window(crop):
             cy0, cy1, cx0, cx1 = 0, oh, 0, ow
@@ -492,7 +599,27 @@ class VideoStabilizer:
                     window_planes(buf, 256, frames_are_rgb, out=gray_all[s:e])
                 ev = torch.cuda.Event()
                 ev.record(up)
+                if detect:   # same stream: ordered behind the planes (and behind the previous chunk's, whose last plane it reads)
+                    s0 = max(s - 1, 0)
+                    scores_h[s:e].copy_(scene_scores(gray_all[s0:e])[s - s0:], non_blocking=True)
+                    scored[c] = torch.cuda.Event()
+                    scored[c].record(up)
             return buf, ev
+
+        def detect_cuts(need):
+            """extends the cut list over the planes 0 .. need-1 (the host waits for the upload that scored plane need-1)"""
+            nonlocal decided
+            k = next(k for k, (s, e) in enumerate(chunks) if e >= need)
+            t0 = time.perf_counter()
+            scored[k].synchronize()
+            self.scene_wait_s += time.perf_counter() - t0
+            last = cuts[-1] if cuts else 0
+            first = max(decided, 1)
+            for t, v in enumerate(scores_h[first:need].tolist(), first):
+                if v > scene_threshold and t - last >= scene_min_len:   # find_scene_cuts' rule, continued
+                    cuts.append(t)
+                    last = t
+            decided = max(decided, need)
 
         def finish(warped, buf, s, e, lane):
             """output resize + crop of the warped core frames s .. e-1 (output positions) on `lane`, and their way to `out`"""
@@ -519,6 +646,10 @@ class VideoStabilizer:
             else:
                 out[s:e].copy_(warped)
         staged, uploaded = {}, 0
+        if detect:
+            scores_h = torch.empty((n_all,), dtype=torch.float32, pin_memory=True)
+            scored, decided = {}, 0
+            self.scene_wait_s = 0.0   # host time spent in those waits (tools/scene_cuts_bench.py)
         try:
             for c, (s, e) in enumerate(chunks):
                 lane = lanes[c % len(lanes)]
@@ -536,12 +667,16 @@ class VideoStabilizer:
                 # core frames of this chunk (the halo frames at the clip's ends are uploaded with it but not stabilised)
                 cs, ce = max(s, halo_left), min(e, halo_left + T)
                 hl, hr = min(half, cs), min(half, n_all - ce)
+                if detect:
+                    detect_cuts(ce + hr)
+                # the cuts inside this chunk's slice of the planes, in the slice's index space (None without cuts: the path as it was)
+                sc = [t - (cs - hl) for t in cuts if cs - hl < t < ce + hr] or None
                 with torch.cuda.stream(lane):
                     if auto:   # pass 1: fields and per-frame bounds only (no halos here: core frames = output positions)
-                        self._fields(gray_all[cs - hl:ce + hr], hl, hr, fields[cs:ce])
+                        self._fields(gray_all[cs - hl:ce + hr], hl, hr, fields[cs:ce], sc)
                         _field_homography(fields[cs:ce], h, w, hom[cs:ce], bounds[cs:ce])
                         continue
-                    warped = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr, pixel_format=pixel_format)
+                    warped = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr, pixel_format=pixel_format, scene_cuts=sc)
                     finish(warped, buf, cs - halo_left, ce - halo_left, lane)
         finally:
             if restore is not None:
@@ -550,7 +685,7 @@ class VideoStabilizer:
                 mod.two_queues = restore[3]
                 mod.enable_graph(restore[0], restore[1], per_stream=restore[2])
         if auto:
-            crop = auto_crop_window(bounds, (h, w), (oh, ow), self.period)   # (the copy to the host waits for pass 1)
+            crop = auto_crop_window(bounds, (h, w), (oh, ow), self.period, scene_cuts=cuts or None)   # (the copy to the host waits for pass 1)
             if yuv:   # the BGR path's window, rounded inward to even edges
                 x0, x1, y0, y1 = int(crop[0]), int(crop[1]), int(crop[2]), int(crop[3])
                 crop = (x0 + (x0 & 1), x1 - (x1 & 1), y0 + (y0 & 1), y1 - (y1 & 1))
