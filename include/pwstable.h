@@ -39,6 +39,7 @@
  *   pws_grid_sample_fwd / _bwd    F.grid_sample (+ autograd)       main_new.py:106,109,116,118,197,214,716
  *   pws_upsample_bilinear_ac      UpsamplingBilinear2d(size=...)   main_new.py:706-710
  *   pws_upsample_grid_sample_fwd  the two above fused (720p path)  main_new.py:706-716
+ *   pws_upsample_grid_sample_bicubic_*  the fused path with grid_sample(mode="bicubic") (no counterpart in the reference)
  *   pws_adam_step                 optim.Adam(...).step()           main_new.py:63,216
  *   pws_field_homography          the automatic crop's per-frame findHomography + perspectiveTransform  main_new.py:550-603
  *   pws_scene_change              the window's end clamp, applied at hard cuts too (cut score)          main_new.py:627-633
@@ -412,6 +413,22 @@ int pws_area_resize_plane_u16(const unsigned short *in, size_t in_stride, unsign
  * a plane read 64 (Y) / 512 (U, V), BT.601 black.  h even, w % 4 == 0, frames and out 8-byte aligned.  6 bytes of frame traffic per pixel. */
 int pws_upsample_grid_sample_yuv420_u16(const unsigned short *frames, const float *field, unsigned short *out, int n, int h, int w, int fh,
                                         int fw, int layout, int align_corners, pws_stream_t stream);
+
+/* Bicubic twins of the four fused warps above (csrc/warp_bicubic.hip): same arguments, layouts, alignment rules and error codes; the field
+ * is resized and un-normalised with the same fp32 operations, then 4 x 4 taps are blended with Keys' cubic convolution, A = -0.75 -- torch's
+ * F.grid_sample(mode="bicubic", padding_mode="zeros").  With x0 = floor(ix), t = ix - x0 the weights of columns x0-1 .. x0+2 are
+ * [c2(t+1), c1(t), c1(1-t), c2(2-t)], c1(s) = ((A+2)s - (A+3))s^2 + 1, c2(s) = ((As - 5A)s + 8A)s - 4A, rows alike; a tap outside the plane reads
+ * the pad value (0; 16 / 128 for 8-bit Y / chroma, 64 / 512 for 10-bit), a pixel whose 16 taps are all outside is the pad value exactly.  A
+ * cubic overshoots: integer outputs are clamped to 0..255 / 0..1023, then truncated; float output is not clamped.  Forward only.  Every plane
+ * must hold the 4-column window: w >= 4, and w >= 8 for the 4:2:0 formats (PWS_EINVAL otherwise). */
+int pws_upsample_grid_sample_bicubic_fwd(const float *input, const float *field, float *out, int n, int c, int h, int w, int fh, int fw,
+                                         int align_corners, pws_stream_t stream);
+int pws_upsample_grid_sample_bicubic_u8(const unsigned char *frame_hwc, const float *field, unsigned char *out_hwc, int n, int h, int w,
+                                        int fh, int fw, int swap_rb, int align_corners, pws_stream_t stream);
+int pws_upsample_grid_sample_bicubic_yuv420_u8(const unsigned char *frames, const float *field, unsigned char *out, int n, int h, int w,
+                                               int fh, int fw, int layout, int align_corners, pws_stream_t stream);
+int pws_upsample_grid_sample_bicubic_yuv420_u16(const unsigned short *frames, const float *field, unsigned short *out, int n, int h, int w,
+                                                int fh, int fw, int layout, int align_corners, pws_stream_t stream);
 
 /* The automatic crop of the reference's video loop (main_new.py:484-606, a block it keeps inside a string literal), per frame
  * (csrc/homography.hip): field[n,fh,fw,2] resized to the h0 x w0 source frame as pws_upsample_bilinear_ac does is sampled on the

@@ -126,25 +126,40 @@ class UpsamplingBilinear2d(torch.nn.Module):
         return upsample_bilinear2d(x, self.size)
 
 
-def upsample_grid_sample(input, field, align_corners=None):
+INTERPOLATIONS = ("bilinear", "bicubic")
+
+
+def _entry(mode, name):
+    """The C entry point of a fused warp for ``mode``: the bilinear ``pws_upsample_grid_sample_<name>`` or its bicubic twin
+    ``pws_upsample_grid_sample_bicubic_<name>`` (Keys cubic convolution, A = -0.75: torch's ``grid_sample(mode="bicubic")``; integer
+    outputs are clamped to the format's range, then truncated).  Anything else is a ValueError, raised before the library is touched."""
+    if mode not in INTERPOLATIONS:
+        raise ValueError("mode must be one of %s, got %r" % (INTERPOLATIONS, mode))
+    return "pws_upsample_grid_sample_" + ("bicubic_" if mode == "bicubic" else "") + name
+
+
+def upsample_grid_sample(input, field, align_corners=None, mode="bilinear"):
     """grid_sample(input, UpsamplingBilinear2d(size=input.shape[-2:])(field)) without materialising the resized field.
 
-    input: (N,C,H,W) frame; field: (N,h,w,2) warp field as returned by ``netG(x, False)``.
+    input: (N,C,H,W) frame; field: (N,h,w,2) warp field as returned by ``netG(x, False)``.  mode = "bicubic": the same warp with
+    ``grid_sample(mode="bicubic")``'s 16 taps (forward only; W >= 4).
     """
+    fn = _entry(mode, "fwd")
     A.require_cuda(input, field)
     input, field = input.contiguous(), field.contiguous()
     n, c, h, w = input.shape
     fh, fw = field.shape[1], field.shape[2]
     out = torch.empty_like(input)
-    A.check(A.lib().pws_upsample_grid_sample_fwd(A.ptr(input), A.ptr(field), A.ptr(out), n, c, h, w, fh, fw,
-                                                 _ac(align_corners), A.current_stream()), "pws_upsample_grid_sample_fwd")
+    A.check(getattr(A.lib(), fn)(A.ptr(input), A.ptr(field), A.ptr(out), n, c, h, w, fh, fw, _ac(align_corners), A.current_stream()), fn)
     return out
 
 
-def upsample_grid_sample_u8(frames_hwc, field, swap_rb=False, align_corners=None, out=None):
+def upsample_grid_sample_u8(frames_hwc, field, swap_rb=False, align_corners=None, out=None, mode="bilinear"):
     """The 720p step of the reference's ``process()`` on the frames as OpenCV delivers them (main_new.py:679-721):
     ``frames_hwc`` (N,H,W,3) uint8 -> [optional BGR<->RGB swap] -> float CHW -> grid_sample with the field resized to (H,W)
-    (UpsamplingBilinear2d) -> ``astype(uint8)`` HWC, in one kernel and 6 bytes of frame traffic per pixel.  W % 4 == 0."""
+    (UpsamplingBilinear2d) -> ``astype(uint8)`` HWC, in one kernel and 6 bytes of frame traffic per pixel.  W % 4 == 0.
+    mode = "bicubic": 16 taps per pixel (``grid_sample(mode="bicubic")``), the blend clamped to 0..255 before it is truncated."""
+    fn = _entry(mode, "u8")
     A.require_cuda(field)
     A.require_cuda(frames_hwc, dtype=torch.uint8)
     if frames_hwc.dim() != 4 or frames_hwc.shape[3] != 3:
@@ -153,9 +168,8 @@ def upsample_grid_sample_u8(frames_hwc, field, swap_rb=False, align_corners=None
     n, h, w, _ = frames_hwc.shape
     if out is None:
         out = torch.empty_like(frames_hwc)
-    A.check(A.lib().pws_upsample_grid_sample_u8(A.ptr(frames_hwc), A.ptr(field), A.ptr(out), n, h, w, field.shape[1], field.shape[2],
-                                                int(bool(swap_rb)), _ac(align_corners), A.current_stream()),
-            "pws_upsample_grid_sample_u8")
+    A.check(getattr(A.lib(), fn)(A.ptr(frames_hwc), A.ptr(field), A.ptr(out), n, h, w, field.shape[1], field.shape[2],
+                                 int(bool(swap_rb)), _ac(align_corners), A.current_stream()), fn)
     return out
 
 
@@ -187,10 +201,12 @@ def yuv420_shape(frames, pixel_format, w_multiple=4):
     return t, h, w
 
 
-def upsample_grid_sample_yuv420(frames, field, pixel_format, align_corners=None, out=None):
+def upsample_grid_sample_yuv420(frames, field, pixel_format, align_corners=None, out=None, mode="bilinear"):
     """upsample_grid_sample_u8 for packed 4:2:0 frames, YUV in and YUV out: ``frames`` (N, H * 3 // 2, W) uint8 in ``pixel_format``
     "nv12" or "i420"; every plane is warped by ``field`` (N, fh, fw, 2) resized (align_corners=True) to the plane's own size, taps outside
-    a plane read BT.601 black (16 in Y, 128 in U and V), the fp32 blend is truncated.  H even, W % 4 == 0.  One kernel launch."""
+    a plane read BT.601 black (16 in Y, 128 in U and V), the fp32 blend is truncated.  H even, W % 4 == 0.  One kernel launch.
+    mode = "bicubic": 16 taps per sample, the blend clamped to 0..255 before it is truncated; W >= 8."""
+    fn = _entry(mode, "yuv420_u8")
     A.require_cuda(field)
     A.require_cuda(frames, dtype=torch.uint8)
     layout = yuv420_layout(pixel_format)
@@ -200,8 +216,8 @@ def upsample_grid_sample_yuv420(frames, field, pixel_format, align_corners=None,
     frames, field = frames.contiguous(), field.contiguous()
     if out is None:
         out = torch.empty_like(frames)
-    A.check(A.lib().pws_upsample_grid_sample_yuv420_u8(A.ptr(frames), A.ptr(field), A.ptr(out), n, h, w, field.shape[1], field.shape[2], layout,
-                                                       _ac(align_corners), A.current_stream()), "pws_upsample_grid_sample_yuv420_u8")
+    A.check(getattr(A.lib(), fn)(A.ptr(frames), A.ptr(field), A.ptr(out), n, h, w, field.shape[1], field.shape[2], layout,
+                                 _ac(align_corners), A.current_stream()), fn)
     return out
 
 
@@ -233,11 +249,13 @@ def yuv420_16_shape(frames, pixel_format, w_multiple=4):
     return t, h, w
 
 
-def upsample_grid_sample_yuv420_16(frames, field, pixel_format, align_corners=None, out=None):
+def upsample_grid_sample_yuv420_16(frames, field, pixel_format, align_corners=None, out=None, mode="bilinear"):
     """upsample_grid_sample_yuv420 for 10-bit frames, YUV in and YUV out: ``frames`` (N, H * 3 // 2, W) uint16 in ``pixel_format`` "p010"
     (sample = word >> 6; output words have zero low bits) or "i010" (sample = min(word, 1023)); every plane is warped by ``field``
     (N, fh, fw, 2) resized (align_corners=True) to the plane's own size, bilinear in fp32 on the 10-bit values, taps outside a plane read
-    BT.601 black (64 in Y, 512 in U and V), the blend is truncated and clamped to 0..1023.  H even, W % 4 == 0.  One kernel launch."""
+    BT.601 black (64 in Y, 512 in U and V), the blend is truncated and clamped to 0..1023.  H even, W % 4 == 0.  One kernel launch.
+    mode = "bicubic": 16 taps per sample on the 10-bit values, clamped to 0..1023, then truncated; W >= 8."""
+    fn = _entry(mode, "yuv420_u16")
     layout = yuv420_16_layout(pixel_format)
     n, h, w = yuv420_16_shape(frames, pixel_format)   # (a tensor that is not uint16 is a ValueError, like a bad shape)
     A.require_cuda(field)
@@ -247,8 +265,8 @@ def upsample_grid_sample_yuv420_16(frames, field, pixel_format, align_corners=No
     frames, field = frames.contiguous(), field.contiguous()
     if out is None:
         out = torch.empty_like(frames)
-    A.check(A.lib().pws_upsample_grid_sample_yuv420_u16(A.ptr(frames), A.ptr(field), A.ptr(out), n, h, w, field.shape[1], field.shape[2], layout,
-                                                        _ac(align_corners), A.current_stream()), "pws_upsample_grid_sample_yuv420_u16")
+    A.check(getattr(A.lib(), fn)(A.ptr(frames), A.ptr(field), A.ptr(out), n, h, w, field.shape[1], field.shape[2], layout,
+                                 _ac(align_corners), A.current_stream()), fn)
     return out
 
 

@@ -300,8 +300,11 @@ def _windows(gray_padded, start, count, period):
 
 
 class VideoStabilizer:
-    def __init__(self, netG, batch=32, period=30, device=None, swap_rb=False):
+    def __init__(self, netG, batch=32, period=30, device=None, swap_rb=False, interpolation="bilinear"):
         self.net = netG
+        if interpolation not in PF.INTERPOLATIONS:
+            raise ValueError("interpolation must be one of %s, got %r" % (PF.INTERPOLATIONS, interpolation))
+        self.interpolation = interpolation   # how run / run_video make an output pixel: 4 taps, or grid_sample(mode="bicubic")'s 16
         self.swap_rb = bool(swap_rb)   # uint8 frames only: BGR (cv2) in, RGB out, as main_new.py:679
         self.batch = int(batch)
         self.period = int(period)
@@ -368,7 +371,8 @@ class VideoStabilizer:
         frames to stabilise plus whatever real neighbours exist on either side (up to period//2); frames: (T, C, H, W)
         float32 0..255, or (T, H, W, 3) uint8 as OpenCV delivers them (then the warp runs in the uint8 kernel: 4x less
         PCIe and HBM traffic per frame, ``self.swap_rb`` applies the reference's BGR->RGB).  Tensors may be on the device or in
-        (pinned) host memory.  Returns a tensor of the frames' shape and dtype on the inputs' side.
+        (pinned) host memory.  Returns a tensor of the frames' shape and dtype on the inputs' side.  Every warp below runs with
+        ``self.interpolation`` ("bilinear", or "bicubic": functional.upsample_grid_sample*(mode="bicubic")); nothing else depends on it.
         pixel_format = "nv12" / "i420": frames are packed 4:2:0 (T, H * 3 // 2, W) uint8 (H even, W % 4 == 0), warped plane by plane in
         the fused YUV kernel (functional.upsample_grid_sample_yuv420: BT.601 black padding); ``self.swap_rb`` does not apply.
         pixel_format = "p010" / "i010": the same for 10-bit frames (T, H * 3 // 2, W) uint16 (functional.upsample_grid_sample_yuv420_16).
@@ -422,13 +426,13 @@ class VideoStabilizer:
             win = _windows(gp, start, e - s, self.period)
             field = self.net(win, False)
             if yuv16:
-                warped = PF.upsample_grid_sample_yuv420_16(cur.contiguous(), field, pixel_format, align_corners=self.align_corners)
+                warped = PF.upsample_grid_sample_yuv420_16(cur.contiguous(), field, pixel_format, align_corners=self.align_corners, mode=self.interpolation)
             elif yuv:
-                warped = PF.upsample_grid_sample_yuv420(cur.contiguous(), field, pixel_format, align_corners=self.align_corners)
+                warped = PF.upsample_grid_sample_yuv420(cur.contiguous(), field, pixel_format, align_corners=self.align_corners, mode=self.interpolation)
             elif cur.dtype == torch.uint8:
-                warped = PF.upsample_grid_sample_u8(cur.contiguous(), field, swap_rb=self.swap_rb, align_corners=self.align_corners)
+                warped = PF.upsample_grid_sample_u8(cur.contiguous(), field, swap_rb=self.swap_rb, align_corners=self.align_corners, mode=self.interpolation)
             else:
-                warped = PF.upsample_grid_sample(cur.contiguous(), field, align_corners=self.align_corners)
+                warped = PF.upsample_grid_sample(cur.contiguous(), field, align_corners=self.align_corners, mode=self.interpolation)
             if on_host:
                 done = torch.cuda.Event()
                 done.record(compute)
@@ -712,11 +716,11 @@ class VideoStabilizer:
                 if ev is not None:
                     compute.wait_event(ev)
                 if yuv16:
-                    warped = PF.upsample_grid_sample_yuv420_16(buf.contiguous(), fields[s:e], pixel_format, align_corners=self.align_corners)
+                    warped = PF.upsample_grid_sample_yuv420_16(buf.contiguous(), fields[s:e], pixel_format, align_corners=self.align_corners, mode=self.interpolation)
                 elif yuv:
-                    warped = PF.upsample_grid_sample_yuv420(buf.contiguous(), fields[s:e], pixel_format, align_corners=self.align_corners)
+                    warped = PF.upsample_grid_sample_yuv420(buf.contiguous(), fields[s:e], pixel_format, align_corners=self.align_corners, mode=self.interpolation)
                 else:
-                    warped = PF.upsample_grid_sample_u8(buf.contiguous(), fields[s:e], swap_rb=self.swap_rb, align_corners=self.align_corners)
+                    warped = PF.upsample_grid_sample_u8(buf.contiguous(), fields[s:e], swap_rb=self.swap_rb, align_corners=self.align_corners, mode=self.interpolation)
                 finish(warped, buf, s, e, compute)
         if on_host:
             down.synchronize()
