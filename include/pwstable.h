@@ -40,6 +40,7 @@
  *   pws_upsample_bilinear_ac      UpsamplingBilinear2d(size=...)   main_new.py:706-710
  *   pws_upsample_grid_sample_fwd  the two above fused (720p path)  main_new.py:706-716
  *   pws_upsample_grid_sample_bicubic_*  the fused path with grid_sample(mode="bicubic") (no counterpart in the reference)
+ *   pws_border_keep_*             out[t] = covered ? warped[t] : out[t-1] over a scene's warped frames (no counterpart in the reference)
  *   pws_adam_step                 optim.Adam(...).step()           main_new.py:63,216
  *   pws_field_homography          the automatic crop's per-frame findHomography + perspectiveTransform  main_new.py:550-603
  *   pws_scene_change              the window's end clamp, applied at hard cuts too (cut score)          main_new.py:627-633
@@ -429,6 +430,22 @@ int pws_upsample_grid_sample_bicubic_yuv420_u8(const unsigned char *frames, cons
                                                int fh, int fw, int layout, int align_corners, pws_stream_t stream);
 int pws_upsample_grid_sample_bicubic_yuv420_u16(const unsigned short *frames, const float *field, unsigned short *out, int n, int h, int w,
                                                 int fh, int fw, int layout, int align_corners, pws_stream_t stream);
+
+/* "Keep" borders for the fused byte warps above (csrc/border_keep.hip; no counterpart in the reference): n consecutive WARPED frames of one
+ * scene, modified in place.  A pixel of frame t whose source position (ix, iy) -- formed from field[t] with the warps' own fp32 operations --
+ * does not satisfy m <= ix <= w-1-m and m <= iy <= h-1-m (per plane: its own size and field resize; m = 0, or 1 with `bicubic`: all 4 / all 16
+ * taps inside; NaN is outside) takes the value of frame t-1 after the same rule, frame -1 being `initial` (one frame in the frames' layout):
+ * an earlier output frame, copied as it is, or -- initial_is_source -- a source frame read as the warp would write it (swap_rb; P010 words
+ * masked to v10 << 6; I010 words clamped to 1023).  Coverage is binary: every output sample is a copy of one of those two samples.  `initial`
+ * must not overlap `frames`.  Arguments, layouts, alignment rules (they hold for `initial` too) and error codes are the warps': w % 4 == 0,
+ * even h for 4:2:0, and w >= 8 for 4:2:0 with `bicubic` (PWS_EINVAL otherwise).  One launch; the traffic is the fields plus the uncovered
+ * pixels, not the frames. */
+int pws_border_keep_u8(unsigned char *frames_hwc, const float *field, const unsigned char *initial, int initial_is_source, int n, int h, int w,
+                       int fh, int fw, int swap_rb, int align_corners, int bicubic, pws_stream_t stream);
+int pws_border_keep_yuv420_u8(unsigned char *frames, const float *field, const unsigned char *initial, int initial_is_source, int n, int h,
+                              int w, int fh, int fw, int layout, int align_corners, int bicubic, pws_stream_t stream);
+int pws_border_keep_yuv420_u16(unsigned short *frames, const float *field, const unsigned short *initial, int initial_is_source, int n, int h,
+                               int w, int fh, int fw, int layout, int align_corners, int bicubic, pws_stream_t stream);
 
 /* The automatic crop of the reference's video loop (main_new.py:484-606, a block it keeps inside a string literal), per frame
  * (csrc/homography.hip): field[n,fh,fw,2] resized to the h0 x w0 source frame as pws_upsample_bilinear_ac does is sampled on the

@@ -270,6 +270,48 @@ def upsample_grid_sample_yuv420_16(frames, field, pixel_format, align_corners=No
     return out
 
 
+BORDERS = ("black", "keep")
+
+
+def keep_borders_(warped, field, initial, pixel_format="bgr24", initial_is_source=False, swap_rb=False, align_corners=None, mode="bilinear"):
+    """vid.stab's ``crop=keep`` for the integer fused warps, IN PLACE on ``warped``: T consecutive warped frames of one scene ((T, H, W, 3)
+    uint8 for "bgr24", packed (T, H * 3 // 2, W) uint8 for "nv12" / "i420", uint16 for "p010" / "i010"; contiguous) and the ``field``
+    (T, fh, fw, 2) that warped them.  ``out[t] = covered ? warped[t] : out[t-1]`` per plane, where a pixel is covered iff its source position
+    (the warp's own, bit for bit) satisfies ``m <= ix <= W-1-m`` and ``m <= iy <= H-1-m`` with m = 0 for mode "bilinear" (all 4 taps inside)
+    and 1 for "bicubic" (all 16); NaN is not covered.  ``out[-1]`` is ``initial``, one frame of the frames' layout that does not overlap
+    ``warped``: an earlier output frame, copied as it is, or -- ``initial_is_source`` -- a SOURCE frame read as the warp would write it
+    (``swap_rb`` for BGR, P010 words masked to ``v10 << 6``, I010 words clamped to 1023).  Coverage is binary: every sample of the result is a
+    copy of one of the two.  One launch (csrc/border_keep.hip).  Shape and alignment rules are the warps'.  Float frames are a ValueError.
+    Returns ``warped``."""
+    if mode not in INTERPOLATIONS:
+        raise ValueError("mode must be one of %s, got %r" % (INTERPOLATIONS, mode))
+    if not isinstance(warped, torch.Tensor) or warped.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError("keep_borders_: frames must be uint8 or uint16 (the integer pixel formats), got %s" % (getattr(warped, "dtype", type(warped)),))
+    if pixel_format == "bgr24":
+        if warped.dtype != torch.uint8 or warped.dim() != 4 or warped.shape[3] != 3:
+            raise ValueError("keep_borders_: bgr24 frames must be uint8 (T,H,W,3), got %s %s" % (warped.dtype, tuple(warped.shape)))
+        n, h, w = warped.shape[:3]
+        fn, extra = "pws_border_keep_u8", int(bool(swap_rb))
+    elif pixel_format in PIXEL_FORMATS_16:
+        n, h, w = yuv420_16_shape(warped, pixel_format)
+        fn, extra = "pws_border_keep_yuv420_u16", yuv420_16_layout(pixel_format)
+    else:
+        n, h, w = yuv420_shape(warped, pixel_format)   # (an unknown format, or a tensor that is not uint8, is a ValueError)
+        fn, extra = "pws_border_keep_yuv420_u8", yuv420_layout(pixel_format)
+    A.require_cuda(field)
+    A.require_cuda(warped, initial, dtype=warped.dtype)
+    if not warped.is_contiguous():
+        raise ValueError("keep_borders_: frames are modified in place and must be contiguous")
+    if tuple(initial.shape) != tuple(warped.shape[1:]):
+        raise ValueError("keep_borders_: initial must be one frame %s, got %s" % (tuple(warped.shape[1:]), tuple(initial.shape)))
+    if field.dim() != 4 or field.shape[0] != n or field.shape[3] != 2:
+        raise ValueError("keep_borders_: field must be (%d, fh, fw, 2), got %s" % (n, tuple(field.shape)))
+    field, initial = field.contiguous(), initial.contiguous()
+    A.check(getattr(A.lib(), fn)(A.ptr(warped), A.ptr(field), A.ptr(initial), int(bool(initial_is_source)), n, h, w, field.shape[1],
+                                 field.shape[2], extra, _ac(align_corners), int(mode == "bicubic"), A.current_stream()), fn)
+    return warped
+
+
 def adam_step_(p, g, m, v, lr, beta1, beta2, eps, step):
     """In-place fused Adam on flat fp32 CUDA buffers."""
     A.require_cuda(p, g, m, v)

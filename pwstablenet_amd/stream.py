@@ -300,8 +300,13 @@ def _windows(gray_padded, start, count, period):
 
 
 class VideoStabilizer:
-    def __init__(self, netG, batch=32, period=30, device=None, swap_rb=False, interpolation="bilinear"):
+    def __init__(self, netG, batch=32, period=30, device=None, swap_rb=False, interpolation="bilinear", borders="black"):
         self.net = netG
+        if borders not in PF.BORDERS:
+            raise ValueError("borders must be one of %s, got %r" % (PF.BORDERS, borders))
+        # what run / run_video show where a frame's field samples outside the source: the warp's pad colour, or -- "keep", vid.stab's
+        # crop=keep -- the previous output frame of the scene (functional.keep_borders_, one more launch per batch and scene)
+        self.borders = borders
         if interpolation not in PF.INTERPOLATIONS:
             raise ValueError("interpolation must be one of %s, got %r" % (PF.INTERPOLATIONS, interpolation))
         self.interpolation = interpolation   # how run / run_video make an output pixel: 4 taps, or grid_sample(mode="bicubic")'s 16
@@ -366,7 +371,7 @@ class VideoStabilizer:
             out[s:e].copy_(self.net(_windows(gp, start, e - s, self.period), False))
 
     @torch.no_grad()
-    def run(self, gray, frames, halo_left=0, halo_right=0, out=None, pixel_format="bgr24", scene_cuts=None):
+    def run(self, gray, frames, halo_left=0, halo_right=0, out=None, pixel_format="bgr24", scene_cuts=None, keep_from=None, _keep_wait=None):
         """gray: (T + halo_left + halo_right, 256, 256) float32 in [-1,1] (``x/255*2-1`` as the reference, :650) for the T
         frames to stabilise plus whatever real neighbours exist on either side (up to period//2); frames: (T, C, H, W)
         float32 0..255, or (T, H, W, 3) uint8 as OpenCV delivers them (then the warp runs in the uint8 kernel: 4x less
@@ -378,8 +383,17 @@ class VideoStabilizer:
         pixel_format = "p010" / "i010": the same for 10-bit frames (T, H * 3 // 2, W) uint16 (functional.upsample_grid_sample_yuv420_16).
         scene_cuts: sorted indices into ``gray`` (halo frames count; 1 .. len - 1) at which a new scene starts.  Windows end at them as they
         end at the clip's ends -- the scene's first / last frame is repeated (_layout) -- and the batches restart at every scene, so a scene
-        is stabilised exactly as the clip of that scene alone would be.  None or empty: one scene."""
+        is stabilised exactly as the clip of that scene alone would be.  None or empty: one scene.
+        borders="keep" (integer frames only; float frames are a ValueError): after each batch's warp ``functional.keep_borders_`` runs over
+        it -- a batch never spans a cut, so it is one segment -- starting from the previous batch's last OUTPUT frame, or, at a scene's first
+        frame, from that frame's own SOURCE.  keep_from: the output frame (device tensor, one frame of the frames' layout, before any resize)
+        that precedes frames[0] in its scene, for a clip processed in several calls (run_video passes each chunk's last frame on); without
+        it frames[0] starts from its source -- so a shard with halo_left > 0 has no history and does not promise the unsharded clip's
+        bytes in its wedges."""
         half = self.period // 2
+        keep = self.borders == "keep"
+        if keep and frames.dtype not in (torch.uint8, torch.uint16):
+            raise ValueError("run: borders=\"keep\" is for the integer pixel formats (uint8 / uint16 frames), got %s" % (frames.dtype,))
         yuv = pixel_format != "bgr24"
         yuv16 = pixel_format in PF.PIXEL_FORMATS_16
         if yuv16:
@@ -417,6 +431,7 @@ class VideoStabilizer:
 
         nxt = fetch(0)
         pending = []
+        cutset, prev = set(cuts or ()), None
         for k, (s, e, start) in enumerate(batches):
             cur, ev = nxt
             if k + 1 < len(batches):
@@ -433,6 +448,19 @@ class VideoStabilizer:
                 warped = PF.upsample_grid_sample_u8(cur.contiguous(), field, swap_rb=self.swap_rb, align_corners=self.align_corners, mode=self.interpolation)
             else:
                 warped = PF.upsample_grid_sample(cur.contiguous(), field, align_corners=self.align_corners, mode=self.interpolation)
+            if keep:
+                if (s + halo_left) in cutset or (s == 0 and keep_from is None):
+                    init, src = cur.contiguous()[0], True   # a scene's first frame: its own source, as the warp would write it
+                elif prev is not None:
+                    init, src = prev, False
+                else:   # the caller's history: possibly written on another stream (run_video's other lane)
+                    if _keep_wait is not None:
+                        compute.wait_event(_keep_wait)
+                    keep_from.record_stream(compute)
+                    init, src = keep_from, False
+                PF.keep_borders_(warped, field, init, pixel_format, initial_is_source=src, swap_rb=self.swap_rb and not yuv,
+                                 align_corners=self.align_corners, mode=self.interpolation)
+                prev = warped[-1]   # (a view: keeps the batch alive until the next one has read it)
             if on_host:
                 done = torch.cuda.Event()
                 done.record(compute)
@@ -498,6 +526,16 @@ class VideoStabilizer:
         halo) that detects on its own slice has no history before its halo and may place scene_min_len differently from the whole clip:
         sharded hosts compute ``scene_scores`` per shard, gather, call ``find_scene_cuts`` once and pass explicit lists.  The cuts used are
         left in ``self.scene_cuts``.  None (the default): one scene, every path as without the argument.
+        VideoStabilizer(borders="keep"): the field of view is kept instead of cropped -- an output pixel the current frame does not cover (a
+        tap of the warp outside the source) keeps the value the previous output frame of its scene had there, and a scene's first frame
+        starts from its own source, so no wedge ever shows the pad colour (functional.keep_borders_ has the definition).  The pass runs on
+        the warped frames BEFORE the output resize and the crop; each chunk starts from the previous chunk's last warped frame (the tensor
+        is kept alive, not copied), and with in_flight > 1 a chunk's first pass waits for an event recorded behind the previous chunk's last
+        pass on the other lane -- generator and warp stay unordered between the lanes, and the frames are those of in_flight = 1 bit for
+        bit.  Cuts reset the history ("auto" needs no extra wait: a chunk's cuts are known before it is issued).  An explicit crop,
+        output_size, half_size_output, halos and host or device input work as before; a shard with halo_left > 0 has no history, starts its
+        first frame from that frame's source and does not promise the unsharded clip's bytes in its wedges; crop="auto" is a ValueError
+        (it removes what "keep" fills).
         Returns (T, H, W, 3) -- or (T, H/2, W/2, 3) / (T, height, width, 3), or the crop window of it -- uint8 on the inputs' side; for YUV
         (T, oh * 3 // 2, ow) of the output (or crop window) size oh x ow."""
         half = self.period // 2
@@ -536,6 +574,8 @@ class VideoStabilizer:
             if halo_left or halo_right:
                 raise ValueError("run_video: crop=\"auto\" needs the whole clip (a shard cannot see the clip's crop recurrence): gather "
                                  "the shards' field_homography bounds and pass crop=auto_crop_window(...)")
+            if self.borders == "keep":
+                raise ValueError("run_video: crop=\"auto\" removes the wedges that borders=\"keep\" fills: choose one")
             _check_lattice(h, w)
         detect = isinstance(scene_cuts, str)
         if detect and scene_cuts != "auto":
@@ -650,6 +690,8 @@ class VideoStabilizer:
             else:
                 out[s:e].copy_(warped)
         staged, uploaded = {}, 0
+        keep = self.borders == "keep"
+        carry, carried = None, None   # borders="keep": the last warped (pre-resize) frame so far, and the event behind the pass that made it
         if detect:
             scores_h = torch.empty((n_all,), dtype=torch.float32, pin_memory=True)
             scored, decided = {}, 0
@@ -680,7 +722,13 @@ class VideoStabilizer:
                         self._fields(gray_all[cs - hl:ce + hr], hl, hr, fields[cs:ce], sc)
                         _field_homography(fields[cs:ce], h, w, hom[cs:ce], bounds[cs:ce])
                         continue
-                    warped = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr, pixel_format=pixel_format, scene_cuts=sc)
+                    warped = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr, pixel_format=pixel_format, scene_cuts=sc,
+                                      keep_from=carry, _keep_wait=carried)
+                    if keep:   # the next chunk's pass (on the other lane, if any) starts from this chunk's last frame: no copy, one event
+                        carry = warped[-1]
+                        if len(lanes) > 1:
+                            carried = torch.cuda.Event()
+                            carried.record(lane)
                     finish(warped, buf, cs - halo_left, ce - halo_left, lane)
         finally:
             if restore is not None:
