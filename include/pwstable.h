@@ -44,6 +44,7 @@
  *   pws_adam_step                 optim.Adam(...).step()           main_new.py:63,216
  *   pws_field_homography          the automatic crop's per-frame findHomography + perspectiveTransform  main_new.py:550-603
  *   pws_scene_change              the window's end clamp, applied at hard cuts too (cut score)          main_new.py:627-633
+ *   pws_field_zoom                the warp field resampled over a per-frame window: zoom to fill (no counterpart in the reference)
  *   pws_pack_* / pws_netg_pack_weights   state_dict (OIHW / IOHW) -> kernel layout; main_new.py:60,471
  *
  * Layouts.  Frames / images: NCHW fp32 as in the reference.  Warp fields: N,H,W,2 fp32 (x then y,
@@ -458,6 +459,24 @@ int pws_border_keep_yuv420_u16(unsigned short *frames, const float *field, const
  * h0 >= 300 and w0 >= 600 (the lattice must fit); field and pts_out 8-byte aligned. */
 int pws_field_homography(const float *field, int n, int fh, int fw, int h0, int w0, double *m_out, float *bounds_out, float *pts_out,
                          pws_stream_t stream);
+
+/* Zoom to fill (csrc/field_zoom.hip; no counterpart in the reference).  Every fused warp above resizes its small field to the frame
+ * (align_corners=True) before it samples, so a zoom into a window of the warped frame is a resampling of the FIELD over that window: the
+ * field's values are kept, only its domain changes, and the warp that follows produces the zoomed frame in its single resampling pass.
+ * field[n,fh,fw,2] -> out[n,fh,fw,2]; coef[n,4] = Ax, Bx, Ay, By of frame t, in DEVICE memory.  For node (i, j) of frame t:
+ *   sx = clamp(fmaf(Bx, (float)j, Ax), 0, fw-1), x0 = floor(sx), x1 = x0 + (x0 < fw-1), lx = sx - x0, hx = 1 - lx; sy, y0, y1, ly, hy alike
+ *   from Ay, By, i; out[t,i,j,c] = fma(ly, fma(lx, F[y1,x1], hx * F[y1,x0]), hy * fma(lx, F[y0,x1], hx * F[y0,x0])) per component c (the
+ *   warps' own field interpolation).  Ax = Ay = 0, Bx = By = 1 returns a finite field bit for bit (a -0.0 may come back as +0.0).
+ * NaN coefficients sample node 0; no coefficient can make the kernel read outside field[t].
+ * uncovered (n, int32; may be NULL): uncovered[t] = the number of nodes of out[t] whose source position ix = unnormalize(out.x, w0),
+ * iy = unnormalize(out.y, h0) (the warps' fp32 un-normalisation, `align_corners` theirs) does not satisfy margin <= ix <= w0-1-margin and
+ * margin <= iy <= h0-1-margin (margin 0: the bilinear warp's 4 taps inside; 1: the bicubic warp's 16; NaN is not covered): pws_border_keep's
+ * rule, taken at the field's nodes.  Integer counts: the same on every run.  h0, w0, align_corners and margin are read only then.
+ * Any fh, fw >= 2; n == 0 returns PWS_OK and launches nothing.  PWS_EINVAL: NULL field / coef / out, fh or fw < 2, h0 or w0 < 1 or
+ * margin < 0 with `uncovered`, field or out not 8-byte aligned, out overlapping field (the same pointer included).  One launch (and a
+ * 4 n byte clear of `uncovered`). */
+int pws_field_zoom(const float *field, int n, int fh, int fw, const float *coef, float *out, int h0, int w0, int align_corners, int margin,
+                   int *uncovered, pws_stream_t stream);
 
 /* Scene-cut score for edited footage (csrc/scene.hip).  The reference clamps a frame's 31-plane window at the clip's first and last frame
  * only (main_new.py:627-633); the streaming stabiliser applies the same clamp at every hard cut, which it finds from the L1 distance of

@@ -312,6 +312,82 @@ def keep_borders_(warped, field, initial, pixel_format="bgr24", initial_is_sourc
     return warped
 
 
+def _zoom_windows(windows, n, frame_hw, what="zoom_fields"):
+    """``windows`` -- one (x0, x1, y0, y1) or (n, 4) of them, a sequence or a tensor on either side -- as n tuples of floats; ValueError unless
+    every one satisfies 0 <= x0 < x1 <= W0 and 0 <= y0 < y1 <= H0 (source-pixel EDGE coordinates: pixel k covers [k, k + 1))."""
+    h0, w0 = int(frame_hw[0]), int(frame_hw[1])
+    if isinstance(windows, torch.Tensor):
+        windows = windows.detach().to("cpu", torch.float64).tolist()
+    try:
+        windows = list(windows)
+        if len(windows) == 4 and not any(hasattr(v, "__len__") for v in windows):
+            windows = [windows] * n
+        windows = [tuple(float(v) for v in row) for row in windows]
+    except (TypeError, ValueError):
+        raise ValueError("%s: windows must be (x0, x1, y0, y1) or (T, 4) of them" % what) from None
+    if len(windows) != n or any(len(row) != 4 for row in windows):
+        raise ValueError("%s: windows must be one (x0, x1, y0, y1) or one per frame (%d, 4)" % (what, n))
+    for t, (x0, x1, y0, y1) in enumerate(windows):
+        if not (0 <= x0 < x1 <= w0 and 0 <= y0 < y1 <= h0):   # (False for NaN)
+            raise ValueError("%s: window %d x [%g, %g) y [%g, %g) does not lie inside the %d x %d frame" % (what, t, x0, x1, y0, y1, w0, h0))
+    return windows
+
+
+def zoom_coefficients(windows, frame_hw, field_hw):
+    """The (Ax, Bx, Ay, By) of ``pws_field_zoom`` for checked windows (``_zoom_windows``), in float64 on the host, rounded once to float32:
+    (T, 4) float32 in pinned host memory.  Node j of the field stands for output pixel x = j (W0-1)/(fw-1) under the warps' align_corners=True
+    resize; its centre x + 0.5 maps to x0 + (x + 0.5) Bx in the window, Bx = (x1 - x0) / W0, whose pixel coordinate, on the field's scale,
+    is Bx j + Ax with Ax = (x0 + 0.5 Bx - 0.5) (fw-1)/(W0-1).  The whole frame gives exactly (0, 1, 0, 1)."""
+    h0, w0 = int(frame_hw[0]), int(frame_hw[1])
+    fh, fw = int(field_hw[0]), int(field_hw[1])
+    if h0 < 2 or w0 < 2:
+        raise ValueError("zoom_fields: the frame must be at least 2 x 2 pixels, got %d x %d" % (w0, h0))
+    rows = []
+    for x0, x1, y0, y1 in windows:
+        bx, by = (x1 - x0) / w0, (y1 - y0) / h0
+        rows.append([(x0 + 0.5 * bx - 0.5) * (fw - 1) / (w0 - 1), bx, (y0 + 0.5 * by - 0.5) * (fh - 1) / (h0 - 1), by])
+    coef = torch.tensor(rows, dtype=torch.float64).reshape(len(rows), 4).to(torch.float32)
+    return coef.pin_memory() if torch.cuda.is_available() else coef
+
+
+def _field_zoom(field, coef, frame_hw, align_corners, mode, out, uncovered):
+    """pws_field_zoom on device tensors: ``coef`` (T, 4) float32, ``uncovered`` (T,) int32 or None."""
+    A.check(A.lib().pws_field_zoom(A.ptr(field), field.shape[0], field.shape[1], field.shape[2], A.ptr(coef), A.ptr(out), int(frame_hw[0]),
+                                   int(frame_hw[1]), _ac(align_corners), int(mode == "bicubic"), A.ptr(uncovered), A.current_stream()),
+            "pws_field_zoom")
+    return out
+
+
+def zoom_fields(field, windows, frame_hw, align_corners=False, mode="bilinear", out=None, return_uncovered=False):
+    """Zoom to fill, composed into the field: ``field`` (T, fh, fw, 2) as ``netG(window, False)`` returns it, resampled over ``windows`` --
+    one (x0, x1, y0, y1) or (T, 4) of them, a sequence or a tensor, in source-pixel edge coordinates of the ``frame_hw`` = (H0, W0) frame
+    (``auto_crop_window(..., output_hw=None)``'s convention: pixel k covers [k, k + 1), 0 <= x0 < x1 <= W0; fractional edges are fine,
+    anything else is a ValueError).  A fused warp given the result produces the window of the frame it would have produced from ``field``,
+    enlarged to the full frame, in its single resampling pass: node j samples the field at Bx j + Ax (``zoom_coefficients``), clamped to the
+    field, with the warps' own field interpolation.  The field's values are kept, only its domain changes; the whole frame returns the
+    field bit for bit.  The result is the warp of the RESAMPLED field -- sampled at the field's nodes, interpolated linearly between them
+    by the warp -- not the exact composition.  One launch (csrc/field_zoom.hip); ``out`` must not overlap ``field``.
+    return_uncovered: also a (T,) int32 device tensor, the number of nodes of each output field whose source position lies outside
+    ``[m, W0-1-m] x [m, H0-1-m]`` -- m = 0 for mode "bilinear", 1 for "bicubic": ``keep_borders_``' coverage rule at the field's nodes, with
+    ``align_corners`` the warp's.  0 means no node of the frame samples outside the source."""
+    if mode not in INTERPOLATIONS:
+        raise ValueError("mode must be one of %s, got %r" % (INTERPOLATIONS, mode))
+    A.require_cuda(field)
+    if field.dim() != 4 or field.shape[3] != 2 or field.shape[1] < 2 or field.shape[2] < 2:
+        raise ValueError("zoom_fields: field must be (T, fh, fw, 2) with fh, fw >= 2, got %s" % (tuple(field.shape),))
+    field = field.contiguous()
+    n = field.shape[0]
+    coef = zoom_coefficients(_zoom_windows(windows, n, frame_hw), frame_hw, field.shape[1:3]).to(field.device, non_blocking=True)
+    if out is None:
+        out = torch.empty_like(field)
+    A.require_cuda(out)
+    if tuple(out.shape) != tuple(field.shape) or not out.is_contiguous():
+        raise ValueError("zoom_fields: out must be a contiguous %s float32 tensor" % (tuple(field.shape),))
+    unc = torch.empty((n,), device=field.device, dtype=torch.int32) if return_uncovered else None
+    _field_zoom(field, coef, frame_hw, align_corners, mode, out, unc)
+    return (out, unc) if return_uncovered else out
+
+
 def adam_step_(p, g, m, v, lr, beta1, beta2, eps, step):
     """In-place fused Adam on flat fp32 CUDA buffers."""
     A.require_cuda(p, g, m, v)

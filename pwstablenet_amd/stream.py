@@ -290,6 +290,54 @@ def auto_crop_window(bounds, frame_hw, output_hw=None, period=30, scene_cuts=Non
     return x0, x1, y0, y1
 
 
+def zoom_window(window, frame_hw):
+    """The largest window of the frame's aspect centred inside ``window`` = (x0, x1, y0, y1) (source-pixel edge coordinates, as
+    ``auto_crop_window(..., output_hw=None)`` returns them): with k = min((x1 - x0) / W0, (y1 - y0) / H0) and the window's centre (cx, cy),
+    (cx - k W0 / 2, cx + k W0 / 2, cy - k H0 / 2, cy + k H0 / 2), kept inside ``window`` against the last rounding.  Zooming the H0 x W0
+    frame into it scales both axes alike (vid.stab's ``zoom``).  Host arithmetic, float64."""
+    x0, x1, y0, y1 = (float(v) for v in window)
+    h0, w0 = int(frame_hw[0]), int(frame_hw[1])
+    if not (x1 > x0 and y1 > y0 and h0 > 0 and w0 > 0):
+        raise ValueError("zoom_window: the window x [%g, %g) y [%g, %g) is empty" % (x0, x1, y0, y1))
+    k = min((x1 - x0) / w0, (y1 - y0) / h0)
+    cx, cy = 0.5 * (x0 + x1), 0.5 * (y0 + y1)
+    return (max(x0, cx - 0.5 * k * w0), min(x1, cx + 0.5 * k * w0), max(y0, cy - 0.5 * k * h0), min(y1, cy + 0.5 * k * h0))
+
+
+def zoom_schedule(bounds, frame_hw, speed=0.002, min_window=0.5, scene_cuts=None):
+    """Per-frame zoom windows from a clip's per-frame bounds (``field_homography``; (T, 4) top, bottom, left, right in source pixels): vid.stab's
+    ``optzoom=2``.  Every window is centred on the frame's centre and has the frame's aspect, window t = the fraction k[t] of the frame.
+    Frame t asks for k_req[t] = min(1, 2 min(W0/2 - left, right - W0/2) / W0, 2 min(H0/2 - top, bottom - H0/2) / H0), the largest centred window
+    inside its bounds; kc = max(k_req, min_window) (a frame that asks for more zoom than 1 / min_window keeps some wedge); inside each scene
+    k[t] = min over s of kc[s] + speed |t - s|: the largest schedule that never exceeds kc and never changes by more than ``speed`` per frame
+    (two linear sweeps).  scene_cuts: sorted indices at which a new scene starts; the schedule is free to jump there.  NaN bounds are a
+    ValueError naming the frame.  Returns T windows (x0, x1, y0, y1) for ``zoom_fields`` / ``run(zoom=)``.  Host arithmetic, float64."""
+    if isinstance(bounds, torch.Tensor):
+        bounds = bounds.detach().to("cpu", torch.float64).tolist()
+    bounds = [[float(v) for v in row] for row in bounds]
+    if any(len(row) != 4 for row in bounds):
+        raise ValueError("zoom_schedule: bounds must be (T, 4): top, bottom, left, right")
+    h0, w0 = int(frame_hw[0]), int(frame_hw[1])
+    speed, min_window = float(speed), float(min_window)
+    if not (speed >= 0.0 and 0.0 < min_window <= 1.0):
+        raise ValueError("zoom_schedule: speed must be >= 0 and min_window in (0, 1], got %r and %r" % (speed, min_window))
+    T = len(bounds)
+    kc = []
+    for t, row in enumerate(bounds):
+        if not all(math.isfinite(v) for v in row):
+            raise ValueError("zoom_schedule: frame %d has no homography (bounds %r)" % (t, row))
+        top, bottom, left, right = row
+        k_req = min(1.0, 2.0 * min(0.5 * w0 - left, right - 0.5 * w0) / w0, 2.0 * min(0.5 * h0 - top, bottom - 0.5 * h0) / h0)
+        kc.append(max(k_req, min_window))
+    k = list(kc)
+    for a, b in (_scenes(T, _check_cuts(scene_cuts, T, "zoom_schedule")) if scene_cuts is not None and len(scene_cuts) else [(0, T)]):
+        for t in range(a + 1, b):
+            k[t] = min(k[t], k[t - 1] + speed)
+        for t in range(b - 2, a - 1, -1):
+            k[t] = min(k[t], k[t + 1] + speed)
+    return [(0.5 * w0 - 0.5 * v * w0, 0.5 * w0 + 0.5 * v * w0, 0.5 * h0 - 0.5 * v * h0, 0.5 * h0 + 0.5 * v * h0) for v in k]
+
+
 def _windows(gray_padded, start, count, period):
     """(count, period+1, 256, 256) windows: window b covers padded frames [start+b, start+b+period].  An OVERLAPPING VIEW of the
     plane buffer (sample stride = one plane): the generator's first layer reads it in place (pws_netg_opts.x_sample_stride); no
@@ -320,6 +368,8 @@ class VideoStabilizer:
         self._lanes = []   # compute streams of run_video(in_flight > 1)
         self.scene_cuts = []   # the cuts the last run_video used (frames' index space)
         self.scene_wait_s = 0.0   # host time the last run_video(scene_cuts="auto") spent waiting for scores
+        self.zoom_windows = None     # the T windows the last run / run_video with a zoom used (None without one)
+        self.zoom_uncovered = None   # and, per frame, the zoomed field's nodes that sample outside the source: (T,) int32 on the device
 
     def _pad(self, gray, halo_left, halo_right):
         """Replicates the first / last available frame so that every frame owns a full window (reference :627-633)."""
@@ -371,7 +421,8 @@ class VideoStabilizer:
             out[s:e].copy_(self.net(_windows(gp, start, e - s, self.period), False))
 
     @torch.no_grad()
-    def run(self, gray, frames, halo_left=0, halo_right=0, out=None, pixel_format="bgr24", scene_cuts=None, keep_from=None, _keep_wait=None):
+    def run(self, gray, frames, halo_left=0, halo_right=0, out=None, pixel_format="bgr24", scene_cuts=None, keep_from=None, _keep_wait=None,
+            zoom=None, _zoom_unc=None):
         """gray: (T + halo_left + halo_right, 256, 256) float32 in [-1,1] (``x/255*2-1`` as the reference, :650) for the T
         frames to stabilise plus whatever real neighbours exist on either side (up to period//2); frames: (T, C, H, W)
         float32 0..255, or (T, H, W, 3) uint8 as OpenCV delivers them (then the warp runs in the uint8 kernel: 4x less
@@ -389,9 +440,15 @@ class VideoStabilizer:
         frame, from that frame's own SOURCE.  keep_from: the output frame (device tensor, one frame of the frames' layout, before any resize)
         that precedes frames[0] in its scene, for a clip processed in several calls (run_video passes each chunk's last frame on); without
         it frames[0] starts from its source -- so a shard with halo_left > 0 has no history and does not promise the unsharded clip's
-        bytes in its wedges."""
+        bytes in its wedges.
+        zoom: one window (x0, x1, y0, y1) or (T, 4) windows for the T frames, in source-pixel edge coordinates (functional.zoom_fields): each
+        batch's field goes through ``zoom_fields`` after the generator and before the warp, so the output shows that window of the stabilised
+        frame at the full frame size, still resampled once.  The windows are left in ``self.zoom_windows``, the per-frame counts of field
+        nodes that sample outside the source in ``self.zoom_uncovered``.  Not with borders="keep" (ValueError)."""
         half = self.period // 2
         keep = self.borders == "keep"
+        if zoom is not None and keep:
+            raise ValueError("run: zoom removes the wedges that borders=\"keep\" fills: choose one")
         if keep and frames.dtype not in (torch.uint8, torch.uint16):
             raise ValueError("run: borders=\"keep\" is for the integer pixel formats (uint8 / uint16 frames), got %s" % (frames.dtype,))
         yuv = pixel_format != "bgr24"
@@ -413,6 +470,12 @@ class VideoStabilizer:
         gray_d = gray.to(dev, non_blocking=True) if not gray.is_cuda else gray  # 256 KB per frame: copied once
         if out is None:
             out = torch.empty_like(frames, pin_memory=on_host) if on_host else torch.empty_like(frames)
+        if zoom is not None:
+            frame_hw = (PF.yuv420_16_shape(frames, pixel_format) if yuv16 else PF.yuv420_shape(frames, pixel_format))[1:] if yuv else (
+                tuple(frames.shape[1:3]) if frames.dtype == torch.uint8 else tuple(frames.shape[2:4]))
+            self.zoom_windows = PF._zoom_windows(zoom, T, frame_hw, "run")
+            self.zoom_uncovered = _zoom_unc if _zoom_unc is not None else torch.empty((T,), device=dev, dtype=torch.int32)
+            zcoef = None   # (the field's size is the generator's to say: formed at the first batch, uploaded once)
         if T == 0:
             return out
         gp, batches = self._layout(gray_d.contiguous(), halo_left, halo_right, T, cuts)
@@ -440,6 +503,12 @@ class VideoStabilizer:
                 compute.wait_event(ev)
             win = _windows(gp, start, e - s, self.period)
             field = self.net(win, False)
+            if zoom is not None:
+                if zcoef is None:
+                    zcoef = PF.zoom_coefficients(self.zoom_windows, frame_hw, field.shape[1:3]).to(dev, non_blocking=True)
+                field = field.contiguous()
+                field = PF._field_zoom(field, zcoef[s:e], frame_hw, self.align_corners, self.interpolation, torch.empty_like(field),
+                                       self.zoom_uncovered[s:e])
             if yuv16:
                 warped = PF.upsample_grid_sample_yuv420_16(cur.contiguous(), field, pixel_format, align_corners=self.align_corners, mode=self.interpolation)
             elif yuv:
@@ -478,7 +547,8 @@ class VideoStabilizer:
 
     @torch.no_grad()
     def run_video(self, frames, chunk=32, half_size_output=False, frames_are_rgb=False, halo_left=0, halo_right=0, crop=None,
-                  output_size=None, in_flight=1, pixel_format="bgr24", scene_cuts=None, scene_threshold=0.25, scene_min_len=16):
+                  output_size=None, in_flight=1, pixel_format="bgr24", scene_cuts=None, scene_threshold=0.25, scene_min_len=16, zoom=None,
+                  zoom_speed=0.002, zoom_min=0.5):
         """The whole device side of the reference's ``process()`` loop for one decoded clip: ``frames`` (T, H, W, 3) uint8 as
         cv2 delivers them, in (pinned) host memory or on the device.  Per chunk of ``chunk`` frames: H2D on a side stream,
         gray + INTER_AREA 256x256 window planes computed there from the uploaded frames (so nothing but the uint8 frames
@@ -536,6 +606,19 @@ class VideoStabilizer:
         output_size, half_size_output, halos and host or device input work as before; a shard with halo_left > 0 has no history, starts its
         first frame from that frame's source and does not promise the unsharded clip's bytes in its wedges; crop="auto" is a ValueError
         (it removes what "keep" fills).
+        zoom: zoom to fill (vid.stab's ``zoom`` / ``optzoom``) -- the third answer to the wedges: the output keeps the size that was asked for,
+        and shows a window of the stabilised frame enlarged to it.  The zoom is composed into each frame's FIELD (functional.zoom_fields, one
+        small launch per batch) and the warp that follows resamples the source once, as without a zoom; windows are fractional, also for the
+        YUV formats.  A float k in (0, 1]: the centred window of that fraction of the frame, in the single pass, through ``run(zoom=)``; 1.0
+        gives the frames of zoom=None.  "auto": pass 1 is crop="auto"'s (fields and bounds stay on the device); the clip's one window is
+        ``zoom_window(auto_crop_window(bounds, (H, W), None, period, cuts), (H, W))``; pass 2 zooms each chunk's kept fields and warps.
+        "adaptive": the same two passes with a window per frame, ``zoom_schedule(bounds, (H, W), zoom_speed, zoom_min, cuts)``: as little
+        zoom as each frame needs, changing by at most ``zoom_speed`` of the frame per frame, never below the fraction ``zoom_min``.  The
+        windows used are left in ``self.zoom_windows`` (T tuples), and ``self.zoom_uncovered`` is a (T,) int32 device tensor: per frame, the
+        nodes of the zoomed field that still sample outside the source (no synchronisation: read it when you need it).  output_size,
+        half_size_output, in_flight, scene_cuts, host or device input and every pixel_format work as without a zoom.  ValueError: zoom with
+        any crop or with borders="keep"; "auto" / "adaptive" with halos or below the 600 x 300 lattice size; any other string; a float
+        outside (0, 1].
         Returns (T, H, W, 3) -- or (T, H/2, W/2, 3) / (T, height, width, 3), or the crop window of it -- uint8 on the inputs' side; for YUV
         (T, oh * 3 // 2, ow) of the output (or crop window) size oh x ow."""
         half = self.period // 2
@@ -577,6 +660,31 @@ class VideoStabilizer:
             if self.borders == "keep":
                 raise ValueError("run_video: crop=\"auto\" removes the wedges that borders=\"keep\" fills: choose one")
             _check_lattice(h, w)
+        self.zoom_windows = self.zoom_uncovered = None
+        zmode = None
+        if zoom is not None:
+            if crop is not None:
+                raise ValueError("run_video: zoom fills the frame that a crop would cut: give zoom or crop, not both")
+            if self.borders == "keep":
+                raise ValueError("run_video: zoom removes the wedges that borders=\"keep\" fills: choose one")
+            if isinstance(zoom, str):
+                if zoom not in ("auto", "adaptive"):
+                    raise ValueError("zoom must be None, a fraction in (0, 1], \"auto\" or \"adaptive\", got %r" % (zoom,))
+                if halo_left or halo_right:
+                    raise ValueError("run_video: zoom=%r needs the whole clip (a shard cannot see the clip's bounds): gather the shards' "
+                                     "field_homography bounds and pass windows to run(zoom=)" % (zoom,))
+                _check_lattice(h, w)
+                zmode = zoom
+            else:
+                try:
+                    zk = float(zoom)
+                except (TypeError, ValueError):
+                    raise ValueError("zoom must be None, a fraction in (0, 1], \"auto\" or \"adaptive\", got %r" % (zoom,)) from None
+                if not 0.0 < zk <= 1.0:
+                    raise ValueError("zoom: the fraction of the frame must lie in (0, 1], got %r" % (zoom,))
+                zmode = "fixed"
+                zwin = (0.5 * w - 0.5 * zk * w, 0.5 * w + 0.5 * zk * w, 0.5 * h - 0.5 * zk * h, 0.5 * h + 0.5 * zk * h)
+        two_pass = auto or zmode in ("auto", "adaptive")   # pass 1: fields and bounds; the host's decision; pass 2: the warp
         detect = isinstance(scene_cuts, str)
         if detect and scene_cuts != "auto":
             raise ValueError("scene_cuts must be None, \"auto\" or a sorted sequence of frame indices, got %r" % (scene_cuts,))
@@ -622,7 +730,9 @@ class VideoStabilizer:
             for lane in lanes[1:]:
                 lane.wait_stream(compute)
         gray_all = torch.empty((n_all, 256, 256), device=dev, dtype=torch.float32)
-        if auto:
+        if zmode is not None:
+            zunc = torch.empty((T,), device=dev, dtype=torch.int32)
+        if two_pass:
             fields = torch.empty((T, 256, 256, 2), device=dev, dtype=torch.float32)
             hom = torch.empty((T, 9), device=dev, dtype=torch.float64)
             bounds = torch.empty((T, 4), device=dev, dtype=torch.float32)
@@ -718,12 +828,16 @@ class VideoStabilizer:
                 # the cuts inside this chunk's slice of the planes, in the slice's index space (None without cuts: the path as it was)
                 sc = [t - (cs - hl) for t in cuts if cs - hl < t < ce + hr] or None
                 with torch.cuda.stream(lane):
-                    if auto:   # pass 1: fields and per-frame bounds only (no halos here: core frames = output positions)
+                    if two_pass:   # pass 1: fields and per-frame bounds only (no halos here: core frames = output positions)
                         self._fields(gray_all[cs - hl:ce + hr], hl, hr, fields[cs:ce], sc)
                         _field_homography(fields[cs:ce], h, w, hom[cs:ce], bounds[cs:ce])
                         continue
-                    warped = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr, pixel_format=pixel_format, scene_cuts=sc,
-                                      keep_from=carry, _keep_wait=carried)
+                    if zmode is not None:   # ("fixed": the one window, in the single pass)
+                        warped = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr, pixel_format=pixel_format,
+                                          scene_cuts=sc, zoom=zwin, _zoom_unc=zunc[cs - halo_left:ce - halo_left])
+                    else:
+                        warped = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr, pixel_format=pixel_format, scene_cuts=sc,
+                                          keep_from=carry, _keep_wait=carried)
                     if keep:   # the next chunk's pass (on the other lane, if any) starts from this chunk's last frame: no copy, one event
                         carry = warped[-1]
                         if len(lanes) > 1:
@@ -736,6 +850,14 @@ class VideoStabilizer:
                     compute.wait_stream(lane)   # the caller's stream sees every chunk; gray_all and the outputs may be freed behind it
                 mod.two_queues = restore[3]
                 mod.enable_graph(restore[0], restore[1], per_stream=restore[2])
+        if zmode is not None:
+            self.zoom_windows, self.zoom_uncovered = [zwin] * T if zmode == "fixed" else None, zunc
+        if two_pass and not auto:   # (the copy of the bounds to the host waits for pass 1)
+            if zmode == "auto":
+                self.zoom_windows = [zoom_window(auto_crop_window(bounds, (h, w), None, self.period, scene_cuts=cuts or None), (h, w))] * T
+            else:
+                self.zoom_windows = zoom_schedule(bounds, (h, w), zoom_speed, zoom_min, scene_cuts=cuts or None)
+            zcoef = PF.zoom_coefficients(PF._zoom_windows(self.zoom_windows, T, (h, w), "run_video"), (h, w), fields.shape[1:3]).to(dev, non_blocking=True)
         if auto:
             crop = auto_crop_window(bounds, (h, w), (oh, ow), self.period, scene_cuts=cuts or None)   # (the copy to the host waits for pass 1)
             if yuv:   # the BGR path's window, rounded inward to even edges
@@ -745,7 +867,8 @@ class VideoStabilizer:
                     raise ValueError("run_video: the even crop window x [%d, %d) y [%d, %d) is empty" % crop)
             cy0, cy1, cx0, cx1 = crop_window(crop)
             out = alloc_out()
-            # pass 2: warp + output resize + crop with the kept fields; chunk k+1 uploads while chunk k computes
+        if two_pass:
+            # pass 2: [zoom +] warp + output resize + crop with the kept fields; chunk k+1 uploads while chunk k computes
 
             def fetch(c):
                 s, e = chunks[c]
@@ -763,12 +886,15 @@ class VideoStabilizer:
                     nxt = fetch(c + 1)
                 if ev is not None:
                     compute.wait_event(ev)
+                fld = fields[s:e]
+                if zmode is not None:
+                    fld = PF._field_zoom(fld, zcoef[s:e], (h, w), self.align_corners, self.interpolation, torch.empty_like(fld), zunc[s:e])
                 if yuv16:
-                    warped = PF.upsample_grid_sample_yuv420_16(buf.contiguous(), fields[s:e], pixel_format, align_corners=self.align_corners, mode=self.interpolation)
+                    warped = PF.upsample_grid_sample_yuv420_16(buf.contiguous(), fld, pixel_format, align_corners=self.align_corners, mode=self.interpolation)
                 elif yuv:
-                    warped = PF.upsample_grid_sample_yuv420(buf.contiguous(), fields[s:e], pixel_format, align_corners=self.align_corners, mode=self.interpolation)
+                    warped = PF.upsample_grid_sample_yuv420(buf.contiguous(), fld, pixel_format, align_corners=self.align_corners, mode=self.interpolation)
                 else:
-                    warped = PF.upsample_grid_sample_u8(buf.contiguous(), fields[s:e], swap_rb=self.swap_rb, align_corners=self.align_corners, mode=self.interpolation)
+                    warped = PF.upsample_grid_sample_u8(buf.contiguous(), fld, swap_rb=self.swap_rb, align_corners=self.align_corners, mode=self.interpolation)
                 finish(warped, buf, s, e, compute)
         if on_host:
             down.synchronize()
