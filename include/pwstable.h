@@ -45,6 +45,7 @@
  *   pws_field_homography          the automatic crop's per-frame findHomography + perspectiveTransform  main_new.py:550-603
  *   pws_scene_change              the window's end clamp, applied at hard cuts too (cut score)          main_new.py:627-633
  *   pws_field_zoom                the warp field resampled over a per-frame window: zoom to fill (no counterpart in the reference)
+ *   pws_field_rigid               the warp field blended towards its fitted homography: rigid warp mode (no counterpart in the reference)
  *   pws_pack_* / pws_netg_pack_weights   state_dict (OIHW / IOHW) -> kernel layout; main_new.py:60,471
  *
  * Layouts.  Frames / images: NCHW fp32 as in the reference.  Warp fields: N,H,W,2 fp32 (x then y,
@@ -477,6 +478,29 @@ int pws_field_homography(const float *field, int n, int fh, int fw, int h0, int 
  * 4 n byte clear of `uncovered`). */
 int pws_field_zoom(const float *field, int n, int fh, int fw, const float *coef, float *out, int h0, int w0, int align_corners, int margin,
                    int *uncovered, pws_stream_t stream);
+
+/* Rigid warp mode (csrc/field_rigid.hip; no counterpart in the reference).  pws_field_homography's M is the globally rigid version of the
+ * correction a frame's field holds; this blends the field towards it, node by node, and the warp that follows is untouched.
+ * field[n,fh,fw,2] -> out[n,fh,fw,2]; m[n,9] fp64 in DEVICE memory, exactly as pws_field_homography writes it: M maps a field value
+ * (normalised source coordinates) to the output position u = 2x/w0 - 1, v = 2y/h0 - 1 (no half-pixel term).  For node (i, j) of frame t:
+ *   x = j (w0-1)/(fw-1), y = i (h0-1)/(fh-1) (the frame pixel at which the warps' align_corners=True resize reads exactly this node);
+ *   A = adj(M) (M^-1 up to scale: no division), (X, Y, D) = A (u, v, 1), Dc = A[2][2]; P = (X/D, Y/D), fp64, each rounded once to fp32.
+ *   Frame t is FITTED when M's nine entries are finite, det M is finite and non-zero and Dc != 0.  A node of a fitted frame is VALID when
+ *   D/Dc >= 2^-20: on the frame centre's side of the horizon, and not on it.
+ *   (The float64 sums of products behind X, Y, D may be contracted into FMAs: against another float64 evaluation P agrees to one
+ *   float32 ulp, and the horizon decision within a relative 2^-52 of the threshold.)
+ *   A valid node gets P when rigidity == 1 (exactly the homography, not F + (P - F)), F itself when rigidity == 0, and
+ *   fmaf(rigidity, P - F, F) per component otherwise
+ *   (a NaN in F is healed at 1 and propagates below it); every other node, and every node of an unfitted frame, keeps F bit for bit.
+ * unfit (n, int32; may be NULL): the nodes of frame t that kept F for that reason (fh * fw for an unfitted frame).
+ * residual (n, fp32; may be NULL): the largest max(|Fx - Px| * (w0/2), |Fy - Py| * (h0/2)) -- fp32: one subtraction, one product -- over the
+ * valid nodes of frame t whose F is finite, 0 without any: how far the field was from rigid, in source pixels.  An integer atomic max on the
+ * bits of a non-negative float, and integer counts: the same on every run.  Both are cleared by the call.
+ * The kernel is element-wise: out == field is allowed.  Any fh, fw >= 2; n == 0 returns PWS_OK, launches nothing and writes nothing.
+ * PWS_EINVAL: NULL field / m / out, n < 0, fh or fw < 2, h0 or w0 < 1, rigidity outside [0, 1] or NaN, field / out / m not 8-byte
+ * aligned, residual / unfit not 4-byte aligned, out overlapping field in part.  One launch (and a 4 n byte clear per statistic). */
+int pws_field_rigid(const float *field, int n, int fh, int fw, const double *m, float rigidity, int h0, int w0, float *out, float *residual,
+                    int *unfit, pws_stream_t stream);
 
 /* Scene-cut score for edited footage (csrc/scene.hip).  The reference clamps a frame's 31-plane window at the clip's first and last frame
  * only (main_new.py:627-633); the streaming stabiliser applies the same clamp at every hard cut, which it finds from the L1 distance of

@@ -388,6 +388,62 @@ def zoom_fields(field, windows, frame_hw, align_corners=False, mode="bilinear", 
     return (out, unc) if return_uncovered else out
 
 
+def _check_rigidity(rigidity, what):
+    """``rigidity`` as a float in [0, 1]; ValueError otherwise (NaN included)."""
+    try:
+        r = float(rigidity)
+    except (TypeError, ValueError):
+        raise ValueError("%s: rigidity must be a number in [0, 1], got %r" % (what, rigidity)) from None
+    if not 0.0 <= r <= 1.0:
+        raise ValueError("%s: rigidity must lie in [0, 1], got %r" % (what, rigidity))
+    return r
+
+
+def _field_rigid(field, m, frame_hw, rigidity, out, residual, unfit):
+    """pws_field_rigid on device tensors: ``m`` (T, 9) or (T, 3, 3) float64, ``residual`` (T,) float32 / ``unfit`` (T,) int32 or None."""
+    A.check(A.lib().pws_field_rigid(A.ptr(field), field.shape[0], field.shape[1], field.shape[2], A.ptr(m), float(rigidity), int(frame_hw[0]),
+                                    int(frame_hw[1]), A.ptr(out), A.ptr(residual), A.ptr(unfit), A.current_stream()), "pws_field_rigid")
+    return out
+
+
+def rigid_fields(field, m, frame_hw, rigidity=1.0, out=None, return_stats=False):
+    """Rigid warp mode, composed into the field: ``field`` (T, fh, fw, 2) as ``netG(window, False)`` returns it, blended towards the
+    homographies ``m`` -- (T, 3, 3) or (T, 9) float64 on the device, as ``stream.field_homography(field, frame_hw)`` returns them: M maps a
+    field value to the output position u = 2x/W0 - 1, v = 2y/H0 - 1 of the ``frame_hw`` = (H0, W0) frame.  Node (i, j) stands for frame
+    pixel x = j (W0-1)/(fw-1), y = i (H0-1)/(fh-1); P = M^-1 (u, v) is where the homography alone would have it sample, in float64, rounded
+    once.  The node becomes P at ``rigidity`` 1 -- every frame is warped by its fitted homography: straight lines stay straight -- and
+    F + rigidity (P - F) below it; 0 returns the field bit for bit (the statistics are still computed).  A frame whose M is not finite or not invertible, and a node on or beyond the
+    homography's horizon, keep F bit for bit.  One element-wise launch (csrc/field_rigid.hip; include/pwstable.h has the full
+    definition); ``out`` may be ``field`` itself.  Any frame size: the 600 x 300 minimum is the fit's, not this function's.
+    return_stats: also residual (T,) float32 -- per frame, how far the field was from rigid: the largest |F - P| in source pixels -- and
+    unfit (T,) int32, the number of nodes that kept F because no homography applied to them; both on the device.
+    ValueError: shapes or dtypes other than these, a host tensor, rigidity outside [0, 1]."""
+    r = _check_rigidity(rigidity, "rigid_fields")
+    for name, t, dtype in (("field", field, torch.float32), ("m", m, torch.float64)) + ((("out", out, torch.float32),) if out is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
+            raise ValueError("rigid_fields: %s must be a %s tensor on the device, got %s" % (
+                name, dtype, "%s on %s" % (t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t)))
+    if field.dim() != 4 or field.shape[3] != 2 or field.shape[1] < 2 or field.shape[2] < 2:
+        raise ValueError("rigid_fields: field must be (T, fh, fw, 2) with fh, fw >= 2, got %s" % (tuple(field.shape),))
+    n = field.shape[0]
+    if tuple(m.shape) not in ((n, 3, 3), (n, 9)):
+        raise ValueError("rigid_fields: m must be (%d, 3, 3) or (%d, 9), got %s" % (n, n, tuple(m.shape)))
+    h0, w0 = int(frame_hw[0]), int(frame_hw[1])
+    if h0 < 1 or w0 < 1:
+        raise ValueError("rigid_fields: bad frame size %d x %d" % (w0, h0))
+    if out is not None and (tuple(out.shape) != tuple(field.shape) or not out.is_contiguous()):
+        raise ValueError("rigid_fields: out must be a contiguous %s float32 tensor" % (tuple(field.shape),))
+    if out is not None and out.data_ptr() == field.data_ptr() and not field.is_contiguous():
+        raise ValueError("rigid_fields: out=field needs a contiguous field")
+    field, m = field.contiguous(), m.contiguous()
+    if out is None:
+        out = torch.empty_like(field)
+    res = torch.empty((n,), device=field.device, dtype=torch.float32) if return_stats else None
+    unfit = torch.empty((n,), device=field.device, dtype=torch.int32) if return_stats else None
+    _field_rigid(field, m, (h0, w0), r, out, res, unfit)
+    return (out, res, unfit) if return_stats else out
+
+
 def adam_step_(p, g, m, v, lr, beta1, beta2, eps, step):
     """In-place fused Adam on flat fp32 CUDA buffers."""
     A.require_cuda(p, g, m, v)

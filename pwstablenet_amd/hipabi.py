@@ -236,6 +236,7 @@ SIGNATURES = {
     "pws_field_homography": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "pws_scene_change": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "pws_field_zoom": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "pws_field_rigid": (_I, [_P, _I, _I, _I, _P, _F, _I, _I, _P, _P, _P, _P]),
     "pws_bn_ws_bytes": (_S, [_I]),
     "pws_bn_train_fwd": (_I, [_P, _S, _I, _P, _P, _I, _P, _P, _P, _P, _F, _F, _I, _P, _S, _P]),
     "pws_bn_train_bwd": (_I, [_P, _P, _P, _P, _P, _I, _S, _I, _P, _P, _P, _S, _P]),

@@ -173,9 +173,10 @@ def _field_homography(field, h0, w0, m_out, bounds_out, pts_out=None):
                                          A.ptr(bounds_out), A.ptr(pts_out), A.current_stream()), "pws_field_homography")
 
 
-def _check_lattice(h0, w0):
+def _check_lattice(h0, w0, what="automatic crop"):
+    """``what``: the feature that asked for the fit, for the message."""
     if h0 < 300 or w0 < 600:
-        raise ValueError("automatic crop: the 20 x 20 sampling lattice needs a frame of at least 600 x 300 pixels, got %d x %d" % (w0, h0))
+        raise ValueError("%s: the homography fit's 20 x 20 sampling lattice needs a frame of at least 600 x 300 pixels, got %d x %d" % (what, w0, h0))
 
 
 def field_homography(field, frame_hw, return_points=False):
@@ -348,8 +349,12 @@ def _windows(gray_padded, start, count, period):
 
 
 class VideoStabilizer:
-    def __init__(self, netG, batch=32, period=30, device=None, swap_rb=False, interpolation="bilinear", borders="black"):
+    def __init__(self, netG, batch=32, period=30, device=None, swap_rb=False, interpolation="bilinear", borders="black", rigidity=0.0):
         self.net = netG
+        # how far run / run_video pull each frame's field towards the homography fitted to it (functional.rigid_fields): 0 = the field as the
+        # generator regressed it (no fit, no launch), 1 = every frame warped by its homography alone -- no local distortion, and no parallax
+        # correction either
+        self.rigidity = PF._check_rigidity(rigidity, "VideoStabilizer")
         if borders not in PF.BORDERS:
             raise ValueError("borders must be one of %s, got %r" % (PF.BORDERS, borders))
         # what run / run_video show where a frame's field samples outside the source: the warp's pad colour, or -- "keep", vid.stab's
@@ -370,6 +375,8 @@ class VideoStabilizer:
         self.scene_wait_s = 0.0   # host time the last run_video(scene_cuts="auto") spent waiting for scores
         self.zoom_windows = None     # the T windows the last run / run_video with a zoom used (None without one)
         self.zoom_uncovered = None   # and, per frame, the zoomed field's nodes that sample outside the source: (T,) int32 on the device
+        self.rigid_residual = None   # rigidity > 0: per frame of the last run / run_video, how far the generator's field was from its fitted
+        self.rigid_unfit = None      # homography (source pixels, (T,) float32) and the nodes no homography applied to ((T,) int32); on the device
 
     def _pad(self, gray, halo_left, halo_right):
         """Replicates the first / last available frame so that every frame owns a full window (reference :627-633)."""
@@ -422,7 +429,7 @@ class VideoStabilizer:
 
     @torch.no_grad()
     def run(self, gray, frames, halo_left=0, halo_right=0, out=None, pixel_format="bgr24", scene_cuts=None, keep_from=None, _keep_wait=None,
-            zoom=None, _zoom_unc=None):
+            zoom=None, _zoom_unc=None, _rigid_stats=None):
         """gray: (T + halo_left + halo_right, 256, 256) float32 in [-1,1] (``x/255*2-1`` as the reference, :650) for the T
         frames to stabilise plus whatever real neighbours exist on either side (up to period//2); frames: (T, C, H, W)
         float32 0..255, or (T, H, W, 3) uint8 as OpenCV delivers them (then the warp runs in the uint8 kernel: 4x less
@@ -444,9 +451,15 @@ class VideoStabilizer:
         zoom: one window (x0, x1, y0, y1) or (T, 4) windows for the T frames, in source-pixel edge coordinates (functional.zoom_fields): each
         batch's field goes through ``zoom_fields`` after the generator and before the warp, so the output shows that window of the stabilised
         frame at the full frame size, still resampled once.  The windows are left in ``self.zoom_windows``, the per-frame counts of field
-        nodes that sample outside the source in ``self.zoom_uncovered``.  Not with borders="keep" (ValueError)."""
+        nodes that sample outside the source in ``self.zoom_uncovered``.  Not with borders="keep" (ValueError).
+        VideoStabilizer(rigidity=r), r > 0: each batch's field is fitted (``field_homography``) and blended towards its homography
+        (``functional.rigid_fields``, into a fresh tensor: the generator's output may be a graph's static buffer) right after the generator;
+        the zoom, the warp and borders="keep" all see the adjusted field.  Nothing here depends on other frames, so halos are fine; frames
+        below the fit's 600 x 300 lattice are a ValueError.  ``self.rigid_residual`` (T,) float32 and ``self.rigid_unfit`` (T,) int32 are left on
+        the device (None at rigidity 0, which takes no new path)."""
         half = self.period // 2
         keep = self.borders == "keep"
+        rigid = self.rigidity > 0.0
         if zoom is not None and keep:
             raise ValueError("run: zoom removes the wedges that borders=\"keep\" fills: choose one")
         if keep and frames.dtype not in (torch.uint8, torch.uint16):
@@ -470,9 +483,17 @@ class VideoStabilizer:
         gray_d = gray.to(dev, non_blocking=True) if not gray.is_cuda else gray  # 256 KB per frame: copied once
         if out is None:
             out = torch.empty_like(frames, pin_memory=on_host) if on_host else torch.empty_like(frames)
-        if zoom is not None:
+        if zoom is not None or rigid:
             frame_hw = (PF.yuv420_16_shape(frames, pixel_format) if yuv16 else PF.yuv420_shape(frames, pixel_format))[1:] if yuv else (
                 tuple(frames.shape[1:3]) if frames.dtype == torch.uint8 else tuple(frames.shape[2:4]))
+        if rigid:
+            _check_lattice(int(frame_hw[0]), int(frame_hw[1]), "rigidity > 0")
+        if _rigid_stats is not None:   # run_video's, a slice per chunk: it publishes the whole tensors itself, once every chunk is issued
+            rres, runf = _rigid_stats
+        else:
+            rres, runf = (torch.empty((T,), device=dev, dtype=torch.float32), torch.empty((T,), device=dev, dtype=torch.int32)) if rigid else (None, None)
+            self.rigid_residual, self.rigid_unfit = rres, runf
+        if zoom is not None:
             self.zoom_windows = PF._zoom_windows(zoom, T, frame_hw, "run")
             self.zoom_uncovered = _zoom_unc if _zoom_unc is not None else torch.empty((T,), device=dev, dtype=torch.int32)
             zcoef = None   # (the field's size is the generator's to say: formed at the first batch, uploaded once)
@@ -503,6 +524,11 @@ class VideoStabilizer:
                 compute.wait_event(ev)
             win = _windows(gp, start, e - s, self.period)
             field = self.net(win, False)
+            if rigid:
+                field = field.contiguous()
+                hom = torch.empty((e - s, 9), device=dev, dtype=torch.float64)
+                _field_homography(field, int(frame_hw[0]), int(frame_hw[1]), hom, torch.empty((e - s, 4), device=dev, dtype=torch.float32))
+                field = PF._field_rigid(field, hom, frame_hw, self.rigidity, torch.empty_like(field), rres[s:e], runf[s:e])
             if zoom is not None:
                 if zcoef is None:
                     zcoef = PF.zoom_coefficients(self.zoom_windows, frame_hw, field.shape[1:3]).to(dev, non_blocking=True)
@@ -619,6 +645,17 @@ class VideoStabilizer:
         half_size_output, in_flight, scene_cuts, host or device input and every pixel_format work as without a zoom.  ValueError: zoom with
         any crop or with borders="keep"; "auto" / "adaptive" with halos or below the 600 x 300 lattice size; any other string; a float
         outside (0, 1].
+        VideoStabilizer(rigidity=r), r > 0: rigid warp mode -- every frame's field is pulled towards the homography fitted to it
+        (functional.rigid_fields; 1 = the homography alone: no local breathing or wobble, and no parallax correction either).  The single-pass
+        paths do it per batch inside run(): generator, fit, blend, [zoom,] warp, [keep].  The two-pass paths (crop="auto", zoom="auto" /
+        "adaptive") already fit M on the raw field in pass 1; they then blend the kept fields in place on the same stream, and pass 2 is
+        unchanged.  The bounds stay those of the RAW fit: M is by construction the rigid part of the raw field and of any blend of the field
+        with P, so a refit of the blended field returns M up to the fit's sampling (at rigidity 1 the four bounds move by 3e-4 pixel or
+        less: INTEGRATION.md, tests/test_rigid_ref_cpu.py).  Every pixel_format, interpolation, borders, crop, zoom, in_flight and halo works
+        as without it; a source below the fit's 600 x 300 lattice is a ValueError.  ``self.rigid_residual`` (T,) float32 -- per frame, the
+        largest distance in source pixels between the generator's field and its homography: the number to choose the setting by -- and
+        ``self.rigid_unfit`` (T,) int32 -- the nodes that kept the raw field because no homography applied to them -- are left on the device
+        (no synchronisation: read them when you need them); both are None at rigidity 0, which takes no new path.
         Returns (T, H, W, 3) -- or (T, H/2, W/2, 3) / (T, height, width, 3), or the crop window of it -- uint8 on the inputs' side; for YUV
         (T, oh * 3 // 2, ow) of the output (or crop window) size oh x ow."""
         half = self.period // 2
@@ -661,6 +698,10 @@ class VideoStabilizer:
                 raise ValueError("run_video: crop=\"auto\" removes the wedges that borders=\"keep\" fills: choose one")
             _check_lattice(h, w)
         self.zoom_windows = self.zoom_uncovered = None
+        self.rigid_residual = self.rigid_unfit = None
+        rigid = self.rigidity > 0.0
+        if rigid:
+            _check_lattice(h, w, "rigidity > 0")
         zmode = None
         if zoom is not None:
             if crop is not None:
@@ -673,7 +714,7 @@ class VideoStabilizer:
                 if halo_left or halo_right:
                     raise ValueError("run_video: zoom=%r needs the whole clip (a shard cannot see the clip's bounds): gather the shards' "
                                      "field_homography bounds and pass windows to run(zoom=)" % (zoom,))
-                _check_lattice(h, w)
+                _check_lattice(h, w, "zoom=%r" % (zoom,))
                 zmode = zoom
             else:
                 try:
@@ -714,6 +755,9 @@ class VideoStabilizer:
         compute = torch.cuda.current_stream(dev)
         up, down = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
         in_flight = max(1, int(in_flight))
+        if rigid:   # (before the lanes fork from the caller's stream: every lane writes its chunks' slices)
+            rres = torch.empty((T,), device=dev, dtype=torch.float32)
+            runf = torch.empty((T,), device=dev, dtype=torch.int32)
         # (the lanes live as long as this object: the generator keeps an arena / a graph per STREAM, and torch's allocator a pool per stream)
         # The caller's stream is lane 0: the runtime deals streams to a handful of hardware queues, and a lane that shares its queue with
         # the upload or the download stream waits behind their copies (two NEW lanes beside up / down: 1 744 -> 1 291 frames/s).
@@ -831,13 +875,16 @@ class VideoStabilizer:
                     if two_pass:   # pass 1: fields and per-frame bounds only (no halos here: core frames = output positions)
                         self._fields(gray_all[cs - hl:ce + hr], hl, hr, fields[cs:ce], sc)
                         _field_homography(fields[cs:ce], h, w, hom[cs:ce], bounds[cs:ce])
+                        if rigid:   # the kept fields, in place; the bounds stay the raw fit's
+                            PF._field_rigid(fields[cs:ce], hom[cs:ce], (h, w), self.rigidity, fields[cs:ce], rres[cs:ce], runf[cs:ce])
                         continue
+                    rstats = (rres[cs - halo_left:ce - halo_left], runf[cs - halo_left:ce - halo_left]) if rigid else None
                     if zmode is not None:   # ("fixed": the one window, in the single pass)
                         warped = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr, pixel_format=pixel_format,
-                                          scene_cuts=sc, zoom=zwin, _zoom_unc=zunc[cs - halo_left:ce - halo_left])
+                                          scene_cuts=sc, zoom=zwin, _zoom_unc=zunc[cs - halo_left:ce - halo_left], _rigid_stats=rstats)
                     else:
                         warped = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr, pixel_format=pixel_format, scene_cuts=sc,
-                                          keep_from=carry, _keep_wait=carried)
+                                          keep_from=carry, _keep_wait=carried, _rigid_stats=rstats)
                     if keep:   # the next chunk's pass (on the other lane, if any) starts from this chunk's last frame: no copy, one event
                         carry = warped[-1]
                         if len(lanes) > 1:
@@ -850,6 +897,8 @@ class VideoStabilizer:
                     compute.wait_stream(lane)   # the caller's stream sees every chunk; gray_all and the outputs may be freed behind it
                 mod.two_queues = restore[3]
                 mod.enable_graph(restore[0], restore[1], per_stream=restore[2])
+        if rigid:
+            self.rigid_residual, self.rigid_unfit = rres, runf
         if zmode is not None:
             self.zoom_windows, self.zoom_uncovered = [zwin] * T if zmode == "fixed" else None, zunc
         if two_pass and not auto:   # (the copy of the bounds to the host waits for pass 1)
