@@ -193,46 +193,23 @@ __global__ void __launch_bounds__(256) keep_yuv420_kernel(unsigned char *frames,
     }
 }
 
-static yuv::Plane make_plane(int ph, int pw, unsigned off0, unsigned off1, unsigned pitch, int fh, int fw, int align_corners) {
-    yuv::Plane p;   // (the warps' geometry and constants: the same fp32 products)
-    p.h = ph, p.w = pw, p.off0 = off0, p.off1 = off1, p.pitch = pitch;
-    p.ry = ph > 1 ? (float)(fh - 1) / (float)(ph - 1) : 0.f;
-    p.rx = pw > 1 ? (float)(fw - 1) / (float)(pw - 1) : 0.f;
-    p.kx = align_corners ? 0.5f * (float)(pw - 1) : 0.5f * (float)pw, p.kx1 = 0.5f * (float)(pw - 1);
-    p.ky = align_corners ? 0.5f * (float)(ph - 1) : 0.5f * (float)ph, p.ky1 = 0.5f * (float)(ph - 1);
-    p.nrg = (unsigned)((ph + 3) / 4);
-    return p;
-}
-
-// SB: bytes per sample.  Checks and plane geometry are the warps' (w >= 8 with the bicubic margin, as the bicubic warps ask)
+// SB: bytes per sample.  Checks and plane geometry are the warps' (yuv::launch_yuv420; w >= 8 with the bicubic margin, as the bicubic warps ask)
 template <int SB>
 static int keep_yuv420(const char *what, void *frames, const float *field, const void *initial, int initial_is_source, int n, int h, int w, int fh,
                        int fw, int layout, int align_corners, int bicubic, pws_stream_t stream) {
-    PWS_REQUIRE(n >= 0 && h > 0 && w > 0 && fh > 0 && fw > 0, "%s: bad shape", what);
-    PWS_REQUIRE(layout == 0 || layout == 1, "%s: layout must be 0 (%s) or 1 (%s), got %d", what, SB == 1 ? "NV12" : "P010", SB == 1 ? "I420" : "I010", layout);
-    PWS_REQUIRE(h % 2 == 0 && w % 4 == 0 && h >= 2, "%s: h must be even and w a multiple of 4 (got %d x %d)", what, w, h);
-    PWS_REQUIRE(!bicubic || w >= 8, "%s: w must be at least 8 with the bicubic margin, got %d", what, w);
-    if (n == 0) return PWS_OK;
-    PWS_REQUIRE(frames && field && initial, "%s: NULL pointer", what);
-    PWS_REQUIRE(((reinterpret_cast<size_t>(frames) | reinterpret_cast<size_t>(initial)) & (SB == 1 ? 3 : 7)) == 0,
-                "%s: frames and initial must be %d-byte aligned", what, SB == 1 ? 4 : 8);
-    PWS_REQUIRE((size_t)h * w < (1u << (SB == 1 ? 29 : 28)) && w < (1 << (SB == 1 ? 23 : 22)) && n < 65536, "%s: frame or batch too large", what);
-    const unsigned fbytes = (unsigned)((size_t)h * w * 3 / 2) * SB;
-    const unsigned hw = (unsigned)(h * w) * SB, hc = (unsigned)(h / 2), wc = (unsigned)(w / 2);   // byte offsets and pitches
-    const yuv::Plane py = keep::make_plane(h, w, 0u, 0u, (unsigned)w * SB, fh, fw, align_corners);
-    const yuv::Plane pc = layout == 0 ? keep::make_plane(h / 2, w / 2, hw, hw, (unsigned)w * SB, fh, fw, align_corners)
-                                      : keep::make_plane(h / 2, w / 2, hw, hw + hc * wc * SB, wc * SB, fh, fw, align_corners);
-    const unsigned gx = (py.nrg + pc.nrg + 7u) & ~7u, cpr = (unsigned)((w + 255) / 256);   // (chroma rows need half the chunks: the rest return)
-    const int fmy = yuv_fmode(py.rx), fmc = yuv_fmode(pc.rx);
+    yuv::Launch420 L;
+    const int rc = yuv::launch_yuv420<SB>(what, frames, field, initial, "initial", n, h, w, fh, fw, layout, align_corners, bicubic ? 8 : 0,
+                                          "with the bicubic margin", L);
+    if (rc != PWS_OK || n == 0) return rc;
     const float m = bicubic ? 1.f : 0.f;
     unsigned char *fr = reinterpret_cast<unsigned char *>(frames);
     const unsigned char *ini = reinterpret_cast<const unsigned char *>(initial);
     if (layout == 0)
-        hipLaunchKernelGGL((keep::keep_yuv420_kernel<SB, 0>), dim3(gx, cpr, 1), dim3(256), 0, as_stream(stream), fr, field, ini, py, pc, fmy, fmc, n, fh,
-                           fw, fbytes, initial_is_source, m);
+        hipLaunchKernelGGL((keep::keep_yuv420_kernel<SB, 0>), dim3(L.gx, L.cpr, 1), dim3(256), 0, as_stream(stream), fr, field, ini, L.py, L.pc, L.fmy,
+                           L.fmc, n, fh, fw, L.fbytes, initial_is_source, m);
     else
-        hipLaunchKernelGGL((keep::keep_yuv420_kernel<SB, 1>), dim3(gx, cpr, 1), dim3(256), 0, as_stream(stream), fr, field, ini, py, pc, fmy, fmc, n, fh,
-                           fw, fbytes, initial_is_source, m);
+        hipLaunchKernelGGL((keep::keep_yuv420_kernel<SB, 1>), dim3(L.gx, L.cpr, 1), dim3(256), 0, as_stream(stream), fr, field, ini, L.py, L.pc, L.fmy,
+                           L.fmc, n, fh, fw, L.fbytes, initial_is_source, m);
     return check_launch("keep_yuv420_kernel");
 }
 
@@ -251,7 +228,7 @@ extern "C" int pws_border_keep_u8(unsigned char *frames_hwc, const float *field,
                 "pws_border_keep_u8: frames and initial must be 4-byte aligned");
     const unsigned cpr = (unsigned)((w + 255) / 256);
     PWS_REQUIRE(n < 65536 && cpr < 65536 && (size_t)w * 3 < (1u << 24) && h < (1 << 24), "pws_border_keep_u8: frame or batch too large");
-    const yuv::Plane P = keep::make_plane(h, w, 0u, 0u, 3u * (unsigned)w, fh, fw, align_corners);
+    const yuv::Plane P = yuv::make_plane(h, w, 0u, 0u, 3u * (unsigned)w, fh, fw, align_corners);
     const unsigned gx = (P.nrg + 7u) & ~7u, fbytes = (unsigned)((size_t)h * w * 3);
     hipLaunchKernelGGL(keep::keep_u8_kernel, dim3(gx, cpr, 1), dim3(256), 0, as_stream(stream), frames_hwc, field, initial, P, yuv_fmode(P.rx), n, fh,
                        fw, fbytes, initial_is_source, swap_rb, bicubic ? 1.f : 0.f);

@@ -960,7 +960,7 @@ extern "C" int pws_upsample_grid_sample_u8(const unsigned char *frame_hwc, const
 // plane, the field's row pair and its vertical weights are wave-uniform as in the BGR kernel above.  Per lane and tap row ONE aligned
 // 8-byte load + one v_alignbyte fetches a pixel's horizontal tap pair (2 bytes, or U V U V for NV12); the field's row pair is fetched once
 // per wave and handed round with ds_bpermute where the wave's pixels span few enough field columns (FMODE 2: one column per lane; 3: two);
-// float -> byte is one SDWA convert.
+// float -> byte is one SDWA convert.  The kernel and its launcher follow the 16-bit row function below: one body serves both depths.
 // One wave's row chunk of one plane kind.  B: bytes per pixel of a source plane (1; NV12 chroma 2); NP: source planes (I420 chroma 2).
 template <int KIND, int FMODE>
 __device__ __forceinline__ void yuv_warp_row(const unsigned char *__restrict__ frame, unsigned char *__restrict__ ofr, const float *__restrict__ field,
@@ -1077,81 +1077,8 @@ __device__ __forceinline__ void yuv_warp_row(const unsigned char *__restrict__ f
     }
 }
 
-template <int LAYOUT, int FMY, int FMC>   // LAYOUT 0 NV12, 1 I420; FMY / FMC: field access mode of the Y / chroma planes
-__global__ void __launch_bounds__(256) upsample_grid_sample_yuv420_kernel(const unsigned char *__restrict__ input, const float *__restrict__ field,
-                                                                          unsigned char *__restrict__ out, yuv::Plane py, yuv::Plane pc, int fh,
-                                                                          int fw, unsigned fbytes) {
-    const unsigned rg = xcd_remap(blockIdx.x, gridDim.x);
-    const unsigned n = blockIdx.z;
-    const int ox0 = (int)(blockIdx.y * 256u + (threadIdx.x & 63u) * 4u);
-    const unsigned char *frame = input + (size_t)n * fbytes;
-    unsigned char *ofr = out + (size_t)n * fbytes;
-    const bool last = n + 1 == gridDim.z;
-    if (rg < py.nrg) {
-        const unsigned oy = __builtin_amdgcn_readfirstlane(rg * 4u + (threadIdx.x >> 6));
-        if (oy >= (unsigned)py.h || blockIdx.y * 256u >= (unsigned)py.w) return;
-        yuv_warp_row<yuv::PLANE_Y, FMY>(frame, ofr, field, py, n, oy, ox0, fh, fw, fbytes, last);
-    } else if (rg < py.nrg + pc.nrg) {
-        const unsigned oy = __builtin_amdgcn_readfirstlane((rg - py.nrg) * 4u + (threadIdx.x >> 6));
-        if (oy >= (unsigned)pc.h || blockIdx.y * 256u >= (unsigned)pc.w) return;
-        yuv_warp_row<LAYOUT == 0 ? yuv::PLANE_NV12_UV : yuv::PLANE_I420_UV, FMC>(frame, ofr, field, pc, n, oy, ox0, fh, fw, fbytes, last);
-    }
-}
-
-extern "C" int pws_upsample_grid_sample_yuv420_u8(const unsigned char *frames, const float *field, unsigned char *out, int n, int h, int w,
-                                                  int fh, int fw, int layout, int align_corners, pws_stream_t stream) {
-    PWS_REQUIRE(n >= 0 && h > 0 && w > 0 && fh > 0 && fw > 0, "pws_upsample_grid_sample_yuv420_u8: bad shape");
-    PWS_REQUIRE(layout == 0 || layout == 1, "pws_upsample_grid_sample_yuv420_u8: layout must be 0 (NV12) or 1 (I420), got %d", layout);
-    PWS_REQUIRE(h % 2 == 0 && w % 4 == 0 && h >= 2, "pws_upsample_grid_sample_yuv420_u8: h must be even and w a multiple of 4 (got %d x %d)", w, h);
-    if (n == 0) return PWS_OK;
-    PWS_REQUIRE(frames && field && out, "pws_upsample_grid_sample_yuv420_u8: NULL pointer");
-    PWS_REQUIRE(((reinterpret_cast<size_t>(frames) | reinterpret_cast<size_t>(out)) & 3) == 0,
-                "pws_upsample_grid_sample_yuv420_u8: frames and out must be 4-byte aligned");
-    PWS_REQUIRE((size_t)h * w < (1u << 29) && w < (1 << 23) && n < 65536, "pws_upsample_grid_sample_yuv420_u8: frame or batch too large");
-    const unsigned fbytes = (unsigned)((size_t)h * w * 3 / 2);
-    auto plane = [&](int ph, int pw, unsigned off0, unsigned off1, unsigned pitch) {
-        yuv::Plane p;
-        p.h = ph, p.w = pw, p.off0 = off0, p.off1 = off1, p.pitch = pitch;
-        p.ry = ph > 1 ? (float)(fh - 1) / (float)(ph - 1) : 0.f;
-        p.rx = pw > 1 ? (float)(fw - 1) / (float)(pw - 1) : 0.f;
-        p.kx = align_corners ? 0.5f * (float)(pw - 1) : 0.5f * (float)pw, p.kx1 = 0.5f * (float)(pw - 1);
-        p.ky = align_corners ? 0.5f * (float)(ph - 1) : 0.5f * (float)ph, p.ky1 = 0.5f * (float)(ph - 1);
-        p.nrg = (unsigned)((ph + 3) / 4);
-        return p;
-    };
-    const unsigned hw = (unsigned)(h * w), hc = (unsigned)(h / 2), wc = (unsigned)(w / 2);
-    const yuv::Plane py = plane(h, w, 0u, 0u, (unsigned)w);
-    const yuv::Plane pc = layout == 0 ? plane(h / 2, w / 2, hw, hw, (unsigned)w) : plane(h / 2, w / 2, hw, hw + hc * wc, wc);
-    const unsigned gx = (py.nrg + pc.nrg + 7u) & ~7u, cpr = (unsigned)((w + 255) / 256);   // (chroma rows need half the chunks: the rest return)
-    const int fmy = yuv_fmode(py.rx), fmc = yuv_fmode(pc.rx);
-    const size_t total = (size_t)n * h * w;
-    ProfScope prof(KID_UPSAMPLE_GRID_SAMPLE_U8, (double)total * 1.5 * (40.0 + 8.0), (double)total * 3.0 + 8.0 * (double)n * fh * fw,
-                   as_stream(stream));
-#define PWS_YUV_LAUNCH(L_, FY_, FC_)                                                                                                      \
-    hipLaunchKernelGGL((upsample_grid_sample_yuv420_kernel<L_, FY_, FC_>), dim3(gx, cpr, (unsigned)n), dim3(256), 0, as_stream(stream), frames, \
-                       field, out, py, pc, fh, fw, fbytes)
-#define PWS_YUV_FC(L_, FY_)                                                                                                               \
-    do {                                                                                                                                  \
-        if (fmc == 3) PWS_YUV_LAUNCH(L_, FY_, 3);                                                                                         \
-        else if (fmc == 2) PWS_YUV_LAUNCH(L_, FY_, 2);                                                                                    \
-        else PWS_YUV_LAUNCH(L_, FY_, 0);                                                                                                  \
-    } while (0)
-#define PWS_YUV_FY(L_)                                                                                                                    \
-    do {                                                                                                                                  \
-        if (fmy == 2) PWS_YUV_FC(L_, 2);                                                                                                  \
-        else if (fmy == 3) PWS_YUV_FC(L_, 3);                                                                                             \
-        else PWS_YUV_FC(L_, 0);                                                                                                           \
-    } while (0)
-    if (layout == 0) PWS_YUV_FY(0);
-    else PWS_YUV_FY(1);
-#undef PWS_YUV_FY
-#undef PWS_YUV_FC
-#undef PWS_YUV_LAUNCH
-    return check_launch("upsample_grid_sample_yuv420_kernel");
-}
-
-// ---------------------------------------------------------------------------------------------- fused 10-bit 4:2:0 path (P010 / I010)
-// The YUV warp above for 16-bit frames ([n][h*3/2][w] little-endian words in the 8-bit formats' plane order): LAYOUT 0 P010 (sample = word >> 6,
+// ---------------------------------------------------------------------------------------------- 10-bit 4:2:0 rows (P010 / I010)
+// The row function above for 16-bit frames ([n][h*3/2][w] little-endian words in the 8-bit formats' plane order): LAYOUT 0 P010 (sample = word >> 6,
 // stored << 6 with zero low bits), 1 I010 (sample = min(word, 1023)).  The blend runs in fp32 on the 10-bit values with the same field
 // interpolation, un-normalisation and 4-term order, is truncated and clamped to 0..1023; taps outside a plane read BT.601 black at 10 bits,
 // 64 in Y and 512 in U and V.  Twice the bytes of the 8-bit kernel on the SAME count of vector memory instructions per lane (counted in the
@@ -1269,10 +1196,19 @@ __device__ __forceinline__ void yuv16_warp_row(const unsigned char *__restrict__
     }
 }
 
-template <int LAYOUT, int FMY, int FMC>   // LAYOUT 0 P010, 1 I010; FMY / FMC: field access mode of the Y / chroma planes
-__global__ void __launch_bounds__(256) upsample_grid_sample_yuv420_u16_kernel(const unsigned char *__restrict__ input, const float *__restrict__ field,
-                                                                              unsigned char *__restrict__ out, yuv::Plane py, yuv::Plane pc, int fh,
-                                                                              int fw, unsigned fbytes) {
+// ---------------------------------------------------------------------------------------------- the 4:2:0 kernel and launcher, both depths
+// SB: bytes per sample (1: yuv_warp_row, 2: yuv16_warp_row); LAYOUT 0 NV12 / P010, 1 I420 / I010
+template <int SB, int KIND, int FMODE, int LAYOUT>
+__device__ __forceinline__ void yuv420_warp_row(const unsigned char *__restrict__ frame, unsigned char *__restrict__ ofr, const float *__restrict__ field,
+                                                const yuv::Plane &P, unsigned n, unsigned oy, int ox0, int fh, int fw, unsigned fbytes, bool last_sample) {
+    if constexpr (SB == 1) yuv_warp_row<KIND, FMODE>(frame, ofr, field, P, n, oy, ox0, fh, fw, fbytes, last_sample);
+    else yuv16_warp_row<KIND, FMODE, LAYOUT>(frame, ofr, field, P, n, oy, ox0, fh, fw, fbytes, last_sample);
+}
+
+template <int SB, int LAYOUT, int FMY, int FMC>   // FMY / FMC: field access mode of the Y / chroma planes
+__global__ void __launch_bounds__(256) upsample_grid_sample_yuv420_kernel(const unsigned char *__restrict__ input, const float *__restrict__ field,
+                                                                          unsigned char *__restrict__ out, yuv::Plane py, yuv::Plane pc, int fh,
+                                                                          int fw, unsigned fbytes) {
     const unsigned rg = xcd_remap(blockIdx.x, gridDim.x);
     const unsigned n = blockIdx.z;
     const int ox0 = (int)(blockIdx.y * 256u + (threadIdx.x & 63u) * 4u);
@@ -1282,66 +1218,57 @@ __global__ void __launch_bounds__(256) upsample_grid_sample_yuv420_u16_kernel(co
     if (rg < py.nrg) {
         const unsigned oy = __builtin_amdgcn_readfirstlane(rg * 4u + (threadIdx.x >> 6));
         if (oy >= (unsigned)py.h || blockIdx.y * 256u >= (unsigned)py.w) return;
-        yuv16_warp_row<yuv::PLANE_Y, FMY, LAYOUT>(frame, ofr, field, py, n, oy, ox0, fh, fw, fbytes, last);
+        yuv420_warp_row<SB, yuv::PLANE_Y, FMY, LAYOUT>(frame, ofr, field, py, n, oy, ox0, fh, fw, fbytes, last);
     } else if (rg < py.nrg + pc.nrg) {
         const unsigned oy = __builtin_amdgcn_readfirstlane((rg - py.nrg) * 4u + (threadIdx.x >> 6));
         if (oy >= (unsigned)pc.h || blockIdx.y * 256u >= (unsigned)pc.w) return;
-        yuv16_warp_row<LAYOUT == 0 ? yuv::PLANE_NV12_UV : yuv::PLANE_I420_UV, FMC, LAYOUT>(frame, ofr, field, pc, n, oy, ox0, fh, fw, fbytes, last);
+        yuv420_warp_row<SB, LAYOUT == 0 ? yuv::PLANE_NV12_UV : yuv::PLANE_I420_UV, FMC, LAYOUT>(frame, ofr, field, pc, n, oy, ox0, fh, fw, fbytes, last);
     }
+}
+
+// SB: bytes per sample.  The checks and the plane geometry are yuv::launch_yuv420's, shared with the bicubic warps and the keep pass
+template <int SB>
+static int warp_yuv420(const char *what, const void *frames, const float *field, void *out, int n, int h, int w, int fh, int fw, int layout,
+                       int align_corners, pws_stream_t stream) {
+    yuv::Launch420 L;
+    const int rc = yuv::launch_yuv420<SB>(what, frames, field, out, "out", n, h, w, fh, fw, layout, align_corners, 0, "", L);
+    if (rc != PWS_OK || n == 0) return rc;
+    const size_t total = (size_t)n * h * w;
+    // (both depths are booked under the 8-bit integer warps' id on purpose: one row "fused byte warp" in the per-kernel stats, told apart by
+    // the bytes booked per launch -- 3 per pixel at 8 bits, 6 at 16; a clip has one depth, so a run does not mix them)
+    ProfScope prof(KID_UPSAMPLE_GRID_SAMPLE_U8, (double)total * 1.5 * (40.0 + 8.0), (double)total * 3.0 * SB + 8.0 * (double)n * fh * fw,
+                   as_stream(stream));
+    const unsigned char *src = reinterpret_cast<const unsigned char *>(frames);
+    unsigned char *dst = reinterpret_cast<unsigned char *>(out);
+#define PWS_YUV_LAUNCH(L_, FY_, FC_)                                                                                                      \
+    hipLaunchKernelGGL((upsample_grid_sample_yuv420_kernel<SB, L_, FY_, FC_>), dim3(L.gx, L.cpr, (unsigned)n), dim3(256), 0, as_stream(stream), src, \
+                       field, dst, L.py, L.pc, fh, fw, L.fbytes)
+#define PWS_YUV_FC(L_, FY_)                                                                                                               \
+    do {                                                                                                                                  \
+        if (L.fmc == 3) PWS_YUV_LAUNCH(L_, FY_, 3);                                                                                       \
+        else if (L.fmc == 2) PWS_YUV_LAUNCH(L_, FY_, 2);                                                                                  \
+        else PWS_YUV_LAUNCH(L_, FY_, 0);                                                                                                  \
+    } while (0)
+#define PWS_YUV_FY(L_)                                                                                                                    \
+    do {                                                                                                                                  \
+        if (L.fmy == 2) PWS_YUV_FC(L_, 2);                                                                                                \
+        else if (L.fmy == 3) PWS_YUV_FC(L_, 3);                                                                                           \
+        else PWS_YUV_FC(L_, 0);                                                                                                           \
+    } while (0)
+    if (layout == 0) PWS_YUV_FY(0);
+    else PWS_YUV_FY(1);
+#undef PWS_YUV_FY
+#undef PWS_YUV_FC
+#undef PWS_YUV_LAUNCH
+    return check_launch("upsample_grid_sample_yuv420_kernel");
+}
+
+extern "C" int pws_upsample_grid_sample_yuv420_u8(const unsigned char *frames, const float *field, unsigned char *out, int n, int h, int w,
+                                                  int fh, int fw, int layout, int align_corners, pws_stream_t stream) {
+    return warp_yuv420<1>("pws_upsample_grid_sample_yuv420_u8", frames, field, out, n, h, w, fh, fw, layout, align_corners, stream);
 }
 
 extern "C" int pws_upsample_grid_sample_yuv420_u16(const unsigned short *frames, const float *field, unsigned short *out, int n, int h, int w,
                                                    int fh, int fw, int layout, int align_corners, pws_stream_t stream) {
-    PWS_REQUIRE(n >= 0 && h > 0 && w > 0 && fh > 0 && fw > 0, "pws_upsample_grid_sample_yuv420_u16: bad shape");
-    PWS_REQUIRE(layout == 0 || layout == 1, "pws_upsample_grid_sample_yuv420_u16: layout must be 0 (P010) or 1 (I010), got %d", layout);
-    PWS_REQUIRE(h % 2 == 0 && w % 4 == 0 && h >= 2, "pws_upsample_grid_sample_yuv420_u16: h must be even and w a multiple of 4 (got %d x %d)", w, h);
-    if (n == 0) return PWS_OK;
-    PWS_REQUIRE(frames && field && out, "pws_upsample_grid_sample_yuv420_u16: NULL pointer");
-    PWS_REQUIRE(((reinterpret_cast<size_t>(frames) | reinterpret_cast<size_t>(out)) & 7) == 0,
-                "pws_upsample_grid_sample_yuv420_u16: frames and out must be 8-byte aligned");
-    PWS_REQUIRE((size_t)h * w < (1u << 28) && w < (1 << 22) && n < 65536, "pws_upsample_grid_sample_yuv420_u16: frame or batch too large");
-    const unsigned fbytes = (unsigned)((size_t)h * w * 3);   // (a multiple of 8: every sample starts 8-byte aligned)
-    auto plane = [&](int ph, int pw, unsigned off0, unsigned off1, unsigned pitch) {
-        yuv::Plane p;
-        p.h = ph, p.w = pw, p.off0 = off0, p.off1 = off1, p.pitch = pitch;
-        p.ry = ph > 1 ? (float)(fh - 1) / (float)(ph - 1) : 0.f;
-        p.rx = pw > 1 ? (float)(fw - 1) / (float)(pw - 1) : 0.f;
-        p.kx = align_corners ? 0.5f * (float)(pw - 1) : 0.5f * (float)pw, p.kx1 = 0.5f * (float)(pw - 1);
-        p.ky = align_corners ? 0.5f * (float)(ph - 1) : 0.5f * (float)ph, p.ky1 = 0.5f * (float)(ph - 1);
-        p.nrg = (unsigned)((ph + 3) / 4);
-        return p;
-    };
-    const unsigned hw2 = 2u * (unsigned)(h * w), hc = (unsigned)(h / 2), wc = (unsigned)(w / 2);   // byte offsets and pitches
-    const yuv::Plane py = plane(h, w, 0u, 0u, 2u * (unsigned)w);
-    const yuv::Plane pc = layout == 0 ? plane(h / 2, w / 2, hw2, hw2, 2u * (unsigned)w) : plane(h / 2, w / 2, hw2, hw2 + 2u * hc * wc, 2u * wc);
-    const unsigned gx = (py.nrg + pc.nrg + 7u) & ~7u, cpr = (unsigned)((w + 255) / 256);   // (chroma rows need half the chunks: the rest return)
-    const int fmy = yuv_fmode(py.rx), fmc = yuv_fmode(pc.rx);
-    const size_t total = (size_t)n * h * w;
-    // (booked under the 8-bit integer warps' id on purpose, like the NV12 / I420 launch above: one row "fused byte warp" in the per-kernel
-    // stats, told apart by the bytes booked per launch -- 6 per pixel here against 3; a clip has one depth, so a run does not mix them)
-    ProfScope prof(KID_UPSAMPLE_GRID_SAMPLE_U8, (double)total * 1.5 * (40.0 + 8.0), (double)total * 6.0 + 8.0 * (double)n * fh * fw,
-                   as_stream(stream));
-    const unsigned char *src = reinterpret_cast<const unsigned char *>(frames);
-    unsigned char *dst = reinterpret_cast<unsigned char *>(out);
-#define PWS_YUV16_LAUNCH(L_, FY_, FC_)                                                                                                    \
-    hipLaunchKernelGGL((upsample_grid_sample_yuv420_u16_kernel<L_, FY_, FC_>), dim3(gx, cpr, (unsigned)n), dim3(256), 0, as_stream(stream), src, \
-                       field, dst, py, pc, fh, fw, fbytes)
-#define PWS_YUV16_FC(L_, FY_)                                                                                                             \
-    do {                                                                                                                                  \
-        if (fmc == 3) PWS_YUV16_LAUNCH(L_, FY_, 3);                                                                                       \
-        else if (fmc == 2) PWS_YUV16_LAUNCH(L_, FY_, 2);                                                                                  \
-        else PWS_YUV16_LAUNCH(L_, FY_, 0);                                                                                                \
-    } while (0)
-#define PWS_YUV16_FY(L_)                                                                                                                  \
-    do {                                                                                                                                  \
-        if (fmy == 2) PWS_YUV16_FC(L_, 2);                                                                                                \
-        else if (fmy == 3) PWS_YUV16_FC(L_, 3);                                                                                           \
-        else PWS_YUV16_FC(L_, 0);                                                                                                         \
-    } while (0)
-    if (layout == 0) PWS_YUV16_FY(0);
-    else PWS_YUV16_FY(1);
-#undef PWS_YUV16_FY
-#undef PWS_YUV16_FC
-#undef PWS_YUV16_LAUNCH
-    return check_launch("upsample_grid_sample_yuv420_u16_kernel");
+    return warp_yuv420<2>("pws_upsample_grid_sample_yuv420_u16", frames, field, out, n, h, w, fh, fw, layout, align_corners, stream);
 }

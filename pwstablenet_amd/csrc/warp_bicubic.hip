@@ -339,17 +339,6 @@ __global__ void __launch_bounds__(256) bicubic_fwd_kernel(const float *__restric
     }
 }
 
-static yuv::Plane make_plane(int ph, int pw, unsigned off0, unsigned off1, unsigned pitch, int fh, int fw, int align_corners) {
-    yuv::Plane p;   // (the twins' geometry and constants: the same fp32 products)
-    p.h = ph, p.w = pw, p.off0 = off0, p.off1 = off1, p.pitch = pitch;
-    p.ry = ph > 1 ? (float)(fh - 1) / (float)(ph - 1) : 0.f;
-    p.rx = pw > 1 ? (float)(fw - 1) / (float)(pw - 1) : 0.f;
-    p.kx = align_corners ? 0.5f * (float)(pw - 1) : 0.5f * (float)pw, p.kx1 = 0.5f * (float)(pw - 1);
-    p.ky = align_corners ? 0.5f * (float)(ph - 1) : 0.5f * (float)ph, p.ky1 = 0.5f * (float)(ph - 1);
-    p.nrg = (unsigned)((ph + 3) / 4);
-    return p;
-}
-
 }  // namespace bic
 }  // namespace pws
 
@@ -388,7 +377,7 @@ extern "C" int pws_upsample_grid_sample_bicubic_u8(const unsigned char *frame_hw
     PWS_REQUIRE((reinterpret_cast<size_t>(out_hwc) & 3) == 0, "pws_upsample_grid_sample_bicubic_u8: out must be 4-byte aligned");
     const unsigned cpr = (unsigned)((w + 255) / 256);
     PWS_REQUIRE(n < 65536 && cpr < 65536 && (size_t)w * 3 < (1u << 24) && h < (1 << 24), "pws_upsample_grid_sample_bicubic_u8: frame or batch too large");
-    const yuv::Plane P = bic::make_plane(h, w, 0u, 0u, 3u * (unsigned)w, fh, fw, align_corners);
+    const yuv::Plane P = yuv::make_plane(h, w, 0u, 0u, 3u * (unsigned)w, fh, fw, align_corners);
     const unsigned gx = (P.nrg + 7u) & ~7u, fbytes = (unsigned)((size_t)h * w * 3);
     const int fmode = yuv_fmode(P.rx);
     const size_t total = (size_t)n * h * w;
@@ -403,37 +392,25 @@ extern "C" int pws_upsample_grid_sample_bicubic_u8(const unsigned char *frame_hw
     return check_launch("bicubic_u8_kernel");
 }
 
-// SB: bytes per sample.  Checks and plane geometry are the twins' (w >= 8 on top: a chroma plane holds the 4-column window)
+// SB: bytes per sample.  Checks and plane geometry are the twins' (yuv::launch_yuv420; w >= 8 on top: a chroma plane holds the 4-column window)
 template <int SB>
 static int bicubic_yuv420(const char *what, const void *frames, const float *field, void *out, int n, int h, int w, int fh, int fw, int layout,
                           int align_corners, pws_stream_t stream) {
-    PWS_REQUIRE(n >= 0 && h > 0 && w > 0 && fh > 0 && fw > 0, "%s: bad shape", what);
-    PWS_REQUIRE(layout == 0 || layout == 1, "%s: layout must be 0 (%s) or 1 (%s), got %d", what, SB == 1 ? "NV12" : "P010", SB == 1 ? "I420" : "I010", layout);
-    PWS_REQUIRE(h % 2 == 0 && w % 4 == 0 && h >= 2, "%s: h must be even and w a multiple of 4 (got %d x %d)", what, w, h);
-    PWS_REQUIRE(w >= 8, "%s: w must be at least 8 (the chroma planes hold the 4-tap window), got %d", what, w);
-    if (n == 0) return PWS_OK;
-    PWS_REQUIRE(frames && field && out, "%s: NULL pointer", what);
-    PWS_REQUIRE(((reinterpret_cast<size_t>(frames) | reinterpret_cast<size_t>(out)) & (SB == 1 ? 3 : 7)) == 0, "%s: frames and out must be %d-byte aligned",
-                what, SB == 1 ? 4 : 8);
-    PWS_REQUIRE((size_t)h * w < (1u << (SB == 1 ? 29 : 28)) && w < (1 << (SB == 1 ? 23 : 22)) && n < 65536, "%s: frame or batch too large", what);
-    const unsigned fbytes = (unsigned)((size_t)h * w * 3 / 2) * SB;
-    const unsigned hw = (unsigned)(h * w) * SB, hc = (unsigned)(h / 2), wc = (unsigned)(w / 2);   // byte offsets and pitches
-    const yuv::Plane py = bic::make_plane(h, w, 0u, 0u, (unsigned)w * SB, fh, fw, align_corners);
-    const yuv::Plane pc = layout == 0 ? bic::make_plane(h / 2, w / 2, hw, hw, (unsigned)w * SB, fh, fw, align_corners)
-                                      : bic::make_plane(h / 2, w / 2, hw, hw + hc * wc * SB, wc * SB, fh, fw, align_corners);
-    const unsigned gx = (py.nrg + pc.nrg + 7u) & ~7u, cpr = (unsigned)((w + 255) / 256);   // (chroma rows need half the chunks: the rest return)
-    const int fmy = yuv_fmode(py.rx), fmc = yuv_fmode(pc.rx);
+    yuv::Launch420 L;
+    const int rc = yuv::launch_yuv420<SB>(what, frames, field, out, "out", n, h, w, fh, fw, layout, align_corners, 8,
+                                          "(the chroma planes hold the 4-tap window)", L);
+    if (rc != PWS_OK || n == 0) return rc;
     const size_t total = (size_t)n * h * w;
     ProfScope prof(KID_UPSAMPLE_GRID_SAMPLE_U8, (double)total * 1.5 * (80.0 + 40.0), (double)total * 3.0 * SB + 8.0 * (double)n * fh * fw,
                    as_stream(stream));
     const unsigned char *src = reinterpret_cast<const unsigned char *>(frames);
     unsigned char *dst = reinterpret_cast<unsigned char *>(out);
     if (layout == 0)
-        hipLaunchKernelGGL((bic::bicubic_yuv420_kernel<SB, 0>), dim3(gx, cpr, (unsigned)n), dim3(256), 0, as_stream(stream), src, field, dst, py, pc, fmy,
-                           fmc, fh, fw, fbytes);
+        hipLaunchKernelGGL((bic::bicubic_yuv420_kernel<SB, 0>), dim3(L.gx, L.cpr, (unsigned)n), dim3(256), 0, as_stream(stream), src, field, dst, L.py, L.pc,
+                           L.fmy, L.fmc, fh, fw, L.fbytes);
     else
-        hipLaunchKernelGGL((bic::bicubic_yuv420_kernel<SB, 1>), dim3(gx, cpr, (unsigned)n), dim3(256), 0, as_stream(stream), src, field, dst, py, pc, fmy,
-                           fmc, fh, fw, fbytes);
+        hipLaunchKernelGGL((bic::bicubic_yuv420_kernel<SB, 1>), dim3(L.gx, L.cpr, (unsigned)n), dim3(256), 0, as_stream(stream), src, field, dst, L.py, L.pc,
+                           L.fmy, L.fmc, fh, fw, L.fbytes);
     return check_launch("bicubic_yuv420_kernel");
 }
 

@@ -1,6 +1,7 @@
 // What the bilinear warp kernels (grid_sample.hip) and the bicubic ones (warp_bicubic.hip) share, so that both form a pixel's source
 // position (ix, iy) with the same fp32 operations: the field's interpolation (mul_rounded of common.h, field_lerp / pk_field_lerp and the
-// wave-shared fetch yuv_field4), the un-normalisation, the plane geometry of packed 4:2:0 frames, and the byte / 10-bit conversions.
+// wave-shared fetch yuv_field4), the un-normalisation, the plane geometry of packed 4:2:0 frames with the launchers' shared checks (yuv::make_plane,
+// yuv::launch_yuv420), and the byte / 10-bit conversions.
 #pragma once
 #include "common.h"
 
@@ -155,6 +156,47 @@ template <int LAYOUT>
 __device__ __forceinline__ unsigned place10(float blend) {   // truncate (the blend is >= 0), clamp to 10 bits, the layout's placement
     const unsigned v = min((unsigned)blend, 1023u);
     return LAYOUT == 0 ? v << 6 : v;
+}
+
+// ---- host side: the geometry of a plane, and what the launchers of the 4:2:0 kernels (bilinear, bicubic, keep) check and derive alike
+static Plane make_plane(int ph, int pw, unsigned off0, unsigned off1, unsigned pitch, int fh, int fw, int align_corners) {
+    Plane p;   // (the field's resize ratios and the un-normalisation constants: every kernel gets the same fp32 products)
+    p.h = ph, p.w = pw, p.off0 = off0, p.off1 = off1, p.pitch = pitch;
+    p.ry = ph > 1 ? (float)(fh - 1) / (float)(ph - 1) : 0.f;
+    p.rx = pw > 1 ? (float)(fw - 1) / (float)(pw - 1) : 0.f;
+    p.kx = align_corners ? 0.5f * (float)(pw - 1) : 0.5f * (float)pw, p.kx1 = 0.5f * (float)(pw - 1);
+    p.ky = align_corners ? 0.5f * (float)(ph - 1) : 0.5f * (float)ph, p.ky1 = 0.5f * (float)(ph - 1);
+    p.nrg = (unsigned)((ph + 3) / 4);
+    return p;
+}
+
+struct Launch420 {   // one launch over every plane of every frame: grid (gx, cpr, frames or 1), 256 threads
+    Plane py, pc;
+    unsigned fbytes, gx, cpr;   // bytes per frame, row groups of Y then chroma (padded to the 8 XCDs), 256-pixel chunks per Y row
+    int fmy, fmc;               // field access mode of the Y / chroma planes
+};
+// SB: bytes per sample (1: NV12 / I420, 2: P010 / I010).  `other`: the second frame pointer (`other_name`: "out" / "initial").  min_w > 0: the
+// caller's own minimum width, `min_w_why` the words after "w must be at least <min_w> ".  PWS_OK with n == 0 means: nothing to launch.
+template <int SB>
+static int launch_yuv420(const char *what, const void *frames, const float *field, const void *other, const char *other_name, int n, int h, int w,
+                         int fh, int fw, int layout, int align_corners, int min_w, const char *min_w_why, Launch420 &L) {
+    PWS_REQUIRE(n >= 0 && h > 0 && w > 0 && fh > 0 && fw > 0, "%s: bad shape", what);
+    PWS_REQUIRE(layout == 0 || layout == 1, "%s: layout must be 0 (%s) or 1 (%s), got %d", what, SB == 1 ? "NV12" : "P010", SB == 1 ? "I420" : "I010", layout);
+    PWS_REQUIRE(h % 2 == 0 && w % 4 == 0 && h >= 2, "%s: h must be even and w a multiple of 4 (got %d x %d)", what, w, h);
+    PWS_REQUIRE(w >= min_w, "%s: w must be at least %d %s, got %d", what, min_w, min_w_why, w);
+    if (n == 0) return PWS_OK;
+    PWS_REQUIRE(frames && field && other, "%s: NULL pointer", what);
+    PWS_REQUIRE(((reinterpret_cast<size_t>(frames) | reinterpret_cast<size_t>(other)) & (SB == 1 ? 3 : 7)) == 0, "%s: frames and %s must be %d-byte aligned",
+                what, other_name, SB == 1 ? 4 : 8);
+    PWS_REQUIRE((size_t)h * w < (1u << (SB == 1 ? 29 : 28)) && w < (1 << (SB == 1 ? 23 : 22)) && n < 65536, "%s: frame or batch too large", what);
+    L.fbytes = (unsigned)((size_t)h * w * 3 / 2) * SB;   // (16 bit: a multiple of 8, every frame starts 8-byte aligned)
+    const unsigned hw = (unsigned)(h * w) * SB, hc = (unsigned)(h / 2), wc = (unsigned)(w / 2);   // byte offsets and pitches
+    L.py = make_plane(h, w, 0u, 0u, (unsigned)w * SB, fh, fw, align_corners);
+    L.pc = layout == 0 ? make_plane(h / 2, w / 2, hw, hw, (unsigned)w * SB, fh, fw, align_corners)
+                       : make_plane(h / 2, w / 2, hw, hw + hc * wc * SB, wc * SB, fh, fw, align_corners);
+    L.gx = (L.py.nrg + L.pc.nrg + 7u) & ~7u, L.cpr = (unsigned)((w + 255) / 256);   // (chroma rows need half the chunks: the rest return)
+    L.fmy = yuv_fmode(L.py.rx), L.fmc = yuv_fmode(L.pc.rx);
+    return PWS_OK;
 }
 }  // namespace yuv
 }  // namespace pws

@@ -8,6 +8,8 @@ plus ``upsample_bilinear2d(x, size)`` (== ``torch.nn.UpsamplingBilinear2d(size=.
 ``upsample_grid_sample(input, field)`` of the 720p path.  torch is used for device memory, streams and
 autograd bookkeeping only.
 """
+import collections
+
 import torch
 
 from . import hipabi as A
@@ -138,20 +140,127 @@ def _entry(mode, name):
     return "pws_upsample_grid_sample_" + ("bicubic_" if mode == "bicubic" else "") + name
 
 
+PIXEL_FORMATS = ("bgr24", "nv12", "i420")
+YUV420_LAYOUT = {"nv12": 0, "i420": 1}
+PIXEL_FORMATS_16 = ("p010", "i010")
+YUV420_16_LAYOUT = {"p010": 0, "i010": 1}
+BORDERS = ("black", "keep")
+
+
+class FrameFormat(collections.namedtuple("FrameFormat", "name dtype packed layout suffix wrapper window_planes plane_resize")):
+    """What the warps, the keep pass and the stabiliser need to know about a pixel format, in one place: its ``name``, the frames' ``dtype``,
+    whether they are ``packed`` 4:2:0 (T, H * 3 // 2, W) and then their plane ``layout`` (0: Y + interleaved UV, 1: Y + U + V; None for the
+    unpacked formats), the ``suffix`` of the format's C entries (``pws_upsample_grid_sample_[bicubic_]<suffix>``, ``pws_border_keep_<suffix>``),
+    the ``wrapper`` whose name its error messages carry, and the C entries that make its ``window_planes`` and resize its planes
+    (``plane_resize``).  A new format is a row of FRAME_FORMATS (and its kernels)."""
+    __slots__ = ()
+
+    @property
+    def hwc(self):
+        """(T, H, W, 3) frames ("bgr24"); the float frames are (T, C, H, W)."""
+        return not self.packed and self.dtype == torch.uint8
+
+    def frame_shape(self, frames, w_multiple=4):
+        """(T, H, W) of ``frames``.  Packed 4:2:0: (T, H * 3 // 2, W) of the format's dtype, ValueError unless H and W are even and W a multiple
+        of ``w_multiple``.  Unpacked frames are read by position, (T, H, W, 3) or float (T, C, H, W): only another rank is a ValueError here
+        (dtype, channel count and width are checked where the frames are used, behind the check for host tensors)."""
+        if not self.packed:
+            if frames.dim() != 4:
+                raise ValueError("%s: frames must be %s, got %s %s" % (self.wrapper, "uint8 (N,H,W,3)" if self.hwc else "float32 (N,C,H,W)",
+                                                                     frames.dtype, tuple(frames.shape)))
+            return (frames.shape[0],) + tuple(frames.shape[1:3] if self.hwc else frames.shape[2:4])
+        if frames.dim() != 3 or frames.dtype != self.dtype:
+            raise ValueError("%s frames must be %s (T, H * 3 // 2, W), got %s %s" % (self.name, str(self.dtype)[6:], frames.dtype, tuple(frames.shape)))
+        t, ph, w = frames.shape
+        if ph % 3 != 0 or ph == 0:
+            raise ValueError("%s frames: packed height %d is not H * 3 // 2 of an even H" % (self.name, ph))
+        h = ph // 3 * 2
+        if w % 2 != 0 or w % w_multiple != 0:
+            raise ValueError("%s frames: width %d must be even and a multiple of %d" % (self.name, w, w_multiple))
+        return t, h, w
+
+    def extra(self, flag=False):
+        """The one format argument of the C entries: the plane layout of packed frames; for BGR the caller's ``flag`` (swap_rb, frames_are_rgb)."""
+        return self.layout if self.packed else int(bool(flag))
+
+    def warp_entry(self, mode):
+        return _entry(mode, self.suffix)
+
+    @property
+    def keep_entry(self):
+        return "pws_border_keep_" + self.suffix
+
+
+FRAME_FORMATS = {f.name: f for f in (
+    FrameFormat("bgr24", torch.uint8, False, None, "u8", "upsample_grid_sample_u8", "pws_gray_area_u8", "pws_area_resize_u8"),
+    FrameFormat("nv12", torch.uint8, True, 0, "yuv420_u8", "upsample_grid_sample_yuv420", "pws_gray_area_yuv420_u8", "pws_area_resize_plane_u8"),
+    FrameFormat("i420", torch.uint8, True, 1, "yuv420_u8", "upsample_grid_sample_yuv420", "pws_gray_area_yuv420_u8", "pws_area_resize_plane_u8"),
+    FrameFormat("p010", torch.uint16, True, 0, "yuv420_u16", "upsample_grid_sample_yuv420_16", "pws_gray_area_yuv420_u16", "pws_area_resize_plane_u16"),
+    FrameFormat("i010", torch.uint16, True, 1, "yuv420_u16", "upsample_grid_sample_yuv420_16", "pws_gray_area_yuv420_u16", "pws_area_resize_plane_u16"),
+)}
+# the float (T, C, H, W) frames that run() accepts under "bgr24": no keep pass, no window planes, no resize
+_FLOAT_FRAMES = FrameFormat("bgr24", torch.float32, False, None, "fwd", "upsample_grid_sample", None, None)
+
+
+def _packed_format(pixel_format, dtype):
+    """The record of a packed 4:2:0 format of that sample dtype; ValueError for any other name."""
+    fmt = FRAME_FORMATS.get(pixel_format)
+    if fmt is None or not fmt.packed or fmt.dtype != dtype:
+        if dtype == torch.uint8:
+            raise ValueError("pixel_format must be one of %s for 4:2:0 frames, got %r (8-bit BT.601 limited-range NV12 / I420 only)"
+                             % (tuple(YUV420_LAYOUT), pixel_format))
+        raise ValueError("pixel_format must be one of %s for 10-bit 4:2:0 frames, got %r (BT.601 limited-range P010 / I010 only)"
+                         % (tuple(YUV420_16_LAYOUT), pixel_format))
+    return fmt
+
+
+def frame_format(pixel_format, frames, what, float_frames=False):
+    """The record that ``pixel_format`` names, for ``frames``; packed frames are checked against it (``FrameFormat.frame_shape``).  A name that
+    is none of FRAME_FORMATS is ``yuv420_layout``'s ValueError; uint16 frames under "bgr24" are a ValueError naming ``what``; float_frames:
+    "bgr24" frames that are not uint8 are float (T, C, H, W) frames."""
+    fmt = FRAME_FORMATS.get(pixel_format) or _packed_format(pixel_format, torch.uint8)
+    if fmt.packed:
+        fmt.frame_shape(frames)
+    elif frames.dtype == torch.uint16:
+        raise ValueError("%s: uint16 frames need pixel_format \"p010\" or \"i010\", got %r" % (what, pixel_format))
+    elif float_frames and frames.dtype != torch.uint8:
+        fmt = _FLOAT_FRAMES
+    return fmt
+
+
+def warp(frames, field, fmt, swap_rb=False, align_corners=None, out=None, mode="bilinear"):
+    """The fused resize + warp of ``frames`` in the format ``fmt`` (a FrameFormat) by ``field`` (N, fh, fw, 2): the one implementation behind
+    ``upsample_grid_sample``, ``upsample_grid_sample_u8``, ``upsample_grid_sample_yuv420`` and ``upsample_grid_sample_yuv420_16``, which
+    document what each format computes.  An invalid ``mode`` is raised before anything else, then the format's shape rules (ValueError),
+    then host tensors or a wrong dtype (RuntimeError).  ``swap_rb`` applies to "bgr24" alone."""
+    fn = fmt.warp_entry(mode)
+    n, h, w = fmt.frame_shape(frames)
+    A.require_cuda(field)
+    A.require_cuda(frames, dtype=fmt.dtype)
+    if fmt.hwc and frames.shape[3] != 3:
+        raise ValueError("%s: frames must be uint8 (N,H,W,3), got %s %s" % (fmt.wrapper, frames.dtype, tuple(frames.shape)))
+    if fmt.packed and (field.dim() != 4 or field.shape[0] != n or field.shape[3] != 2):
+        raise ValueError("%s: field must be (%d, fh, fw, 2), got %s" % (fmt.wrapper, n, tuple(field.shape)))
+    frames, field = frames.contiguous(), field.contiguous()
+    if out is None:
+        out = torch.empty_like(frames)
+    integer = fmt.packed or fmt.hwc   # (the float entry takes the channel count and no format argument)
+    shape = (n, h, w) if integer else (n, frames.shape[1], h, w)
+    extra = (fmt.extra(swap_rb),) if integer else ()
+    A.check(getattr(A.lib(), fn)(A.ptr(frames), A.ptr(field), A.ptr(out), *shape, field.shape[1], field.shape[2], *extra, _ac(align_corners),
+                                 A.current_stream()), fn)
+    return out
+
+
 def upsample_grid_sample(input, field, align_corners=None, mode="bilinear"):
     """grid_sample(input, UpsamplingBilinear2d(size=input.shape[-2:])(field)) without materialising the resized field.
 
     input: (N,C,H,W) frame; field: (N,h,w,2) warp field as returned by ``netG(x, False)``.  mode = "bicubic": the same warp with
     ``grid_sample(mode="bicubic")``'s 16 taps (forward only; W >= 4).
     """
-    fn = _entry(mode, "fwd")
+    _entry(mode, "fwd")
     A.require_cuda(input, field)
-    input, field = input.contiguous(), field.contiguous()
-    n, c, h, w = input.shape
-    fh, fw = field.shape[1], field.shape[2]
-    out = torch.empty_like(input)
-    A.check(getattr(A.lib(), fn)(A.ptr(input), A.ptr(field), A.ptr(out), n, c, h, w, fh, fw, _ac(align_corners), A.current_stream()), fn)
-    return out
+    return warp(input, field, _FLOAT_FRAMES, align_corners=align_corners, mode=mode)
 
 
 def upsample_grid_sample_u8(frames_hwc, field, swap_rb=False, align_corners=None, out=None, mode="bilinear"):
@@ -159,46 +268,22 @@ def upsample_grid_sample_u8(frames_hwc, field, swap_rb=False, align_corners=None
     ``frames_hwc`` (N,H,W,3) uint8 -> [optional BGR<->RGB swap] -> float CHW -> grid_sample with the field resized to (H,W)
     (UpsamplingBilinear2d) -> ``astype(uint8)`` HWC, in one kernel and 6 bytes of frame traffic per pixel.  W % 4 == 0.
     mode = "bicubic": 16 taps per pixel (``grid_sample(mode="bicubic")``), the blend clamped to 0..255 before it is truncated."""
-    fn = _entry(mode, "u8")
+    _entry(mode, "u8")
     A.require_cuda(field)
-    A.require_cuda(frames_hwc, dtype=torch.uint8)
-    if frames_hwc.dim() != 4 or frames_hwc.shape[3] != 3:
-        raise ValueError("upsample_grid_sample_u8: frames must be uint8 (N,H,W,3), got %s %s" % (frames_hwc.dtype, tuple(frames_hwc.shape)))
-    frames_hwc, field = frames_hwc.contiguous(), field.contiguous()
-    n, h, w, _ = frames_hwc.shape
-    if out is None:
-        out = torch.empty_like(frames_hwc)
-    A.check(getattr(A.lib(), fn)(A.ptr(frames_hwc), A.ptr(field), A.ptr(out), n, h, w, field.shape[1], field.shape[2],
-                                 int(bool(swap_rb)), _ac(align_corners), A.current_stream()), fn)
-    return out
-
-
-PIXEL_FORMATS = ("bgr24", "nv12", "i420")
-YUV420_LAYOUT = {"nv12": 0, "i420": 1}
+    A.require_cuda(frames_hwc, dtype=torch.uint8)   # (a host tensor or another dtype wins over a bad shape here, as it always has)
+    return warp(frames_hwc, field, FRAME_FORMATS["bgr24"], swap_rb, align_corners, out, mode)
 
 
 def yuv420_layout(pixel_format):
     """0 (NV12) / 1 (I420) for an 8-bit 4:2:0 pixel format; ValueError for anything else (4:2:2, 4:4:4, full range and BT.709 are not
     supported; the 10-bit formats P010 / I010 have functions of their own: ``yuv420_16_layout``, ``yuv420_16_shape``,
     ``upsample_grid_sample_yuv420_16``)."""
-    if pixel_format not in YUV420_LAYOUT:
-        raise ValueError("pixel_format must be one of %s for 4:2:0 frames, got %r (8-bit BT.601 limited-range NV12 / I420 only)"
-                         % (tuple(YUV420_LAYOUT), pixel_format))
-    return YUV420_LAYOUT[pixel_format]
+    return _packed_format(pixel_format, torch.uint8).layout
 
 
 def yuv420_shape(frames, pixel_format, w_multiple=4):
     """(T, H, W) of packed 4:2:0 frames (T, H * 3 // 2, W) uint8; ValueError unless H and W are even and W a multiple of ``w_multiple``."""
-    yuv420_layout(pixel_format)
-    if frames.dim() != 3 or frames.dtype != torch.uint8:
-        raise ValueError("%s frames must be uint8 (T, H * 3 // 2, W), got %s %s" % (pixel_format, frames.dtype, tuple(frames.shape)))
-    t, ph, w = frames.shape
-    if ph % 3 != 0 or ph == 0:
-        raise ValueError("%s frames: packed height %d is not H * 3 // 2 of an even H" % (pixel_format, ph))
-    h = ph // 3 * 2
-    if w % 2 != 0 or w % w_multiple != 0:
-        raise ValueError("%s frames: width %d must be even and a multiple of %d" % (pixel_format, w, w_multiple))
-    return t, h, w
+    return _packed_format(pixel_format, torch.uint8).frame_shape(frames, w_multiple)
 
 
 def upsample_grid_sample_yuv420(frames, field, pixel_format, align_corners=None, out=None, mode="bilinear"):
@@ -206,47 +291,22 @@ def upsample_grid_sample_yuv420(frames, field, pixel_format, align_corners=None,
     "nv12" or "i420"; every plane is warped by ``field`` (N, fh, fw, 2) resized (align_corners=True) to the plane's own size, taps outside
     a plane read BT.601 black (16 in Y, 128 in U and V), the fp32 blend is truncated.  H even, W % 4 == 0.  One kernel launch.
     mode = "bicubic": 16 taps per sample, the blend clamped to 0..255 before it is truncated; W >= 8."""
-    fn = _entry(mode, "yuv420_u8")
+    _entry(mode, "yuv420_u8")
     A.require_cuda(field)
-    A.require_cuda(frames, dtype=torch.uint8)
-    layout = yuv420_layout(pixel_format)
-    n, h, w = yuv420_shape(frames, pixel_format)
-    if field.dim() != 4 or field.shape[0] != n or field.shape[3] != 2:
-        raise ValueError("upsample_grid_sample_yuv420: field must be (%d, fh, fw, 2), got %s" % (n, tuple(field.shape)))
-    frames, field = frames.contiguous(), field.contiguous()
-    if out is None:
-        out = torch.empty_like(frames)
-    A.check(getattr(A.lib(), fn)(A.ptr(frames), A.ptr(field), A.ptr(out), n, h, w, field.shape[1], field.shape[2], layout,
-                                 _ac(align_corners), A.current_stream()), fn)
-    return out
-
-
-PIXEL_FORMATS_16 = ("p010", "i010")
-YUV420_16_LAYOUT = {"p010": 0, "i010": 1}
+    A.require_cuda(frames, dtype=torch.uint8)   # (wins over the format's name and shape rules here, as it always has)
+    return warp(frames, field, _packed_format(pixel_format, torch.uint8), False, align_corners, out, mode)
 
 
 def yuv420_16_layout(pixel_format):
     """0 (P010: NV12's plane order, the 10-bit sample in the high bits of each 16-bit word) / 1 (I010, ffmpeg's yuv420p10le: I420's plane
     order, the sample in the low 10 bits) for a 10-bit 4:2:0 pixel format; ValueError for anything else."""
-    if pixel_format not in YUV420_16_LAYOUT:
-        raise ValueError("pixel_format must be one of %s for 10-bit 4:2:0 frames, got %r (BT.601 limited-range P010 / I010 only)"
-                         % (tuple(YUV420_16_LAYOUT), pixel_format))
-    return YUV420_16_LAYOUT[pixel_format]
+    return _packed_format(pixel_format, torch.uint16).layout
 
 
 def yuv420_16_shape(frames, pixel_format, w_multiple=4):
     """(T, H, W) of packed 10-bit 4:2:0 frames (T, H * 3 // 2, W) uint16; ValueError unless H and W are even and W a multiple of
     ``w_multiple``."""
-    yuv420_16_layout(pixel_format)
-    if frames.dim() != 3 or frames.dtype != torch.uint16:
-        raise ValueError("%s frames must be uint16 (T, H * 3 // 2, W), got %s %s" % (pixel_format, frames.dtype, tuple(frames.shape)))
-    t, ph, w = frames.shape
-    if ph % 3 != 0 or ph == 0:
-        raise ValueError("%s frames: packed height %d is not H * 3 // 2 of an even H" % (pixel_format, ph))
-    h = ph // 3 * 2
-    if w % 2 != 0 or w % w_multiple != 0:
-        raise ValueError("%s frames: width %d must be even and a multiple of %d" % (pixel_format, w, w_multiple))
-    return t, h, w
+    return _packed_format(pixel_format, torch.uint16).frame_shape(frames, w_multiple)
 
 
 def upsample_grid_sample_yuv420_16(frames, field, pixel_format, align_corners=None, out=None, mode="bilinear"):
@@ -255,22 +315,8 @@ def upsample_grid_sample_yuv420_16(frames, field, pixel_format, align_corners=No
     (N, fh, fw, 2) resized (align_corners=True) to the plane's own size, bilinear in fp32 on the 10-bit values, taps outside a plane read
     BT.601 black (64 in Y, 512 in U and V), the blend is truncated and clamped to 0..1023.  H even, W % 4 == 0.  One kernel launch.
     mode = "bicubic": 16 taps per sample on the 10-bit values, clamped to 0..1023, then truncated; W >= 8."""
-    fn = _entry(mode, "yuv420_u16")
-    layout = yuv420_16_layout(pixel_format)
-    n, h, w = yuv420_16_shape(frames, pixel_format)   # (a tensor that is not uint16 is a ValueError, like a bad shape)
-    A.require_cuda(field)
-    A.require_cuda(frames, dtype=torch.uint16)
-    if field.dim() != 4 or field.shape[0] != n or field.shape[3] != 2:
-        raise ValueError("upsample_grid_sample_yuv420_16: field must be (%d, fh, fw, 2), got %s" % (n, tuple(field.shape)))
-    frames, field = frames.contiguous(), field.contiguous()
-    if out is None:
-        out = torch.empty_like(frames)
-    A.check(getattr(A.lib(), fn)(A.ptr(frames), A.ptr(field), A.ptr(out), n, h, w, field.shape[1], field.shape[2], layout,
-                                 _ac(align_corners), A.current_stream()), fn)
-    return out
-
-
-BORDERS = ("black", "keep")
+    _entry(mode, "yuv420_u16")   # (then the format's name, then shape and dtype -- a tensor that is not uint16 is a ValueError -- then require_cuda)
+    return warp(frames, field, _packed_format(pixel_format, torch.uint16), False, align_corners, out, mode)
 
 
 def keep_borders_(warped, field, initial, pixel_format="bgr24", initial_is_source=False, swap_rb=False, align_corners=None, mode="bilinear"):
@@ -287,17 +333,11 @@ def keep_borders_(warped, field, initial, pixel_format="bgr24", initial_is_sourc
         raise ValueError("mode must be one of %s, got %r" % (INTERPOLATIONS, mode))
     if not isinstance(warped, torch.Tensor) or warped.dtype not in (torch.uint8, torch.uint16):
         raise ValueError("keep_borders_: frames must be uint8 or uint16 (the integer pixel formats), got %s" % (getattr(warped, "dtype", type(warped)),))
-    if pixel_format == "bgr24":
-        if warped.dtype != torch.uint8 or warped.dim() != 4 or warped.shape[3] != 3:
-            raise ValueError("keep_borders_: bgr24 frames must be uint8 (T,H,W,3), got %s %s" % (warped.dtype, tuple(warped.shape)))
-        n, h, w = warped.shape[:3]
-        fn, extra = "pws_border_keep_u8", int(bool(swap_rb))
-    elif pixel_format in PIXEL_FORMATS_16:
-        n, h, w = yuv420_16_shape(warped, pixel_format)
-        fn, extra = "pws_border_keep_yuv420_u16", yuv420_16_layout(pixel_format)
-    else:
-        n, h, w = yuv420_shape(warped, pixel_format)   # (an unknown format, or a tensor that is not uint8, is a ValueError)
-        fn, extra = "pws_border_keep_yuv420_u8", yuv420_layout(pixel_format)
+    fmt = FRAME_FORMATS.get(pixel_format) or _packed_format(pixel_format, torch.uint8)   # (an unknown format is a ValueError)
+    if fmt.hwc and (warped.dtype != torch.uint8 or warped.dim() != 4 or warped.shape[3] != 3):
+        raise ValueError("keep_borders_: bgr24 frames must be uint8 (T,H,W,3), got %s %s" % (warped.dtype, tuple(warped.shape)))
+    n, h, w = fmt.frame_shape(warped)   # (packed frames: a tensor of the other depth's dtype is a ValueError)
+    fn = fmt.keep_entry
     A.require_cuda(field)
     A.require_cuda(warped, initial, dtype=warped.dtype)
     if not warped.is_contiguous():
@@ -308,7 +348,7 @@ def keep_borders_(warped, field, initial, pixel_format="bgr24", initial_is_sourc
         raise ValueError("keep_borders_: field must be (%d, fh, fw, 2), got %s" % (n, tuple(field.shape)))
     field, initial = field.contiguous(), initial.contiguous()
     A.check(getattr(A.lib(), fn)(A.ptr(warped), A.ptr(field), A.ptr(initial), int(bool(initial_is_source)), n, h, w, field.shape[1],
-                                 field.shape[2], extra, _ac(align_corners), int(mode == "bicubic"), A.current_stream()), fn)
+                                 field.shape[2], fmt.extra(swap_rb), _ac(align_corners), int(mode == "bicubic"), A.current_stream()), fn)
     return warped
 
 

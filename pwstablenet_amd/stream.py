@@ -22,22 +22,31 @@ from . import functional as PF
 from . import hipabi as A
 
 
+def _window_planes(frames, fmt, size, out, what, frames_are_rgb=False):
+    """The window planes of frames in the format ``fmt`` (functional.FrameFormat) in one launch: what window_planes, window_planes_yuv and
+    window_planes_yuv16 document.  The format's shape rules (ValueError, width a multiple of 2) come before host tensors or a wrong dtype."""
+    t, h, w = fmt.frame_shape(frames, w_multiple=2)
+    A.require_cuda(frames, dtype=fmt.dtype)
+    if fmt.hwc and frames.shape[3] != 3:
+        raise ValueError("%s: frames must be (T, H, W, 3) uint8, got %s" % (what, tuple(frames.shape),))
+    frames = frames.contiguous()
+    if out is None:
+        out = torch.empty((t, size, size), device=frames.device, dtype=torch.float32)
+    A.require_cuda(out)
+    if tuple(out.shape) != (t, size, size) or not out.is_contiguous():
+        raise ValueError("%s: out must be a contiguous (T, %d, %d) float32 tensor" % (what, size, size))
+    A.check(getattr(A.lib(), fmt.window_planes)(A.ptr(frames), A.ptr(out), t, h, w, size, size, 1, fmt.extra(frames_are_rgb), A.current_stream()),
+            fmt.window_planes)
+    return out
+
+
 def window_planes(frames_hwc, size=256, frames_are_rgb=False, out=None):
     """``cv2.resize(cv2.cvtColor(frame, COLOR_BGR2GRAY), (size, size), INTER_AREA) / 255 * 2 - 1`` for a batch of decoded
     frames (reference main_new.py:639-643,653-667) on the device: (T, H, W, 3) uint8 -> (T, size, size) float32."""
     A.require_cuda(frames_hwc, dtype=torch.uint8)
-    if frames_hwc.dim() != 4 or frames_hwc.shape[3] != 3:
+    if frames_hwc.dim() != 4:
         raise ValueError("window_planes: frames must be (T, H, W, 3) uint8, got %s" % (tuple(frames_hwc.shape),))
-    frames_hwc = frames_hwc.contiguous()
-    t, h, w, _ = frames_hwc.shape
-    if out is None:
-        out = torch.empty((t, size, size), device=frames_hwc.device, dtype=torch.float32)
-    A.require_cuda(out)
-    if tuple(out.shape) != (t, size, size) or not out.is_contiguous():
-        raise ValueError("window_planes: out must be a contiguous (T, %d, %d) float32 tensor" % (size, size))
-    A.check(A.lib().pws_gray_area_u8(A.ptr(frames_hwc), A.ptr(out), t, h, w, size, size, 1, int(bool(frames_are_rgb)),
-                                     A.current_stream()), "pws_gray_area_u8")
-    return out
+    return _window_planes(frames_hwc, PF.FRAME_FORMATS["bgr24"], size, out, "window_planes", frames_are_rgb)
 
 
 def area_half(frames_hwc, swap_rb=False):
@@ -69,18 +78,8 @@ def window_planes_yuv(frames, pixel_format, size=256, out=None):
     """window_planes of the BGR frames ``cv2.cvtColor(frame, COLOR_YUV2BGR_NV12 / COLOR_YUV2BGR_I420)`` would give, straight from packed
     4:2:0 frames (T, H * 3 // 2, W) uint8 in one launch (BT.601 limited range, OpenCV 4.x's 8-bit fixed point): the same planes bit for
     bit, so a YUV clip gets the fields of its BGR decode.  H and W even.  -> (T, size, size) float32."""
-    A.require_cuda(frames, dtype=torch.uint8)
-    layout = PF.yuv420_layout(pixel_format)
-    t, h, w = PF.yuv420_shape(frames, pixel_format, w_multiple=2)
-    frames = frames.contiguous()
-    if out is None:
-        out = torch.empty((t, size, size), device=frames.device, dtype=torch.float32)
-    A.require_cuda(out)
-    if tuple(out.shape) != (t, size, size) or not out.is_contiguous():
-        raise ValueError("window_planes_yuv: out must be a contiguous (T, %d, %d) float32 tensor" % (size, size))
-    A.check(A.lib().pws_gray_area_yuv420_u8(A.ptr(frames), A.ptr(out), t, h, w, size, size, 1, layout, A.current_stream()),
-            "pws_gray_area_yuv420_u8")
-    return out
+    A.require_cuda(frames, dtype=torch.uint8)   # (wins over the format's name and shape rules here, as it always has)
+    return _window_planes(frames, PF._packed_format(pixel_format, torch.uint8), size, out, "window_planes_yuv")
 
 
 def _yuv_planes(x, h, w, pixel_format):
@@ -88,30 +87,36 @@ def _yuv_planes(x, h, w, pixel_format):
     V (T, h/2, w/2)] for I420; P010 as NV12 and I010 as I420, in 16-bit words."""
     t = x.shape[0]
     y = x[:, :h]
-    if pixel_format in ("nv12", "p010"):
+    if PF.FRAME_FORMATS[pixel_format].layout == 0:
         return [y, x[:, h:]]
     c = x.reshape(t, -1)[:, h * w:].reshape(t, 2, h // 2, w // 2)
     return [y, c[:, 0], c[:, 1]]
+
+
+def _area_resize_yuv(frames, fmt, size, what):
+    """INTER_AREA plane by plane for packed 4:2:0 frames in the format ``fmt``: what area_resize_yuv and area_resize_yuv16 document."""
+    t, h, w = fmt.frame_shape(frames, w_multiple=2)
+    A.require_cuda(frames, dtype=fmt.dtype)
+    ow, oh = int(size[0]), int(size[1])
+    if ow % 2 or oh % 2 or not (0 < ow <= w and 0 < oh <= h):
+        raise ValueError("%s: output size %s must be even and within the %d x %d source" % (what, tuple(size), w, h))
+    frames = frames.contiguous()
+    out = torch.empty((t, oh * 3 // 2, ow), device=frames.device, dtype=fmt.dtype)
+    fs, os_ = frames[0].numel(), out[0].numel()   # (in samples)
+    geo = [(1, h, w, oh, ow)] + ([(2, h // 2, w // 2, oh // 2, ow // 2)] if fmt.layout == 0 else [(1, h // 2, w // 2, oh // 2, ow // 2)] * 2)
+    placement = (fmt.layout,) if fmt.dtype == torch.uint16 else ()   # (the 16-bit entry also takes where the 10 bits sit in a word)
+    for (c, ph, pw, qh, qw), src, dst in zip(geo, _yuv_planes(frames, h, w, fmt.name), _yuv_planes(out, oh, ow, fmt.name)):
+        A.check(getattr(A.lib(), fmt.plane_resize)(A.ptr(src), fs, A.ptr(dst), os_, t, ph, pw, c, qh, qw, *placement, A.current_stream()),
+                fmt.plane_resize)
+    return out
 
 
 def area_resize_yuv(frames, pixel_format, size):
     """area_resize for packed 4:2:0 frames, plane by plane: Y to (height, width), the chroma to (height/2, width/2) (NV12's interleaved UV
     as a 2-channel image, I420's U and V as 1-channel images); ``size`` = (width, height), both even.  (T, H * 3 // 2, W) uint8 ->
     (T, height * 3 // 2, width)."""
-    A.require_cuda(frames, dtype=torch.uint8)
-    PF.yuv420_layout(pixel_format)
-    t, h, w = PF.yuv420_shape(frames, pixel_format, w_multiple=2)
-    ow, oh = int(size[0]), int(size[1])
-    if ow % 2 or oh % 2 or not (0 < ow <= w and 0 < oh <= h):
-        raise ValueError("area_resize_yuv: output size %s must be even and within the %d x %d source" % (tuple(size), w, h))
-    frames = frames.contiguous()
-    out = torch.empty((t, oh * 3 // 2, ow), device=frames.device, dtype=torch.uint8)
-    fs, os_ = frames[0].numel(), out[0].numel()
-    geo = [(1, h, w, oh, ow)] + ([(2, h // 2, w // 2, oh // 2, ow // 2)] if pixel_format == "nv12" else [(1, h // 2, w // 2, oh // 2, ow // 2)] * 2)
-    for (c, ph, pw, qh, qw), src, dst in zip(geo, _yuv_planes(frames, h, w, pixel_format), _yuv_planes(out, oh, ow, pixel_format)):
-        A.check(A.lib().pws_area_resize_plane_u8(A.ptr(src), fs, A.ptr(dst), os_, t, ph, pw, c, qh, qw, A.current_stream()),
-                "pws_area_resize_plane_u8")
-    return out
+    A.require_cuda(frames, dtype=torch.uint8)   # (wins over the format's name and shape rules here, as it always has)
+    return _area_resize_yuv(frames, PF._packed_format(pixel_format, torch.uint8), size, "area_resize_yuv")
 
 
 def window_planes_yuv16(frames, pixel_format, size=256, out=None):
@@ -119,38 +124,14 @@ def window_planes_yuv16(frames, pixel_format, size=256, out=None):
     of a 10-bit frame is by definition the plane of its 8-bit reduction ``v8 = min(255, (v10 + 2) >> 2)``, fused into the kernel's loads (no
     8-bit copy of the frames): a P010 / I010 clip gets the fields of the NV12 / I420 clip of its reduced samples bit for bit.  H and W even.
     -> (T, size, size) float32."""
-    layout = PF.yuv420_16_layout(pixel_format)
-    t, h, w = PF.yuv420_16_shape(frames, pixel_format, w_multiple=2)
-    A.require_cuda(frames, dtype=torch.uint16)
-    frames = frames.contiguous()
-    if out is None:
-        out = torch.empty((t, size, size), device=frames.device, dtype=torch.float32)
-    A.require_cuda(out)
-    if tuple(out.shape) != (t, size, size) or not out.is_contiguous():
-        raise ValueError("window_planes_yuv16: out must be a contiguous (T, %d, %d) float32 tensor" % (size, size))
-    A.check(A.lib().pws_gray_area_yuv420_u16(A.ptr(frames), A.ptr(out), t, h, w, size, size, 1, layout, A.current_stream()),
-            "pws_gray_area_yuv420_u16")
-    return out
+    return _window_planes(frames, PF._packed_format(pixel_format, torch.uint16), size, out, "window_planes_yuv16")
 
 
 def area_resize_yuv16(frames, pixel_format, size):
     """area_resize_yuv for 10-bit frames, INTER_AREA plane by plane on the 10-bit values (P010's interleaved UV as a 2-channel image),
     clamped to 0..1023 and stored in the format's placement; ``size`` = (width, height), both even.  (T, H * 3 // 2, W) uint16 ->
     (T, height * 3 // 2, width)."""
-    layout = PF.yuv420_16_layout(pixel_format)
-    t, h, w = PF.yuv420_16_shape(frames, pixel_format, w_multiple=2)
-    A.require_cuda(frames, dtype=torch.uint16)
-    ow, oh = int(size[0]), int(size[1])
-    if ow % 2 or oh % 2 or not (0 < ow <= w and 0 < oh <= h):
-        raise ValueError("area_resize_yuv16: output size %s must be even and within the %d x %d source" % (tuple(size), w, h))
-    frames = frames.contiguous()
-    out = torch.empty((t, oh * 3 // 2, ow), device=frames.device, dtype=torch.uint16)
-    fs, os_ = frames[0].numel(), out[0].numel()   # (in 16-bit words)
-    geo = [(1, h, w, oh, ow)] + ([(2, h // 2, w // 2, oh // 2, ow // 2)] if layout == 0 else [(1, h // 2, w // 2, oh // 2, ow // 2)] * 2)
-    for (c, ph, pw, qh, qw), src, dst in zip(geo, _yuv_planes(frames, h, w, pixel_format), _yuv_planes(out, oh, ow, pixel_format)):
-        A.check(A.lib().pws_area_resize_plane_u16(A.ptr(src), fs, A.ptr(dst), os_, t, ph, pw, c, qh, qw, layout, A.current_stream()),
-                "pws_area_resize_plane_u16")
-    return out
+    return _area_resize_yuv(frames, PF._packed_format(pixel_format, torch.uint16), size, "area_resize_yuv16")
 
 
 def _yuv_crop(x, h, w, pixel_format, cy0, cy1, cx0, cx1):
@@ -160,12 +141,40 @@ def _yuv_crop(x, h, w, pixel_format, cy0, cy1, cx0, cx1):
     out = torch.empty((x.shape[0], ch * 3 // 2, cw), device=x.device, dtype=x.dtype)
     src, dst = _yuv_planes(x, h, w, pixel_format), _yuv_planes(out, ch, cw, pixel_format)
     dst[0].copy_(src[0][:, cy0:cy1, cx0:cx1])
-    if pixel_format in ("nv12", "p010"):
+    if len(src) == 2:
         dst[1].copy_(src[1][:, cy0 // 2:cy1 // 2, cx0:cx1])   # (U V interleaved: chroma columns cx0/2 .. are samples cx0 ..)
     else:
         for k in (1, 2):
             dst[k].copy_(src[k][:, cy0 // 2:cy1 // 2, cx0 // 2:cx1 // 2])
     return out
+
+
+def _output_resize(frames, fmt, size, half):
+    """run_video's resize of warped frames to ``size`` = (width, height); half: BGR's 2 x 2 kernel (the YUV planes take the general one)."""
+    if fmt.packed:
+        return _area_resize_yuv(frames, fmt, size, "run_video")
+    return area_half(frames) if half else area_resize(frames, size)
+
+
+def _frames_shape(fmt, n, h, w):
+    """The shape of n integer frames of h x w pixels in the format ``fmt``."""
+    return (n, h * 3 // 2, w) if fmt.packed else (n, h, w, 3)
+
+
+def _crop(frames, fmt, h, w, cy0, cy1, cx0, cx1):
+    """The window [cy0, cy1) x [cx0, cx1) of h x w frames, packed on the device: only the window crosses PCIe."""
+    return _yuv_crop(frames, h, w, fmt.name, cy0, cy1, cx0, cx1) if fmt.packed else frames[:, cy0:cy1, cx0:cx1, :].contiguous()
+
+
+def _prefetch(frames, s, e, stream, dev):
+    """frames[s:e] on the device and the event to wait for: device-resident frames are read in place (no event), host frames go up on ``stream``."""
+    if frames.is_cuda:
+        return frames[s:e], None
+    with torch.cuda.stream(stream):
+        buf = frames[s:e].to(dev, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(stream)
+    return buf, ev
 
 
 def _field_homography(field, h0, w0, m_out, bounds_out, pts_out=None):
@@ -253,6 +262,21 @@ def _scenes(n, cuts):
     return list(zip(edges[:-1], edges[1:]))
 
 
+def _bounds_rows(bounds, what):
+    """Per-frame bounds (a tensor on either side, an array or a sequence) as T rows of 4 floats."""
+    if isinstance(bounds, torch.Tensor):
+        bounds = bounds.detach().to("cpu", torch.float64).tolist()
+    bounds = [[float(v) for v in row] for row in bounds]
+    if any(len(row) != 4 for row in bounds):
+        raise ValueError("%s: bounds must be (T, 4): top, bottom, left, right" % what)
+    return bounds
+
+
+def _centred_window(k, h, w):
+    """The window (x0, x1, y0, y1) of the fraction k of an h x w frame around its centre (float64, in this order of operations)."""
+    return (0.5 * w - 0.5 * k * w, 0.5 * w + 0.5 * k * w, 0.5 * h - 0.5 * k * h, 0.5 * h + 0.5 * k * h)
+
+
 def auto_crop_window(bounds, frame_hw, output_hw=None, period=30, scene_cuts=None):
     """The reference's crop recurrence (main_new.py:575-603) over a clip's per-frame bounds (``field_homography``; (T, 4) top, bottom,
     left, right in source pixels, a tensor on either side or an array): the window starts at the whole H0 x W0 frame, and each frame i
@@ -262,11 +286,7 @@ def auto_crop_window(bounds, frame_hw, output_hw=None, period=30, scene_cuts=Non
     scene_cuts (sorted indices at which a new scene starts): the reference's end rule holds per scene -- frame i of scene [a, b) is read only
     if a + period//2 < i < b - period//2, since the frames next to a cut see a clamped window as those at the clip's ends do -- and the one
     window is carried from scene to scene (one output size serves the whole clip)."""
-    if isinstance(bounds, torch.Tensor):
-        bounds = bounds.detach().to("cpu", torch.float64).tolist()
-    bounds = [[float(v) for v in row] for row in bounds]
-    if any(len(row) != 4 for row in bounds):
-        raise ValueError("auto_crop_window: bounds must be (T, 4): top, bottom, left, right")
+    bounds = _bounds_rows(bounds, "auto_crop_window")
     h0, w0 = int(frame_hw[0]), int(frame_hw[1])
     T, half, rate = len(bounds), int(period) // 2, 0.5
     x0, x1, y0, y1 = 0.0, float(w0), 0.0, float(h0)
@@ -313,11 +333,7 @@ def zoom_schedule(bounds, frame_hw, speed=0.002, min_window=0.5, scene_cuts=None
     k[t] = min over s of kc[s] + speed |t - s|: the largest schedule that never exceeds kc and never changes by more than ``speed`` per frame
     (two linear sweeps).  scene_cuts: sorted indices at which a new scene starts; the schedule is free to jump there.  NaN bounds are a
     ValueError naming the frame.  Returns T windows (x0, x1, y0, y1) for ``zoom_fields`` / ``run(zoom=)``.  Host arithmetic, float64."""
-    if isinstance(bounds, torch.Tensor):
-        bounds = bounds.detach().to("cpu", torch.float64).tolist()
-    bounds = [[float(v) for v in row] for row in bounds]
-    if any(len(row) != 4 for row in bounds):
-        raise ValueError("zoom_schedule: bounds must be (T, 4): top, bottom, left, right")
+    bounds = _bounds_rows(bounds, "zoom_schedule")
     h0, w0 = int(frame_hw[0]), int(frame_hw[1])
     speed, min_window = float(speed), float(min_window)
     if not (speed >= 0.0 and 0.0 < min_window <= 1.0):
@@ -336,7 +352,7 @@ def zoom_schedule(bounds, frame_hw, speed=0.002, min_window=0.5, scene_cuts=None
             k[t] = min(k[t], k[t - 1] + speed)
         for t in range(b - 2, a - 1, -1):
             k[t] = min(k[t], k[t + 1] + speed)
-    return [(0.5 * w0 - 0.5 * v * w0, 0.5 * w0 + 0.5 * v * w0, 0.5 * h0 - 0.5 * v * h0, 0.5 * h0 + 0.5 * v * h0) for v in k]
+    return [_centred_window(v, h0, w0) for v in k]
 
 
 def _windows(gray_padded, start, count, period):
@@ -464,14 +480,7 @@ class VideoStabilizer:
             raise ValueError("run: zoom removes the wedges that borders=\"keep\" fills: choose one")
         if keep and frames.dtype not in (torch.uint8, torch.uint16):
             raise ValueError("run: borders=\"keep\" is for the integer pixel formats (uint8 / uint16 frames), got %s" % (frames.dtype,))
-        yuv = pixel_format != "bgr24"
-        yuv16 = pixel_format in PF.PIXEL_FORMATS_16
-        if yuv16:
-            PF.yuv420_16_shape(frames, pixel_format)
-        elif yuv:
-            PF.yuv420_shape(frames, pixel_format)
-        elif frames.dtype == torch.uint16:
-            raise ValueError("run: uint16 frames need pixel_format \"p010\" or \"i010\", got %r" % (pixel_format,))
+        fmt = PF.frame_format(pixel_format, frames, "run", float_frames=True)   # (from here on the format is this record)
         if not (0 <= halo_left <= half and 0 <= halo_right <= half):
             raise ValueError("halo must be within [0, %d]" % half)
         T = frames.shape[0]
@@ -484,8 +493,7 @@ class VideoStabilizer:
         if out is None:
             out = torch.empty_like(frames, pin_memory=on_host) if on_host else torch.empty_like(frames)
         if zoom is not None or rigid:
-            frame_hw = (PF.yuv420_16_shape(frames, pixel_format) if yuv16 else PF.yuv420_shape(frames, pixel_format))[1:] if yuv else (
-                tuple(frames.shape[1:3]) if frames.dtype == torch.uint8 else tuple(frames.shape[2:4]))
+            frame_hw = fmt.frame_shape(frames)[1:]
         if rigid:
             _check_lattice(int(frame_hw[0]), int(frame_hw[1]), "rigidity > 0")
         if _rigid_stats is not None:   # run_video's, a slice per chunk: it publishes the whole tensors itself, once every chunk is issued
@@ -504,15 +512,7 @@ class VideoStabilizer:
         h2d, d2h = (torch.cuda.Stream(dev), torch.cuda.Stream(dev)) if on_host else (None, None)
 
         def fetch(k):
-            s, e, _ = batches[k]
-            if not on_host:
-                return frames[s:e], None
-            with torch.cuda.stream(h2d):
-                buf = frames[s:e].to(dev, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(h2d)
-            return buf, ev
-
+            return _prefetch(frames, batches[k][0], batches[k][1], h2d, dev)
         nxt = fetch(0)
         pending = []
         cutset, prev = set(cuts or ()), None
@@ -535,14 +535,7 @@ class VideoStabilizer:
                 field = field.contiguous()
                 field = PF._field_zoom(field, zcoef[s:e], frame_hw, self.align_corners, self.interpolation, torch.empty_like(field),
                                        self.zoom_uncovered[s:e])
-            if yuv16:
-                warped = PF.upsample_grid_sample_yuv420_16(cur.contiguous(), field, pixel_format, align_corners=self.align_corners, mode=self.interpolation)
-            elif yuv:
-                warped = PF.upsample_grid_sample_yuv420(cur.contiguous(), field, pixel_format, align_corners=self.align_corners, mode=self.interpolation)
-            elif cur.dtype == torch.uint8:
-                warped = PF.upsample_grid_sample_u8(cur.contiguous(), field, swap_rb=self.swap_rb, align_corners=self.align_corners, mode=self.interpolation)
-            else:
-                warped = PF.upsample_grid_sample(cur.contiguous(), field, align_corners=self.align_corners, mode=self.interpolation)
+            warped = PF.warp(cur.contiguous(), field, fmt, swap_rb=self.swap_rb, align_corners=self.align_corners, mode=self.interpolation)
             if keep:
                 if (s + halo_left) in cutset or (s == 0 and keep_from is None):
                     init, src = cur.contiguous()[0], True   # a scene's first frame: its own source, as the warp would write it
@@ -553,8 +546,8 @@ class VideoStabilizer:
                         compute.wait_event(_keep_wait)
                     keep_from.record_stream(compute)
                     init, src = keep_from, False
-                PF.keep_borders_(warped, field, init, pixel_format, initial_is_source=src, swap_rb=self.swap_rb and not yuv,
-                                 align_corners=self.align_corners, mode=self.interpolation)
+                PF.keep_borders_(warped, field, init, pixel_format, initial_is_source=src, swap_rb=self.swap_rb, align_corners=self.align_corners,
+                                 mode=self.interpolation)
                 prev = warped[-1]   # (a view: keeps the batch alive until the next one has read it)
             if on_host:
                 done = torch.cuda.Event()
@@ -667,16 +660,11 @@ class VideoStabilizer:
             raise ValueError("frames holds %d frames, fewer than the halos %d + %d" % (n_all, halo_left, halo_right))
         on_host = not frames.is_cuda
         dev = self.device
-        yuv = pixel_format != "bgr24"
-        yuv16 = pixel_format in PF.PIXEL_FORMATS_16
-        if yuv:
-            _, h, w = PF.yuv420_16_shape(frames, pixel_format) if yuv16 else PF.yuv420_shape(frames, pixel_format)
-            if frames_are_rgb:
-                raise ValueError("run_video: frames_are_rgb has no meaning for %s frames" % pixel_format)
-        else:
-            if frames.dtype == torch.uint16:
-                raise ValueError("run_video: uint16 frames need pixel_format \"p010\" or \"i010\", got %r" % (pixel_format,))
-            h, w = frames.shape[1], frames.shape[2]
+        fmt = PF.frame_format(pixel_format, frames, "run_video")   # (from here on the format is this record)
+        yuv = fmt.packed   # even output sizes and crop edges
+        h, w = fmt.frame_shape(frames)[1:]
+        if yuv and frames_are_rgb:
+            raise ValueError("run_video: frames_are_rgb has no meaning for %s frames" % pixel_format)
         if output_size is not None and half_size_output:
             raise ValueError("run_video: give output_size or half_size_output, not both")
         if output_size is not None:
@@ -724,7 +712,7 @@ class VideoStabilizer:
                 if not 0.0 < zk <= 1.0:
                     raise ValueError("zoom: the fraction of the frame must lie in (0, 1], got %r" % (zoom,))
                 zmode = "fixed"
-                zwin = (0.5 * w - 0.5 * zk * w, 0.5 * w + 0.5 * zk * w, 0.5 * h - 0.5 * zk * h, 0.5 * h + 0.5 * zk * h)
+                zwin = _centred_window(zk, h, w)
         two_pass = auto or zmode in ("auto", "adaptive")   # pass 1: fields and bounds; the host's decision; pass 2: the warp
         detect = isinstance(scene_cuts, str)
         if detect and scene_cuts != "auto":
@@ -746,7 +734,7 @@ class VideoStabilizer:
             return cy0, cy1, cx0, cx1
 
         def alloc_out():
-            oshape = (T, (cy1 - cy0) * 3 // 2, cx1 - cx0) if yuv else (T, cy1 - cy0, cx1 - cx0, 3)
+            oshape = _frames_shape(fmt, T, cy1 - cy0, cx1 - cx0)
             return torch.empty(oshape, dtype=frames.dtype, pin_memory=True) if on_host else torch.empty(oshape, dtype=frames.dtype, device=dev)
         cy0, cy1, cx0, cx1 = crop_window(None if auto else crop)
         out = None if auto and T > 0 else alloc_out()
@@ -789,12 +777,7 @@ class VideoStabilizer:
             s, e = chunks[c]
             with torch.cuda.stream(up):
                 buf = frames[s:e].to(dev, non_blocking=True) if on_host else frames[s:e]
-                if yuv16:
-                    window_planes_yuv16(buf, pixel_format, 256, out=gray_all[s:e])
-                elif yuv:
-                    window_planes_yuv(buf, pixel_format, 256, out=gray_all[s:e])
-                else:
-                    window_planes(buf, 256, frames_are_rgb, out=gray_all[s:e])
+                _window_planes(buf, fmt, 256, gray_all[s:e], "run_video", frames_are_rgb)
                 ev = torch.cuda.Event()
                 ev.record(up)
                 if detect:   # same stream: ordered behind the planes (and behind the previous chunk's, whose last plane it reads)
@@ -821,18 +804,10 @@ class VideoStabilizer:
 
         def finish(warped, buf, s, e, lane):
             """output resize + crop of the warped core frames s .. e-1 (output positions) on `lane`, and their way to `out`"""
-            if yuv:
-                if (oh, ow) != (h, w):
-                    warped = (area_resize_yuv16 if yuv16 else area_resize_yuv)(warped, pixel_format, (ow, oh))
-                if crop is not None:
-                    warped = _yuv_crop(warped, oh, ow, pixel_format, cy0, cy1, cx0, cx1)   # packed on the device: only the window crosses PCIe
-            else:
-                if half_size_output:
-                    warped = area_half(warped)
-                elif output_size is not None and (oh, ow) != (h, w):
-                    warped = area_resize(warped, (ow, oh))
-                if crop is not None:
-                    warped = warped[:, cy0:cy1, cx0:cx1, :].contiguous()   # packed on the device: only the window crosses PCIe
+            if (oh, ow) != (h, w):
+                warped = _output_resize(warped, fmt, (ow, oh), half_size_output)
+            if crop is not None:
+                warped = _crop(warped, fmt, oh, ow, cy0, cy1, cx0, cx1)
             if on_host:
                 buf.record_stream(lane)
                 done = torch.cuda.Event()
@@ -920,14 +895,7 @@ class VideoStabilizer:
             # pass 2: [zoom +] warp + output resize + crop with the kept fields; chunk k+1 uploads while chunk k computes
 
             def fetch(c):
-                s, e = chunks[c]
-                if not on_host:
-                    return frames[s:e], None
-                with torch.cuda.stream(up):
-                    buf = frames[s:e].to(dev, non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(up)
-                return buf, ev
+                return _prefetch(frames, chunks[c][0], chunks[c][1], up, dev)
             nxt = fetch(0)
             for c, (s, e) in enumerate(chunks):
                 buf, ev = nxt
@@ -938,12 +906,7 @@ class VideoStabilizer:
                 fld = fields[s:e]
                 if zmode is not None:
                     fld = PF._field_zoom(fld, zcoef[s:e], (h, w), self.align_corners, self.interpolation, torch.empty_like(fld), zunc[s:e])
-                if yuv16:
-                    warped = PF.upsample_grid_sample_yuv420_16(buf.contiguous(), fld, pixel_format, align_corners=self.align_corners, mode=self.interpolation)
-                elif yuv:
-                    warped = PF.upsample_grid_sample_yuv420(buf.contiguous(), fld, pixel_format, align_corners=self.align_corners, mode=self.interpolation)
-                else:
-                    warped = PF.upsample_grid_sample_u8(buf.contiguous(), fld, swap_rb=self.swap_rb, align_corners=self.align_corners, mode=self.interpolation)
+                warped = PF.warp(buf.contiguous(), fld, fmt, swap_rb=self.swap_rb, align_corners=self.align_corners, mode=self.interpolation)
                 finish(warped, buf, s, e, compute)
         if on_host:
             down.synchronize()
