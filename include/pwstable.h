@@ -63,7 +63,9 @@ extern "C" {
 
 #define PWS_VERSION 5   /* 2: pws_netg_opts carries flags + x_sample_stride (round 3); 4: dpacked is the compact gradient slab
                           (pws_netg_grad_floats / pws_netg_grad_layout), pws_netg_backward_lists (round 4); 5: pws_netg_backward_plan,
-                          pws_netg_pack_weights_train (round 5; additions only) */
+                          pws_netg_pack_weights_train (round 5; additions only).  Later additions that change no existing entry
+                          point or struct keep the version: the warps' and stabiliser's entries, pws_conv2d_fwd_plan / _bwd_data_plan /
+                          pws_netg_forward_plan */
 
 #define PWS_OK 0
 #define PWS_EINVAL (-22) /* bad argument / unsupported shape */
@@ -258,6 +260,32 @@ typedef struct pws_conv_bwd_data_args {
     int store;         /* PWS_STORE_BF16: gout and every dst[].ptr hold bf16 elements (accumulation rounds to bf16) */
 } pws_conv_bwd_data_args;
 int pws_conv2d_bwd_data(const pws_conv_bwd_data_args *args, pws_stream_t stream);
+
+/* ---------------------------------------------------------------- which kernel a conv call runs (host only, no GPU needed)
+ * One conv launch as the dispatch ladder decides it (pwstablenet_amd/csrc/conv_dispatch.hip): the record a plan call reports is the
+ * record the launching call acts on -- grid, workgroup and LDS are computed once, by the plan step of the chosen kernel family. */
+#define PWS_FOLLOW_NONE 0
+#define PWS_FOLLOW_REDUCE 1 /* splitk_reduce_kernel adds the K splits' partial sums (and runs the epilogue) */
+#define PWS_FOLLOW_SIGN 2   /* sign_bits_kernel writes pws_conv_args.out_sign behind the launch(es) */
+typedef struct pws_conv_choice {
+    int kernel_id;    /* index for pws_prof_kernel_name() */
+    int variant[4];   /* what the family's template switch keys on, unused entries 0.  Tiled kernels (conv_mfma_kernel, conv_bf16_kernel):
+                         tile index of the candidate table (deep tiles: 8 + index), TH, TW, TN.  conv_ring_kernel: mode, pixels per unit,
+                         tile width, sign-bit epilogue.  conv_ringf_kernel: mode, tile height, channels per unit / 32, half workgroups.
+                         wino_ring_kernel: mode, 16-wide units, ablation.  One-shot kernels: pixel tiles, channel tiles and waves along M
+                         per workgroup, taps held.  wino_kernel: mode. */
+    unsigned grid[3];
+    int threads;      /* workgroup size */
+    int lds_bytes;    /* dynamic LDS of the launch */
+    int ksplit;       /* K splits (1 = none) */
+    int follow;       /* PWS_FOLLOW_* bits */
+    int tag;          /* pws_netg_forward_plan: the layer index; else 0 */
+} pws_conv_choice;
+/* What pws_conv2d_fwd / pws_conv2d_bwd_data would launch for `args` on a device of `compute_units` CUs: same argument checks, same
+ * return codes, no launch and no HIP call.  Pointers are inspected for NULL and alignment only, never dereferenced.  n == 0: PWS_OK and
+ * kernel_id -1.  PWS_OPT_EXPERIMENT switches act as they do on a launch. */
+int pws_conv2d_fwd_plan(const pws_conv_args *args, int compute_units, pws_conv_choice *out);
+int pws_conv2d_bwd_data_plan(const pws_conv_bwd_data_args *args, int compute_units, pws_conv_choice *out);
 
 typedef struct pws_conv_bwd_weight_args {
     int kind;          /* K3S1 | K3S2 | K5S1 | CONVT_K3S1 | CONVT_K4S2 */
@@ -647,6 +675,13 @@ typedef struct pws_netg_opts {
 int pws_netg_forward_opts(const float *packed, const float *x, int n, int input_nc, int ngf, int is_training, int align_corners,
                           void *ws, size_t ws_bytes, float *grids, float *resid, float *thetas, const pws_netg_opts *opts,
                           pws_stream_t stream);
+/* The conv launches pws_netg_forward_opts would issue for this configuration on a device of `compute_units` CUs, in issue order:
+ * one pws_conv_choice per conv launch (tag = layer index; the heads are not conv launches) into out[0 .. max).  Walks the forward's
+ * graph over a fixed 256-byte aligned stand-in for arena, weights and window (the alignment the real call requires) and asks the
+ * dispatch ladder without launching: no HIP call, no stream, no event.  Returns the number of conv launches (may exceed max) or a
+ * negative error.  out may be NULL when max == 0. */
+int pws_netg_forward_plan(int n, int input_nc, int ngf, int is_training, const pws_netg_opts *opts, int compute_units,
+                          pws_conv_choice *out, int max);
 
 /* ---- training: backward of the whole generator (is_training=1 forward must have run on the SAME ws, untouched since).
  * Data-gradient weights: a second packed buffer (pws_netg_packed_dgrad_floats) filled by pws_netg_pack_weights_dgrad.

@@ -59,6 +59,32 @@ struct PerDeviceInt {
     int v[kMaxDevices] = {};
     int &cur() { return v[current_device_slot()]; }
 };
+// Compute units of the current device (queried once per device; 256 when the query fails): what the persistent kernels size their grids by.
+inline int device_cus() {
+    static PerDeviceInt ncu_dev;
+    int &ncu = ncu_dev.cur();
+    if (ncu == 0) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
+    }
+    return ncu;
+}
+// Dynamic-LDS opt-in of one kernel, once per device.  `what` names the kernel in the error text; `say_bytes`: the text carries the size.
+template <auto Kernel>
+inline int lds_attr_once(int bytes, const char *what, bool say_bytes = true) {
+    static PerDeviceFlag attr_set_dev;
+    bool &attr_set = attr_set_dev.cur();   // hipFuncSetAttribute acts on the CURRENT device's function object
+    if (attr_set) return PWS_OK;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) {
+        if (say_bytes) set_error("hipFuncSetAttribute(%s, %d B LDS): %s", what, bytes, hipGetErrorString(e));
+        else set_error("hipFuncSetAttribute(%s): %s", what, hipGetErrorString(e));
+        return PWS_EHIP;
+    }
+    attr_set = true;
+    return PWS_OK;
+}
 
 #if defined(__HIPCC__)
 // a * b rounded to fp32 as a value of its own.  hipcc's default -ffp-contract=fast fuses a product into the add / subtract that
@@ -106,11 +132,20 @@ struct ProfScope {  // brackets one launch with events when profiling is enabled
     }
 };
 
+// One conv call's context on its way down the dispatch ladder (conv_dispatch.hip; the families: conv_common.h): where to launch, the CU
+// count the persistent kernels size themselves by, whether to launch at all, and where to report what was chosen.
+using ConvChoice = pws_conv_choice;
+struct ConvCtx {
+    hipStream_t stream;
+    int compute_units;
+    bool launch;          // false: plan only -- no HIP call of any kind
+    ConvChoice *report;   // nullable; its tag is the caller's
+};
+int conv2d_fwd_impl(const pws_conv_args *a, const ConvCtx &cx);             // conv_dispatch.hip
+int conv2d_bwd_data_impl(const pws_conv_bwd_data_args *a, const ConvCtx &cx);
+
 int nchw_to_nhwc_pad_strided(const float *x, size_t sample_stride, float *out, int n, int c, int h, int w, int cpad, int store, hipStream_t st);   // conv_bf16.hip
 
-struct ProfHint {
-    double flops, bytes;
-};
 // use_BN training path: pieces of the two heads sequenced by netg_exec.h / netg_backward.cpp (head.hip / head_bwd.hip)
 int theta_z1(const float *x, int n, int c, int hidden, const float *w_flat, const float *b_flat, float *ws, float *z1, hipStream_t st);
 int theta_z2(const float *h, int n, int hidden, const float *w_lin, const float *b_lin, float *z2, hipStream_t st);
@@ -123,10 +158,8 @@ int field_bwd_dx_dw(const float *x, int ld, const float *gz, int n, int h, int w
 int theta_bwd_bn_lin(const float *dz2, const float *h, int n, int hidden, const float *w_lin, float *dw_lin, float *dh, hipStream_t st);
 int theta_bwd_flat(const float *x, int n, int c, int hidden, const float *w_flat, const float *dz1, float *dw_flat, float *dx,
                    int dx_accumulate, hipStream_t st);
-int wino_k3s1_launch(const pws_conv_args *a, const ProfHint &ph, hipStream_t st);  // conv_wino.hip
 // conv_wring.hip: Winograd on the persistent LDS ring (F(2x2,3x3) for the 3x3 stride-1 kinds, F(2x2,2x2) per parity class for the
 // transposed k4 s2 kind); weights = pws_conv_args.w_wring (pws_pack_conv_weight_wring).
-int wring_try(const pws_conv_args *a, const ProfHint &ph, hipStream_t st);   // 1: not covered
 int wring_pack(const float *pk, float *ur, int cin_pad, int cout, int ct4, hipStream_t st);
 // Ring layout [32-channel block][16-channel chunk][component xi][nt][kq][co16][st]: co = 32 block + 2 co16 + nt,
 // ci = 16 chunk + 4 kq + st -- one (block, chunk) is NC x 2 KB contiguous, and inside it a 1 KB run is one lane-linear B-operand

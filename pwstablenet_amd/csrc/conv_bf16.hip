@@ -596,43 +596,29 @@ __global__ void __launch_bounds__(256) cvt_f32_to_bf16_kernel(const float *__res
 
 // ------------------------------------------------------------------------------------------------ host side
 template <class C, bool IO16>
-static int launch_bf_io(ConvKParams &kp, hipStream_t st) {
-    static PerDeviceFlag attr_set_dev;
-    bool &attr_set = attr_set_dev.cur();   // hipFuncSetAttribute acts on the CURRENT device's function object
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_bf16_kernel<C, IO16>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(conv_bf16_kernel, %d B LDS): %s", C::LDS_BYTES, hipGetErrorString(e));
-            return PWS_EHIP;
-        }
-        attr_set = true;
-    }
-    const dim3 grid = conv_grid(kp, C::BN);
+static int launch_bf_io(const ConvKParams &kp, const ConvChoice &c, hipStream_t st) {
 #ifdef PWS_INTERFERENCE_PROBE   // diagnostic build only (round 5: the six probe instantiations are no longer part of the shipped library; -DPWS_INTERFERENCE_PROBE brings them back for tools/probes/kernel_victim_probe.py)
     if constexpr (IO16 && C::KS == 3 && C::TH == 16 && C::TW == 16 && C::STRIDE == 1 && C::SUBPIX == 0) {   // the probe variants of this one tile (see conv_bf16_kernel)
         switch (exp_mask(EXP_BF16_PROBE, 64)) {
-#define PWS_BF_ABL_CASE(k) case k: (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_bf16_kernel<C, IO16, k>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES); hipLaunchKernelGGL((conv_bf16_kernel<C, IO16, k>), grid, dim3(C::THREADS), C::LDS_BYTES, st, kp); return check_launch("conv_bf16_kernel");
+#define PWS_BF_ABL_CASE(k) case k: return launch_planned<&conv_bf16_kernel<C, IO16, k>>(kp, c, st, "conv_bf16_kernel");
             PWS_BF_ABL_CASE(1) PWS_BF_ABL_CASE(14) PWS_BF_ABL_CASE(16) PWS_BF_ABL_CASE(30) PWS_BF_ABL_CASE(32) PWS_BF_ABL_CASE(46)
         default: break;
         }
     }
 #endif
-    hipLaunchKernelGGL((conv_bf16_kernel<C, IO16>), grid, dim3(C::THREADS), C::LDS_BYTES, st, kp);
-    return check_launch("conv_bf16_kernel");
+    return launch_planned<&conv_bf16_kernel<C, IO16>>(kp, c, st, "conv_bf16_kernel");
 }
 
 // C: configuration for fp32 storage; CS: same tile with 64 channels per wave, used for bf16 storage (may be C itself)
 template <class C, class CS>
-static int launch_bf(ConvKParams &kp, hipStream_t st, const ProfInfo &) {
-    static_assert(C::TH == CS::TH && C::TW == CS::TW && C::TN == CS::TN && C::CK == CS::CK, "same tile");
-    if (kp.io_bf16) return launch_bf_io<CS, true>(kp, st);
-    return launch_bf_io<C, false>(kp, st);
+static int launch_bf(const ConvKParams &kp, const ConvChoice &c, hipStream_t st) {
+    return kp.io_bf16 ? launch_bf_io<CS, true>(kp, c, st) : launch_bf_io<C, false>(kp, c, st);
 }
 
 template <class C, class CS = C>
 static constexpr TileChoice bchoice() {
-    return TileChoice{C::TH, C::TW, C::TN, C::CK, C::BN, KID_CONV_BF16, &launch_bf<C, CS>};
+    static_assert(C::TH == CS::TH && C::TW == CS::TW && C::TN == CS::TN && C::CK == CS::CK && C::BN == CS::BN, "same tile");
+    return TileChoice{C::TH, C::TW, C::TN, C::CK, C::BN, KID_CONV_BF16, {{C::THREADS, C::LDS_BYTES}, {CS::THREADS, CS::LDS_BYTES}}, &launch_bf<C, CS>};
 }
 
 // (*_S: the 64-pixel tiles with 2 waves x 64 channels instead of 4 waves x 32: what the bf16-storage epilogue needs)
@@ -725,62 +711,28 @@ static const TileChoice *deep_tile(const TileChoice *deep, const ConvKParams &kp
 
 using B_K5S1_T256 = BfCfg<5, 1, 2, 0, 16, 16, 1, 32, 4, 1, 2, 2>;
 
-static int launch_k5(ConvKParams &kp, hipStream_t st, const ProfInfo &pi) {
+// The tiled kernels take whatever the ring and the one-shot kernel left: the deep tile where it wins, else the kind's table.
+static void plan_bf16_tiles(const TileChoice *deep, const TileChoice *cands, int ncand, ConvKParams &kp, int kchan, float *final_out, float *ws,
+                            size_t ws_floats, const TileChoice **tile, ConvChoice *c) {
+    if (const TileChoice *d = deep ? deep_tile(deep, kp, kchan) : nullptr)
+        *tile = plan_tiles(d, 1, kp, kchan, final_out, ws, ws_floats, kFillBlocksBf16, 8 + (int)(d - deep), c);
+    else
+        *tile = plan_tiles(cands, ncand, kp, kchan, final_out, ws, ws_floats, kFillBlocksBf16, 0, c);
+}
+
+// the first layer as one NHWC source (conv_bf16_k5_kernel): one tile shape, no K split
+static void plan_k5(ConvKParams &kp, float *out, ConvChoice *c) {
     using C = B_K5S1_T256;
-    static PerDeviceFlag attr_set_dev;
-    bool &attr_set = attr_set_dev.cur();   // hipFuncSetAttribute acts on the CURRENT device's function object
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_bf16_k5_kernel<C, false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, K5Lds<C>::BYTES);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_bf16_k5_kernel<C, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, K5Lds<C>::BYTES);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(conv_bf16_k5_kernel): %s", hipGetErrorString(e));
-            return PWS_EHIP;
-        }
-        attr_set = true;
-    }
+    kp.out = out;
     kp.tiles_x = (kp.LW + C::TW - 1) / C::TW, kp.tiles_y = (kp.LH + C::TH - 1) / C::TH;
     kp.ntiles = (unsigned)(kp.tiles_x * kp.tiles_y * kp.N);
     kp.ksplit = 1, kp.chunks_per_split = 0, kp.split_stride = 0;
-    ProfScope prof(KID_CONV_BF16, pi.flops, pi.bytes, st);
-    const dim3 grid(kp.ntiles, (kp.cout + C::BN - 1) / C::BN);
-    if (kp.io_bf16)
-        hipLaunchKernelGGL((conv_bf16_k5_kernel<C, true>), grid, dim3(C::THREADS), K5Lds<C>::BYTES, st, kp);
-    else
-        hipLaunchKernelGGL((conv_bf16_k5_kernel<C, false>), grid, dim3(C::THREADS), K5Lds<C>::BYTES, st, kp);
-    return check_launch("conv_bf16_k5_kernel");
+    *c = conv_choice(KID_CONV_BF16, 16, C::TH, C::TW, C::TN, dim3(kp.ntiles, (kp.cout + C::BN - 1) / C::BN), C::THREADS, K5Lds<C>::BYTES);
 }
-
-// Forward kinds.  kp is fully prepared by conv2d_fwd_impl (conv_mfma.hip); returns 1 when this launch is not covered by
-// the bf16 kernels (the caller then runs the fp32 path), else the launch status.
-int conv_ring_try(int kind, bool dgrad, const ConvKParams &kp, hipStream_t st, const ProfInfo &pi);   // conv_ring.hip; 1 = not covered
-int conv_skinny16_try(int kind, bool dgrad, ConvKParams &kp, int kchan, float *final_out, float *ws, size_t ws_floats, hipStream_t st,
-                      const ProfInfo &pi);   // conv_skinny16.hip (the deep levels, bf16 storage); 1 = not covered
-
-static int conv_bf16_fwd_rest(int kind, ConvKParams &kp, int cin_total, float *out, float *ws, size_t ws_floats, hipStream_t st,
-                              const ProfInfo &pi, bool *tiled) {
-    if (kind != PWS_CONV_K5S1) {
-        const int rc = conv_skinny16_try(kind, false, kp, cin_total, out, ws, ws_floats, st, pi);
-        if (rc != 1) return rc;
-    }
-    *tiled = true;
-    switch (kind) {
-    case PWS_CONV_K3S1:
-    case PWS_CONVT_K3S1:
-        if (const TileChoice *d = deep_tile(kBK3S1Deep, kp, cin_total)) return select_and_launch(d, 1, kp, cin_total, out, ws, ws_floats, st, pi, kFillBlocksBf16);
-        return select_and_launch(kBK3S1, 5, kp, cin_total, out, ws, ws_floats, st, pi, kFillBlocksBf16);
-    case PWS_CONV_K3S2: return select_and_launch(kBK3S2, 5, kp, cin_total, out, ws, ws_floats, st, pi, kFillBlocksBf16);
-    case PWS_CONVT_K4S2:
-        if (const TileChoice *d = deep_tile(kBCT4Deep, kp, cin_total)) return select_and_launch(d, 1, kp, cin_total, out, ws, ws_floats, st, pi, kFillBlocksBf16);
-        return select_and_launch(kBCT4, 5, kp, cin_total, out, ws, ws_floats, st, pi, kFillBlocksBf16);
-    case PWS_CONV_K5S1:
-        if (kp.nsrc != 1) return 1;
-        kp.out = out;
-        return launch_k5(kp, st, pi);
-    default: return 1;
-    }
+static int run_k5(const ConvKParams &kp, const ConvChoice &c, hipStream_t st) {
+    using C = B_K5S1_T256;
+    if (kp.io_bf16) return launch_planned<&conv_bf16_k5_kernel<C, true>>(kp, c, st, "conv_bf16_k5_kernel", 0, false);
+    return launch_planned<&conv_bf16_k5_kernel<C, false>>(kp, c, st, "conv_bf16_k5_kernel", 0, false);
 }
 
 // Sign bits of a bf16 NHWC tensor (ConvKParams.out_sign) for the forward kernels that do not write them themselves: one lane per
@@ -797,45 +749,68 @@ __global__ void __launch_bounds__(256) sign_bits_kernel(const __bf16 *__restrict
     sign[pix * (size_t)sign_ld + g] = (unsigned char)m;
 }
 
-int conv_bf16_fwd(int kind, ConvKParams &kp, int cin_total, float *out, float *ws, size_t ws_floats, hipStream_t st,
-                  const ProfInfo &pi) {
-    for (int s = 0; s < kp.nsrc; ++s)
-        if (kp.src_c[s] % 32 != 0) return 1;
-    {   // the persistent LDS-ring kernel takes the launches it covers (bf16 storage, maps >= 16 x 32; round 6: the first layer too)
-        kp.out = out;
-        const int rc = conv_ring_try(kind, false, kp, st, pi);   // (writes kp.out_sign itself)
-        if (rc != 1) return rc;
-    }
-    bool tiled = false;   // conv_bf16_kernel / conv_bf16_k5_kernel ran (not the one-shot kernel)
-    const int rc = conv_bf16_fwd_rest(kind, kp, cin_total, out, ws, ws_floats, st, pi, &tiled);
-    if (rc != PWS_OK || !kp.out_sign || !kp.io_bf16) return rc;
-    if (tiled && kp.epi16 && kp.ksplit <= 1) return rc;   // its 16-byte epilogue wrote the sign bytes (no split-K reduce in between)
+static int run_sign_bits(const ConvKParams &kp, const float *out, hipStream_t st) {
     const size_t pixels = (size_t)kp.N * kp.OH * kp.OW, items = pixels * (size_t)(kp.cout / 8);
     hipLaunchKernelGGL(sign_bits_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const __bf16 *>(out), kp.out_ld, pixels,
                        kp.cout / 8, static_cast<unsigned char *>(kp.out_sign), kp.out_sign_ld);
     return check_launch("sign_bits_kernel");
 }
 
-// Data-gradient kinds (kp prepared by conv2d_bwd_data_impl).
-int conv_bf16_dgrad(int kind, ConvKParams &kp, int cout_f, float *ws, size_t ws_floats, hipStream_t st, const ProfInfo &pi) {
-    if (cout_f % 32 != 0) return 1;
-    {
-        int rc = conv_ring_try(kind, true, kp, st, pi);
-        if (rc != 1) return rc;
-        rc = conv_skinny16_try(kind, true, kp, cout_f, nullptr, ws, ws_floats, st, pi);
-        if (rc != 1) return rc;
+// Forward kinds.  kp is fully prepared by conv2d_fwd_impl (conv_dispatch.hip); false when this launch is not covered by the bf16
+// kernels (the ladder then goes on to the fp32 families).
+bool conv_bf16_fwd(int kind, ConvKParams &kp, int cin_total, float *out, float *ws, size_t ws_floats, const ProfInfo &pi, const ConvCtx &cx,
+                   int *status) {
+    for (int s = 0; s < kp.nsrc; ++s)
+        if (kp.src_c[s] % 32 != 0) return false;
+    // the persistent LDS-ring kernel takes the launches it covers (bf16 storage, maps >= 16 x 32; round 6: the first layer too)
+    kp.out = out;
+    if (conv_ring(kind, false, kp, pi, cx, status)) return true;   // (writes kp.out_sign itself)
+    // A sign pass follows the kernels that do not write kp.out_sign themselves: the one-shot kernel, and the tiled kernels without the
+    // 16-byte epilogue or with a split-K reduce in between.  It is a launch of its own, outside the conv's ProfScope.
+    const bool want_sign = kp.out_sign && kp.io_bf16;
+    ConvCtx inner = cx;
+    ConvChoice c{};
+    inner.report = &c;
+    bool sign = false;
+    if (kind != PWS_CONV_K5S1 && conv_skinny16(kind, false, kp, cin_total, out, ws, ws_floats, pi, inner, status)) {
+        sign = want_sign;
+    } else {
+        const TileChoice *t = nullptr;
+        switch (kind) {
+        case PWS_CONV_K3S1:
+        case PWS_CONVT_K3S1: plan_bf16_tiles(kBK3S1Deep, kBK3S1, 5, kp, cin_total, out, ws, ws_floats, &t, &c); break;
+        case PWS_CONV_K3S2: plan_bf16_tiles(nullptr, kBK3S2, 5, kp, cin_total, out, ws, ws_floats, &t, &c); break;
+        case PWS_CONVT_K4S2: plan_bf16_tiles(kBCT4Deep, kBCT4, 5, kp, cin_total, out, ws, ws_floats, &t, &c); break;
+        case PWS_CONV_K5S1:
+            if (kp.nsrc != 1) return false;
+            plan_k5(kp, out, &c);
+            break;
+        default: return false;
+        }
+        sign = want_sign && !(kp.epi16 && kp.ksplit <= 1);   // (else its 16-byte epilogue writes the sign bytes)
+        conv_accept(inner, c, pi, status, [&] { return t ? run_tiles(*t, c, kp, out, ws, cx.stream) : run_k5(kp, c, cx.stream); });
     }
+    if (sign) c.follow |= PWS_FOLLOW_SIGN;
+    conv_report(cx, c);
+    if (sign && cx.launch && *status == PWS_OK) *status = run_sign_bits(kp, out, cx.stream);
+    return true;
+}
+
+// Data-gradient kinds (kp prepared by conv2d_bwd_data_impl).
+bool conv_bf16_dgrad(int kind, ConvKParams &kp, int cout_f, float *ws, size_t ws_floats, const ProfInfo &pi, const ConvCtx &cx, int *status) {
+    if (cout_f % 32 != 0) return false;
+    if (conv_ring(kind, true, kp, pi, cx, status)) return true;
+    if (conv_skinny16(kind, true, kp, cout_f, nullptr, ws, ws_floats, pi, cx, status)) return true;
+    const TileChoice *t = nullptr;
+    ConvChoice c;
     switch (kind) {
     case PWS_CONV_K3S1:
-    case PWS_CONVT_K3S1:
-        if (const TileChoice *d = deep_tile(kBK3S1Deep, kp, cout_f)) return select_and_launch(d, 1, kp, cout_f, nullptr, ws, ws_floats, st, pi, kFillBlocksBf16);
-        return select_and_launch(kBK3S1, 5, kp, cout_f, nullptr, ws, ws_floats, st, pi, kFillBlocksBf16);
-    case PWS_CONV_K3S2:
-        if (const TileChoice *d = deep_tile(kBSP3Deep, kp, cout_f)) return select_and_launch(d, 1, kp, cout_f, nullptr, ws, ws_floats, st, pi, kFillBlocksBf16);
-        return select_and_launch(kBSP3, 5, kp, cout_f, nullptr, ws, ws_floats, st, pi, kFillBlocksBf16);
-    case PWS_CONVT_K4S2: return select_and_launch(kBK4S2, 4, kp, cout_f, nullptr, ws, ws_floats, st, pi, kFillBlocksBf16);
-    default: return 1;
+    case PWS_CONVT_K3S1: plan_bf16_tiles(kBK3S1Deep, kBK3S1, 5, kp, cout_f, nullptr, ws, ws_floats, &t, &c); break;
+    case PWS_CONV_K3S2: plan_bf16_tiles(kBSP3Deep, kBSP3, 5, kp, cout_f, nullptr, ws, ws_floats, &t, &c); break;
+    case PWS_CONVT_K4S2: plan_bf16_tiles(nullptr, kBK4S2, 4, kp, cout_f, nullptr, ws, ws_floats, &t, &c); break;
+    default: return false;
     }
+    return conv_accept(cx, c, pi, status, [&] { return run_tiles(*t, c, kp, nullptr, ws, cx.stream); });
 }
 
 // [planes][krows][ncols] fp32 -> [planes][ncols padded to 64][krows padded to 32] bf16 (zero padded); one lane per

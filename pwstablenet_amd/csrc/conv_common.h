@@ -121,10 +121,53 @@ struct ProfInfo {
     double flops, bytes;
 };
 
+// ---- deciding and launching apart (conv_dispatch.hip holds the ladder).  Every family's exported function plans -- coverage, variant, parameter
+// block, grid, workgroup, LDS: plain arithmetic, no HIP call, the CU count an argument -- records the plan as a ConvChoice, and launches it
+// only when the call asks for that; its run step takes grid / workgroup / LDS from the plan.  It returns whether the family takes the
+// launch; the launch's status travels in *status.  (ConvChoice / ConvCtx: common.h)
+inline ConvChoice conv_choice(int kid, int v0, int v1, int v2, int v3, dim3 grid, int threads, int lds_bytes, int ksplit = 1, int follow = PWS_FOLLOW_NONE) {
+    return ConvChoice{kid, {v0, v1, v2, v3}, {grid.x, grid.y, grid.z}, threads, lds_bytes, ksplit, follow, 0};
+}
+inline dim3 choice_grid(const ConvChoice &c) { return dim3(c.grid[0], c.grid[1], c.grid[2]); }
+inline void conv_report(const ConvCtx &cx, const ConvChoice &c) {   // (the tag is the caller's)
+    if (!cx.report) return;
+    const int tag = cx.report->tag;
+    *cx.report = c, cx.report->tag = tag;
+}
+// the accepting end of a family: report the choice and, if asked, run it under one ProfScope (which covers a following split-K reduce)
+template <class Run>
+inline bool conv_accept(const ConvCtx &cx, const ConvChoice &c, const ProfInfo &pi, int *status, Run run) {
+    conv_report(cx, c);
+    *status = PWS_OK;
+    if (cx.launch) {
+        ProfScope prof(c.kernel_id, pi.flops, pi.bytes, cx.stream);
+        *status = run();
+    }
+    return true;
+}
+
+// the run step of most families: the kernel's LDS opt-in (attr_bytes, default the launch's own), then the launch exactly as planned
+template <auto Kernel, class P>
+inline int launch_planned(const P &p, const ConvChoice &c, hipStream_t st, const char *what, int attr_bytes = 0, bool say_bytes = true) {
+    if (int rc = lds_attr_once<Kernel>(attr_bytes ? attr_bytes : c.lds_bytes, what, say_bytes)) return rc;
+    hipLaunchKernelGGL(Kernel, choice_grid(c), dim3(c.threads), c.lds_bytes, st, p);
+    return check_launch(what);
+}
+template <class P>
+struct Planned {   // what a family's plan step hands to its run step when the kernel is picked among template instantiations
+    P p;
+    ConvChoice c;
+    int (*run)(const P &, const ConvChoice &, hipStream_t);
+};
+
+struct LaunchShape {
+    int threads, lds_bytes;
+};
 struct TileChoice {  // one instantiation, described for the selector
     int th, tw, tn, ck, bn;
     int kid;
-    int (*launch)(ConvKParams &, hipStream_t, const ProfInfo &);
+    LaunchShape shape[2];   // fp32 / bf16 storage (ConvKParams.io_bf16)
+    int (*launch)(const ConvKParams &, const ConvChoice &, hipStream_t);
 };
 
 int launch_splitk_reduce(const ConvKParams &kp, const float *partial, size_t total4, hipStream_t st);  // conv_mfma.hip
@@ -136,12 +179,13 @@ constexpr long kFillBlocksBf16 = 256;  // bf16 kernels: one workgroup per CU is 
                                        // relatively more for the split-K reduce launches: N=8 inference 4550 -> 4700 frames/s;
                                        // 128 / 384 / 512 measured 4580 / 4580 / 4550; fp32: 512 best, 256 and 1024 -2 %)
 
-// Pick the tile and the K split for one launch.
+// Pick the tile and the K split for one launch of a tiled kernel (fills kp's tiling; kp.out = the partial buffer when K is split).
 //  1. drop tiles that are mostly padding for this extent (a 16x16 tile on an 8x8 map);
 //  2. take the largest remaining tile whose grid has >= kFill workgroups, else the one with the most workgroups;
 //  3. if the grid is still < kFill and a workspace was given, split K (>= 2 chunks per split, <= 64 splits).
-[[maybe_unused]] static int select_and_launch(const TileChoice *cands, int ncand, ConvKParams &kp, int cin_total, float *final_out,
-                             float *ws, size_t ws_floats, hipStream_t st, const ProfInfo &pi, long kFill = kFillBlocks) {
+// `vbase` + the tile's index is variant[0] of the choice.
+[[maybe_unused]] static const TileChoice *plan_tiles(const TileChoice *cands, int ncand, ConvKParams &kp, int cin_total, float *final_out, float *ws,
+                                                     size_t ws_floats, long kFill, int vbase, ConvChoice *choice) {
     const TileChoice *best = nullptr;
     long best_blocks = -1;
     double best_score = -1.0;
@@ -177,13 +221,34 @@ constexpr long kFillBlocksBf16 = 256;  // bf16 kernels: one workgroup per CU is 
     kp.ksplit = (int)cdiv(total_chunks, kp.chunks_per_split);  // no empty splits
     kp.split_stride = out_floats;
     kp.out = kp.ksplit > 1 ? ws : final_out;
-    ProfScope prof(c.kid, pi.flops, pi.bytes, st);  // covers the split-K reduce as well
-    int rc = c.launch(kp, st, pi);
+    const LaunchShape &sh = c.shape[kp.io_bf16 ? 1 : 0];
+    *choice = conv_choice(c.kid, vbase + (int)(&c - cands), c.th, c.tw, c.tn, conv_grid(kp, c.bn), sh.threads, sh.lds_bytes, kp.ksplit,
+                          kp.ksplit > 1 ? PWS_FOLLOW_REDUCE : PWS_FOLLOW_NONE);
+    return &c;
+}
+// Launch what plan_tiles chose, and the split-K reduce behind it.
+[[maybe_unused]] static int run_tiles(const TileChoice &c, const ConvChoice &choice, ConvKParams &kp, float *final_out, const float *ws, hipStream_t st) {
+    const int rc = c.launch(kp, choice, st);
     if (rc != PWS_OK || kp.ksplit == 1) return rc;
-    const size_t total4 = out_floats / 4;
     kp.out = final_out;
-    return launch_splitk_reduce(kp, ws, total4, st);
+    return launch_splitk_reduce(kp, ws, kp.split_stride / 4, st);
 }
 
+// ---- the families, in the ladder's vocabulary (conv_dispatch.hip): true = this family takes the launch
+bool conv_bf16_fwd(int kind, ConvKParams &kp, int cin_total, float *out, float *ws, size_t ws_floats, const ProfInfo &pi, const ConvCtx &cx,
+                   int *status);   // conv_bf16.hip: conv_ring_kernel, conv_skinny16_kernel, conv_bf16_kernel / conv_bf16_k5_kernel (+ sign pass)
+bool conv_bf16_dgrad(int kind, ConvKParams &kp, int cout_f, float *ws, size_t ws_floats, const ProfInfo &pi, const ConvCtx &cx, int *status);
+bool conv_ring(int kind, bool dgrad, const ConvKParams &kp, const ProfInfo &pi, const ConvCtx &cx, int *status);                     // conv_ring.hip
+bool conv_skinny16(int kind, bool dgrad, ConvKParams &kp, int kchan, float *final_out, float *ws, size_t ws_floats, const ProfInfo &pi,
+                   const ConvCtx &cx, int *status);                                                                                   // conv_skinny16.hip
+bool conv_wring(const pws_conv_args *a, const ProfInfo &pi, const ConvCtx &cx, int *status);                                         // conv_wring.hip
+bool conv_wino(const pws_conv_args *a, const ProfInfo &pi, const ConvCtx &cx, int *status);                                          // conv_wino.hip (always takes it)
+bool conv_ringf(int kind, const ConvKParams &kp, const ProfInfo &pi, const ConvCtx &cx, int *status);                                // conv_ring_f32.hip
+bool conv_skinny(int kind, ConvKParams &kp, float *final_out, float *ws, size_t ws_floats, const ProfInfo &pi, const ConvCtx &cx, int *status);   // conv_skinny.hip
+bool conv_first_wino(const ConvKParams &kp, const float *u, const ProfInfo &pi, const ConvCtx &cx, int *status);                     // conv_first_wino.hip
+bool conv_first(const ConvKParams &kp, const ProfInfo &pi, const ConvCtx &cx, int *status);                                          // conv_first.hip
+// conv_mfma.hip: the direct fp32 kernel's tile tables (always takes it)
+bool conv_mfma(int kind, bool dgrad, bool nchw, ConvKParams &kp, int cin_total, float *final_out, float *ws, size_t ws_floats, const ProfInfo &pi,
+               const ConvCtx &cx, int *status);
 
 }  // namespace pws

@@ -284,20 +284,20 @@ __global__ void __launch_bounds__(FT_THREADS, 3) conv_first_kernel(const FirstPa
     }
 }
 
-// Runs the first-layer launch described by kp (prepared by pws_conv2d_fwd, conv_mfma.hip) when it is covered: fp32, NCHW source of 17
+// The first-layer launch described by kp (prepared by conv2d_fwd_impl, conv_dispatch.hip) when it is covered: fp32, NCHW source of 17
 // to 32 channels with 16-byte aligned rows, whole 8 x 32 tiles, an even cout / out_ld, enough units for half the chip
-// (PWS_OPT_EXPERIMENT 25: never; 29: also for the tests' small launches).  Returns 1 when not covered.
-int conv_first_try(const ConvKParams &kp, hipStream_t st, const ProfInfo &pi) {
-    if (kp.io_bf16 || kp.ndst != 0 || kp.nsrc != 1 || exp_is(EXP_FIRST_MFMA)) return 1;
-    if (kp.src_c[0] > FT_CP || kp.cin_pad != FT_CP || kp.W % FT_TW != 0 || kp.H % FT_TH != 0 || kp.cout % 4 != 0 || kp.out_ld % 2 != 0) return 1;
+// (PWS_OPT_EXPERIMENT 25: never; 29: also for the tests' small launches).  The plan step: false when not covered.
+static bool first_plan(const ConvKParams &kp, int ncu, FirstParams &p, ConvChoice &c) {
+    if (kp.io_bf16 || kp.ndst != 0 || kp.nsrc != 1 || exp_is(EXP_FIRST_MFMA)) return false;
+    if (kp.src_c[0] > FT_CP || kp.cin_pad != FT_CP || kp.W % FT_TW != 0 || kp.H % FT_TH != 0 || kp.cout % 4 != 0 || kp.out_ld % 2 != 0) return false;
     const size_t sstride = kp.src_ld[0] ? (size_t)kp.src_ld[0] : (size_t)kp.src_c[0] * kp.H * kp.W;
     if ((reinterpret_cast<size_t>(kp.src_ptr[0]) & 15) || sstride % 4 != 0 || (reinterpret_cast<size_t>(kp.out) & 7) ||
         (kp.bias && (reinterpret_cast<size_t>(kp.bias) & 7)))
-        return 1;
+        return false;
     if ((size_t)kp.src_c[0] * kp.H * kp.W * 4 >= (1u << 31) || (size_t)25 * FT_CP * kp.cout * 4 >= (1u << 31) ||
         (size_t)kp.H * kp.W * kp.out_ld * 4 >= (1u << 31))
-        return 1;
-    FirstParams p{};
+        return false;
+    p = FirstParams{};
     p.src = kp.src_ptr[0], p.C = kp.src_c[0], p.N = kp.N, p.H = kp.H, p.W = kp.W, p.sstride = sstride;
     p.w = kp.w, p.w_bytes = (unsigned)(25 * FT_CP * kp.cout * 4), p.cout = kp.cout;
     p.bias = kp.bias, p.act = kp.act, p.out = kp.out, p.out_ld = kp.out_ld;
@@ -305,40 +305,37 @@ int conv_first_try(const ConvKParams &kp, hipStream_t st, const ProfInfo &pi) {
     p.ncob = (unsigned)((kp.cout + 63) / 64);
     p.nunits = (unsigned)(p.tiles_x * p.tiles_y) * (unsigned)kp.N * p.ncob;
     p.ablate = exp_mask(EXP_FIRST_ABLATE, 16);
-    static PerDeviceInt ncu_dev;
-    int &ncu = ncu_dev.cur();
-    if (ncu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
+    if (p.nunits < (unsigned)(ncu / 2) && !exp_is(EXP_FIRST_SMALL)) return false;
+    c = conv_choice(KID_CONV_FIRST, 0, 0, 0, 0, dim3(p.nunits < (unsigned)ncu ? p.nunits : (unsigned)ncu), FT_THREADS, FT_LDS);   // one persistent workgroup per CU
+    return true;
+}
+
+static int first_run(const FirstParams &p, const ConvChoice &c, hipStream_t st) { return launch_planned<&conv_first_kernel>(p, c, st, "conv_first_kernel"); }
+// measurement aid (tools/first_ablate.sh, EXP_FIRST_CLOCK): the shader clock the chip holds inside this kernel (unprofiled, synchronises)
+static int first_run_clocked(FirstParams &p, const ConvChoice &c, hipStream_t st) {
+    static unsigned long long *clk = nullptr;
+    if (!clk && hipHostMalloc(&clk, 2 * 1024 * sizeof(unsigned long long)) != hipSuccess) return PWS_EHIP;
+    p.clk = clk;
+    if (int rc = first_run(p, c, st)) return rc;
+    if (hipStreamSynchronize(st) != hipSuccess) return PWS_EHIP;
+    const unsigned grid = c.grid[0];
+    double cyc = 0, ticks = 0;
+    for (unsigned i = 0; i < grid; ++i) cyc += (double)clk[2 * i], ticks += (double)clk[2 * i + 1];
+    fprintf(stderr, "conv_first_kernel: %.0f shader cycles and %.1f us per workgroup (mean of %u): %.0f MHz\n", cyc / grid, ticks / grid / 100.0, grid,
+            cyc / ticks * 100.0);
+    return PWS_OK;
+}
+
+bool conv_first(const ConvKParams &kp, const ProfInfo &pi, const ConvCtx &cx, int *status) {
+    FirstParams p;
+    ConvChoice c;
+    if (!first_plan(kp, cx.compute_units, p, c)) return false;
+    if (exp_is(EXP_FIRST_CLOCK)) {
+        conv_report(cx, c);
+        *status = cx.launch ? first_run_clocked(p, c, cx.stream) : PWS_OK;
+        return true;
     }
-    if (p.nunits < (unsigned)(ncu / 2) && !exp_is(EXP_FIRST_SMALL)) return 1;
-    static PerDeviceFlag attr_set_dev;
-    bool &attr_set = attr_set_dev.cur();   // hipFuncSetAttribute acts on the CURRENT device's function object
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_first_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, FT_LDS);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(conv_first_kernel, %d B LDS): %s", FT_LDS, hipGetErrorString(e));
-            return PWS_EHIP;
-        }
-        attr_set = true;
-    }
-    const unsigned grid = p.nunits < (unsigned)ncu ? p.nunits : (unsigned)ncu;   // one persistent workgroup per CU
-    if (exp_is(EXP_FIRST_CLOCK)) {   // measurement aid (tools/first_ablate.sh): the shader clock the chip holds inside this kernel
-        static unsigned long long *clk = nullptr;
-        if (!clk && hipHostMalloc(&clk, 2 * 1024 * sizeof(unsigned long long)) != hipSuccess) return PWS_EHIP;
-        p.clk = clk;
-        hipLaunchKernelGGL(conv_first_kernel, dim3(grid), dim3(FT_THREADS), FT_LDS, st, p);
-        if (hipStreamSynchronize(st) != hipSuccess) return PWS_EHIP;
-        double cyc = 0, ticks = 0;
-        for (unsigned i = 0; i < grid; ++i) cyc += (double)clk[2 * i], ticks += (double)clk[2 * i + 1];
-        fprintf(stderr, "conv_first_kernel: %.0f shader cycles and %.1f us per workgroup (mean of %u): %.0f MHz\n", cyc / grid, ticks / grid / 100.0, grid,
-                cyc / ticks * 100.0);
-        return check_launch("conv_first_kernel");
-    }
-    ProfScope prof(KID_CONV_FIRST, pi.flops, pi.bytes, st);
-    hipLaunchKernelGGL(conv_first_kernel, dim3(grid), dim3(FT_THREADS), FT_LDS, st, p);
-    return check_launch("conv_first_kernel");
+    return conv_accept(cx, c, pi, status, [&] { return first_run(p, c, cx.stream); });
 }
 
 }  // namespace pws

@@ -347,45 +347,33 @@ __global__ void __launch_bounds__(W5_THREADS, 2) wino5_first_kernel(const Wino5P
     else run(std::false_type{});
 }
 
-// Runs the first-layer launch described by kp on the Winograd kernel when it is covered: fp32, NCHW source of 17 .. 32 channels with
+// The first-layer launch described by kp on the Winograd kernel when it is covered: fp32, NCHW source of 17 .. 32 channels with
 // 16-byte aligned rows, exactly 64 output channels, whole 8 x 16 units, transformed weights given (pws_conv_args.w_wring), enough units for
-// the chip (PWS_OPT_EXPERIMENT 26: never; 30: also for the tests' small launches).  Returns 1 when not covered (conv_first_kernel is next).
-int wino5_first_try(const ConvKParams &kp, const float *u, hipStream_t st, const ProfInfo &pi) {
-    if (!u || kp.io_bf16 || kp.ndst != 0 || kp.nsrc != 1 || exp_is(EXP_FIRST_NO_WINO) || exp_is(EXP_FIRST_MFMA)) return 1;
-    if (kp.src_c[0] > 32 || kp.cin_pad != 32 || kp.cout != 64 || kp.W % (2 * W5_TC) != 0 || kp.H % (2 * W5_TR) != 0 || kp.out_ld % 4 != 0) return 1;
+// the chip (PWS_OPT_EXPERIMENT 26: never; 30: also for the tests' small launches).  The plan step: false when not covered (conv_first_kernel is next).
+static bool wino5_plan(const ConvKParams &kp, const float *u, int ncu, Wino5Params &p, ConvChoice &c) {
+    if (!u || kp.io_bf16 || kp.ndst != 0 || kp.nsrc != 1 || exp_is(EXP_FIRST_NO_WINO) || exp_is(EXP_FIRST_MFMA)) return false;
+    if (kp.src_c[0] > 32 || kp.cin_pad != 32 || kp.cout != 64 || kp.W % (2 * W5_TC) != 0 || kp.H % (2 * W5_TR) != 0 || kp.out_ld % 4 != 0) return false;
     const size_t sstride = kp.src_ld[0] ? (size_t)kp.src_ld[0] : (size_t)kp.src_c[0] * kp.H * kp.W;
     if ((reinterpret_cast<size_t>(kp.src_ptr[0]) & 15) || sstride % 4 != 0 || (reinterpret_cast<size_t>(kp.out) & 15) ||
         (kp.bias && (reinterpret_cast<size_t>(kp.bias) & 15)) || (reinterpret_cast<size_t>(u) & 15))
-        return 1;
-    if ((size_t)kp.src_c[0] * kp.H * kp.W * 4 >= (1u << 30)) return 1;   // kW5Oob (+ a unit's scalar offset) must stay beyond the descriptor's records and below 2^32
-    Wino5Params p{};
+        return false;
+    if ((size_t)kp.src_c[0] * kp.H * kp.W * 4 >= (1u << 30)) return false;   // kW5Oob (+ a unit's scalar offset) must stay beyond the descriptor's records and below 2^32
+    p = Wino5Params{};
     p.src = static_cast<const float *>(kp.src_ptr[0]), p.C = kp.src_c[0], p.N = kp.N, p.H = kp.H, p.W = kp.W, p.sstride = sstride;
     p.u = u, p.bias = kp.bias, p.act = kp.act, p.out = static_cast<float *>(kp.out), p.out_ld = kp.out_ld;
     p.tiles_x = kp.W / (2 * W5_TC), p.tiles_y = kp.H / (2 * W5_TR);
     p.nunits = (unsigned)(p.tiles_x * p.tiles_y) * (unsigned)kp.N;
     p.ablate = exp_mask(EXP_WINO5_ABLATE, 64);
-    static PerDeviceInt ncu_dev;
-    int &ncu = ncu_dev.cur();
-    if (ncu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-    }
-    if (p.nunits < (unsigned)(2 * ncu) && !exp_is(EXP_WINO5_SMALL)) return 1;   // a unit is short (8 k-steps): the pipeline wants a few per workgroup
-    static PerDeviceFlag attr_set_dev;
-    bool &attr_set = attr_set_dev.cur();   // hipFuncSetAttribute acts on the CURRENT device's function object
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&wino5_first_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, W5_LDS);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(wino5_first_kernel, %d B LDS): %s", W5_LDS, hipGetErrorString(e));
-            return PWS_EHIP;
-        }
-        attr_set = true;
-    }
-    const unsigned grid = p.nunits < (unsigned)ncu ? p.nunits : (unsigned)ncu;   // one persistent workgroup per CU
-    ProfScope prof(KID_CONV_FIRST_WINO, pi.flops, pi.bytes, st);
-    hipLaunchKernelGGL(wino5_first_kernel, dim3(grid), dim3(W5_THREADS), W5_LDS, st, p);
-    return check_launch("wino5_first_kernel");
+    if (p.nunits < (unsigned)(2 * ncu) && !exp_is(EXP_WINO5_SMALL)) return false;   // a unit is short (8 k-steps): the pipeline wants a few per workgroup
+    c = conv_choice(KID_CONV_FIRST_WINO, 0, 0, 0, 0, dim3(p.nunits < (unsigned)ncu ? p.nunits : (unsigned)ncu), W5_THREADS, W5_LDS);   // one persistent workgroup per CU
+    return true;
+}
+
+bool conv_first_wino(const ConvKParams &kp, const float *u, const ProfInfo &pi, const ConvCtx &cx, int *status) {
+    Wino5Params p;
+    ConvChoice c;
+    if (!wino5_plan(kp, u, cx.compute_units, p, c)) return false;
+    return conv_accept(cx, c, pi, status, [&] { return launch_planned<&wino5_first_kernel>(p, c, cx.stream, "wino5_first_kernel"); });
 }
 
 }  // namespace pws

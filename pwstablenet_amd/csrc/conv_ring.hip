@@ -31,7 +31,7 @@
 // Arithmetic is that of conv_bf16_kernel: bf16 x bf16 products exact in fp32, fp32 accumulation (v_mfma_f32_32x32x16_bf16), the
 // K order differs (plane-major for the stride-2 kinds), one rounding to bf16 in the epilogue.
 // Round 6: (a) units of 256 and 128 pixels (RgCfg::PIX) for the launches that give fewer than ~200 units of 512 -- the 32 x 32 ... 8 x 8 levels of a training
-// batch, the 64 x 64 ... 16 x 16 levels of batch-8 inference -- which used to fall back to conv_bf16_kernel or leave half the chip idle (conv_ring_try picks the
+// batch, the 64 x 64 ... 16 x 16 levels of batch-8 inference -- which used to fall back to conv_bf16_kernel or leave half the chip idle (ring_plan picks the
 // unit); (b) the first layer (RM_K5: 5x5 on the NHWC-32 copy of the window) with its 25 x 64 weight rows RESIDENT in LDS and input tiles only in the ring.
 #include <cstdlib>
 #include <type_traits>
@@ -131,7 +131,7 @@ struct RgCfg {
     static constexpr int W_OFF = IN_WI * 1024;
     static constexpr int LDS_RING_BYTES = R * GROUP_BYTES;
     static constexpr int W_RES_OFF = LDS_RING_BYTES;              // WRES: the resident weight rows
-    // the layer's bias vector (conv_ring_try: cout <= BIAS_FLOATS) sits behind the ring -- or, where the ring fills the LDS (the
+    // the layer's bias vector (ring_plan: cout <= BIAS_FLOATS) sits behind the ring -- or, where the ring fills the LDS (the
     // 3x3 kind on 16-wide maps: 2 x 80 KB), in the filler tail of the last ring buffer, which a ring of depth 2 need not write
     // (its waits are vmcnt(0): no piece count to keep constant)
     static constexpr int FILL_BYTES = (NL * LWAVES - IN_WI - W_WI) * 1024;
@@ -228,7 +228,7 @@ __global__ void __launch_bounds__(C::THREADS, C::WAVES_PER_SIMD) conv_ring_kerne
     const unsigned nxc = G < (unsigned)kXcds ? G : (unsigned)kXcds;
     const unsigned xcd = blockIdx.x % nxc, slot = blockIdx.x / nxc;
     const unsigned nx = G / nxc + (xcd < G % nxc ? 1u : 0u);   // workgroups on this XCD
-    // (32-bit: nunits < 2^28, conv_ring_try; through uni(): both roles use these, they belong in scalar registers)
+    // (32-bit: nunits < 2^28, ring_plan; through uni(): both roles use these, they belong in scalar registers)
     const unsigned c_begin = uni(xcd * p.nunits / nxc);
     const unsigned c_end = uni((xcd + 1) * p.nunits / nxc);
     if (c_begin + slot >= c_end) return;
@@ -332,7 +332,7 @@ __global__ void __launch_bounds__(C::THREADS, C::WAVES_PER_SIMD) conv_ring_kerne
                 for (int ps = 0; ps < p.nsrc; ++ps) {
                     const int ld = sel4(p.src_ld, ps), srcc = sel4(p.src_c, ps);
                     const size_t img1 = (size_t)p.H * p.W * ld * 2;   // bytes of one sample
-                    const size_t img = img1 * C::TN;                   // ... of the samples of a tile (N % TN == 0: conv_ring_try)
+                    const size_t img = img1 * C::TN;                   // ... of the samples of a tile (N % TN == 0: ring_plan)
                     const char *base_in = uni(static_cast<const char *>(sel4(p.src_ptr, ps)) + (size_t)PU.n0 * img1);
                     const __amdgpu_buffer_rsrc_t d_rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(base_in), 0, (int)uni((unsigned)img), 0x00020000);
                     const unsigned ldb = (unsigned)ld * 2u;
@@ -848,98 +848,87 @@ __global__ void __launch_bounds__(C::THREADS, C::WAVES_PER_SIMD) conv_ring_kerne
 }
 
 // ------------------------------------------------------------------------------------------------ host side
+using RingPlan = Planned<RingParams>;
+template <class C, bool DG, bool SG>
+static int ring_run(const RingParams &rp, const ConvChoice &c, hipStream_t st) { return launch_planned<&conv_ring_kernel<C, DG, SG>>(rp, c, st, "conv_ring_kernel"); }
+// the unit geometry of configuration C: one persistent workgroup per CU
 template <class C, bool DG, bool SG = false>
-static int ring_launch(RingParams &rp, hipStream_t st) {
-    static PerDeviceFlag attr_set_dev;
-    bool &attr_set = attr_set_dev.cur();   // hipFuncSetAttribute acts on the CURRENT device's function object
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_ring_kernel<C, DG, SG>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           C::LDS_BYTES);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(conv_ring_kernel, %d B LDS): %s", C::LDS_BYTES, hipGetErrorString(e));
-            return PWS_EHIP;
-        }
-        attr_set = true;
-    }
-    static PerDeviceInt ncu_dev;
-    int &ncu = ncu_dev.cur();
-    if (ncu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-    }
-    rp.tiles_x = rp.LW / C::TW, rp.tiles_y = rp.LH / C::TH, rp.tn = C::TN;   // whole tiles only (conv_ring_try)
+static bool ring_plan_cfg(RingPlan &pl, int ncu) {
+    RingParams &rp = pl.p;
+    rp.tiles_x = rp.LW / C::TW, rp.tiles_y = rp.LH / C::TH, rp.tn = C::TN;   // whole tiles only (conv_ring)
     rp.ncob = (unsigned)((rp.cout + 63) / 64), rp.ncls = (unsigned)C::NCLS;
     rp.nunits = (unsigned)(rp.tiles_x * rp.tiles_y) * (unsigned)(rp.N / C::TN) * rp.ncob * rp.ncls;
     {
         auto magic = [](unsigned d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + d - 1) / d); };
         unsigned dmax = rp.ncls > rp.ncob ? rp.ncls : rp.ncob;
         dmax = dmax > (unsigned)rp.tiles_x ? dmax : (unsigned)rp.tiles_x, dmax = dmax > (unsigned)rp.tiles_y ? dmax : (unsigned)rp.tiles_y;
-        if ((unsigned long long)rp.nunits * dmax >= 0x100000000ull) return 1;   // (never at this generator's sizes) the multiply-high division would not be exact
+        if ((unsigned long long)rp.nunits * dmax >= 0x100000000ull) return false;   // (never at this generator's sizes) the multiply-high division would not be exact
         rp.m_cls = magic(rp.ncls), rp.m_cob = magic(rp.ncob), rp.m_tx = magic((unsigned)rp.tiles_x), rp.m_ty = magic((unsigned)rp.tiles_y);
     }
     int cin = 0;
     for (int s = 0; s < rp.nsrc; ++s) cin += rp.src_c[s];
     rp.gpp = cin / C::CKG;
-    const unsigned grid = rp.nunits < (unsigned)ncu ? rp.nunits : (unsigned)ncu;   // one persistent workgroup per CU
-    hipLaunchKernelGGL((conv_ring_kernel<C, DG, SG>), dim3(grid), dim3(C::THREADS), C::LDS_BYTES, st, rp);
-    return check_launch("conv_ring_kernel");
+    pl.c.grid[0] = rp.nunits < (unsigned)ncu ? rp.nunits : (unsigned)ncu, pl.c.grid[1] = pl.c.grid[2] = 1;
+    pl.c.threads = C::THREADS, pl.c.lds_bytes = C::LDS_BYTES;
+    pl.run = &ring_run<C, DG, SG>;
+    return true;
 }
 
 // Tile shapes.  Units of 512 pixels: 16 x 32 pixels of one sample for maps at least 32 wide, 16 x 16 x 2 samples for 16-wide maps, 8 x 8 x 8 samples for
 // 8 x 8 maps (2x2-tap kinds only: the 3x3 kind's group of 8 halo'd samples does not fit two ring buffers).  Units of 256 pixels (round 6): 16 x 16 of
 // one sample, 8 x 8 x 4 samples; of 128 pixels: 8 x 8 x 2 samples, 4 x 4 x 8 samples.
 template <int MODE, bool DG, bool SG = false>
-static int ring_launch_tile(int pix, int tw, RingParams &rp, hipStream_t st) {
+static bool ring_plan_tile(int pix, int tw, RingPlan &pl, int ncu) {
     constexpr int RS = MODE == RM_K3S1 ? 2 : 3;   // ring depth of the small units (the 3x3 kind's 36 KB of weights per group leave room for two)
     if (pix == 256) {
         using C16 = RgCfg<MODE, 16, 16, 1, RS>;
         using C8 = RgCfg<MODE, 8, 8, 4, RS>;
-        static_assert(C16::BIAS_FLOATS == 1024 && C8::BIAS_FLOATS == 1024, "conv_ring_try's bias-slot check");
-        if (tw == 16) return ring_launch<C16, DG, SG>(rp, st);
-        if (tw == 8) return ring_launch<C8, DG, SG>(rp, st);
-        return 1;
+        static_assert(C16::BIAS_FLOATS == 1024 && C8::BIAS_FLOATS == 1024, "conv_ring's bias-slot check");
+        if (tw == 16) return ring_plan_cfg<C16, DG, SG>(pl, ncu);
+        if (tw == 8) return ring_plan_cfg<C8, DG, SG>(pl, ncu);
+        return false;
     }
     if (pix == 128) {
         using C8 = RgCfg<MODE, 8, 8, 2, RS>;
         using C4 = RgCfg<MODE, 4, 4, 8, RS>;
-        static_assert(C8::BIAS_FLOATS == 1024 && C4::BIAS_FLOATS == 1024, "conv_ring_try's bias-slot check");
-        if (tw == 8) return ring_launch<C8, DG, SG>(rp, st);
-        if (tw == 4) return ring_launch<C4, DG, SG>(rp, st);
-        return 1;
+        static_assert(C8::BIAS_FLOATS == 1024 && C4::BIAS_FLOATS == 1024, "conv_ring's bias-slot check");
+        if (tw == 8) return ring_plan_cfg<C8, DG, SG>(pl, ncu);
+        if (tw == 4) return ring_plan_cfg<C4, DG, SG>(pl, ncu);
+        return false;
     }
     if constexpr (MODE == RM_K3S1 || MODE == RM_CT4 || MODE == RM_K4S2)
-        if (tw == 32 && !exp_is(EXP_RING_8WAVE)) return ring_launch<RgCfg<MODE, 16, 32, 1, MODE == RM_K3S1 ? 2 : 3, 4>, DG, SG>(rp, st);   // (EXP_RING_8WAVE: the 8-wave kernel)
-    if (tw == 32) return ring_launch<RgCfg<MODE, 16, 32, 1, MODE == RM_K3S1 ? 2 : 3>, DG, SG>(rp, st);
-    if (tw == 16) return ring_launch<RgCfg<MODE, 16, 16, 2, 2>, DG, SG>(rp, st);
-    if constexpr (MODE != RM_K3S1) return ring_launch<RgCfg<MODE, 8, 8, 8, 2>, DG, SG>(rp, st);
-    return 1;
+        if (tw == 32 && !exp_is(EXP_RING_8WAVE)) return ring_plan_cfg<RgCfg<MODE, 16, 32, 1, MODE == RM_K3S1 ? 2 : 3, 4>, DG, SG>(pl, ncu);   // (EXP_RING_8WAVE: the 8-wave kernel)
+    if (tw == 32) return ring_plan_cfg<RgCfg<MODE, 16, 32, 1, MODE == RM_K3S1 ? 2 : 3>, DG, SG>(pl, ncu);
+    if (tw == 16) return ring_plan_cfg<RgCfg<MODE, 16, 16, 2, 2>, DG, SG>(pl, ncu);
+    if constexpr (MODE != RM_K3S1) return ring_plan_cfg<RgCfg<MODE, 8, 8, 8, 2>, DG, SG>(pl, ncu);
+    return false;
 }
 
-// Runs the launch described by kp (prepared by conv2d_fwd_impl / conv2d_bwd_data_impl, conv_mfma.hip) on the ring kernel when it
+// The launch described by kp (prepared by conv2d_fwd_impl / conv2d_bwd_data_impl, conv_dispatch.hip) on the ring kernel when it
 // is covered: bf16 storage with 16-byte epilogue stores, every source a multiple of 32 channels, a logical map of at least
-// 16 x 32 pixels and enough units to give every CU one.  Returns 1 when not covered (the caller runs conv_bf16_kernel).
-int conv_ring_try(int kind, bool dgrad, const ConvKParams &kp, hipStream_t st, const ProfInfo &pi) {
-    if (!kp.io_bf16 || !kp.epi16 || exp_is(EXP_RING_OFF)) return 1;
+// 16 x 32 pixels and enough units to give every CU one.  The plan step: false when not covered.
+static bool ring_plan(int kind, bool dgrad, const ConvKParams &kp, int ncu, RingPlan &pl) {
+    if (!kp.io_bf16 || !kp.epi16 || exp_is(EXP_RING_OFF)) return false;
 #ifdef PWS_INTERFERENCE_PROBE
-    if (exp_in(EXP_BF16_PROBE, 64)) return 1;   // (the probe variants of conv_bf16_kernel)
+    if (exp_in(EXP_BF16_PROBE, 64)) return false;   // (the probe variants of conv_bf16_kernel)
 #endif
     for (int s = 0; s < kp.nsrc; ++s)
-        if (kp.src_c[s] % 32 != 0 || kp.src_ld[s] % 8 != 0 || (reinterpret_cast<size_t>(kp.src_ptr[s]) & 15)) return 1;
+        if (kp.src_c[s] % 32 != 0 || kp.src_ld[s] % 8 != 0 || (reinterpret_cast<size_t>(kp.src_ptr[s]) & 15)) return false;
     int mode;
     int planes;
     if (kind == PWS_CONV_K3S1 || kind == PWS_CONVT_K3S1) mode = RM_K3S1, planes = 9;
     else if (kind == PWS_CONV_K3S2) mode = dgrad ? RM_SP3 : RM_K3S2, planes = dgrad ? 16 : 9;
     else if (kind == PWS_CONVT_K4S2) mode = dgrad ? RM_K4S2 : RM_CT4, planes = 16;
     else if (kind == PWS_CONV_K5S1 && !dgrad) mode = RM_K5, planes = 25;
-    else return 1;
+    else return false;
     // the first layer (round 6): ONE source of 32 channels (the NHWC-32 copy of the window), ONE 64-channel output block -- what makes its weights resident;
     // 8 x 32 tiles
-    if (mode == RM_K5 && (kp.nsrc != 1 || kp.src_c[0] != 32 || kp.cout > 64 || kp.kpad_bf != 32 || kp.LW % 32 != 0 || kp.LH % 8 != 0)) return 1;
+    if (mode == RM_K5 && (kp.nsrc != 1 || kp.src_c[0] != 32 || kp.cout > 64 || kp.kpad_bf != 32 || kp.LW % 32 != 0 || kp.LH % 8 != 0)) return false;
     const size_t sample_bytes = (size_t)kp.H * kp.W * 2;
     for (int s = 0; s < kp.nsrc; ++s)
-        if (sample_bytes * kp.src_ld[s] >= (1u << 31)) return 1;
-    RingParams rp{};
+        if (sample_bytes * kp.src_ld[s] >= (1u << 31)) return false;
+    RingParams &rp = pl.p;
+    rp = RingParams{};
     for (int s = 0; s < 4; ++s) {
         rp.src_ptr[s] = kp.src_ptr[s], rp.src_c[s] = kp.src_c[s], rp.src_ld[s] = kp.src_ld[s];
         rp.dst_ptr[s] = kp.dst_ptr[s], rp.dst_c0[s] = kp.dst_c0[s], rp.dst_c1[s] = kp.dst_c1[s], rp.dst_ld[s] = kp.dst_ld[s];
@@ -948,7 +937,7 @@ int conv_ring_try(int kind, bool dgrad, const ConvKParams &kp, hipStream_t st, c
     rp.nsrc = kp.nsrc, rp.N = kp.N, rp.H = kp.H, rp.W = kp.W, rp.LH = kp.LH, rp.LW = kp.LW, rp.OH = kp.OH, rp.OW = kp.OW;
     rp.cout = kp.cout, rp.kpad = kp.kpad_bf, rp.npad = kp.npad_bf, rp.w_bf = kp.w_bf;
     rp.w_bytes = (size_t)planes * kp.npad_bf * kp.kpad_bf * 2;
-    if (rp.w_bytes >= (1u << 31)) return 1;
+    if (rp.w_bytes >= (1u << 31)) return false;
     rp.bias = kp.bias, rp.act = kp.act, rp.out = kp.out, rp.out_ld = kp.out_ld, rp.ndst = kp.ndst;
     rp.out_sign = dgrad ? nullptr : static_cast<unsigned char *>(kp.out_sign), rp.out_sign_ld = kp.out_sign_ld;
     for (int s = 0; s < 4; ++s) rp.dst_sign[s] = static_cast<const unsigned char *>(kp.dst_sign[s]), rp.dst_sign_ld[s] = kp.dst_sign_ld[s];
@@ -967,7 +956,7 @@ int conv_ring_try(int kind, bool dgrad, const ConvKParams &kp, hipStream_t st, c
     int pix = 0, tw = 0;
     if (mode == RM_K5) {
         pix = 256, tw = 32;
-        if (px / 256 < 192 && !exp_is(EXP_RING_SMALL)) return 1;
+        if (px / 256 < 192 && !exp_is(EXP_RING_SMALL)) return false;
     } else {
         int tw512 = 0;
         if (kp.LW % 32 == 0 && kp.LH % 16 == 0) tw512 = 32;
@@ -985,29 +974,35 @@ int conv_ring_try(int kind, bool dgrad, const ConvKParams &kp, hipStream_t st, c
         const int force_pix = exp_is(EXP_RING_UNIT256) ? 256 : (exp_is(EXP_RING_UNIT128) ? 128 : 0);   // tests: that unit size or nothing
         if (force_pix == 256 && tw256) pix = 256, tw = tw256;
         else if (force_pix == 128 && tw128) pix = 128, tw = tw128;
-        else if (force_pix) return 1;
+        else if (force_pix) return false;
         else if (tw512 && (px / 512 * per_px >= 192 || exp_is(EXP_RING_SMALL))) pix = 512, tw = tw512;
         else if (tw256 && px / 256 * per_px >= 192) pix = 256, tw = tw256;
         else if (tw128 && px / 128 * per_px >= min_small) pix = 128, tw = tw128;
-        else return 1;   // too few units for 256 persistent workgroups: the split-K kernels do better
+        else return false;   // too few units for 256 persistent workgroups: the split-K kernels do better
     }
-    if (kp.cout > (pix == 512 && tw == 16 && mode == RM_K3S1 ? 512 : 1024)) return 1;   // the bias vector's LDS slot (RgCfg::BIAS_FLOATS)
-    if (px / pix * per_px >= (1l << 28)) return 1;   // 32-bit unit arithmetic in the kernel
+    if (kp.cout > (pix == 512 && tw == 16 && mode == RM_K3S1 ? 512 : 1024)) return false;   // the bias vector's LDS slot (RgCfg::BIAS_FLOATS)
+    if (px / pix * per_px >= (1l << 28)) return false;   // 32-bit unit arithmetic in the kernel
     // the sign-bit variant of the data-gradient epilogue: when EVERY destination with an act' has its sign bits (PWS_OPT_EXPERIMENT 12: never)
     bool sg = dgrad && !exp_is(EXP_NO_SIGN_BITS), any_act = false;
     for (int s = 0; s < kp.ndst; ++s)
         if (kp.dst_act[s] != PWS_ACT_NONE) any_act = true, sg = sg && kp.dst_sign[s] != nullptr;
     sg = sg && any_act;
-    ProfScope prof(KID_CONV_RING, pi.flops, pi.bytes, st);
+    pl.c = conv_choice(KID_CONV_RING, mode, pix, tw, sg ? 1 : 0, dim3(0), 0, 0);
     switch (mode) {
     case RM_K5:   // (one tile row per wave on 8 matrix waves -- the epilogue of one wave under the matrix phase of the other -- measured the same: 480-510 against 490 us)
-        return ring_launch<RgCfg<RM_K5, 8, 32, 1, 2, 2>, false, false>(rp, st);
-    case RM_K3S1: return !dgrad ? ring_launch_tile<RM_K3S1, false>(pix, tw, rp, st) : (sg ? ring_launch_tile<RM_K3S1, true, true>(pix, tw, rp, st) : ring_launch_tile<RM_K3S1, true>(pix, tw, rp, st));
-    case RM_CT4: return ring_launch_tile<RM_CT4, false>(pix, tw, rp, st);
-    case RM_SP3: return sg ? ring_launch_tile<RM_SP3, true, true>(pix, tw, rp, st) : ring_launch_tile<RM_SP3, true>(pix, tw, rp, st);
-    case RM_K3S2: return ring_launch_tile<RM_K3S2, false>(pix, tw, rp, st);
-    default: return sg ? ring_launch_tile<RM_K4S2, true, true>(pix, tw, rp, st) : ring_launch_tile<RM_K4S2, true>(pix, tw, rp, st);
+        return ring_plan_cfg<RgCfg<RM_K5, 8, 32, 1, 2, 2>, false, false>(pl, ncu);
+    case RM_K3S1: return !dgrad ? ring_plan_tile<RM_K3S1, false>(pix, tw, pl, ncu) : (sg ? ring_plan_tile<RM_K3S1, true, true>(pix, tw, pl, ncu) : ring_plan_tile<RM_K3S1, true>(pix, tw, pl, ncu));
+    case RM_CT4: return ring_plan_tile<RM_CT4, false>(pix, tw, pl, ncu);
+    case RM_SP3: return sg ? ring_plan_tile<RM_SP3, true, true>(pix, tw, pl, ncu) : ring_plan_tile<RM_SP3, true>(pix, tw, pl, ncu);
+    case RM_K3S2: return ring_plan_tile<RM_K3S2, false>(pix, tw, pl, ncu);
+    default: return sg ? ring_plan_tile<RM_K4S2, true, true>(pix, tw, pl, ncu) : ring_plan_tile<RM_K4S2, true>(pix, tw, pl, ncu);
     }
+}
+
+bool conv_ring(int kind, bool dgrad, const ConvKParams &kp, const ProfInfo &pi, const ConvCtx &cx, int *status) {
+    RingPlan pl;
+    if (!ring_plan(kind, dgrad, kp, cx.compute_units, pl)) return false;
+    return conv_accept(cx, pl.c, pi, status, [&] { return pl.run(pl.p, pl.c, cx.stream); });
 }
 
 }  // namespace pws

@@ -45,7 +45,7 @@ struct RingfParams {
     int tiles_x, tiles_y;
     unsigned ncob, ncls, nunits;
     int gpp;              // K groups per plane = sum(src_c) / 16
-    int ablate;           // TIMING ONLY (EXP_RINGF_VARIANT + 16 v + mask, conv_ringf_try): 1 no matrix phase, 2 no DMA, 4 no stores
+    int ablate;           // TIMING ONLY (EXP_RINGF_VARIANT + 16 v + mask, ringf_plan): 1 no matrix phase, 2 no DMA, 4 no stores
 };
 
 template <int MODE_, int TH_, int R_, int NT_ = 2, int MW_ = 8>
@@ -60,7 +60,7 @@ struct RfCfg {
     static constexpr int NPLANES = MODE == RF_K3S2 ? 4 : 1;   // input parity planes
     static constexpr int NCLS = MODE == RF_CT4 ? 4 : 1;       // output parity classes
     // MW = 4: half a workgroup (half the tile's rows), two of them per CU -- each SIMD then carries two barrier domains, and one
-    // workgroup's matrix waves fill the pipe while the other's wait at a barrier or drain an epilogue (conv_ringf_try)
+    // workgroup's matrix waves fill the pipe while the other's wait at a barrier or drain an epilogue (ringf_plan)
     static constexpr int MWAVES = MW_, LWAVES = 4, THREADS = 64 * (MWAVES + LWAVES);
     static constexpr int WPC = MWAVES == 8 ? 1 : 2;                                    // persistent workgroups per CU
     static constexpr int MINW = (THREADS / 64 * WPC + 3) / 4;                         // waves per SIMD (register budget)
@@ -382,77 +382,64 @@ __global__ void __launch_bounds__(C::THREADS, C::MINW) conv_ringf_kernel(const R
 }
 
 // ------------------------------------------------------------------------------------------------ host side
+using RingfPlan = Planned<RingfParams>;
 template <class C>
-static int ringf_launch(RingfParams &rp, hipStream_t st) {
-    static PerDeviceFlag attr_set_dev;
-    bool &attr_set = attr_set_dev.cur();   // hipFuncSetAttribute acts on the CURRENT device's function object
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_ringf_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           C::LDS_BYTES);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(conv_ringf_kernel, %d B LDS): %s", C::LDS_BYTES, hipGetErrorString(e));
-            return PWS_EHIP;
-        }
-        attr_set = true;
-    }
-    static PerDeviceInt ncu_dev;
-    int &ncu = ncu_dev.cur();
-    if (ncu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-    }
-    rp.tiles_x = rp.LW / C::TW, rp.tiles_y = rp.LH / C::TH;   // whole tiles only (conv_ringf_try)
+static int ringf_run(const RingfParams &rp, const ConvChoice &c, hipStream_t st) { return launch_planned<&conv_ringf_kernel<C>>(rp, c, st, "conv_ringf_kernel"); }
+// the unit geometry of configuration C: persistent workgroups, C::WPC per CU
+template <class C>
+static void ringf_plan_cfg(RingfPlan &pl, int ncu) {
+    RingfParams &rp = pl.p;
+    rp.tiles_x = rp.LW / C::TW, rp.tiles_y = rp.LH / C::TH;   // whole tiles only (ringf_plan)
     rp.ncob = (unsigned)((rp.cout + C::CO_UNIT - 1) / C::CO_UNIT), rp.ncls = (unsigned)C::NCLS;
     rp.nunits = (unsigned)(rp.tiles_x * rp.tiles_y) * (unsigned)rp.N * rp.ncob * rp.ncls;
     int cin = 0;
     for (int s = 0; s < rp.nsrc; ++s) cin += rp.src_c[s];
     rp.gpp = cin / C::CKG;
     const unsigned slots = (unsigned)(ncu * C::WPC);
-    const unsigned grid = rp.nunits < slots ? rp.nunits : slots;   // persistent workgroups: C::WPC per CU
-    hipLaunchKernelGGL((conv_ringf_kernel<C>), dim3(grid), dim3(C::THREADS), C::LDS_BYTES, st, rp);
-    return check_launch("conv_ringf_kernel");
+    pl.c.grid[0] = rp.nunits < slots ? rp.nunits : slots, pl.c.grid[1] = pl.c.grid[2] = 1;
+    pl.c.threads = C::THREADS, pl.c.lds_bytes = C::LDS_BYTES;
+    pl.run = &ringf_run<C>;
 }
 
 template <int MODE>
-static int ringf_launch_tile(int th, int nt, bool half, RingfParams &rp, hipStream_t st) {
+static void ringf_plan_tile(int th, int nt, bool half, RingfPlan &pl, int ncu) {
     constexpr int KS2 = MODE != RF_K3S1;
     if constexpr (MODE == RF_K3S2) {
         if (half) {   // two workgroups per CU, LDS <= 80 KB each: the 64-channel units fit a ring of TWO groups only (the loader runs
                       // one group ahead, vmcnt(0) before each barrier); the 32-channel units keep a ring of four
-            if (th == 8) return ringf_launch<RfCfg<MODE, 8, 2, 2, 4>>(rp, st);     // 2 x 36 KB (A/B only: v = 2)
-            if (nt == 2) return ringf_launch<RfCfg<MODE, 4, 2, 2, 4>>(rp, st);     // 2 x 28 KB = 56 KB
-            return ringf_launch<RfCfg<MODE, 4, 4, 1, 4>>(rp, st);                  // 4 x 20 KB = 80 KB
+            if (th == 8) return ringf_plan_cfg<RfCfg<MODE, 8, 2, 2, 4>>(pl, ncu);     // 2 x 36 KB (A/B only: v = 2)
+            if (nt == 2) return ringf_plan_cfg<RfCfg<MODE, 4, 2, 2, 4>>(pl, ncu);     // 2 x 28 KB = 56 KB
+            return ringf_plan_cfg<RfCfg<MODE, 4, 4, 1, 4>>(pl, ncu);                  // 4 x 20 KB = 80 KB
         }
-        if (th == 8 && nt == 1) return ringf_launch<RfCfg<MODE, 8, 4, 1>>(rp, st);
+        if (th == 8 && nt == 1) return ringf_plan_cfg<RfCfg<MODE, 8, 4, 1>>(pl, ncu);
     }
-    if (th == 16) return ringf_launch<RfCfg<MODE, 16, KS2 ? 3 : 2>>(rp, st);
-    return ringf_launch<RfCfg<MODE, 8, KS2 ? 4 : 2>>(rp, st);
+    if (th == 16) return ringf_plan_cfg<RfCfg<MODE, 16, KS2 ? 3 : 2>>(pl, ncu);
+    return ringf_plan_cfg<RfCfg<MODE, 8, KS2 ? 4 : 2>>(pl, ncu);
 }
 
-// Runs the fp32 forward launch described by kp (prepared by conv2d_fwd_impl, conv_mfma.hip) on the fp32 ring kernel when it is
+// The fp32 forward launch described by kp (prepared by conv2d_fwd_impl, conv_dispatch.hip) on the fp32 ring kernel when it is
 // covered: NHWC fp32 sources (multiples of 16 channels, 16-byte aligned), maps at least 32 wide in whole tiles, enough units to
-// occupy the chip.  `prefer_other`: the caller has a faster specialised kernel for this launch when the map is large (Winograd for
-// the 3x3 kind).  Returns 1 when not covered.
-int conv_ringf_try(int kind, const ConvKParams &kp, hipStream_t st, const ProfInfo &pi) {
-    if (kp.io_bf16 || kp.ndst != 0 || exp_is(EXP_RINGF_OFF)) return 1;
+// occupy the chip.  (The ladder asks the Winograd kernels first for the 3x3 kind.)  The plan step: false when not covered.
+static bool ringf_plan(int kind, const ConvKParams &kp, int ncu, RingfPlan &pl) {
+    if (kp.io_bf16 || kp.ndst != 0 || exp_is(EXP_RINGF_OFF)) return false;
     for (int s = 0; s < kp.nsrc; ++s)
-        if (kp.src_ld[s] == 0 || kp.src_c[s] % 16 != 0 || kp.src_ld[s] % 4 != 0 || (reinterpret_cast<size_t>(kp.src_ptr[s]) & 15)) return 1;
-    if (kp.LW % 32 != 0 || kp.LH % 8 != 0 || kp.cout % 4 != 0) return 1;
+        if (kp.src_ld[s] == 0 || kp.src_c[s] % 16 != 0 || kp.src_ld[s] % 4 != 0 || (reinterpret_cast<size_t>(kp.src_ptr[s]) & 15)) return false;
+    if (kp.LW % 32 != 0 || kp.LH % 8 != 0 || kp.cout % 4 != 0) return false;
     // (8-byte stores of channel pairs through one buffer descriptor per output sample)
-    if (kp.out_ld % 2 != 0 || (reinterpret_cast<size_t>(kp.out) & 7) || (size_t)kp.OH * kp.OW * kp.out_ld * 4 >= (1u << 31)) return 1;
+    if (kp.out_ld % 2 != 0 || (reinterpret_cast<size_t>(kp.out) & 7) || (size_t)kp.OH * kp.OW * kp.out_ld * 4 >= (1u << 31)) return false;
     int mode, planes;
     if (kind == PWS_CONV_K3S1 || kind == PWS_CONVT_K3S1) mode = RF_K3S1, planes = 9;
     else if (kind == PWS_CONV_K3S2) mode = RF_K3S2, planes = 9;
     else if (kind == PWS_CONVT_K4S2) mode = RF_CT4, planes = 16;
-    else return 1;
+    else return false;
     for (int s = 0; s < kp.nsrc; ++s)
-        if ((size_t)kp.H * kp.W * 4 * kp.src_ld[s] >= (1u << 31)) return 1;
-    RingfParams rp{};
+        if ((size_t)kp.H * kp.W * 4 * kp.src_ld[s] >= (1u << 31)) return false;
+    RingfParams &rp = pl.p;
+    rp = RingfParams{};
     for (int s = 0; s < 4; ++s) rp.src_ptr[s] = kp.src_ptr[s], rp.src_c[s] = kp.src_c[s], rp.src_ld[s] = kp.src_ld[s];
     rp.nsrc = kp.nsrc, rp.N = kp.N, rp.H = kp.H, rp.W = kp.W, rp.LH = kp.LH, rp.LW = kp.LW, rp.OH = kp.OH, rp.OW = kp.OW;
     rp.cout = kp.cout, rp.cin_pad = kp.cin_pad, rp.w = kp.w, rp.w_bytes = (size_t)planes * kp.cin_pad * kp.cout * 4;
-    if (rp.w_bytes >= (1u << 31)) return 1;
+    if (rp.w_bytes >= (1u << 31)) return false;
     rp.bias = kp.bias, rp.act = kp.act, rp.out = kp.out, rp.out_ld = kp.out_ld;
     const long per256 = (long)kp.LW * kp.LH * kp.N / 256 * ((kp.cout + 63) / 64) * (mode == RF_CT4 ? 4 : 1);   // units of 8 x 32 tiles
     // 16 x 32 tiles when they still give every CU two units, else 8 x 32; too few even then: the split-K kernels do better
@@ -473,8 +460,8 @@ int conv_ringf_try(int kind, const ConvKParams &kp, hipStream_t st, const ProfIn
     else if (forced || (mode == RF_K3S2 && per256 >= 256)) th = 8;
     // (units of 32 output channels where 64-channel units fill only half the chip: 256 -> 256 @64^2 x 8 = 256 such units)
     else if (mode == RF_K3S2 && per256_32 >= 256) th = 8, nt = 1;
-    else return 1;
-    if (mode == RF_CT4 && !forced) return 1;
+    else return false;
+    if (mode == RF_CT4 && !forced) return false;
     // Stride-2 launches of 8 x 32 tiles (one unit per CU at the headline's shapes) run as HALF workgroups: 4 x 32 tiles, two
     // workgroups per CU with a barrier domain each, so one fills the matrix pipe while the other waits at its barrier or drains its
     // epilogue.  They leave a CU's LDS partly free (2 x 56 KB for 64-channel units; 2 x 80 KB for 32-channel units): in the bench's
@@ -493,12 +480,19 @@ int conv_ringf_try(int kind, const ConvKParams &kp, hipStream_t st, const ProfIn
         else if (v == 2) half = true;
     }
     if (half) th /= 2;
-    ProfScope prof(KID_CONV_RINGF, pi.flops, pi.bytes, st);
+    pl.c = conv_choice(KID_CONV_RINGF, mode, th, nt, half ? 1 : 0, dim3(0), 0, 0);
     switch (mode) {
-    case RF_K3S1: return ringf_launch_tile<RF_K3S1>(th, nt, false, rp, st);
-    case RF_CT4: return ringf_launch_tile<RF_CT4>(th, nt, false, rp, st);
-    default: return ringf_launch_tile<RF_K3S2>(th, nt, half, rp, st);
+    case RF_K3S1: ringf_plan_tile<RF_K3S1>(th, nt, false, pl, ncu); break;
+    case RF_CT4: ringf_plan_tile<RF_CT4>(th, nt, false, pl, ncu); break;
+    default: ringf_plan_tile<RF_K3S2>(th, nt, half, pl, ncu); break;
     }
+    return true;
+}
+
+bool conv_ringf(int kind, const ConvKParams &kp, const ProfInfo &pi, const ConvCtx &cx, int *status) {
+    RingfPlan pl;
+    if (!ringf_plan(kind, kp, cx.compute_units, pl)) return false;
+    return conv_accept(cx, pl.c, pi, status, [&] { return pl.run(pl.p, pl.c, cx.stream); });
 }
 
 }  // namespace pws

@@ -197,44 +197,32 @@ __global__ void __launch_bounds__(256) conv_skinny_kernel(const SkParams p) {
 }
 
 template <int MT_W, int NT_W, int WM>
-static int skinny_launch(const SkParams &p, unsigned grid, int lds_bytes, hipStream_t st) {
-    static PerDeviceFlag attr_set_dev;
-    bool &attr_set = attr_set_dev.cur();   // hipFuncSetAttribute acts on the CURRENT device's function object
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_skinny_kernel<MT_W, NT_W, WM>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(conv_skinny_kernel): %s", hipGetErrorString(e));
-            return PWS_EHIP;
-        }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((conv_skinny_kernel<MT_W, NT_W, WM>), dim3(grid), dim3(256), lds_bytes, st, p);
-    return check_launch("conv_skinny_kernel");
+static int skinny_run(const SkParams &p, const ConvChoice &c, hipStream_t st) {
+    return launch_planned<&conv_skinny_kernel<MT_W, NT_W, WM>>(p, c, st, "conv_skinny_kernel", 160 * 1024, false);
 }
 
-// Runs the fp32 forward launch described by kp (prepared by conv2d_fwd_impl, conv_mfma.hip) on the one-shot kernel when it is
+// The fp32 forward launch described by kp (prepared by conv2d_fwd_impl, conv_dispatch.hip) on the one-shot kernel when it is
 // covered: NHWC fp32 sources in multiples of 16 channels, at most 128 output pixels per parity class, cout a multiple of 4, and a
-// workspace for the K split.  Returns 1 when not covered (the caller runs conv_mfma_kernel's small tiles).
-int conv_skinny_try(int kind, ConvKParams &kp, float *final_out, float *ws, size_t ws_floats, hipStream_t st, const ProfInfo &pi) {
-    if (kp.io_bf16 || kp.ndst != 0 || exp_is(EXP_SKINNY_OFF)) return 1;
+// workspace for the K split.  The plan step: false when not covered (conv_mfma_kernel's small tiles are next).
+static bool skinny_plan(int kind, const ConvKParams &kp, float *final_out, float *ws, size_t ws_floats, SkParams &p, ConvChoice &c) {
+    if (kp.io_bf16 || kp.ndst != 0 || exp_is(EXP_SKINNY_OFF)) return false;
     int mode;
     if (kind == PWS_CONV_K3S1 || kind == PWS_CONVT_K3S1) mode = SK_K3S1;
     else if (kind == PWS_CONV_K3S2) mode = SK_K3S2;
     else if (kind == PWS_CONVT_K4S2) mode = SK_CT4;
-    else return 1;
+    else return false;
     const long M = (long)kp.N * kp.LH * kp.LW;
-    if (M < 1 || M > 128 || kp.cout % 4 != 0) return 1;
+    if (M < 1 || M > 128 || kp.cout % 4 != 0) return false;
     int cin = 0;
     for (int s = 0; s < kp.nsrc; ++s) {
-        if (kp.src_ld[s] == 0 || kp.src_c[s] % 16 != 0 || kp.src_ld[s] % 4 != 0 || (reinterpret_cast<size_t>(kp.src_ptr[s]) & 15)) return 1;
+        if (kp.src_ld[s] == 0 || kp.src_c[s] % 16 != 0 || kp.src_ld[s] % 4 != 0 || (reinterpret_cast<size_t>(kp.src_ptr[s]) & 15)) return false;
         cin += kp.src_c[s];
     }
-    if (cin != kp.cin_pad) return 1;
+    if (cin != kp.cin_pad) return false;
     const int ntaps = mode == SK_CT4 ? 4 : 9, ncls = mode == SK_CT4 ? 4 : 1;
     const size_t w_bytes = (size_t)(mode == SK_CT4 ? 16 : 9) * kp.cin_pad * kp.cout * 4;
-    if (w_bytes >= (1u << 31)) return 1;
-    SkParams p{};
+    if (w_bytes >= (1u << 31)) return false;
+    p = SkParams{};
     for (int s = 0; s < 4; ++s) p.src_ptr[s] = kp.src_ptr[s], p.src_c[s] = kp.src_c[s], p.src_ld[s] = kp.src_ld[s];
     p.nsrc = kp.nsrc, p.N = kp.N, p.H = kp.H, p.W = kp.W, p.LH = kp.LH, p.LW = kp.LW, p.OH = kp.OH, p.OW = kp.OW, p.mode = mode;
     p.cin_pad = kp.cin_pad, p.cout = kp.cout, p.w = kp.w, p.w_bytes = (unsigned)w_bytes, p.bias = kp.bias, p.act = kp.act, p.out_ld = kp.out_ld;
@@ -250,25 +238,37 @@ int conv_skinny_try(int kind, ConvKParams &kp, float *final_out, float *ws, size
     if (ksplit < kmin) ksplit = kmin;
     const size_t out_floats = (size_t)kp.N * kp.OH * kp.OW * kp.cout;
     if (ksplit > 1 && (!ws || (size_t)ksplit * out_floats > ws_floats)) {
-        if (!ws || (size_t)kmin * out_floats > ws_floats) return 1;
+        if (!ws || (size_t)kmin * out_floats > ws_floats) return false;
         ksplit = (int)(ws_floats / out_floats);
     }
     p.cps = (int)cdiv(p.nchunks, ksplit);
     p.ksplit = (int)cdiv(p.nchunks, p.cps);   // no empty splits
-    if (p.cps > maxc) return 1;
+    if (p.cps > maxc) return false;
     p.split_stride = out_floats;
     p.out = p.ksplit > 1 ? ws : final_out;
-    const unsigned grid = (unsigned)(blocks1 * p.ksplit);
-    const int lds_bytes = p.cps * ntaps * 4096;
-    if (exp_is(EXP_SKINNY_SKIP)) return PWS_OK;   // TIMING ONLY: the launch is skipped (what the deep levels cost end to end)
-    ProfScope prof(KID_CONV_SKINNY, pi.flops, pi.bytes, st);   // covers the split-K reduce as well
-    int rc;
-    if (M <= 16) rc = skinny_launch<1, 1, 1>(p, grid, lds_bytes, st);
-    else if (M <= 32) rc = skinny_launch<1, 2, 2>(p, grid, lds_bytes, st);
-    else rc = skinny_launch<2, 4, 4>(p, grid, lds_bytes, st);
-    if (rc != PWS_OK || p.ksplit == 1) return rc;
-    kp.ksplit = p.ksplit, kp.split_stride = out_floats, kp.out = final_out;
-    return launch_splitk_reduce(kp, ws, out_floats / 4, st);
+    const int v = M <= 16 ? 0 : (M <= 32 ? 1 : 2);   // <MT_W, NT_W, WM> = <1, 1, 1> / <1, 2, 2> / <2, 4, 4>
+    c = conv_choice(KID_CONV_SKINNY, v == 2 ? 2 : 1, v == 0 ? 1 : 2 * v, v == 0 ? 1 : 2 * v, ntaps, dim3((unsigned)(blocks1 * p.ksplit)), 256,
+                    p.cps * ntaps * 4096, p.ksplit, p.ksplit > 1 ? PWS_FOLLOW_REDUCE : PWS_FOLLOW_NONE);
+    return true;
+}
+
+bool conv_skinny(int kind, ConvKParams &kp, float *final_out, float *ws, size_t ws_floats, const ProfInfo &pi, const ConvCtx &cx, int *status) {
+    SkParams p;
+    ConvChoice c;
+    if (!skinny_plan(kind, kp, final_out, ws, ws_floats, p, c)) return false;
+    if (exp_is(EXP_SKINNY_SKIP)) {   // TIMING ONLY: the launch is skipped (what the deep levels cost end to end)
+        conv_report(cx, c), *status = PWS_OK;
+        return true;
+    }
+    return conv_accept(cx, c, pi, status, [&] {
+        int rc;
+        if (c.variant[1] == 1) rc = skinny_run<1, 1, 1>(p, c, cx.stream);
+        else if (c.variant[1] == 2) rc = skinny_run<1, 2, 2>(p, c, cx.stream);
+        else rc = skinny_run<2, 4, 4>(p, c, cx.stream);
+        if (rc != PWS_OK || p.ksplit == 1) return rc;
+        kp.ksplit = p.ksplit, kp.split_stride = p.split_stride, kp.out = final_out;
+        return launch_splitk_reduce(kp, ws, p.split_stride / 4, cx.stream);
+    });
 }
 
 }  // namespace pws

@@ -192,52 +192,39 @@ __global__ void __launch_bounds__(256) conv_skinny16_kernel(const Sk16Params p) 
 }
 
 template <int MT_W, int NT_W, int WM, int MAXT>
-static int skinny16_launch(const Sk16Params &p, unsigned grid, int lds_bytes, hipStream_t st) {
-    static PerDeviceFlag attr_set_dev;
-    bool &attr_set = attr_set_dev.cur();   // hipFuncSetAttribute acts on the CURRENT device's function object
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_skinny16_kernel<MT_W, NT_W, WM, MAXT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(conv_skinny16_kernel): %s", hipGetErrorString(e));
-            return PWS_EHIP;
-        }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((conv_skinny16_kernel<MT_W, NT_W, WM, MAXT>), dim3(grid), dim3(256), lds_bytes, st, p);
-    return check_launch("conv_skinny16_kernel");
+static int skinny16_run(const Sk16Params &p, const ConvChoice &c, hipStream_t st) {
+    return launch_planned<&conv_skinny16_kernel<MT_W, NT_W, WM, MAXT>>(p, c, st, "conv_skinny16_kernel", 160 * 1024, false);
 }
 
-// Runs the bf16 launch described by kp (prepared by conv2d_fwd_impl / conv2d_bwd_data_impl, conv_mfma.hip) on the one-shot kernel
+// The bf16 launch described by kp (prepared by conv2d_fwd_impl / conv2d_bwd_data_impl, conv_dispatch.hip) on the one-shot kernel
 // when it is covered: bf16 storage, a map of at most 8 x 8 pixels per class and at most 4096 pixels in all, sources in multiples of
 // 32 channels, a workspace for the partial sums.  kchan: channels of the contraction (forward: cin; data gradient: the forward
-// layer's cout).  Returns 1 when not covered (the caller runs conv_bf16_kernel's small tiles).  PWS_OPT_EXPERIMENT 71 switches it off.
-int conv_skinny16_try(int kind, bool dgrad, ConvKParams &kp, int kchan, float *final_out, float *ws, size_t ws_floats, hipStream_t st,
-                      const ProfInfo &pi) {
-    if (!kp.io_bf16 || exp_is(EXP_SKINNY16_OFF) || !ws) return 1;
-    Sk16Params p{};
+// layer's cout).  The plan step: false when not covered (conv_bf16_kernel's small tiles are next).  PWS_OPT_EXPERIMENT 71 switches it off.
+static bool skinny16_plan(int kind, bool dgrad, const ConvKParams &kp, int kchan, float *ws, size_t ws_floats, Sk16Params &p, ConvChoice &c) {
+    if (!kp.io_bf16 || exp_is(EXP_SKINNY16_OFF) || !ws) return false;
+    p = Sk16Params{};
     if (kind == PWS_CONV_K3S1 || kind == PWS_CONVT_K3S1) p.ks = 3, p.stride = 1, p.pad = 1, p.subpix = 0;
     else if (kind == PWS_CONV_K3S2 && !dgrad) p.ks = 3, p.stride = 2, p.pad = 1, p.subpix = 0;
     else if (kind == PWS_CONV_K3S2) p.ks = 2, p.stride = 1, p.pad = 0, p.subpix = 2;
     else if (kind == PWS_CONVT_K4S2 && !dgrad) p.ks = 2, p.stride = 1, p.pad = 0, p.subpix = 1;
     else if (kind == PWS_CONVT_K4S2) p.ks = 4, p.stride = 2, p.pad = 1, p.subpix = 0;
-    else return 1;
-    if (kp.LH > 8 || kp.LW > 8) return 1;
+    else return false;
+    if (kp.LH > 8 || kp.LW > 8) return false;
     const long M = (long)kp.N * kp.LH * kp.LW;
     // Measured at batch 64 (tools/layer_profile.py --batch 64 --math bf16 --train): 64 .. 256 pixels per class 16 - 30 us against 21 - 35 us
     // of conv_bf16_kernel, 1024 pixels +-10 % either way, 4096 pixels 2 - 3.5x SLOWER (an A operand gathered per tap and lane re-reads
     // the input nine times, and every 128-pixel block fetches the layer's weights again): small M only (PWS_OPT_EXPERIMENT 72: up to 4096)
     const long mmax = exp_is(EXP_SKINNY16_4096) ? 4096 : 256;
-    if (M < 1 || M > mmax || kp.cout % 4 != 0 || kchan % 32 != 0) return 1;
+    if (M < 1 || M > mmax || kp.cout % 4 != 0 || kchan % 32 != 0) return false;
     int cin = 0;
     for (int s = 0; s < kp.nsrc; ++s) {
-        if (kp.src_ld[s] == 0 || kp.src_c[s] % 32 != 0 || kp.src_ld[s] % 8 != 0 || (reinterpret_cast<size_t>(kp.src_ptr[s]) & 15)) return 1;
+        if (kp.src_ld[s] == 0 || kp.src_c[s] % 32 != 0 || kp.src_ld[s] % 8 != 0 || (reinterpret_cast<size_t>(kp.src_ptr[s]) & 15)) return false;
         cin += kp.src_c[s];
     }
-    if (cin != kchan || kchan > kp.kpad_bf) return 1;
+    if (cin != kchan || kchan > kp.kpad_bf) return false;
     const int ntaps = p.ks * p.ks, ncls = p.subpix ? 4 : 1;
     const size_t w_bytes = (size_t)ncls * ntaps * kp.npad_bf * kp.kpad_bf * 2;
-    if (w_bytes >= (1u << 31) || (size_t)64 * kp.kpad_bf * 2 >= (1u << 24)) return 1;
+    if (w_bytes >= (1u << 31) || (size_t)64 * kp.kpad_bf * 2 >= (1u << 24)) return false;
     for (int s = 0; s < 4; ++s) p.src_ptr[s] = kp.src_ptr[s], p.src_c[s] = kp.src_c[s], p.src_ld[s] = kp.src_ld[s];
     p.nsrc = kp.nsrc, p.N = kp.N, p.H = kp.H, p.W = kp.W, p.LH = kp.LH, p.LW = kp.LW, p.OH = kp.OH, p.OW = kp.OW;
     p.kpad = kp.kpad_bf, p.npad = kp.npad_bf, p.cout = kp.cout, p.w = kp.w_bf, p.w_bytes = (unsigned)w_bytes;
@@ -255,26 +242,37 @@ int conv_skinny16_try(int kind, bool dgrad, ConvKParams &kp, int kchan, float *f
     if (ksplit < kmin) ksplit = kmin;
     const size_t out_floats = (size_t)kp.N * kp.OH * kp.OW * kp.cout;
     if ((size_t)ksplit * out_floats > ws_floats) {
-        if ((size_t)kmin * out_floats > ws_floats) return 1;
+        if ((size_t)kmin * out_floats > ws_floats) return false;
         ksplit = (int)(ws_floats / out_floats);
     }
     p.cps = (int)cdiv(p.nchunks, ksplit);
     p.ksplit = (int)cdiv(p.nchunks, p.cps);   // no empty splits
-    if (p.cps > maxc) return 1;
+    if (p.cps > maxc) return false;
     p.split_stride = out_floats;
     p.out = ws;
-    const unsigned grid = (unsigned)(blocks1 * p.ksplit);
-    const int lds_bytes = p.cps * ntaps * 4096;
-    ProfScope prof(KID_CONV_SKINNY16, pi.flops, pi.bytes, st);   // covers the split-K reduce as well
-    int rc;
-    if (ntaps == 16) rc = skinny16_launch<1, 4, 4, 16>(p, grid, lds_bytes, st);
-    else if (M <= 16) rc = skinny16_launch<1, 1, 1, 9>(p, grid, lds_bytes, st);
-    else if (M <= 32) rc = skinny16_launch<1, 2, 2, 9>(p, grid, lds_bytes, st);
-    else rc = skinny16_launch<2, 4, 4, 9>(p, grid, lds_bytes, st);
-    if (rc != PWS_OK) return rc;
-    // the ordinary epilogue (bias + activation / the data gradient's scatter) runs in the reduce, also for a single split
-    kp.ksplit = p.ksplit, kp.chunks_per_split = p.cps, kp.split_stride = out_floats, kp.out = final_out;
-    return launch_splitk_reduce(kp, ws, out_floats / 4, st);
+    const int v = ntaps == 16 ? 3 : (M <= 16 ? 0 : (M <= 32 ? 1 : 2));   // <MT_W, NT_W, WM, MAXT> = <1, 1, 1, 9> / <1, 2, 2, 9> / <2, 4, 4, 9> / <1, 4, 4, 16>
+    const int nt_w = v == 0 ? 1 : (v == 1 ? 2 : 4);
+    // (the ordinary epilogue -- bias + activation / the data gradient's scatter -- runs in the reduce, also for a single split)
+    c = conv_choice(KID_CONV_SKINNY16, v == 2 ? 2 : 1, nt_w, nt_w, v == 3 ? 16 : 9, dim3((unsigned)(blocks1 * p.ksplit)), 256, p.cps * ntaps * 4096,
+                    p.ksplit, PWS_FOLLOW_REDUCE);
+    return true;
+}
+
+bool conv_skinny16(int kind, bool dgrad, ConvKParams &kp, int kchan, float *final_out, float *ws, size_t ws_floats, const ProfInfo &pi,
+                   const ConvCtx &cx, int *status) {
+    Sk16Params p;
+    ConvChoice c;
+    if (!skinny16_plan(kind, dgrad, kp, kchan, ws, ws_floats, p, c)) return false;
+    kp.ksplit = p.ksplit, kp.chunks_per_split = p.cps, kp.split_stride = p.split_stride, kp.out = final_out;   // what the reduce (and the caller's sign pass) go by
+    return conv_accept(cx, c, pi, status, [&] {
+        int rc;
+        if (c.variant[3] == 16) rc = skinny16_run<1, 4, 4, 16>(p, c, cx.stream);
+        else if (c.variant[1] == 1) rc = skinny16_run<1, 1, 1, 9>(p, c, cx.stream);
+        else if (c.variant[1] == 2) rc = skinny16_run<1, 2, 2, 9>(p, c, cx.stream);
+        else rc = skinny16_run<2, 4, 4, 9>(p, c, cx.stream);
+        if (rc != PWS_OK) return rc;
+        return launch_splitk_reduce(kp, ws, p.split_stride / 4, cx.stream);
+    });
 }
 
 }  // namespace pws

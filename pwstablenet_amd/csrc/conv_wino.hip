@@ -26,7 +26,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "conv_common.h"
 
 namespace pws {
 
@@ -365,29 +365,16 @@ __global__ void wino_pack_ct4_kernel(const float *__restrict__ pk, float *__rest
 }
 
 template <int MODE>
-static int wino_launch(WinoParams &p, int cout, const ProfHint &ph, hipStream_t st) {
+static void wino_plan_geo(WinoParams &p, ConvChoice &c) {
     using G = WinoGeo<MODE>;
     p.tiles_x = (p.W + G::TW - 1) / G::TW, p.tiles_y = (p.H + G::TH - 1) / G::TH;
     p.ntiles = (unsigned)(p.tiles_x * p.tiles_y * p.N);
-    static PerDeviceFlag attr_set_dev;
-    bool &attr_set = attr_set_dev.cur();   // hipFuncSetAttribute acts on the CURRENT device's function object
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&wino_kernel<MODE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(wino_kernel<%d>): %s", MODE, hipGetErrorString(e));
-            return PWS_EHIP;
-        }
-        attr_set = true;
-    }
-    ProfScope prof(MODE == 0 ? KID_CONV_WINO : KID_CONV_WINO_CT4, ph.flops, ph.bytes, st);
-    hipLaunchKernelGGL(wino_kernel<MODE>, dim3(p.ntiles, (cout + 63) / 64, MODE == 1 ? 4 : 1), dim3(256), G::LDS_BYTES, st, p);
-    return check_launch("wino_kernel");
+    c = conv_choice(MODE == 0 ? KID_CONV_WINO : KID_CONV_WINO_CT4, MODE, 0, 0, 0, dim3(p.ntiles, (p.cout + 63) / 64, MODE == 1 ? 4 : 1), 256, G::LDS_BYTES);
 }
 
-// Called by conv2d_fwd_impl for eligible launches (K3S1 / CONVT_K3S1: F(2x2,3x3); CONVT_K4S2: F(3x3,2x2) per parity class);
-// returns PWS_OK after launching, or a negative error.
-int wino_k3s1_launch(const pws_conv_args *a, const ProfHint &ph, hipStream_t st) {
+// The first-generation Winograd kernel (K3S1 / CONVT_K3S1: F(2x2,3x3); CONVT_K4S2: F(3x3,2x2) per parity class).  It has no coverage
+// test of its own: the ladder (conv_dispatch.hip) calls it for the launches it is meant for, and it takes them.
+bool conv_wino(const pws_conv_args *a, const ProfInfo &pi, const ConvCtx &cx, int *status) {
     WinoParams p{};
     p.nsrc = a->nsrc;
     int cin = 0;
@@ -398,7 +385,13 @@ int wino_k3s1_launch(const pws_conv_args *a, const ProfHint &ph, hipStream_t st)
     p.N = a->n, p.H = a->h, p.W = a->w, p.cin_pad = (cin + 15) / 16 * 16, p.cout = a->cout;
     p.uw = a->w_wino, p.bias = a->bias, p.out = a->out, p.out_ld = a->out_ld, p.act = a->act;
     p.ablate = exp_mask(EXP_WINO_ABLATE, 16);
-    return a->kind == PWS_CONVT_K4S2 ? wino_launch<1>(p, a->cout, ph, st) : wino_launch<0>(p, a->cout, ph, st);
+    const bool ct4 = a->kind == PWS_CONVT_K4S2;
+    ConvChoice c;
+    if (ct4) wino_plan_geo<1>(p, c);
+    else wino_plan_geo<0>(p, c);
+    return conv_accept(cx, c, pi, status, [&] {
+        return ct4 ? launch_planned<&wino_kernel<1>>(p, c, cx.stream, "wino_kernel<1>", 0, false) : launch_planned<&wino_kernel<0>>(p, c, cx.stream, "wino_kernel<0>", 0, false);
+    });
 }
 
 }  // namespace pws

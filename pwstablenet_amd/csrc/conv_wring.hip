@@ -544,58 +544,43 @@ int wring_pack(const float *pk, float *ur, int cin_pad, int cout, int ct4, hipSt
 }
 
 template <int MODE, int G16, int ABL>
-static int wring_launch(const WringParams &p, unsigned grid, hipStream_t st) {
-    using G = WrGeo<MODE, G16>;
-    static PerDeviceFlag attr_set_dev;
-    bool &attr_set = attr_set_dev.cur();   // hipFuncSetAttribute acts on the CURRENT device's function object
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&wino_ring_kernel<MODE, G16, ABL>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           G::LDS_BYTES);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(wino_ring_kernel, %d B LDS): %s", G::LDS_BYTES, hipGetErrorString(e));
-            return PWS_EHIP;
-        }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((wino_ring_kernel<MODE, G16, ABL>), dim3(grid), dim3(WR_WAVES * 64), G::LDS_BYTES, st, p);
-    return check_launch("wino_ring_kernel");
+static int wring_run(const WringParams &p, const ConvChoice &c, hipStream_t st) { return launch_planned<&wino_ring_kernel<MODE, G16, ABL>>(p, c, st, "wino_ring_kernel"); }
+using WringRun = int (*)(const WringParams &, const ConvChoice &, hipStream_t);
+template <int MODE, int G16, int ABL = 0>
+static WringRun wring_pick(ConvChoice &c) {
+    c.threads = WR_WAVES * 64, c.lds_bytes = WrGeo<MODE, G16>::LDS_BYTES;
+    return &wring_run<MODE, G16, ABL>;
 }
 
-// Runs a 3x3 stride-1 (Winograd F(2x2,3x3)) or transposed k4 s2 (F(2x2,2x2) per parity class) forward launch on the Winograd ring
+// A 3x3 stride-1 (Winograd F(2x2,3x3)) or transposed k4 s2 (F(2x2,2x2) per parity class) forward launch on the Winograd ring
 // kernel when it is covered: fp32 NHWC sources in multiples of 16 channels (16-byte aligned), an input map of whole units -- 16 x 32
 // pixels of one sample, or 16 x 16 pixels of two samples for 16-pixel-wide maps --, cout a multiple of 32, 8-byte aligned output
 // pixels, a->w_wring (pws_pack_conv_weight_wring) and enough units to occupy the chip, if need be by splitting K over units
 // (partial sums in a->ws, added by splitk_reduce_kernel).
-// Returns 1 when not covered (the caller goes on to the first-generation Winograd kernel / the direct kernels).
-int wring_try(const pws_conv_args *a, const ProfHint &ph, hipStream_t st) {
-    if (!a->w_wring || exp_is(EXP_WRING_OFF)) return 1;
+// The plan step: false when not covered (the ladder goes on to the first-generation Winograd kernel / the direct kernels); *status = PWS_EINVAL for an
+// ablation mask that is not instantiated.
+static bool wring_plan(const pws_conv_args *a, int ncu, WringParams &p, ConvChoice &c, WringRun *run, int *status) {
+    if (!a->w_wring || exp_is(EXP_WRING_OFF)) return false;
     const bool ct4 = a->kind == PWS_CONVT_K4S2;
-    if (!ct4 && a->kind != PWS_CONV_K3S1 && a->kind != PWS_CONVT_K3S1) return 1;
+    if (!ct4 && a->kind != PWS_CONV_K3S1 && a->kind != PWS_CONVT_K3S1) return false;
     const bool g16 = a->w == 16 && a->n % 2 == 0;
-    if (a->h % WR_TH != 0 || (!g16 && a->w % WR_TW != 0) || a->cout % 32 != 0 || a->out_ld % 2 != 0 || (reinterpret_cast<size_t>(a->out) & 7)) return 1;
+    if (a->h % WR_TH != 0 || (!g16 && a->w % WR_TW != 0) || a->cout % 32 != 0 || a->out_ld % 2 != 0 || (reinterpret_cast<size_t>(a->out) & 7)) return false;
     int cin = 0;
     for (int s = 0; s < a->nsrc; ++s) {
         const pws_src &sr = a->src[s];
-        if (sr.channels % 16 != 0 || sr.ld % 4 != 0 || (reinterpret_cast<size_t>(sr.ptr) & 15)) return 1;
-        if ((size_t)a->h * a->w * 4 * sr.ld * 2 >= (1u << 31)) return 1;
+        if (sr.channels % 16 != 0 || sr.ld % 4 != 0 || (reinterpret_cast<size_t>(sr.ptr) & 15)) return false;
+        if ((size_t)a->h * a->w * 4 * sr.ld * 2 >= (1u << 31)) return false;
         cin += sr.channels;
     }
     const size_t plane = (size_t)cin * a->cout;
     const size_t ur_bytes = (size_t)(ct4 ? 36 : 16) * plane * 4;
-    if (ur_bytes >= (1u << 31)) return 1;
-    WringParams p{};
+    if (ur_bytes >= (1u << 31)) return false;
+    p = WringParams{};
     for (int s = 0; s < a->nsrc; ++s) p.src_ptr[s] = a->src[s].ptr, p.src_c[s] = a->src[s].channels, p.src_ld[s] = a->src[s].ld;
     p.nsrc = a->nsrc, p.N = a->n, p.H = a->h, p.W = a->w, p.cout = a->cout;
     p.ur = a->w_wring, p.ur_bytes = (unsigned)ur_bytes;
     p.bias = a->bias, p.act = a->act, p.out = a->out, p.out_ld = a->out_ld;
     p.tiles_x = g16 ? 1 : a->w / WR_TW, p.tiles_y = a->h / WR_TH;
-    static PerDeviceInt ncu_dev;
-    int &ncu = ncu_dev.cur();
-    if (ncu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-    }
     p.ncob = (unsigned)(a->cout / 32), p.ncls = ct4 ? 2u : 1u;
     const unsigned tiles = (unsigned)(p.tiles_x * p.tiles_y) * (unsigned)(g16 ? a->n / 2 : a->n);
     unsigned units1 = tiles * p.ncob * p.ncls;
@@ -634,42 +619,54 @@ int wring_try(const pws_conv_args *a, const ProfHint &ph, hipStream_t st) {
     p.ablate = exp_mask(EXP_WRING_ABLATE, 1024);
     // a unit is cps x 8 192 (9 216) matrix cycles: fewer units than CUs leave CUs idle for the whole launch, and a non-integer
     // number of rounds costs its tail -- taken from 3/4 of the chip upwards (PWS_OPT_EXPERIMENT 58 / 59 force it for the tests)
-    if (p.nunits < (unsigned)(ncu * 3 / 4) && !exp_is(EXP_WRING_FORCE) && !exp_is(EXP_WRING_MODE2)) return 1;
-    ProfScope prof(ct4 ? KID_CONV_WRING_CT4 : KID_CONV_WRING, ph.flops, ph.bytes, st);   // covers the split-K reduce as well
-    const unsigned grid = p.nunits < (unsigned)ncu ? p.nunits : (unsigned)ncu;   // one persistent workgroup per CU
-    int rc;
+    if (p.nunits < (unsigned)(ncu * 3 / 4) && !exp_is(EXP_WRING_FORCE) && !exp_is(EXP_WRING_MODE2)) return false;
     const int mode = mode2 ? 2 : (ct4 ? 1 : 0);
+    c = conv_choice(ct4 ? KID_CONV_WRING_CT4 : KID_CONV_WRING, mode, g16 ? 1 : 0, p.ablate, 0, dim3(p.nunits < (unsigned)ncu ? p.nunits : (unsigned)ncu), 0, 0,
+                    ksplit, ksplit > 1 ? PWS_FOLLOW_REDUCE : PWS_FOLLOW_NONE);   // one persistent workgroup per CU
     if (p.ablate == 0) {
         switch (mode * 2 + (g16 ? 1 : 0)) {
-        case 0: rc = wring_launch<0, 0, 0>(p, grid, st); break;
-        case 1: rc = wring_launch<0, 1, 0>(p, grid, st); break;
-        case 2: rc = wring_launch<1, 0, 0>(p, grid, st); break;
-        case 3: rc = wring_launch<1, 1, 0>(p, grid, st); break;
-        case 4: rc = wring_launch<2, 0, 0>(p, grid, st); break;
-        default: rc = wring_launch<2, 1, 0>(p, grid, st); break;
+        case 0: *run = wring_pick<0, 0>(c); break;
+        case 1: *run = wring_pick<0, 1>(c); break;
+        case 2: *run = wring_pick<1, 0>(c); break;
+        case 3: *run = wring_pick<1, 1>(c); break;
+        case 4: *run = wring_pick<2, 0>(c); break;
+        default: *run = wring_pick<2, 1>(c); break;
         }
     } else if (mode == 0 && !g16) {   // timing-only ablations (tools/wring_ablate.sh)
         switch (p.ablate) {
-        case 1: rc = wring_launch<0, 0, 1>(p, grid, st); break;
-        case 2: rc = wring_launch<0, 0, 2>(p, grid, st); break;
-        case 4: rc = wring_launch<0, 0, 4>(p, grid, st); break;
-        case 24: rc = wring_launch<0, 0, 24>(p, grid, st); break;
-        case 88: rc = wring_launch<0, 0, 88>(p, grid, st); break;
-        case 64: rc = wring_launch<0, 0, 64>(p, grid, st); break;
-        case 96: rc = wring_launch<0, 0, 96>(p, grid, st); break;
-        case 120: rc = wring_launch<0, 0, 120>(p, grid, st); break;
-        case 512: rc = wring_launch<0, 0, 512>(p, grid, st); break;
-        default: set_error("wino_ring_kernel<0>: ablation mask %d is not instantiated", p.ablate); return PWS_EINVAL;
+        case 1: *run = wring_pick<0, 0, 1>(c); break;
+        case 2: *run = wring_pick<0, 0, 2>(c); break;
+        case 4: *run = wring_pick<0, 0, 4>(c); break;
+        case 24: *run = wring_pick<0, 0, 24>(c); break;
+        case 88: *run = wring_pick<0, 0, 88>(c); break;
+        case 64: *run = wring_pick<0, 0, 64>(c); break;
+        case 96: *run = wring_pick<0, 0, 96>(c); break;
+        case 120: *run = wring_pick<0, 0, 120>(c); break;
+        case 512: *run = wring_pick<0, 0, 512>(c); break;
+        default: set_error("wino_ring_kernel<0>: ablation mask %d is not instantiated", p.ablate); *status = PWS_EINVAL; break;
         }
     } else {
         set_error("wino_ring_kernel: ablations are instantiated for F(2x2,3x3) on 32-pixel-wide maps only");
-        return PWS_EINVAL;
+        *status = PWS_EINVAL;
     }
-    if (rc != PWS_OK || ksplit == 1) return rc;
-    ConvKParams kp{};
-    kp.cout = a->cout, kp.bias = a->bias, kp.out = a->out, kp.out_ld = a->out_ld, kp.act = a->act;
-    kp.ksplit = ksplit, kp.split_stride = out_floats;
-    return launch_splitk_reduce(kp, static_cast<const float *>(a->ws), out_floats / 4, st);
+    return true;
+}
+
+bool conv_wring(const pws_conv_args *a, const ProfInfo &pi, const ConvCtx &cx, int *status) {
+    WringParams p;
+    ConvChoice c;
+    WringRun run = nullptr;
+    *status = PWS_OK;
+    if (!wring_plan(a, cx.compute_units, p, c, &run, status)) return false;
+    if (*status != PWS_OK) return true;
+    return conv_accept(cx, c, pi, status, [&] {
+        const int rc = run(p, c, cx.stream);
+        if (rc != PWS_OK || p.ksplit == 1) return rc;
+        ConvKParams kp{};
+        kp.cout = a->cout, kp.bias = a->bias, kp.out = a->out, kp.out_ld = a->out_ld, kp.act = a->act;
+        kp.ksplit = p.ksplit, kp.split_stride = p.split_stride;
+        return launch_splitk_reduce(kp, static_cast<const float *>(a->ws), p.split_stride / 4, cx.stream);
+    });
 }
 
 }  // namespace pws

@@ -708,13 +708,7 @@ extern "C" int pws_field_head_fwd_s(const float *x, int ld, int n, int h, int w,
                    (double)n * h * w * (4.0 * c + (resid ? 8.0 : 0.0) + (grid ? 8.0 : 0.0)), as_stream(stream));
     // the matrix-core kernels are persistent: 3 workgroups per CU (registers), a multiple of the XCD count (see the kernels);
     // PWS_OPT_EXPERIMENT 92: one tile per workgroup
-    static PerDeviceInt ncu_dev;
-    int &ncu = ncu_dev.cur();
-    if (ncu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-    }
+    const int ncu = device_cus();
     unsigned pgrid = ntiles;
     if (!exp_is(EXP_HEAD_ONE_TILE) && ntiles > (unsigned)(ncu * 3)) {   // equal shares: k tiles per workgroup, as few workgroups as that takes
         const unsigned k = (ntiles + (unsigned)(ncu * 3) - 1) / (unsigned)(ncu * 3);

@@ -639,13 +639,7 @@ int field_bwd_dx_dw(const float *x, int ld, const float *gz, int n, int h, int w
         const int tiles_x = (w + FQ_T - 1) / FQ_T, tiles_y = (h + FQ_T - 1) / FQ_T;
         const long ntiles = (long)tiles_x * tiles_y * n;
         PWS_REQUIRE(ntiles < (1L << 30), "pws_field_head_bwd: too many tiles");
-        static PerDeviceInt ncu_dev;
-        int &ncu = ncu_dev.cur();
-        if (ncu == 0) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-        }
+        const int ncu = device_cus();
         long gx = 3L * ncu;   // three resident workgroups per CU (51 KB of LDS each), each walks ntiles / gx tiles
         if (gx > ntiles) gx = ntiles;
         if (t_deterministic) gx = 1;   // one adding workgroup

@@ -175,14 +175,17 @@ struct Arena {
     char *ws = nullptr;
     size_t bytes = 0;
 };
-// EXEC_SIZE: no arena -- sizes, offsets and the tape only; EXEC_REPLAY: every address, no launch (the backward); EXEC_RUN: the forward
-enum ExecMode { EXEC_SIZE, EXEC_REPLAY, EXEC_RUN };
+// EXEC_SIZE: no arena -- sizes, offsets and the tape only; EXEC_REPLAY: every address, no launch (the backward); EXEC_RUN: the forward;
+// EXEC_PLAN: like EXEC_REPLAY over a stand-in arena, and every conv asks the dispatch ladder what it would launch (pws_netg_forward_plan)
+enum ExecMode { EXEC_SIZE, EXEC_REPLAY, EXEC_RUN, EXEC_PLAN };
+// the stand-in base of arena, weights and window in EXEC_PLAN: non-null and 256-byte aligned, as the real entry points require -- never dereferenced
+inline char *plan_base(int which) { return reinterpret_cast<char *>((size_t)(which + 1) << 40); }   // 0 arena, 1 weights, 2 window
 
 class Exec {
   public:
     Exec(const float *packed, const LayerTable &layers, int n, Arena arena, hipStream_t st, ExecMode mode, const NetgOpts &o, const BnCfg *bn = nullptr)
         : math_(o.math), x_sstride_(o.x_sample_stride), prune_dead_(o.prune_dead), packed_(packed), L_(layers), n_(n), ws_(arena.ws), cap_(arena.bytes),
-          dry_(mode == EXEC_SIZE), launch_(mode == EXEC_RUN) {
+          dry_(mode == EXEC_SIZE), launch_(mode == EXEC_RUN), plan_(mode == EXEC_PLAN) {
         if (bn) {
             bn_on_ = true, bn_ = *bn;
             size_t off = 0;
@@ -221,6 +224,8 @@ class Exec {
     size_t used() const { return off_; }
     int rc() const { return rc_; }
     const std::vector<Op> &tape() const { return tape_; }
+    void plan_for(int compute_units) { plan_cus_ = compute_units; }
+    const std::vector<ConvChoice> &plan() const { return plan_out_; }
     float *splitk_ws() const { return splitk_ws_; }
     float *x_nhwc() const { return x_nhwc_; }
     bool io16() const { return io16_; }
@@ -347,12 +352,12 @@ class Exec {
         if (bn_on_) op.aux[0] = alloc((size_t)n_ * oh * ow * l.cout), op.aux[1] = alloc(2 * (size_t)l.cout);
         tape_.push_back(op);
         for (int k = 1; k < ngroups; ++k) tape_.push_back(Op{OP_CONV, layer, act, 0, false, shifted(x, k), shifted(o, k)});
-        if (!launch_ || rc_ != PWS_OK) return o;
+        if (!(launch_ || plan_) || rc_ != PWS_OK) return o;
         pws_conv_args a{};
         a.kind = l.kind, a.n = ngroups * n_, a.h = x.h, a.w = x.w;
         if (nchw_c > 0 && math_ == PWS_MATH_BF16 && l.wb_off != (size_t)-1 && x_nhwc_ && nchw_c <= 32) {
             // bf16 first layer: the NCHW window is re-laid once as a 32-channel NHWC source (kept for the weight gradient)
-            rc_ = nchw_to_nhwc_pad_strided(nchw_src, x_sstride_, x_nhwc_, n_, nchw_c, x.h, x.w, 32, store(), streams_[q_]);
+            if (launch_) rc_ = nchw_to_nhwc_pad_strided(nchw_src, x_sstride_, x_nhwc_, n_, nchw_c, x.h, x.w, 32, store(), streams_[q_]);
             if (rc_ != PWS_OK) return o;
             a.nsrc = 1, a.src[0] = pws_src{x_nhwc_, 32, 32};
         } else if (nchw_c > 0) {
@@ -371,11 +376,18 @@ class Exec {
             // pws_netg_pack_weights_for(math = bf16) leaves this layer's Winograd copies out.  The bf16 kernels decline a call
             // with a source of channels % 32 != 0 (wb_off only needs the TOTAL cin % 32 == 0: ngf 16 / 48 in up_bottom1.conv_same);
             // pws_conv2d_fwd then falls through to the fp32 kernels, which must not find the stale Winograd pointers: the direct
-            // kernel on w_packed (always packed) takes it.
+            // kernel on w_packed (always packed) takes it (pinned by tests/test_conv_plan_cpu.py).
             a.w_wino = a.w_wring = nullptr;
         }
         a.store = store();
         a.out_sign = o.seg[0].sign, a.out_sign_ld = l.cout / 8;
+        if (plan_) {   // what the ladder would launch, on plan_cus_ compute units
+            ConvChoice c{};
+            c.kernel_id = -1, c.tag = layer;
+            rc_ = conv2d_fwd_impl(&a, ConvCtx{nullptr, plan_cus_, false, &c});
+            plan_out_.push_back(c);
+            return o;
+        }
         g_prof_tag = layer;
         rc_ = pws_conv2d_fwd(&a, streams_[q_]);
         g_prof_tag = -1;
@@ -506,9 +518,11 @@ class Exec {
     int n_;
     char *ws_;
     size_t cap_, off_ = 0;
-    bool dry_, launch_;
+    bool dry_, launch_, plan_;
+    int plan_cus_ = 0;
     int rc_ = PWS_OK;
     std::vector<Op> tape_;
+    std::vector<ConvChoice> plan_out_;
 };
 
 // One forward: what the entry point was given.  thetas may be NULL (then they live in the arena).

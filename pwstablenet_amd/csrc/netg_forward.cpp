@@ -245,6 +245,24 @@ extern "C" int pws_netg_forward_opts(const float *packed, const float *x, int n,
     return E.rc();
 }
 
+extern "C" int pws_netg_forward_plan(int n, int input_nc, int ngf, int is_training, const pws_netg_opts *opts, int compute_units,
+                                     pws_conv_choice *out, int max) {
+    PWS_REQUIRE(n >= 0 && compute_units > 0 && max >= 0 && (out || max == 0), "pws_netg_forward_plan: bad n %d / compute_units %d / out", n, compute_units);
+    PWS_REQUIRE_SHAPE("pws_netg_forward_plan", input_nc, ngf);
+    NetgOpts o;
+    if (int rc = opts_from(opts, &o)) return rc;
+    if (n == 0) return 0;
+    const LayerTable L = build_layers(input_nc, ngf);
+    Exec E(reinterpret_cast<const float *>(plan_base(1)), L, n, Arena{plan_base(0), (size_t)1 << 40}, nullptr, EXEC_PLAN, o);
+    E.plan_for(compute_units);
+    float *grids = reinterpret_cast<float *>(plan_base(2)) + ((size_t)1 << 36);   // (the heads are not planned: any non-null address)
+    forward_graph(E, FwdArgs{reinterpret_cast<const float *>(plan_base(2)), n, input_nc, ngf, is_training, 0, grids, grids, grids});
+    if (E.rc() != PWS_OK) return E.rc();
+    const int count = (int)E.plan().size();
+    for (int i = 0; i < count && i < max; ++i) out[i] = E.plan()[i];
+    return count;
+}
+
 extern "C" int pws_netg_forward(const float *packed, const float *x, int n, int input_nc, int ngf, int is_training,
                                 int align_corners, void *ws, size_t ws_bytes, float *grids, float *resid, float *thetas,
                                 pws_stream_t stream) {

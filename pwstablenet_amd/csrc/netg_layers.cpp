@@ -190,7 +190,7 @@ extern "C" int pws_netg_pack_weights_dgrad(const float *const *params, float *pa
 // Both buffers of a TRAINING step at once.  math == PWS_MATH_BF16: the conv layers whose padded extents are the real ones (every one of them
 // at ngf % 64 == 0) go torch layout -> bf16 forward copy + bf16 data-gradient copy in ONE pass (pack16_all_kernel: one read of the 194 MB,
 // no fp32 packed copies -- nothing reads them in this mode: run_conv and the data-gradient calls take the bf16 copies whenever they
-// exist, and at these channel counts the bf16 kernels never decline); the heads' small tensors and any layer that does not qualify take
+// exist, and at these channel counts the bf16 kernels never decline: tests/test_conv_plan_cpu.py asserts it on the ladder's plan); the heads' small tensors and any layer that does not qualify take
 // the ordinary path.  Otherwise: pws_netg_pack_weights_for + pws_netg_pack_weights_dgrad.
 extern "C" int pws_netg_pack_weights_train(const float *const *params, float *packed, float *packed_dgrad, int input_nc, int ngf, int math,
                                            pws_stream_t stream) {

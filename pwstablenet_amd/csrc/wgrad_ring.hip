@@ -460,13 +460,7 @@ static int wrg_launch(WgradRingParams &p, int nclasses, hipStream_t st) {
         }
         attr_set = true;
     }
-    static PerDeviceInt ncu_dev;
-    int &ncu = ncu_dev.cur();
-    if (ncu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-    }
+    const int ncu = device_cus();
     p.tiles_x = (p.LW + C::TW - 1) / C::TW, p.tiles_y = (p.LH + C::TH - 1) / C::TH;
     p.ntiles = p.tiles_x * p.tiles_y * p.N;
     p.ci_blocks = (p.cin_pad + C::CIB - 1) / C::CIB, p.co_blocks = (p.cout + 63) / 64;

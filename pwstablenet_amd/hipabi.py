@@ -117,6 +117,16 @@ class PwsNetgOpts(ctypes.Structure):
                 ("x_sample_stride", ctypes.c_size_t)]
 
 
+class PwsConvChoice(ctypes.Structure):
+    """pws_conv_choice: one conv launch as the dispatch ladder decides it (pws_conv2d_fwd_plan, pws_netg_forward_plan)."""
+    _fields_ = [("kernel_id", ctypes.c_int), ("variant", ctypes.c_int * 4), ("grid", ctypes.c_uint * 3), ("threads", ctypes.c_int),
+                ("lds_bytes", ctypes.c_int), ("ksplit", ctypes.c_int), ("follow", ctypes.c_int), ("tag", ctypes.c_int)]
+
+    def as_dict(self, L):
+        return {"tag": self.tag, "kernel": L.pws_prof_kernel_name(self.kernel_id).decode(), "variant": list(self.variant),
+                "grid": list(self.grid), "threads": self.threads, "lds_bytes": self.lds_bytes, "ksplit": self.ksplit, "follow": self.follow}
+
+
 class PwsProfRecord(ctypes.Structure):
     _fields_ = [("kernel_id", ctypes.c_int), ("tag", ctypes.c_int), ("flops", ctypes.c_double),
                 ("bytes", ctypes.c_double), ("ms", ctypes.c_float)]
@@ -152,6 +162,9 @@ SIGNATURES = {
     "pws_packed_dgrad_floats": (_S, [_I, _I, _I]),
     "pws_pack_conv_weight_dgrad": (_I, [_P, _P, _I, _I, _I, _P]),
     "pws_conv2d_bwd_data": (_I, [ctypes.POINTER(PwsConvBwdDataArgs), _P]),
+    "pws_conv2d_fwd_plan": (_I, [ctypes.POINTER(PwsConvArgs), _I, ctypes.POINTER(PwsConvChoice)]),
+    "pws_conv2d_bwd_data_plan": (_I, [ctypes.POINTER(PwsConvBwdDataArgs), _I, ctypes.POINTER(PwsConvChoice)]),
+    "pws_netg_forward_plan": (_I, [_I, _I, _I, _I, ctypes.POINTER(PwsNetgOpts), _I, ctypes.POINTER(PwsConvChoice), _I]),
     "pws_conv2d_bwd_weight": (_I, [ctypes.POINTER(PwsConvBwdWeightArgs), _P]),
     "pws_unpack_conv_weight": (_I, [_P, _P, _I, _I, _I, _P]),
     "pws_theta_head_fwd_save": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),

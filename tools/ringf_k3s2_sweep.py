@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The headline's stride-2 launches of conv_ringf_kernel under PWS_OPT_EXPERIMENT ids, in one process:
-python tools/ringf_k3s2_sweep.py 2216,2217,2218,2220,2222,2221,2223,0,2232 (ids: conv_ringf_try, csrc/conv_ring_f32.hip:
+python tools/ringf_k3s2_sweep.py 2216,2217,2218,2220,2222,2221,2223,0,2232 (ids: ringf_plan, csrc/conv_ring_f32.hip:
 2200 + 16 v + mask; v = 1 full workgroups, the parent commit's launches, with the ablation masks; 0 the product; 2232 half workgroups
 also for 16 x 32 tiles)."""
 import os
