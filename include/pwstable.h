@@ -477,6 +477,31 @@ int pws_border_keep_yuv420_u8(unsigned char *frames, const float *field, const u
 int pws_border_keep_yuv420_u16(unsigned short *frames, const float *field, const unsigned short *initial, int initial_is_source, int n, int h,
                                int w, int fh, int fw, int layout, int align_corners, int bicubic, pws_stream_t stream);
 
+/* Packed YUV frames of any chroma subsampling: the *_yuv420_* entries above with `chroma` behind `layout` -- 0: 4:2:0 ([n][h*3/2][w], the
+ * entries above bit for bit), 1: 4:2:2 ([n][2h][w]: Y, then h rows of w/2 interleaved U V pairs -- NV16 / P210, layout 0 -- or U and V planes
+ * of h x w/2 -- I422 / I210, layout 1), 2: 4:4:4 ([n][3h][w]: Y, U, V planes of h x w -- I444 / I410, layout 1 only: interleaved 4:4:4, NV24 /
+ * P410, is PWS_EINVAL).  Per plane the semantics are the 4:2:0 entries': a plane is warped by the field resized to the plane's OWN size, pads
+ * with BT.601 black, 16-bit words are read and written as P010's (layout 0) / I010's (layout 1); the window planes decode pixel (x, y) with
+ * the chroma sample (x >> cx, y >> cy), (cx, cy) = (1, 1), (1, 0), (0, 0).  One shape rule for every subsampling: h even, w % 4 == 0 (the
+ * window planes: h and w even); the bicubic entries and the keep pass with `bicubic` need a chroma plane of 4 columns: w >= 8, any w at
+ * 4:4:4.  Alignment rules as above. */
+int pws_gray_area_yuv_u8(const unsigned char *frames, float *out, int n, int h, int w, int oh, int ow, int normalize, int layout, int chroma,
+                         pws_stream_t stream);
+int pws_gray_area_yuv_u16(const unsigned short *frames, float *out, int n, int h, int w, int oh, int ow, int normalize, int layout, int chroma,
+                          pws_stream_t stream);
+int pws_upsample_grid_sample_yuv_u8(const unsigned char *frames, const float *field, unsigned char *out, int n, int h, int w, int fh, int fw,
+                                    int layout, int chroma, int align_corners, pws_stream_t stream);
+int pws_upsample_grid_sample_yuv_u16(const unsigned short *frames, const float *field, unsigned short *out, int n, int h, int w, int fh, int fw,
+                                     int layout, int chroma, int align_corners, pws_stream_t stream);
+int pws_upsample_grid_sample_bicubic_yuv_u8(const unsigned char *frames, const float *field, unsigned char *out, int n, int h, int w, int fh,
+                                            int fw, int layout, int chroma, int align_corners, pws_stream_t stream);
+int pws_upsample_grid_sample_bicubic_yuv_u16(const unsigned short *frames, const float *field, unsigned short *out, int n, int h, int w, int fh,
+                                             int fw, int layout, int chroma, int align_corners, pws_stream_t stream);
+int pws_border_keep_yuv_u8(unsigned char *frames, const float *field, const unsigned char *initial, int initial_is_source, int n, int h, int w,
+                           int fh, int fw, int layout, int chroma, int align_corners, int bicubic, pws_stream_t stream);
+int pws_border_keep_yuv_u16(unsigned short *frames, const float *field, const unsigned short *initial, int initial_is_source, int n, int h, int w,
+                            int fh, int fw, int layout, int chroma, int align_corners, int bicubic, pws_stream_t stream);
+
 /* The automatic crop of the reference's video loop (main_new.py:484-606, a block it keeps inside a string literal), per frame
  * (csrc/homography.hip): field[n,fh,fw,2] resized to the h0 x w0 source frame as pws_upsample_bilinear_ac does is sampled on the
  * 20 x 20 lattice rows h0/2 + (a-10)*15, columns w0/2 + (b-10)*30 (p1, fp32); the homography M (m33 = 1) from p1 to the lattice's own

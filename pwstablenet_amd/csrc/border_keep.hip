@@ -193,13 +193,14 @@ __global__ void __launch_bounds__(256) keep_yuv420_kernel(unsigned char *frames,
     }
 }
 
-// SB: bytes per sample.  Checks and plane geometry are the warps' (yuv::launch_yuv420; w >= 8 with the bicubic margin, as the bicubic warps ask)
+// SB: bytes per sample; chroma: 0 4:2:0, 1 4:2:2, 2 4:4:4.  Checks and plane geometry are the warps' (yuv::launch_yuv; with the bicubic margin
+// a chroma plane is 4 samples wide or more, as the bicubic warps ask: w >= 8, at 4:4:4 any valid w).  A lane touches its own 4 pixels alone.
 template <int SB>
-static int keep_yuv420(const char *what, void *frames, const float *field, const void *initial, int initial_is_source, int n, int h, int w, int fh,
-                       int fw, int layout, int align_corners, int bicubic, pws_stream_t stream) {
-    yuv::Launch420 L;
-    const int rc = yuv::launch_yuv420<SB>(what, frames, field, initial, "initial", n, h, w, fh, fw, layout, align_corners, bicubic ? 8 : 0,
-                                          "with the bicubic margin", L);
+static int keep_yuv(const char *what, void *frames, const float *field, const void *initial, int initial_is_source, int n, int h, int w, int fh,
+                    int fw, int layout, int chroma, int align_corners, int bicubic, pws_stream_t stream) {
+    yuv::LaunchYuv L;
+    const int rc = yuv::launch_yuv<SB>(what, frames, field, initial, "initial", n, h, w, fh, fw, layout, chroma, align_corners, bicubic ? 4 : 0,
+                                       "with the bicubic margin", L);
     if (rc != PWS_OK || n == 0) return rc;
     const float m = bicubic ? 1.f : 0.f;
     unsigned char *fr = reinterpret_cast<unsigned char *>(frames);
@@ -237,12 +238,24 @@ extern "C" int pws_border_keep_u8(unsigned char *frames_hwc, const float *field,
 
 extern "C" int pws_border_keep_yuv420_u8(unsigned char *frames, const float *field, const unsigned char *initial, int initial_is_source, int n, int h,
                                          int w, int fh, int fw, int layout, int align_corners, int bicubic, pws_stream_t stream) {
-    return keep::keep_yuv420<1>("pws_border_keep_yuv420_u8", frames, field, initial, initial_is_source, n, h, w, fh, fw, layout, align_corners, bicubic,
-                                stream);
+    return keep::keep_yuv<1>("pws_border_keep_yuv420_u8", frames, field, initial, initial_is_source, n, h, w, fh, fw, layout, 0, align_corners, bicubic,
+                             stream);
+}
+
+extern "C" int pws_border_keep_yuv_u8(unsigned char *frames, const float *field, const unsigned char *initial, int initial_is_source, int n, int h,
+                                      int w, int fh, int fw, int layout, int chroma, int align_corners, int bicubic, pws_stream_t stream) {
+    return keep::keep_yuv<1>("pws_border_keep_yuv_u8", frames, field, initial, initial_is_source, n, h, w, fh, fw, layout, chroma, align_corners, bicubic,
+                             stream);
 }
 
 extern "C" int pws_border_keep_yuv420_u16(unsigned short *frames, const float *field, const unsigned short *initial, int initial_is_source, int n,
                                           int h, int w, int fh, int fw, int layout, int align_corners, int bicubic, pws_stream_t stream) {
-    return keep::keep_yuv420<2>("pws_border_keep_yuv420_u16", frames, field, initial, initial_is_source, n, h, w, fh, fw, layout, align_corners, bicubic,
-                                stream);
+    return keep::keep_yuv<2>("pws_border_keep_yuv420_u16", frames, field, initial, initial_is_source, n, h, w, fh, fw, layout, 0, align_corners, bicubic,
+                             stream);
+}
+
+extern "C" int pws_border_keep_yuv_u16(unsigned short *frames, const float *field, const unsigned short *initial, int initial_is_source, int n,
+                                       int h, int w, int fh, int fw, int layout, int chroma, int align_corners, int bicubic, pws_stream_t stream) {
+    return keep::keep_yuv<2>("pws_border_keep_yuv_u16", frames, field, initial, initial_is_source, n, h, w, fh, fw, layout, chroma, align_corners, bicubic,
+                             stream);
 }

@@ -166,17 +166,19 @@ __global__ void __launch_bounds__(256) area_tab_u8_kernel(const unsigned char *_
 //   y = max(0, Y - 16) * 1220542, u = U - 128, v = V - 128
 //   R = sat((y + 1673527 v + 2^19) >> 20), G = sat((y - 852492 v - 409993 u + 2^19) >> 20), B = sat((y + 2116026 u + 2^19) >> 20)
 __device__ __forceinline__ int sat_u8(int v) { return min(max(v, 0), 255); }
-template <int LAYOUT>   // 0 NV12, 1 I420
-__device__ __forceinline__ int gray_yuv420(const unsigned char *f, int H, int W, int x, int y) {
+// 4:2:2 and 4:4:4 frames ([n][2 h][w], [n][3 h][w]: the chroma planes are (h >> CY) x (w >> CX) samples, (CX, CY) = (1, 0) and (0, 0)) take
+// the same arithmetic with the chroma of sample (x >> CX, y >> CY); 4:2:0 is (1, 1).
+template <int LAYOUT, int CX, int CY>   // LAYOUT 0: U V interleaved (NV12, NV16), 1: U plane, V plane (I420, I422, I444)
+__device__ __forceinline__ int gray_yuv(const unsigned char *f, int H, int W, int x, int y) {
     const int Y = f[(size_t)y * W + x];
     const unsigned char *c = f + (size_t)H * W;
     int U, V;
     if (LAYOUT == 0) {
-        const unsigned char *p = c + (size_t)(y >> 1) * W + (x & ~1);
+        const unsigned char *p = c + (size_t)(y >> CY) * (2 * (W >> CX)) + 2 * (x >> CX);
         U = p[0], V = p[1];
     } else {
-        const size_t o = (size_t)(y >> 1) * (W >> 1) + (x >> 1);
-        U = c[o], V = c[o + (size_t)(H >> 1) * (W >> 1)];
+        const size_t o = (size_t)(y >> CY) * (W >> CX) + (x >> CX);
+        U = c[o], V = c[o + (size_t)(H >> CY) * (W >> CX)];
     }
     const int yy = max(0, Y - 16) * 1220542, u = U - 128, v = V - 128;
     const int r = sat_u8((yy + 1673527 * v + (1 << 19)) >> 20);
@@ -186,15 +188,15 @@ __device__ __forceinline__ int gray_yuv420(const unsigned char *f, int H, int W,
 }
 
 // one lane per destination pixel, gray_area_u8_kernel's arithmetic in its order
-template <int LAYOUT>
-__global__ void __launch_bounds__(256) gray_area_yuv420_kernel(const unsigned char *__restrict__ frames, float *__restrict__ out, int H, int W,
-                                                               int OH, int OW, double sy, double sx, int normalize, size_t total) {
+template <int LAYOUT, int CX, int CY>
+__global__ void __launch_bounds__(256) gray_area_yuv_kernel(const unsigned char *__restrict__ frames, float *__restrict__ out, int H, int W,
+                                                            int OH, int OW, double sy, double sx, int normalize, size_t total) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const int dx = (int)(i % OW), dy = (int)((i / OW) % OH);
     const size_t n = i / ((size_t)OW * OH);
     const AreaAxis tx = area_axis(dx, W, sx), ty = area_axis(dy, H, sy);
-    const unsigned char *f = frames + n * ((size_t)H * W * 3 / 2);
+    const unsigned char *f = frames + n * ((size_t)H * W + 2 * (size_t)(H >> CY) * (W >> CX));   // (4:2:0: H W 3 / 2, H and W even)
     float sum = 0.f;
     for (int j = 0; j < ty.n; ++j) {
         int sj, sk;
@@ -203,7 +205,7 @@ __global__ void __launch_bounds__(256) gray_area_yuv420_kernel(const unsigned ch
         float buf = 0.f;
         for (int k = 0; k < tx.n; ++k) {
             tx.tap(k, sk, alpha);
-            buf = buf + mul_rounded((float)gray_yuv420<LAYOUT>(f, H, W, sk, sj), alpha);
+            buf = buf + mul_rounded((float)gray_yuv<LAYOUT, CX, CY>(f, H, W, sk, sj), alpha);
         }
         sum = j == 0 ? mul_rounded(beta, buf) : sum + mul_rounded(beta, buf);
     }
@@ -288,18 +290,18 @@ __device__ __forceinline__ unsigned short place10(int v10) { return (unsigned sh
 template <int LAYOUT>
 __device__ __forceinline__ int reduce8(unsigned short word) { return min(255, (sample10<LAYOUT>(word) + 2) >> 2); }
 
-// gray_yuv420 above on the reduced samples, the reduction fused into the loads (no 8-bit copy of the frames)
-template <int LAYOUT>   // 0 P010 (NV12's plane order), 1 I010 (I420's)
-__device__ __forceinline__ int gray_yuv420_u16(const unsigned short *f, int H, int W, int x, int y) {
+// gray_yuv above on the reduced samples, the reduction fused into the loads (no 8-bit copy of the frames)
+template <int LAYOUT, int CX, int CY>   // LAYOUT 0: P010 / P210 (NV12's plane order), 1: I010 / I210 / I410 (I420's)
+__device__ __forceinline__ int gray_yuv_u16(const unsigned short *f, int H, int W, int x, int y) {
     const int Y = reduce8<LAYOUT>(f[(size_t)y * W + x]);
     const unsigned short *c = f + (size_t)H * W;
     int U, V;
     if (LAYOUT == 0) {
-        const unsigned short *p = c + (size_t)(y >> 1) * W + (x & ~1);
+        const unsigned short *p = c + (size_t)(y >> CY) * (2 * (W >> CX)) + 2 * (x >> CX);
         U = reduce8<LAYOUT>(p[0]), V = reduce8<LAYOUT>(p[1]);
     } else {
-        const size_t o = (size_t)(y >> 1) * (W >> 1) + (x >> 1);
-        U = reduce8<LAYOUT>(c[o]), V = reduce8<LAYOUT>(c[o + (size_t)(H >> 1) * (W >> 1)]);
+        const size_t o = (size_t)(y >> CY) * (W >> CX) + (x >> CX);
+        U = reduce8<LAYOUT>(c[o]), V = reduce8<LAYOUT>(c[o + (size_t)(H >> CY) * (W >> CX)]);
     }
     const int yy = max(0, Y - 16) * 1220542, u = U - 128, v = V - 128;
     const int r = sat_u8((yy + 1673527 * v + (1 << 19)) >> 20);
@@ -308,16 +310,16 @@ __device__ __forceinline__ int gray_yuv420_u16(const unsigned short *f, int H, i
     return (b * 3735 + g * 19235 + r * 9798 + (1 << 14)) >> 15;
 }
 
-// one lane per destination pixel, gray_area_yuv420_kernel's arithmetic in its order: the planes of the NV12 / I420 clip of the reduced samples bit for bit
-template <int LAYOUT>
-__global__ void __launch_bounds__(256) gray_area_yuv420_u16_kernel(const unsigned short *__restrict__ frames, float *__restrict__ out, int H, int W,
-                                                                   int OH, int OW, double sy, double sx, int normalize, size_t total) {
+// one lane per destination pixel, gray_area_yuv_kernel's arithmetic in its order: the planes of the 8-bit clip of the reduced samples bit for bit
+template <int LAYOUT, int CX, int CY>
+__global__ void __launch_bounds__(256) gray_area_yuv_u16_kernel(const unsigned short *__restrict__ frames, float *__restrict__ out, int H, int W,
+                                                                int OH, int OW, double sy, double sx, int normalize, size_t total) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const int dx = (int)(i % OW), dy = (int)((i / OW) % OH);
     const size_t n = i / ((size_t)OW * OH);
     const AreaAxis tx = area_axis(dx, W, sx), ty = area_axis(dy, H, sy);
-    const unsigned short *f = frames + n * ((size_t)H * W * 3 / 2);
+    const unsigned short *f = frames + n * ((size_t)H * W + 2 * (size_t)(H >> CY) * (W >> CX));
     float sum = 0.f;
     for (int j = 0; j < ty.n; ++j) {
         int sj, sk;
@@ -326,7 +328,7 @@ __global__ void __launch_bounds__(256) gray_area_yuv420_u16_kernel(const unsigne
         float buf = 0.f;
         for (int k = 0; k < tx.n; ++k) {
             tx.tap(k, sk, alpha);
-            buf = buf + mul_rounded((float)gray_yuv420_u16<LAYOUT>(f, H, W, sk, sj), alpha);
+            buf = buf + mul_rounded((float)gray_yuv_u16<LAYOUT, CX, CY>(f, H, W, sk, sj), alpha);
         }
         sum = j == 0 ? mul_rounded(beta, buf) : sum + mul_rounded(beta, buf);
     }
@@ -458,24 +460,57 @@ extern "C" int pws_area_resize_u8(const unsigned char *in_hwc, unsigned char *ou
     return check_launch("area_tab_u8_kernel");
 }
 
-extern "C" int pws_gray_area_yuv420_u8(const unsigned char *frames, float *out, int n, int h, int w, int oh, int ow, int normalize, int layout,
-                                       pws_stream_t stream) {
-    PWS_REQUIRE(n >= 0 && h > 0 && w > 0 && oh > 0 && ow > 0 && oh <= h && ow <= w, "pws_gray_area_yuv420_u8: bad shape (down-scaling only)");
-    PWS_REQUIRE(h % 2 == 0 && w % 2 == 0, "pws_gray_area_yuv420_u8: h and w must be even (got %d x %d)", w, h);
-    PWS_REQUIRE(layout == 0 || layout == 1, "pws_gray_area_yuv420_u8: layout must be 0 (NV12) or 1 (I420), got %d", layout);
-    PWS_REQUIRE((double)h / oh <= AREA_MAX_TAPS - 2 && (double)w / ow <= AREA_MAX_TAPS - 2, "pws_gray_area_yuv420_u8: scale above %d",
-                AREA_MAX_TAPS - 2);
+// The window planes of packed YUV frames, both depths.  SB: bytes per sample; chroma: 0 4:2:0, 1 4:2:2, 2 4:4:4 (interleaved 4:4:4 is not
+// offered).  One rule for every subsampling: h and w even.  One lane per destination pixel reads its own taps' samples; every index is inside
+// the frame (taps are inside H x W, chroma indices are theirs shifted right).
+template <int SB>
+static int gray_area_yuv(const char *what, const void *frames, float *out, int n, int h, int w, int oh, int ow, int normalize, int layout, int chroma,
+                         pws_stream_t stream) {
+    PWS_REQUIRE(n >= 0 && h > 0 && w > 0 && oh > 0 && ow > 0 && oh <= h && ow <= w, "%s: bad shape (down-scaling only)", what);
+    PWS_REQUIRE(h % 2 == 0 && w % 2 == 0, "%s: h and w must be even (got %d x %d)", what, w, h);
+    PWS_REQUIRE(layout == 0 || layout == 1, "%s: layout must be 0 (%s) or 1 (%s), got %d", what, SB == 1 ? "NV12" : "P010", SB == 1 ? "I420" : "I010", layout);
+    PWS_REQUIRE(chroma >= 0 && chroma <= 2, "%s: chroma must be 0 (4:2:0), 1 (4:2:2) or 2 (4:4:4), got %d", what, chroma);
+    PWS_REQUIRE(!(chroma == 2 && layout == 0), "%s: interleaved 4:4:4 (%s) is not offered: layout 0 needs chroma 0 or 1", what, SB == 1 ? "NV24" : "P410");
+    PWS_REQUIRE((double)h / oh <= AREA_MAX_TAPS - 2 && (double)w / ow <= AREA_MAX_TAPS - 2, "%s: scale above %d", what, AREA_MAX_TAPS - 2);
     if (n == 0) return PWS_OK;
-    PWS_REQUIRE(frames && out, "pws_gray_area_yuv420_u8: NULL pointer");
+    PWS_REQUIRE(frames && out, "%s: NULL pointer", what);
+    if (SB == 2) PWS_REQUIRE((reinterpret_cast<size_t>(frames) & 1) == 0, "%s: frames must be 2-byte aligned", what);
     const size_t total = (size_t)n * oh * ow;
     const double sy = 1.0 / ((double)oh / h), sx = 1.0 / ((double)ow / w);
-    ProfScope prof(KID_OBJECTIVE, 16.0 * n * h * w, 1.5 * n * h * w + 4.0 * total, as_stream(stream));
+    // (frame I/O has no kernel id of its own: the 16-bit entries are booked under KID_OBJECTIVE like their 8-bit neighbours, on purpose)
+    const double spp = chroma == 0 ? 1.5 : (chroma == 1 ? 2.0 : 3.0);   // samples read per source pixel
+    ProfScope prof(KID_OBJECTIVE, (SB == 1 ? 16.0 : 19.0) * n * h * w, spp * SB * n * h * w + 4.0 * total, as_stream(stream));
     const dim3 grid((unsigned)((total + 255) / 256));
-    if (layout == 0)
-        hipLaunchKernelGGL(gray_area_yuv420_kernel<0>, grid, dim3(256), 0, as_stream(stream), frames, out, h, w, oh, ow, sy, sx, normalize, total);
-    else
-        hipLaunchKernelGGL(gray_area_yuv420_kernel<1>, grid, dim3(256), 0, as_stream(stream), frames, out, h, w, oh, ow, sy, sx, normalize, total);
-    return check_launch("gray_area_yuv420_kernel");
+#define PWS_GRAY_YUV(L_, CX_, CY_)                                                                                                              \
+    do {                                                                                                                                        \
+        if constexpr (SB == 1)                                                                                                                  \
+            hipLaunchKernelGGL((gray_area_yuv_kernel<L_, CX_, CY_>), grid, dim3(256), 0, as_stream(stream),                                     \
+                               reinterpret_cast<const unsigned char *>(frames), out, h, w, oh, ow, sy, sx, normalize, total);                   \
+        else                                                                                                                                    \
+            hipLaunchKernelGGL((gray_area_yuv_u16_kernel<L_, CX_, CY_>), grid, dim3(256), 0, as_stream(stream),                                 \
+                               reinterpret_cast<const unsigned short *>(frames), out, h, w, oh, ow, sy, sx, normalize, total);                  \
+    } while (0)
+    if (chroma == 0) {
+        if (layout == 0) PWS_GRAY_YUV(0, 1, 1);
+        else PWS_GRAY_YUV(1, 1, 1);
+    } else if (chroma == 1) {
+        if (layout == 0) PWS_GRAY_YUV(0, 1, 0);
+        else PWS_GRAY_YUV(1, 1, 0);
+    } else {
+        PWS_GRAY_YUV(1, 0, 0);
+    }
+#undef PWS_GRAY_YUV
+    return check_launch(SB == 1 ? "gray_area_yuv_kernel" : "gray_area_yuv_u16_kernel");
+}
+
+extern "C" int pws_gray_area_yuv420_u8(const unsigned char *frames, float *out, int n, int h, int w, int oh, int ow, int normalize, int layout,
+                                       pws_stream_t stream) {
+    return gray_area_yuv<1>("pws_gray_area_yuv420_u8", frames, out, n, h, w, oh, ow, normalize, layout, 0, stream);
+}
+
+extern "C" int pws_gray_area_yuv_u8(const unsigned char *frames, float *out, int n, int h, int w, int oh, int ow, int normalize, int layout,
+                                    int chroma, pws_stream_t stream) {
+    return gray_area_yuv<1>("pws_gray_area_yuv_u8", frames, out, n, h, w, oh, ow, normalize, layout, chroma, stream);
 }
 
 extern "C" int pws_area_resize_plane_u8(const unsigned char *in, size_t in_stride, unsigned char *out, size_t out_stride, int n, int h, int w,
@@ -510,24 +545,12 @@ extern "C" int pws_area_resize_plane_u8(const unsigned char *in, size_t in_strid
 
 extern "C" int pws_gray_area_yuv420_u16(const unsigned short *frames, float *out, int n, int h, int w, int oh, int ow, int normalize, int layout,
                                         pws_stream_t stream) {
-    PWS_REQUIRE(n >= 0 && h > 0 && w > 0 && oh > 0 && ow > 0 && oh <= h && ow <= w, "pws_gray_area_yuv420_u16: bad shape (down-scaling only)");
-    PWS_REQUIRE(h % 2 == 0 && w % 2 == 0, "pws_gray_area_yuv420_u16: h and w must be even (got %d x %d)", w, h);
-    PWS_REQUIRE(layout == 0 || layout == 1, "pws_gray_area_yuv420_u16: layout must be 0 (P010) or 1 (I010), got %d", layout);
-    PWS_REQUIRE((double)h / oh <= AREA_MAX_TAPS - 2 && (double)w / ow <= AREA_MAX_TAPS - 2, "pws_gray_area_yuv420_u16: scale above %d",
-                AREA_MAX_TAPS - 2);
-    if (n == 0) return PWS_OK;
-    PWS_REQUIRE(frames && out, "pws_gray_area_yuv420_u16: NULL pointer");
-    PWS_REQUIRE((reinterpret_cast<size_t>(frames) & 1) == 0, "pws_gray_area_yuv420_u16: frames must be 2-byte aligned");
-    const size_t total = (size_t)n * oh * ow;
-    const double sy = 1.0 / ((double)oh / h), sx = 1.0 / ((double)ow / w);
-    // (frame I/O has no kernel id of its own: the 16-bit entries are booked under KID_OBJECTIVE like their 8-bit neighbours, on purpose)
-    ProfScope prof(KID_OBJECTIVE, 19.0 * n * h * w, 3.0 * n * h * w + 4.0 * total, as_stream(stream));
-    const dim3 grid((unsigned)((total + 255) / 256));
-    if (layout == 0)
-        hipLaunchKernelGGL(gray_area_yuv420_u16_kernel<0>, grid, dim3(256), 0, as_stream(stream), frames, out, h, w, oh, ow, sy, sx, normalize, total);
-    else
-        hipLaunchKernelGGL(gray_area_yuv420_u16_kernel<1>, grid, dim3(256), 0, as_stream(stream), frames, out, h, w, oh, ow, sy, sx, normalize, total);
-    return check_launch("gray_area_yuv420_u16_kernel");
+    return gray_area_yuv<2>("pws_gray_area_yuv420_u16", frames, out, n, h, w, oh, ow, normalize, layout, 0, stream);
+}
+
+extern "C" int pws_gray_area_yuv_u16(const unsigned short *frames, float *out, int n, int h, int w, int oh, int ow, int normalize, int layout,
+                                     int chroma, pws_stream_t stream) {
+    return gray_area_yuv<2>("pws_gray_area_yuv_u16", frames, out, n, h, w, oh, ow, normalize, layout, chroma, stream);
 }
 
 extern "C" int pws_area_resize_plane_u16(const unsigned short *in, size_t in_stride, unsigned short *out, size_t out_stride, int n, int h, int w,

@@ -950,6 +950,8 @@ extern "C" int pws_upsample_grid_sample_u8(const unsigned char *frame_hwc, const
 }
 
 // ---------------------------------------------------------------------------------------------- fused 4:2:0 YUV path
+// (4:2:2 and 4:4:4 frames -- pws_upsample_grid_sample_yuv_u8 / _u16 -- run the same kernel: a chroma plane of h x w/2 or h x w samples is to
+// the row functions below what the h/2 x w/2 one is, a yuv::Plane; yuv::launch_yuv derives offsets, pitches and sizes for each.)
 // The same warp for packed 4:2:0 frames as decoders hand them over ([n][h*3/2][w] uint8: the Y plane, then NV12's interleaved UV rows or
 // I420's U plane and V plane).  Each plane is warped by the field resized (align_corners=True) to the PLANE's own size, with the float
 // kernel's field interpolation, un-normalisation and 4-term blend order, truncated like astype(uint8).  Chroma samples are taken as centred
@@ -1070,7 +1072,7 @@ __device__ __forceinline__ void yuv_warp_row(const unsigned char *__restrict__ f
     } else {
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
-            unsigned char *o = ofr + ob + (p ? P.off1 - P.off0 : 0u);   // (2-byte aligned only: the V plane starts at h w + h w / 4)
+            unsigned char *o = ofr + ob + (p ? P.off1 - P.off0 : 0u);   // (2-byte aligned only at 4:2:0: the V plane starts at h w + h w / 4; 4 at 4:2:2 / 4:4:4, not relied on)
             if (full) reinterpret_cast<U8x4 *>(o)->v = ow[p];
             else reinterpret_cast<U8x2 *>(o)->v = (unsigned short)ow[p];
         }
@@ -1188,7 +1190,7 @@ __device__ __forceinline__ void yuv16_warp_row(const unsigned char *__restrict__
     } else {
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
-            unsigned char *o = ofr + ob + (p ? P.off1 - P.off0 : 0u);   // (4-byte aligned: the chroma planes' pitch and size are multiples of 4 bytes)
+            unsigned char *o = ofr + ob + (p ? P.off1 - P.off0 : 0u);   // (4-byte aligned: the chroma planes' pitch and size are multiples of 4 bytes, at every subsampling)
             const unsigned w0 = res[p][0] | res[p][1] << 16;
             if (full) *reinterpret_cast<yuv::U32x2 *>(o) = yuv::U32x2{w0, res[p][2] | res[p][3] << 16};   // (one 8-byte store at dword alignment, like the tap loads)
             else *reinterpret_cast<unsigned *>(o) = w0;
@@ -1196,7 +1198,7 @@ __device__ __forceinline__ void yuv16_warp_row(const unsigned char *__restrict__
     }
 }
 
-// ---------------------------------------------------------------------------------------------- the 4:2:0 kernel and launcher, both depths
+// ---------------------------------------------------------------------------------------------- the packed-YUV kernel and launcher, both depths, every subsampling
 // SB: bytes per sample (1: yuv_warp_row, 2: yuv16_warp_row); LAYOUT 0 NV12 / P010, 1 I420 / I010
 template <int SB, int KIND, int FMODE, int LAYOUT>
 __device__ __forceinline__ void yuv420_warp_row(const unsigned char *__restrict__ frame, unsigned char *__restrict__ ofr, const float *__restrict__ field,
@@ -1226,17 +1228,18 @@ __global__ void __launch_bounds__(256) upsample_grid_sample_yuv420_kernel(const 
     }
 }
 
-// SB: bytes per sample.  The checks and the plane geometry are yuv::launch_yuv420's, shared with the bicubic warps and the keep pass
+// SB: bytes per sample; chroma: 0 4:2:0, 1 4:2:2, 2 4:4:4 (the kernel is the 4:2:0 one: its rows take any plane geometry).  The checks and
+// the plane geometry are yuv::launch_yuv's, shared with the bicubic warps and the keep pass
 template <int SB>
-static int warp_yuv420(const char *what, const void *frames, const float *field, void *out, int n, int h, int w, int fh, int fw, int layout,
-                       int align_corners, pws_stream_t stream) {
-    yuv::Launch420 L;
-    const int rc = yuv::launch_yuv420<SB>(what, frames, field, out, "out", n, h, w, fh, fw, layout, align_corners, 0, "", L);
+static int warp_yuv(const char *what, const void *frames, const float *field, void *out, int n, int h, int w, int fh, int fw, int layout,
+                    int chroma, int align_corners, pws_stream_t stream) {
+    yuv::LaunchYuv L;
+    const int rc = yuv::launch_yuv<SB>(what, frames, field, out, "out", n, h, w, fh, fw, layout, chroma, align_corners, 0, "", L);
     if (rc != PWS_OK || n == 0) return rc;
     const size_t total = (size_t)n * h * w;
     // (both depths are booked under the 8-bit integer warps' id on purpose: one row "fused byte warp" in the per-kernel stats, told apart by
-    // the bytes booked per launch -- 3 per pixel at 8 bits, 6 at 16; a clip has one depth, so a run does not mix them)
-    ProfScope prof(KID_UPSAMPLE_GRID_SAMPLE_U8, (double)total * 1.5 * (40.0 + 8.0), (double)total * 3.0 * SB + 8.0 * (double)n * fh * fw,
+    // the bytes booked per launch -- at 4:2:0 3 per pixel at 8 bits, 6 at 16; a clip has one depth, so a run does not mix them)
+    ProfScope prof(KID_UPSAMPLE_GRID_SAMPLE_U8, (double)total * L.spp * (40.0 + 8.0), (double)total * 2.0 * L.spp * SB + 8.0 * (double)n * fh * fw,
                    as_stream(stream));
     const unsigned char *src = reinterpret_cast<const unsigned char *>(frames);
     unsigned char *dst = reinterpret_cast<unsigned char *>(out);
@@ -1265,10 +1268,20 @@ static int warp_yuv420(const char *what, const void *frames, const float *field,
 
 extern "C" int pws_upsample_grid_sample_yuv420_u8(const unsigned char *frames, const float *field, unsigned char *out, int n, int h, int w,
                                                   int fh, int fw, int layout, int align_corners, pws_stream_t stream) {
-    return warp_yuv420<1>("pws_upsample_grid_sample_yuv420_u8", frames, field, out, n, h, w, fh, fw, layout, align_corners, stream);
+    return warp_yuv<1>("pws_upsample_grid_sample_yuv420_u8", frames, field, out, n, h, w, fh, fw, layout, 0, align_corners, stream);
+}
+
+extern "C" int pws_upsample_grid_sample_yuv_u8(const unsigned char *frames, const float *field, unsigned char *out, int n, int h, int w, int fh,
+                                               int fw, int layout, int chroma, int align_corners, pws_stream_t stream) {
+    return warp_yuv<1>("pws_upsample_grid_sample_yuv_u8", frames, field, out, n, h, w, fh, fw, layout, chroma, align_corners, stream);
 }
 
 extern "C" int pws_upsample_grid_sample_yuv420_u16(const unsigned short *frames, const float *field, unsigned short *out, int n, int h, int w,
                                                    int fh, int fw, int layout, int align_corners, pws_stream_t stream) {
-    return warp_yuv420<2>("pws_upsample_grid_sample_yuv420_u16", frames, field, out, n, h, w, fh, fw, layout, align_corners, stream);
+    return warp_yuv<2>("pws_upsample_grid_sample_yuv420_u16", frames, field, out, n, h, w, fh, fw, layout, 0, align_corners, stream);
+}
+
+extern "C" int pws_upsample_grid_sample_yuv_u16(const unsigned short *frames, const float *field, unsigned short *out, int n, int h, int w, int fh,
+                                                int fw, int layout, int chroma, int align_corners, pws_stream_t stream) {
+    return warp_yuv<2>("pws_upsample_grid_sample_yuv_u16", frames, field, out, n, h, w, fh, fw, layout, chroma, align_corners, stream);
 }

@@ -207,7 +207,7 @@ __device__ __forceinline__ void warp_row(const unsigned char *__restrict__ frame
         } else {
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
-                unsigned char *o = ofr + ob + (p ? P.off1 - P.off0 : 0u);   // (2-byte aligned only: the V plane starts at h w + h w / 4)
+                unsigned char *o = ofr + ob + (p ? P.off1 - P.off0 : 0u);   // (2-byte aligned only at 4:2:0: the V plane starts at h w + h w / 4; 4 at 4:2:2 / 4:4:4, not relied on)
                 if (full) reinterpret_cast<U8x4 *>(o)->v = ow[p];
                 else reinterpret_cast<U8x2 *>(o)->v = (unsigned short)ow[p];
             }
@@ -227,7 +227,7 @@ __device__ __forceinline__ void warp_row(const unsigned char *__restrict__ frame
         } else {
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
-                unsigned char *o = ofr + ob + (p ? P.off1 - P.off0 : 0u);   // (4-byte aligned: the chroma planes' pitch and size are multiples of 4 bytes)
+                unsigned char *o = ofr + ob + (p ? P.off1 - P.off0 : 0u);   // (4-byte aligned: the chroma planes' pitch and size are multiples of 4 bytes, at every subsampling)
                 const unsigned w0 = res[p][0] | res[p][1] << 16;
                 if (full) *reinterpret_cast<yuv::U32x2 *>(o) = yuv::U32x2{w0, res[p][2] | res[p][3] << 16};
                 else *reinterpret_cast<unsigned *>(o) = w0;
@@ -392,16 +392,18 @@ extern "C" int pws_upsample_grid_sample_bicubic_u8(const unsigned char *frame_hw
     return check_launch("bicubic_u8_kernel");
 }
 
-// SB: bytes per sample.  Checks and plane geometry are the twins' (yuv::launch_yuv420; w >= 8 on top: a chroma plane holds the 4-column window)
+// SB: bytes per sample; chroma: 0 4:2:0, 1 4:2:2, 2 4:4:4.  Checks and plane geometry are the twins' (yuv::launch_yuv).  On top: a chroma
+// plane holds the 4-column window (clamp_window: W >= 4), which is w >= 8 at 4:2:0 and 4:2:2 and w >= 4 -- any valid w -- at 4:4:4; plane
+// heights below 4 take the clamped branch of warp_row (H >= 4 is tested there), so 4:2:2's and 4:4:4's taller chroma planes change nothing.
 template <int SB>
-static int bicubic_yuv420(const char *what, const void *frames, const float *field, void *out, int n, int h, int w, int fh, int fw, int layout,
-                          int align_corners, pws_stream_t stream) {
-    yuv::Launch420 L;
-    const int rc = yuv::launch_yuv420<SB>(what, frames, field, out, "out", n, h, w, fh, fw, layout, align_corners, 8,
-                                          "(the chroma planes hold the 4-tap window)", L);
+static int bicubic_yuv(const char *what, const void *frames, const float *field, void *out, int n, int h, int w, int fh, int fw, int layout,
+                       int chroma, int align_corners, pws_stream_t stream) {
+    yuv::LaunchYuv L;
+    const int rc = yuv::launch_yuv<SB>(what, frames, field, out, "out", n, h, w, fh, fw, layout, chroma, align_corners, 4,
+                                       "(the chroma planes hold the 4-tap window)", L);
     if (rc != PWS_OK || n == 0) return rc;
     const size_t total = (size_t)n * h * w;
-    ProfScope prof(KID_UPSAMPLE_GRID_SAMPLE_U8, (double)total * 1.5 * (80.0 + 40.0), (double)total * 3.0 * SB + 8.0 * (double)n * fh * fw,
+    ProfScope prof(KID_UPSAMPLE_GRID_SAMPLE_U8, (double)total * L.spp * (80.0 + 40.0), (double)total * 2.0 * L.spp * SB + 8.0 * (double)n * fh * fw,
                    as_stream(stream));
     const unsigned char *src = reinterpret_cast<const unsigned char *>(frames);
     unsigned char *dst = reinterpret_cast<unsigned char *>(out);
@@ -416,10 +418,20 @@ static int bicubic_yuv420(const char *what, const void *frames, const float *fie
 
 extern "C" int pws_upsample_grid_sample_bicubic_yuv420_u8(const unsigned char *frames, const float *field, unsigned char *out, int n, int h, int w,
                                                           int fh, int fw, int layout, int align_corners, pws_stream_t stream) {
-    return bicubic_yuv420<1>("pws_upsample_grid_sample_bicubic_yuv420_u8", frames, field, out, n, h, w, fh, fw, layout, align_corners, stream);
+    return bicubic_yuv<1>("pws_upsample_grid_sample_bicubic_yuv420_u8", frames, field, out, n, h, w, fh, fw, layout, 0, align_corners, stream);
+}
+
+extern "C" int pws_upsample_grid_sample_bicubic_yuv_u8(const unsigned char *frames, const float *field, unsigned char *out, int n, int h, int w,
+                                                       int fh, int fw, int layout, int chroma, int align_corners, pws_stream_t stream) {
+    return bicubic_yuv<1>("pws_upsample_grid_sample_bicubic_yuv_u8", frames, field, out, n, h, w, fh, fw, layout, chroma, align_corners, stream);
 }
 
 extern "C" int pws_upsample_grid_sample_bicubic_yuv420_u16(const unsigned short *frames, const float *field, unsigned short *out, int n, int h, int w,
                                                            int fh, int fw, int layout, int align_corners, pws_stream_t stream) {
-    return bicubic_yuv420<2>("pws_upsample_grid_sample_bicubic_yuv420_u16", frames, field, out, n, h, w, fh, fw, layout, align_corners, stream);
+    return bicubic_yuv<2>("pws_upsample_grid_sample_bicubic_yuv420_u16", frames, field, out, n, h, w, fh, fw, layout, 0, align_corners, stream);
+}
+
+extern "C" int pws_upsample_grid_sample_bicubic_yuv_u16(const unsigned short *frames, const float *field, unsigned short *out, int n, int h, int w,
+                                                        int fh, int fw, int layout, int chroma, int align_corners, pws_stream_t stream) {
+    return bicubic_yuv<2>("pws_upsample_grid_sample_bicubic_yuv_u16", frames, field, out, n, h, w, fh, fw, layout, chroma, align_corners, stream);
 }

@@ -1,7 +1,7 @@
 // What the bilinear warp kernels (grid_sample.hip) and the bicubic ones (warp_bicubic.hip) share, so that both form a pixel's source
 // position (ix, iy) with the same fp32 operations: the field's interpolation (mul_rounded of common.h, field_lerp / pk_field_lerp and the
-// wave-shared fetch yuv_field4), the un-normalisation, the plane geometry of packed 4:2:0 frames with the launchers' shared checks (yuv::make_plane,
-// yuv::launch_yuv420), and the byte / 10-bit conversions.
+// wave-shared fetch yuv_field4), the un-normalisation, the plane geometry of packed 4:2:0 / 4:2:2 / 4:4:4 frames with the launchers' shared checks (yuv::make_plane,
+// yuv::launch_yuv), and the byte / 10-bit conversions.
 #pragma once
 #include "common.h"
 
@@ -158,7 +158,7 @@ __device__ __forceinline__ unsigned place10(float blend) {   // truncate (the bl
     return LAYOUT == 0 ? v << 6 : v;
 }
 
-// ---- host side: the geometry of a plane, and what the launchers of the 4:2:0 kernels (bilinear, bicubic, keep) check and derive alike
+// ---- host side: the geometry of a plane, and what the launchers of the packed-YUV kernels (bilinear, bicubic, keep) check and derive alike
 static Plane make_plane(int ph, int pw, unsigned off0, unsigned off1, unsigned pitch, int fh, int fw, int align_corners) {
     Plane p;   // (the field's resize ratios and the un-normalisation constants: every kernel gets the same fp32 products)
     p.h = ph, p.w = pw, p.off0 = off0, p.off1 = off1, p.pitch = pitch;
@@ -170,31 +170,60 @@ static Plane make_plane(int ph, int pw, unsigned off0, unsigned off1, unsigned p
     return p;
 }
 
-struct Launch420 {   // one launch over every plane of every frame: grid (gx, cpr, frames or 1), 256 threads
+struct LaunchYuv {   // one launch over every plane of every frame: grid (gx, cpr, frames or 1), 256 threads
     Plane py, pc;
     unsigned fbytes, gx, cpr;   // bytes per frame, row groups of Y then chroma (padded to the 8 XCDs), 256-pixel chunks per Y row
     int fmy, fmc;               // field access mode of the Y / chroma planes
+    double spp;                 // samples per pixel (1.5, 2, 3): what the callers' ProfScope books per pixel
 };
-// SB: bytes per sample (1: NV12 / I420, 2: P010 / I010).  `other`: the second frame pointer (`other_name`: "out" / "initial").  min_w > 0: the
-// caller's own minimum width, `min_w_why` the words after "w must be at least <min_w> ".  PWS_OK with n == 0 means: nothing to launch.
+// SB: bytes per sample (1: NV12 / I420 and their 4:2:2 / 4:4:4 kin, 2: P010 / I010 and theirs).  chroma: 0 4:2:0, 1 4:2:2, 2 4:4:4 -- the chroma
+// planes are (h >> cy) x (w >> cx) samples, (cx, cy) = (1, 1), (1, 0), (0, 0).  `other`: the second frame pointer (`other_name`: "out" /
+// "initial").  min_cw > 0: the caller's own minimum width of a CHROMA plane (the bicubic window: 4), asked of w as min_cw << cx, `min_w_why`
+// the words after "w must be at least <that> ".  PWS_OK with n == 0 means: nothing to launch.
+//
+// What the row functions (yuv_warp_row, yuv16_warp_row, bic::warp_row, keep::keep_row) assume of a geometry, derived here for all three
+// subsamplings from h even, w % 4 == 0 (so h w is a multiple of 8 and cw = w >> cx is even; cw is a multiple of 4 at 4:4:4):
+//  * 32-bit byte offsets.  A frame is (h w + 2 ch cw) SB bytes: 1.5, 2 or 3 h w SB.  With h w SB < 2^29 (the check below) that is below
+//    1.5 * 2^30, and so is every offset the row functions form; the largest sum they compare, (m & ~3) + 16 with m < fbytes (the exact-load
+//    tests), stays far below 2^32.  Frame n starts at n * fbytes in size_t.  __umul24(row, pitch): rows < h < 2^24 (checked), pitch <= w SB < 2^23
+//    (checked; the interleaved 4:4:4 row of 2 w SB is not offered).
+//  * Alignment.  Plane starts and pitches, in bytes: Y 0 and w SB; interleaved chroma h w SB and 2 cw SB; planar U h w SB, V (h w + ch cw) SB,
+//    pitch cw SB.  8 bit: everything but the planar chroma is a multiple of 4 (their 4-byte stores; frames are 4-byte aligned and fbytes is a
+//    multiple of 4 -- 12, 16, 24 times h w / 8); planar chroma is a multiple of 2 at 4:2:0 (ch cw = h w / 4 may be 2 mod 4), of 4 at 4:2:2 and
+//    4:4:4, and is accessed through the byte-aligned U8x4 / U8x2 either way.  16 bit: Y rows and interleaved chroma rows are multiples of 8 bytes
+//    (uint2 / U32x4 stores; frames are 8-byte aligned, fbytes a multiple of 8), planar chroma of 4 (cw SB = 2 cw, cw even; plane sizes ch cw SB
+//    likewise), its stores are dword-aligned U32x2.  The tap loads align their own address down to 4 bytes from the frame's start.
+//  * Reads behind a tap pair / window (up to 6 bytes, bilinear 8 bit; 4 bytes, the others) are inside the frame, or inside the next frame,
+//    everywhere but at the end of the LAST plane of the LAST sample: the row functions compare the largest offset a wave reads -- taken in the
+//    V plane (off1) for planar chroma -- with fbytes, whatever the geometry, and fall back to exact loads.  The chroma planes are the frame's
+//    last bytes in every layout here (V ends at fbytes; interleaved UV ends at fbytes), so "fbytes" is the only fact that rule needs, and
+//    the exact loads touch the pair / window alone, which the clamps (x <= W - 2 resp. W - 4, y <= H - 1) keep inside the plane.
+//  * Writes: a lane stores its own 4 pixels (2 in the last lane of a chroma row of width 2 mod 4: 4:2:0 and 4:2:2 only) and nothing else.
+//  * Grid: a chroma row takes (cw + 255) / 256 of the cpr chunks -- half of them at 4:2:0 and 4:2:2, ALL of them at 4:4:4; the kernels
+//    return for chunks past a plane's width.
 template <int SB>
-static int launch_yuv420(const char *what, const void *frames, const float *field, const void *other, const char *other_name, int n, int h, int w,
-                         int fh, int fw, int layout, int align_corners, int min_w, const char *min_w_why, Launch420 &L) {
+static int launch_yuv(const char *what, const void *frames, const float *field, const void *other, const char *other_name, int n, int h, int w,
+                      int fh, int fw, int layout, int chroma, int align_corners, int min_cw, const char *min_w_why, LaunchYuv &L) {
     PWS_REQUIRE(n >= 0 && h > 0 && w > 0 && fh > 0 && fw > 0, "%s: bad shape", what);
     PWS_REQUIRE(layout == 0 || layout == 1, "%s: layout must be 0 (%s) or 1 (%s), got %d", what, SB == 1 ? "NV12" : "P010", SB == 1 ? "I420" : "I010", layout);
+    PWS_REQUIRE(chroma >= 0 && chroma <= 2, "%s: chroma must be 0 (4:2:0), 1 (4:2:2) or 2 (4:4:4), got %d", what, chroma);
+    PWS_REQUIRE(!(chroma == 2 && layout == 0), "%s: interleaved 4:4:4 (%s) is not offered: layout 0 needs chroma 0 or 1", what, SB == 1 ? "NV24" : "P410");
     PWS_REQUIRE(h % 2 == 0 && w % 4 == 0 && h >= 2, "%s: h must be even and w a multiple of 4 (got %d x %d)", what, w, h);
-    PWS_REQUIRE(w >= min_w, "%s: w must be at least %d %s, got %d", what, min_w, min_w_why, w);
+    const int cx = chroma == 2 ? 0 : 1, cy = chroma == 0 ? 1 : 0;
+    PWS_REQUIRE(w >= (min_cw << cx), "%s: w must be at least %d %s, got %d", what, min_cw << cx, min_w_why, w);
     if (n == 0) return PWS_OK;
     PWS_REQUIRE(frames && field && other, "%s: NULL pointer", what);
     PWS_REQUIRE(((reinterpret_cast<size_t>(frames) | reinterpret_cast<size_t>(other)) & (SB == 1 ? 3 : 7)) == 0, "%s: frames and %s must be %d-byte aligned",
                 what, other_name, SB == 1 ? 4 : 8);
-    PWS_REQUIRE((size_t)h * w < (1u << (SB == 1 ? 29 : 28)) && w < (1 << (SB == 1 ? 23 : 22)) && n < 65536, "%s: frame or batch too large", what);
-    L.fbytes = (unsigned)((size_t)h * w * 3 / 2) * SB;   // (16 bit: a multiple of 8, every frame starts 8-byte aligned)
-    const unsigned hw = (unsigned)(h * w) * SB, hc = (unsigned)(h / 2), wc = (unsigned)(w / 2);   // byte offsets and pitches
+    PWS_REQUIRE((size_t)h * w < (1u << (SB == 1 ? 29 : 28)) && w < (1 << (SB == 1 ? 23 : 22)) && h < (1 << 24) && n < 65536,
+                "%s: frame or batch too large", what);
+    const unsigned hw = (unsigned)(h * w) * SB, hc = (unsigned)(h >> cy), wc = (unsigned)(w >> cx);   // byte offsets and pitches
+    L.fbytes = hw + 2u * hc * wc * SB;   // (4:2:0: h w 3 / 2 samples.  16 bit: a multiple of 8, every frame starts 8-byte aligned)
+    L.spp = 1.0 + 2.0 / (double)(1 << (cx + cy));
     L.py = make_plane(h, w, 0u, 0u, (unsigned)w * SB, fh, fw, align_corners);
-    L.pc = layout == 0 ? make_plane(h / 2, w / 2, hw, hw, (unsigned)w * SB, fh, fw, align_corners)
-                       : make_plane(h / 2, w / 2, hw, hw + hc * wc * SB, wc * SB, fh, fw, align_corners);
-    L.gx = (L.py.nrg + L.pc.nrg + 7u) & ~7u, L.cpr = (unsigned)((w + 255) / 256);   // (chroma rows need half the chunks: the rest return)
+    L.pc = layout == 0 ? make_plane((int)hc, (int)wc, hw, hw, 2u * wc * SB, fh, fw, align_corners)
+                       : make_plane((int)hc, (int)wc, hw, hw + hc * wc * SB, wc * SB, fh, fw, align_corners);
+    L.gx = (L.py.nrg + L.pc.nrg + 7u) & ~7u, L.cpr = (unsigned)((w + 255) / 256);   // (chroma rows need half the chunks, all at 4:4:4: the rest return)
     L.fmy = yuv_fmode(L.py.rx), L.fmc = yuv_fmode(L.pc.rx);
     return PWS_OK;
 }

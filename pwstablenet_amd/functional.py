@@ -147,12 +147,19 @@ YUV420_16_LAYOUT = {"p010": 0, "i010": 1}
 BORDERS = ("black", "keep")
 
 
-class FrameFormat(collections.namedtuple("FrameFormat", "name dtype packed layout suffix wrapper window_planes plane_resize")):
+CHROMA_SHIFTS = ((1, 1), (1, 0), (0, 0))   # (cx, cy) of chroma 0 (4:2:0), 1 (4:2:2), 2 (4:4:4): a chroma plane is (H >> cy) x (W >> cx)
+_PACKED_ROWS = ("H * 3 // 2", "2 * H", "3 * H")
+
+
+class FrameFormat(collections.namedtuple("FrameFormat", "name dtype packed layout suffix wrapper window_planes plane_resize chroma",
+                                         defaults=(None,))):
     """What the warps, the keep pass and the stabiliser need to know about a pixel format, in one place: its ``name``, the frames' ``dtype``,
-    whether they are ``packed`` 4:2:0 (T, H * 3 // 2, W) and then their plane ``layout`` (0: Y + interleaved UV, 1: Y + U + V; None for the
-    unpacked formats), the ``suffix`` of the format's C entries (``pws_upsample_grid_sample_[bicubic_]<suffix>``, ``pws_border_keep_<suffix>``),
-    the ``wrapper`` whose name its error messages carry, and the C entries that make its ``window_planes`` and resize its planes
-    (``plane_resize``).  A new format is a row of FRAME_FORMATS (and its kernels)."""
+    whether they are ``packed`` YUV planes (T, packed rows, W) and then their plane ``layout`` (0: Y + interleaved UV, 1: Y + U + V; None for
+    the unpacked formats) and ``chroma`` subsampling (0: 4:2:0, 1: 4:2:2, 2: 4:4:4; None for the unpacked formats), the ``suffix`` of the
+    format's C entries (``pws_upsample_grid_sample_[bicubic_]<suffix>``, ``pws_border_keep_<suffix>``), the ``wrapper`` whose name its error
+    messages carry, and the C entries that make its ``window_planes`` and resize its planes (``plane_resize``).  A new format is a row of
+    FRAME_FORMATS -- the five formats of the 4:2:0 generation, whose names and order are pinned -- or of CHROMA_FORMATS (4:2:2 and 4:4:4),
+    and its kernels; names are resolved through ``lookup_format``, which reads both tables."""
     __slots__ = ()
 
     @property
@@ -160,28 +167,64 @@ class FrameFormat(collections.namedtuple("FrameFormat", "name dtype packed layou
         """(T, H, W, 3) frames ("bgr24"); the float frames are (T, C, H, W)."""
         return not self.packed and self.dtype == torch.uint8
 
+    @property
+    def shifts(self):
+        """(cx, cy): a chroma plane of packed H x W frames is (H >> cy) x (W >> cx) samples; luma pixel (x, y) has chroma sample
+        (x >> cx, y >> cy)."""
+        return CHROMA_SHIFTS[self.chroma]
+
+    @property
+    def multiples(self):
+        """(mx, my): what x and y edges of a window of packed frames must be multiples of, so that the window's chroma is whole samples."""
+        cx, cy = self.shifts
+        return 1 << cx, 1 << cy
+
+    def packed_rows(self, h):
+        """Rows of W samples that a packed frame of even height ``h`` takes: Y, then two chroma planes of (h >> cy) x (W >> cx)."""
+        cx, cy = self.shifts
+        return h + ((2 * (h >> cy)) >> cx)
+
     def frame_shape(self, frames, w_multiple=4):
-        """(T, H, W) of ``frames``.  Packed 4:2:0: (T, H * 3 // 2, W) of the format's dtype, ValueError unless H and W are even and W a multiple
-        of ``w_multiple``.  Unpacked frames are read by position, (T, H, W, 3) or float (T, C, H, W): only another rank is a ValueError here
-        (dtype, channel count and width are checked where the frames are used, behind the check for host tensors)."""
+        """(T, H, W) of ``frames``.  Packed frames: (T, packed_rows(H), W) of the format's dtype -- H * 3 // 2 rows for 4:2:0, 2 * H for 4:2:2,
+        3 * H for 4:4:4 -- ValueError unless H and W are even and W a multiple of ``w_multiple``.  Unpacked frames are read by position,
+        (T, H, W, 3) or float (T, C, H, W): only another rank is a ValueError here (dtype, channel count and width are checked where the
+        frames are used, behind the check for host tensors)."""
         if not self.packed:
             if frames.dim() != 4:
                 raise ValueError("%s: frames must be %s, got %s %s" % (self.wrapper, "uint8 (N,H,W,3)" if self.hwc else "float32 (N,C,H,W)",
                                                                      frames.dtype, tuple(frames.shape)))
             return (frames.shape[0],) + tuple(frames.shape[1:3] if self.hwc else frames.shape[2:4])
+        rows = _PACKED_ROWS[self.chroma]
         if frames.dim() != 3 or frames.dtype != self.dtype:
-            raise ValueError("%s frames must be %s (T, H * 3 // 2, W), got %s %s" % (self.name, str(self.dtype)[6:], frames.dtype, tuple(frames.shape)))
+            raise ValueError("%s frames must be %s (T, %s, W), got %s %s" % (self.name, str(self.dtype)[6:], rows, frames.dtype, tuple(frames.shape)))
         t, ph, w = frames.shape
-        if ph % 3 != 0 or ph == 0:
-            raise ValueError("%s frames: packed height %d is not H * 3 // 2 of an even H" % (self.name, ph))
-        h = ph // 3 * 2
+        unit = self.packed_rows(2)   # (the packed rows of two picture rows: 3, 4, 6)
+        if ph % unit != 0 or ph == 0:
+            raise ValueError("%s frames: packed height %d is not %s of an even H" % (self.name, ph, rows))
+        h = ph // unit * 2
         if w % 2 != 0 or w % w_multiple != 0:
             raise ValueError("%s frames: width %d must be even and a multiple of %d" % (self.name, w, w_multiple))
         return t, h, w
 
+    def planes(self, x, h, w):
+        """Views of the planes of packed frames x (T, packed_rows(h), w): [Y (T, h, w), UV (T, h >> cy, 2 * (w >> cx))] for layout 0 (U V
+        interleaved), [Y, U, V] with U and V (T, h >> cy, w >> cx) for layout 1."""
+        cx, cy = self.shifts
+        t = x.shape[0]
+        y = x[:, :h]
+        if self.layout == 0:
+            return [y, x[:, h:]]   # (4:2:0 and 4:2:2: a row of w >> 1 pairs is w samples)
+        c = x.reshape(t, -1)[:, h * w:].reshape(t, 2, h >> cy, w >> cx)
+        return [y, c[:, 0], c[:, 1]]
+
     def extra(self, flag=False):
-        """The one format argument of the C entries: the plane layout of packed frames; for BGR the caller's ``flag`` (swap_rb, frames_are_rgb)."""
+        """The first format argument of the C entries: the plane layout of packed frames; for BGR the caller's ``flag`` (swap_rb, frames_are_rgb)."""
         return self.layout if self.packed else int(bool(flag))
+
+    def args(self, flag=False):
+        """The format arguments of the C entries, in their order: ``extra(flag)``, and for the entries that take it (the 4:2:2 / 4:4:4
+        formats' ``*_yuv_*``) the chroma subsampling behind it.  The ``*_yuv420_*`` entries take the layout alone."""
+        return (self.extra(flag),) + ((self.chroma,) if self.chroma else ())
 
     def warp_entry(self, mode):
         return _entry(mode, self.suffix)
@@ -193,13 +236,32 @@ class FrameFormat(collections.namedtuple("FrameFormat", "name dtype packed layou
 
 FRAME_FORMATS = {f.name: f for f in (
     FrameFormat("bgr24", torch.uint8, False, None, "u8", "upsample_grid_sample_u8", "pws_gray_area_u8", "pws_area_resize_u8"),
-    FrameFormat("nv12", torch.uint8, True, 0, "yuv420_u8", "upsample_grid_sample_yuv420", "pws_gray_area_yuv420_u8", "pws_area_resize_plane_u8"),
-    FrameFormat("i420", torch.uint8, True, 1, "yuv420_u8", "upsample_grid_sample_yuv420", "pws_gray_area_yuv420_u8", "pws_area_resize_plane_u8"),
-    FrameFormat("p010", torch.uint16, True, 0, "yuv420_u16", "upsample_grid_sample_yuv420_16", "pws_gray_area_yuv420_u16", "pws_area_resize_plane_u16"),
-    FrameFormat("i010", torch.uint16, True, 1, "yuv420_u16", "upsample_grid_sample_yuv420_16", "pws_gray_area_yuv420_u16", "pws_area_resize_plane_u16"),
+    FrameFormat("nv12", torch.uint8, True, 0, "yuv420_u8", "upsample_grid_sample_yuv420", "pws_gray_area_yuv420_u8", "pws_area_resize_plane_u8", 0),
+    FrameFormat("i420", torch.uint8, True, 1, "yuv420_u8", "upsample_grid_sample_yuv420", "pws_gray_area_yuv420_u8", "pws_area_resize_plane_u8", 0),
+    FrameFormat("p010", torch.uint16, True, 0, "yuv420_u16", "upsample_grid_sample_yuv420_16", "pws_gray_area_yuv420_u16", "pws_area_resize_plane_u16", 0),
+    FrameFormat("i010", torch.uint16, True, 1, "yuv420_u16", "upsample_grid_sample_yuv420_16", "pws_gray_area_yuv420_u16", "pws_area_resize_plane_u16", 0),
 )}
+# 4:2:2 and 4:4:4, named the libyuv way (ffmpeg: nv16, yuv422p, p210le, yuv422p10le, yuv444p, yuv444p10le): a table of their own, FRAME_FORMATS
+# being pinned to the five above.  Interleaved 4:4:4 (NV24 / P410) is not offered.
+CHROMA_FORMATS = {f.name: f for f in (
+    FrameFormat("nv16", torch.uint8, True, 0, "yuv_u8", "upsample_grid_sample_yuv", "pws_gray_area_yuv_u8", "pws_area_resize_plane_u8", 1),
+    FrameFormat("i422", torch.uint8, True, 1, "yuv_u8", "upsample_grid_sample_yuv", "pws_gray_area_yuv_u8", "pws_area_resize_plane_u8", 1),
+    FrameFormat("p210", torch.uint16, True, 0, "yuv_u16", "upsample_grid_sample_yuv", "pws_gray_area_yuv_u16", "pws_area_resize_plane_u16", 1),
+    FrameFormat("i210", torch.uint16, True, 1, "yuv_u16", "upsample_grid_sample_yuv", "pws_gray_area_yuv_u16", "pws_area_resize_plane_u16", 1),
+    FrameFormat("i444", torch.uint8, True, 1, "yuv_u8", "upsample_grid_sample_yuv", "pws_gray_area_yuv_u8", "pws_area_resize_plane_u8", 2),
+    FrameFormat("i410", torch.uint16, True, 1, "yuv_u16", "upsample_grid_sample_yuv", "pws_gray_area_yuv_u16", "pws_area_resize_plane_u16", 2),
+)}
+PACKED_FORMATS = tuple(n for n in FRAME_FORMATS if FRAME_FORMATS[n].packed) + tuple(CHROMA_FORMATS)   # every packed YUV format, both depths
 # the float (T, C, H, W) frames that run() accepts under "bgr24": no keep pass, no window planes, no resize
 _FLOAT_FRAMES = FrameFormat("bgr24", torch.float32, False, None, "fwd", "upsample_grid_sample", None, None)
+
+
+def lookup_format(pixel_format):
+    """The record that ``pixel_format`` names in FRAME_FORMATS or CHROMA_FORMATS, or None: the one place where a name becomes a record."""
+    try:
+        return FRAME_FORMATS.get(pixel_format) or CHROMA_FORMATS.get(pixel_format)
+    except TypeError:   # (an unhashable "name")
+        return None
 
 
 def _packed_format(pixel_format, dtype):
@@ -214,11 +276,21 @@ def _packed_format(pixel_format, dtype):
     return fmt
 
 
+def _yuv_format(pixel_format, dtype=None):
+    """The record of any packed YUV format (of that sample dtype, if one is given); ValueError for any other name."""
+    fmt = lookup_format(pixel_format)
+    if fmt is None or not fmt.packed or (dtype is not None and fmt.dtype != dtype):
+        names = tuple(n for n in PACKED_FORMATS if dtype is None or lookup_format(n).dtype == dtype)
+        raise ValueError("pixel_format must be one of %s for packed %sYUV frames, got %r (BT.601 limited range)"
+                         % (names, {None: "", torch.uint8: "8-bit ", torch.uint16: "10-bit "}[dtype], pixel_format))
+    return fmt
+
+
 def frame_format(pixel_format, frames, what, float_frames=False):
     """The record that ``pixel_format`` names, for ``frames``; packed frames are checked against it (``FrameFormat.frame_shape``).  A name that
-    is none of FRAME_FORMATS is ``yuv420_layout``'s ValueError; uint16 frames under "bgr24" are a ValueError naming ``what``; float_frames:
+    is in neither table (``lookup_format``) is ``yuv420_layout``'s ValueError; uint16 frames under "bgr24" are a ValueError naming ``what``; float_frames:
     "bgr24" frames that are not uint8 are float (T, C, H, W) frames."""
-    fmt = FRAME_FORMATS.get(pixel_format) or _packed_format(pixel_format, torch.uint8)
+    fmt = lookup_format(pixel_format) or _packed_format(pixel_format, torch.uint8)
     if fmt.packed:
         fmt.frame_shape(frames)
     elif frames.dtype == torch.uint16:
@@ -230,7 +302,8 @@ def frame_format(pixel_format, frames, what, float_frames=False):
 
 def warp(frames, field, fmt, swap_rb=False, align_corners=None, out=None, mode="bilinear"):
     """The fused resize + warp of ``frames`` in the format ``fmt`` (a FrameFormat) by ``field`` (N, fh, fw, 2): the one implementation behind
-    ``upsample_grid_sample``, ``upsample_grid_sample_u8``, ``upsample_grid_sample_yuv420`` and ``upsample_grid_sample_yuv420_16``, which
+    ``upsample_grid_sample``, ``upsample_grid_sample_u8``, ``upsample_grid_sample_yuv420``, ``upsample_grid_sample_yuv420_16`` and
+    ``upsample_grid_sample_yuv``, which
     document what each format computes.  An invalid ``mode`` is raised before anything else, then the format's shape rules (ValueError),
     then host tensors or a wrong dtype (RuntimeError).  ``swap_rb`` applies to "bgr24" alone."""
     fn = fmt.warp_entry(mode)
@@ -246,7 +319,7 @@ def warp(frames, field, fmt, swap_rb=False, align_corners=None, out=None, mode="
         out = torch.empty_like(frames)
     integer = fmt.packed or fmt.hwc   # (the float entry takes the channel count and no format argument)
     shape = (n, h, w) if integer else (n, frames.shape[1], h, w)
-    extra = (fmt.extra(swap_rb),) if integer else ()
+    extra = fmt.args(swap_rb) if integer else ()
     A.check(getattr(A.lib(), fn)(A.ptr(frames), A.ptr(field), A.ptr(out), *shape, field.shape[1], field.shape[2], *extra, _ac(align_corners),
                                  A.current_stream()), fn)
     return out
@@ -275,8 +348,8 @@ def upsample_grid_sample_u8(frames_hwc, field, swap_rb=False, align_corners=None
 
 
 def yuv420_layout(pixel_format):
-    """0 (NV12) / 1 (I420) for an 8-bit 4:2:0 pixel format; ValueError for anything else (4:2:2, 4:4:4, full range and BT.709 are not
-    supported; the 10-bit formats P010 / I010 have functions of their own: ``yuv420_16_layout``, ``yuv420_16_shape``,
+    """0 (NV12) / 1 (I420) for an 8-bit 4:2:0 pixel format; ValueError for anything else (4:2:2 and 4:4:4 have formats of their own,
+    CHROMA_FORMATS, behind ``upsample_grid_sample_yuv`` and ``yuv_shape``; full range and BT.709 are not supported; the 10-bit formats P010 / I010 have functions of their own: ``yuv420_16_layout``, ``yuv420_16_shape``,
     ``upsample_grid_sample_yuv420_16``)."""
     return _packed_format(pixel_format, torch.uint8).layout
 
@@ -319,9 +392,32 @@ def upsample_grid_sample_yuv420_16(frames, field, pixel_format, align_corners=No
     return warp(frames, field, _packed_format(pixel_format, torch.uint16), False, align_corners, out, mode)
 
 
+def yuv_shape(frames, pixel_format, w_multiple=4):
+    """(T, H, W) of packed YUV frames in any packed ``pixel_format`` (PACKED_FORMATS), of its dtype: (T, H * 3 // 2, W) for the 4:2:0 formats,
+    (T, 2 * H, W) for "nv16" / "i422" / "p210" / "i210", (T, 3 * H, W) for "i444" / "i410"; ValueError unless H and W are even and W a
+    multiple of ``w_multiple``."""
+    return _yuv_format(pixel_format).frame_shape(frames, w_multiple)
+
+
+def upsample_grid_sample_yuv(frames, field, pixel_format, align_corners=None, out=None, mode="bilinear"):
+    """The fused warp for packed YUV frames of ANY packed format, YUV in and YUV out.  The 4:2:0 names give the bits of
+    ``upsample_grid_sample_yuv420`` / ``upsample_grid_sample_yuv420_16``.  4:2:2 -- "nv16" (Y, then H rows of W/2 interleaved U V pairs) and
+    "i422" (Y, U, V with H x W/2 chroma planes), uint8 (N, 2 * H, W); "p210" / "i210", the same in uint16 words placed as P010's / I010's -- and
+    4:4:4 -- "i444" uint8, "i410" uint16 (low 10 bits), (N, 3 * H, W): Y, U, V planes of H x W.  Every plane is warped by ``field``
+    (N, fh, fw, 2) resized (align_corners=True) to the plane's OWN size (chroma is taken as centred on its own grid), taps outside a plane read
+    BT.601 limited-range black (16 / 128; 64 / 512 at 10 bits), the fp32 blend is truncated (10 bits: and clamped to 0..1023).  A plane comes
+    out bit for bit as the same-sized plane of a 4:2:0 frame does.  H even, W % 4 == 0 for every format.  One kernel launch.
+    mode = "bicubic": 16 taps per sample, clamped to the sample range, then truncated; the chroma planes hold the 4-tap window: W >= 8, any W
+    for 4:4:4."""
+    if mode not in INTERPOLATIONS:
+        raise ValueError("mode must be one of %s, got %r" % (INTERPOLATIONS, mode))
+    return warp(frames, field, _yuv_format(pixel_format), False, align_corners, out, mode)   # (name, then shape and dtype, then require_cuda)
+
+
 def keep_borders_(warped, field, initial, pixel_format="bgr24", initial_is_source=False, swap_rb=False, align_corners=None, mode="bilinear"):
     """vid.stab's ``crop=keep`` for the integer fused warps, IN PLACE on ``warped``: T consecutive warped frames of one scene ((T, H, W, 3)
-    uint8 for "bgr24", packed (T, H * 3 // 2, W) uint8 for "nv12" / "i420", uint16 for "p010" / "i010"; contiguous) and the ``field``
+    uint8 for "bgr24", packed (T, H * 3 // 2, W) uint8 for "nv12" / "i420", uint16 for "p010" / "i010", the 4:2:2 and 4:4:4 formats of
+    CHROMA_FORMATS in their packed shapes; contiguous) and the ``field``
     (T, fh, fw, 2) that warped them.  ``out[t] = covered ? warped[t] : out[t-1]`` per plane, where a pixel is covered iff its source position
     (the warp's own, bit for bit) satisfies ``m <= ix <= W-1-m`` and ``m <= iy <= H-1-m`` with m = 0 for mode "bilinear" (all 4 taps inside)
     and 1 for "bicubic" (all 16); NaN is not covered.  ``out[-1]`` is ``initial``, one frame of the frames' layout that does not overlap
@@ -333,7 +429,7 @@ def keep_borders_(warped, field, initial, pixel_format="bgr24", initial_is_sourc
         raise ValueError("mode must be one of %s, got %r" % (INTERPOLATIONS, mode))
     if not isinstance(warped, torch.Tensor) or warped.dtype not in (torch.uint8, torch.uint16):
         raise ValueError("keep_borders_: frames must be uint8 or uint16 (the integer pixel formats), got %s" % (getattr(warped, "dtype", type(warped)),))
-    fmt = FRAME_FORMATS.get(pixel_format) or _packed_format(pixel_format, torch.uint8)   # (an unknown format is a ValueError)
+    fmt = lookup_format(pixel_format) or _packed_format(pixel_format, torch.uint8)   # (an unknown format is a ValueError)
     if fmt.hwc and (warped.dtype != torch.uint8 or warped.dim() != 4 or warped.shape[3] != 3):
         raise ValueError("keep_borders_: bgr24 frames must be uint8 (T,H,W,3), got %s %s" % (warped.dtype, tuple(warped.shape)))
     n, h, w = fmt.frame_shape(warped)   # (packed frames: a tensor of the other depth's dtype is a ValueError)
@@ -348,7 +444,7 @@ def keep_borders_(warped, field, initial, pixel_format="bgr24", initial_is_sourc
         raise ValueError("keep_borders_: field must be (%d, fh, fw, 2), got %s" % (n, tuple(field.shape)))
     field, initial = field.contiguous(), initial.contiguous()
     A.check(getattr(A.lib(), fn)(A.ptr(warped), A.ptr(field), A.ptr(initial), int(bool(initial_is_source)), n, h, w, field.shape[1],
-                                 field.shape[2], fmt.extra(swap_rb), _ac(align_corners), int(mode == "bicubic"), A.current_stream()), fn)
+                                 field.shape[2], *fmt.args(swap_rb), _ac(align_corners), int(mode == "bicubic"), A.current_stream()), fn)
     return warped
 
 

@@ -35,7 +35,7 @@ def _window_planes(frames, fmt, size, out, what, frames_are_rgb=False):
     A.require_cuda(out)
     if tuple(out.shape) != (t, size, size) or not out.is_contiguous():
         raise ValueError("%s: out must be a contiguous (T, %d, %d) float32 tensor" % (what, size, size))
-    A.check(getattr(A.lib(), fmt.window_planes)(A.ptr(frames), A.ptr(out), t, h, w, size, size, 1, fmt.extra(frames_are_rgb), A.current_stream()),
+    A.check(getattr(A.lib(), fmt.window_planes)(A.ptr(frames), A.ptr(out), t, h, w, size, size, 1, *fmt.args(frames_are_rgb), A.current_stream()),
             fmt.window_planes)
     return out
 
@@ -79,31 +79,41 @@ def window_planes_yuv(frames, pixel_format, size=256, out=None):
     4:2:0 frames (T, H * 3 // 2, W) uint8 in one launch (BT.601 limited range, OpenCV 4.x's 8-bit fixed point): the same planes bit for
     bit, so a YUV clip gets the fields of its BGR decode.  H and W even.  -> (T, size, size) float32."""
     A.require_cuda(frames, dtype=torch.uint8)   # (wins over the format's name and shape rules here, as it always has)
-    return _window_planes(frames, PF._packed_format(pixel_format, torch.uint8), size, out, "window_planes_yuv")
+    return _window_planes(frames, _yuv_format(pixel_format, torch.uint8), size, out, "window_planes_yuv")
+
+
+def _yuv_format(pixel_format, dtype):
+    """The record of a packed YUV format of that sample dtype: a 4:2:0 name, or -- the 4:2:0 wrappers' ValueError for any other name staying
+    word for word -- one of the 4:2:2 / 4:4:4 names of functional.CHROMA_FORMATS."""
+    fmt = PF.lookup_format(pixel_format)
+    if fmt is not None and fmt.packed and fmt.dtype == dtype:
+        return fmt
+    return PF._packed_format(pixel_format, dtype)
 
 
 def _yuv_planes(x, h, w, pixel_format):
-    """Views of the planes of packed 4:2:0 frames x (T, h * 3 // 2, w): [Y (T, h, w), UV (T, h/2, w)] for NV12, [Y, U (T, h/2, w/2),
-    V (T, h/2, w/2)] for I420; P010 as NV12 and I010 as I420, in 16-bit words."""
-    t = x.shape[0]
-    y = x[:, :h]
-    if PF.FRAME_FORMATS[pixel_format].layout == 0:
-        return [y, x[:, h:]]
-    c = x.reshape(t, -1)[:, h * w:].reshape(t, 2, h // 2, w // 2)
-    return [y, c[:, 0], c[:, 1]]
+    """Views of the planes of packed frames x (T, packed rows of h, w) (FrameFormat.planes): [Y (T, h, w), UV (T, h/2, w)] for NV12, [Y, U
+    (T, h/2, w/2), V (T, h/2, w/2)] for I420; P010 as NV12 and I010 as I420, in 16-bit words; chroma planes of h x w/2 for the 4:2:2 formats
+    and h x w for 4:4:4."""
+    return PF.lookup_format(pixel_format).planes(x, h, w)
 
 
 def _area_resize_yuv(frames, fmt, size, what):
-    """INTER_AREA plane by plane for packed 4:2:0 frames in the format ``fmt``: what area_resize_yuv and area_resize_yuv16 document."""
+    """INTER_AREA plane by plane for packed frames in the format ``fmt``: what area_resize_yuv and area_resize_yuv16 document.  The output
+    size is a multiple of the format's subsampling per axis (4:2:0: both even; 4:2:2: the width; 4:4:4: free)."""
     t, h, w = fmt.frame_shape(frames, w_multiple=2)
     A.require_cuda(frames, dtype=fmt.dtype)
     ow, oh = int(size[0]), int(size[1])
-    if ow % 2 or oh % 2 or not (0 < ow <= w and 0 < oh <= h):
-        raise ValueError("%s: output size %s must be even and within the %d x %d source" % (what, tuple(size), w, h))
+    (cx, cy), (mx, my) = fmt.shifts, fmt.multiples
+    if ow % mx or oh % my or not (0 < ow <= w and 0 < oh <= h):
+        if fmt.chroma == 0:
+            raise ValueError("%s: output size %s must be even and within the %d x %d source" % (what, tuple(size), w, h))
+        raise ValueError("%s: %s output size %s must be a multiple of %d x %d and within the %d x %d source" % (what, fmt.name, tuple(size), mx, my, w, h))
     frames = frames.contiguous()
-    out = torch.empty((t, oh * 3 // 2, ow), device=frames.device, dtype=fmt.dtype)
+    out = torch.empty(_frames_shape(fmt, t, oh, ow), device=frames.device, dtype=fmt.dtype)
     fs, os_ = frames[0].numel(), out[0].numel()   # (in samples)
-    geo = [(1, h, w, oh, ow)] + ([(2, h // 2, w // 2, oh // 2, ow // 2)] if fmt.layout == 0 else [(1, h // 2, w // 2, oh // 2, ow // 2)] * 2)
+    ch_, cw_, qh_, qw_ = h >> cy, w >> cx, oh >> cy, ow >> cx   # the chroma planes, source and output
+    geo = [(1, h, w, oh, ow)] + ([(2, ch_, cw_, qh_, qw_)] if fmt.layout == 0 else [(1, ch_, cw_, qh_, qw_)] * 2)
     placement = (fmt.layout,) if fmt.dtype == torch.uint16 else ()   # (the 16-bit entry also takes where the 10 bits sit in a word)
     for (c, ph, pw, qh, qw), src, dst in zip(geo, _yuv_planes(frames, h, w, fmt.name), _yuv_planes(out, oh, ow, fmt.name)):
         A.check(getattr(A.lib(), fmt.plane_resize)(A.ptr(src), fs, A.ptr(dst), os_, t, ph, pw, c, qh, qw, *placement, A.current_stream()),
@@ -116,7 +126,7 @@ def area_resize_yuv(frames, pixel_format, size):
     as a 2-channel image, I420's U and V as 1-channel images); ``size`` = (width, height), both even.  (T, H * 3 // 2, W) uint8 ->
     (T, height * 3 // 2, width)."""
     A.require_cuda(frames, dtype=torch.uint8)   # (wins over the format's name and shape rules here, as it always has)
-    return _area_resize_yuv(frames, PF._packed_format(pixel_format, torch.uint8), size, "area_resize_yuv")
+    return _area_resize_yuv(frames, _yuv_format(pixel_format, torch.uint8), size, "area_resize_yuv")
 
 
 def window_planes_yuv16(frames, pixel_format, size=256, out=None):
@@ -124,28 +134,30 @@ def window_planes_yuv16(frames, pixel_format, size=256, out=None):
     of a 10-bit frame is by definition the plane of its 8-bit reduction ``v8 = min(255, (v10 + 2) >> 2)``, fused into the kernel's loads (no
     8-bit copy of the frames): a P010 / I010 clip gets the fields of the NV12 / I420 clip of its reduced samples bit for bit.  H and W even.
     -> (T, size, size) float32."""
-    return _window_planes(frames, PF._packed_format(pixel_format, torch.uint16), size, out, "window_planes_yuv16")
+    return _window_planes(frames, _yuv_format(pixel_format, torch.uint16), size, out, "window_planes_yuv16")
 
 
 def area_resize_yuv16(frames, pixel_format, size):
     """area_resize_yuv for 10-bit frames, INTER_AREA plane by plane on the 10-bit values (P010's interleaved UV as a 2-channel image),
     clamped to 0..1023 and stored in the format's placement; ``size`` = (width, height), both even.  (T, H * 3 // 2, W) uint16 ->
     (T, height * 3 // 2, width)."""
-    return _area_resize_yuv(frames, PF._packed_format(pixel_format, torch.uint16), size, "area_resize_yuv16")
+    return _area_resize_yuv(frames, _yuv_format(pixel_format, torch.uint16), size, "area_resize_yuv16")
 
 
 def _yuv_crop(x, h, w, pixel_format, cy0, cy1, cx0, cx1):
-    """The (even) window [cy0, cy1) x [cx0, cx1) of packed 4:2:0 frames, packed again on the device: Y [cy0:cy1, cx0:cx1], chroma
-    [cy0/2:cy1/2, cx0/2:cx1/2]."""
+    """The window [cy0, cy1) x [cx0, cx1) of packed frames (edges: multiples of the format's subsampling per axis -- even for 4:2:0), packed
+    again on the device: Y [cy0:cy1, cx0:cx1], chroma [cy0 >> cy:cy1 >> cy, cx0 >> cx:cx1 >> cx]."""
+    fmt = PF.lookup_format(pixel_format)
+    cx, cy = fmt.shifts
     ch, cw = cy1 - cy0, cx1 - cx0
-    out = torch.empty((x.shape[0], ch * 3 // 2, cw), device=x.device, dtype=x.dtype)
-    src, dst = _yuv_planes(x, h, w, pixel_format), _yuv_planes(out, ch, cw, pixel_format)
+    out = torch.empty(_frames_shape(fmt, x.shape[0], ch, cw), device=x.device, dtype=x.dtype)
+    src, dst = fmt.planes(x, h, w), fmt.planes(out, ch, cw)
     dst[0].copy_(src[0][:, cy0:cy1, cx0:cx1])
     if len(src) == 2:
-        dst[1].copy_(src[1][:, cy0 // 2:cy1 // 2, cx0:cx1])   # (U V interleaved: chroma columns cx0/2 .. are samples cx0 ..)
+        dst[1].copy_(src[1][:, cy0 >> cy:cy1 >> cy, cx0:cx1])   # (U V interleaved, cx = 1: chroma columns cx0/2 .. are samples cx0 ..)
     else:
         for k in (1, 2):
-            dst[k].copy_(src[k][:, cy0 // 2:cy1 // 2, cx0 // 2:cx1 // 2])
+            dst[k].copy_(src[k][:, cy0 >> cy:cy1 >> cy, cx0 >> cx:cx1 >> cx])
     return out
 
 
@@ -158,7 +170,7 @@ def _output_resize(frames, fmt, size, half):
 
 def _frames_shape(fmt, n, h, w):
     """The shape of n integer frames of h x w pixels in the format ``fmt``."""
-    return (n, h * 3 // 2, w) if fmt.packed else (n, h, w, 3)
+    return (n, fmt.packed_rows(h), w) if fmt.packed else (n, h, w, 3)
 
 
 def _crop(frames, fmt, h, w, cy0, cy1, cx0, cx1):
@@ -455,6 +467,8 @@ class VideoStabilizer:
         pixel_format = "nv12" / "i420": frames are packed 4:2:0 (T, H * 3 // 2, W) uint8 (H even, W % 4 == 0), warped plane by plane in
         the fused YUV kernel (functional.upsample_grid_sample_yuv420: BT.601 black padding); ``self.swap_rb`` does not apply.
         pixel_format = "p010" / "i010": the same for 10-bit frames (T, H * 3 // 2, W) uint16 (functional.upsample_grid_sample_yuv420_16).
+        pixel_format = "nv16" / "i422" / "p210" / "i210" (4:2:2, (T, 2 * H, W)) and "i444" / "i410" (4:4:4, (T, 3 * H, W)): the same, plane by
+        plane with the chroma planes at their own size (functional.upsample_grid_sample_yuv).
         scene_cuts: sorted indices into ``gray`` (halo frames count; 1 .. len - 1) at which a new scene starts.  Windows end at them as they
         end at the clip's ends -- the scene's first / last frame is repeated (_layout) -- and the batches restart at every scene, so a scene
         is stabilised exactly as the clip of that scene alone would be.  None or empty: one scene.
@@ -604,6 +618,11 @@ class VideoStabilizer:
         I420 clip of the reduced samples bit for bit), the warp and the output resize work on the 10-bit values
         (functional.upsample_grid_sample_yuv420_16: black is 64 / 512; area_resize_yuv16); everything else as for NV12 / I420.  A tensor
         whose dtype does not belong to the pixel format is a ValueError.
+        pixel_format = "nv16" / "i422" (uint8) and "p210" / "i210" (uint16), 4:2:2 frames (T, 2 * H, W) -- ProRes, XAVC, DNxHR -- and "i444"
+        (uint8) / "i410" (uint16), 4:4:4 frames (T, 3 * H, W): everything as for the 4:2:0 format of the same depth and plane order, with chroma
+        planes of H x W/2 resp. H x W samples (functional.upsample_grid_sample_yuv; the window planes decode pixel (x, y) with chroma sample
+        (x >> cx, y >> cy)).  H even and W % 4 == 0 as for 4:2:0.  Output sizes and crop edges must be multiples of the subsampling per axis:
+        4:2:2 x even and y free, 4:4:4 both free; crop="auto" rounds the BGR path's window inward to those multiples.
         scene_cuts: edited footage.  A sorted sequence of indices into ``frames`` (halo frames count; 1 .. len - 1) at which a new scene starts
         (a hard cut), or "auto" to find them.  Windows end at a cut as they end at the clip's ends (the scene's first / last frame repeated)
         and the generator batches restart there (run()), so every scene is stabilised as a clip of its own, inside the one chunk pipeline;
@@ -661,7 +680,8 @@ class VideoStabilizer:
         on_host = not frames.is_cuda
         dev = self.device
         fmt = PF.frame_format(pixel_format, frames, "run_video")   # (from here on the format is this record)
-        yuv = fmt.packed   # even output sizes and crop edges
+        yuv = fmt.packed   # output sizes and crop edges: multiples of the subsampling per axis (4:2:0: even)
+        mx, my = fmt.multiples if yuv else (1, 1)
         h, w = fmt.frame_shape(frames)[1:]
         if yuv and frames_are_rgb:
             raise ValueError("run_video: frames_are_rgb has no meaning for %s frames" % pixel_format)
@@ -673,8 +693,10 @@ class VideoStabilizer:
                 raise ValueError("run_video: output_size %s must not exceed the %d x %d source (INTER_AREA down-scaling)" % (tuple(output_size), w, h))
         else:
             oh, ow = (h // 2, w // 2) if half_size_output else (h, w)
-        if yuv and (oh % 2 or ow % 2):
-            raise ValueError("run_video: the %s output size %d x %d must be even" % (pixel_format, ow, oh))
+        if yuv and (oh % my or ow % mx):
+            if fmt.chroma == 0:
+                raise ValueError("run_video: the %s output size %d x %d must be even" % (pixel_format, ow, oh))
+            raise ValueError("run_video: the %s output size %d x %d must be a multiple of %d x %d" % (pixel_format, ow, oh, mx, my))
         auto = isinstance(crop, str)
         if auto:
             if crop != "auto":
@@ -729,8 +751,11 @@ class VideoStabilizer:
                 cx0, cx1, cy0, cy1 = int(crop[0]) + th, int(crop[1]) - th, int(crop[2]) + th, int(crop[3]) - th
                 if not (0 <= cx0 < cx1 <= ow and 0 <= cy0 < cy1 <= oh):
                     raise ValueError("crop window x [%d, %d) y [%d, %d) does not lie inside the %d x %d output frame" % (cx0, cx1, cy0, cy1, ow, oh))
-                if yuv and (cx0 | cx1 | cy0 | cy1) & 1:
-                    raise ValueError("crop window x [%d, %d) y [%d, %d) of %s frames must have even edges" % (cx0, cx1, cy0, cy1, pixel_format))
+                if yuv and ((cx0 | cx1) % mx or (cy0 | cy1) % my):
+                    if fmt.chroma == 0:
+                        raise ValueError("crop window x [%d, %d) y [%d, %d) of %s frames must have even edges" % (cx0, cx1, cy0, cy1, pixel_format))
+                    raise ValueError("crop window x [%d, %d) y [%d, %d) of %s frames must have edges that are multiples of %d (x) and %d (y)"
+                                     % (cx0, cx1, cy0, cy1, pixel_format, mx, my))
             return cy0, cy1, cx0, cx1
 
         def alloc_out():
@@ -884,9 +909,9 @@ class VideoStabilizer:
             zcoef = PF.zoom_coefficients(PF._zoom_windows(self.zoom_windows, T, (h, w), "run_video"), (h, w), fields.shape[1:3]).to(dev, non_blocking=True)
         if auto:
             crop = auto_crop_window(bounds, (h, w), (oh, ow), self.period, scene_cuts=cuts or None)   # (the copy to the host waits for pass 1)
-            if yuv:   # the BGR path's window, rounded inward to even edges
+            if yuv:   # the BGR path's window, rounded inward to the format's multiples (4:2:0: even edges; 4:4:4: as it is)
                 x0, x1, y0, y1 = int(crop[0]), int(crop[1]), int(crop[2]), int(crop[3])
-                crop = (x0 + (x0 & 1), x1 - (x1 & 1), y0 + (y0 & 1), y1 - (y1 & 1))
+                crop = (x0 + (-x0) % mx, x1 - x1 % mx, y0 + (-y0) % my, y1 - y1 % my)
                 if not (crop[1] > crop[0] and crop[3] > crop[2]):
                     raise ValueError("run_video: the even crop window x [%d, %d) y [%d, %d) is empty" % crop)
             cy0, cy1, cx0, cx1 = crop_window(crop)
