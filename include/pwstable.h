@@ -41,6 +41,7 @@
  *   pws_upsample_grid_sample_fwd  the two above fused (720p path)  main_new.py:706-716
  *   pws_upsample_grid_sample_bicubic_*  the fused path with grid_sample(mode="bicubic") (no counterpart in the reference)
  *   pws_border_keep_*             out[t] = covered ? warped[t] : out[t-1] over a scene's warped frames (no counterpart in the reference)
+ *   pws_border_mosaic_*           uncovered pixels from the nearest covering frame within a radius, past or future (no counterpart in the reference)
  *   pws_adam_step                 optim.Adam(...).step()           main_new.py:63,216
  *   pws_field_homography          the automatic crop's per-frame findHomography + perspectiveTransform  main_new.py:550-603
  *   pws_scene_change              the window's end clamp, applied at hard cuts too (cut score)          main_new.py:627-633
@@ -501,6 +502,26 @@ int pws_border_keep_yuv_u8(unsigned char *frames, const float *field, const unsi
                            int fh, int fw, int layout, int chroma, int align_corners, int bicubic, pws_stream_t stream);
 int pws_border_keep_yuv_u16(unsigned short *frames, const float *field, const unsigned short *initial, int initial_is_source, int n, int h, int w,
                             int fh, int fw, int layout, int chroma, int align_corners, int bicubic, pws_stream_t stream);
+
+/* "Mosaic" borders for the fused integer warps (csrc/border_mosaic.hip; no counterpart in the reference): `frames` holds n contiguous WARPED
+ * frames of one scene, as the black-border warps above wrote them, and `field` the n fields that warped them.  Planes, source positions and
+ * coverage are pws_border_keep's (per plane: its own size and field resize; m = 0, or 1 with `bicubic`; NaN is outside).  Frames
+ * [start, stop) are filled in place; all n frames are donors.  A position p of frame t that is not covered takes the sample of the nearest
+ * frame that covers p: k = 1 .. radius in this order, frame t-k if t-k >= 0 and it covers p (the past wins a tie), else frame t+k if
+ * t+k < n and it covers p.  Without a donor within `radius` the warp's sample stays and the position counts as unfilled.  Covered samples
+ * are never modified and donors are read only where they are covered, so filled frames are as good donors as unfilled ones: the result
+ * for [start, stop) depends on frames [start-radius, stop+radius) alone, and any chunking gives the same bytes.
+ * unfilled: (stop - start) int32 in DEVICE memory, WRITTEN (cleared on the stream, then added to by the kernel): per frame the number of
+ * Y-plane positions (BGR: pixel positions) without a donor.  `chroma` is 0 / 1 / 2 for 4:2:0 / 4:2:2 / 4:4:4 and is always passed.
+ * Shapes, layouts, alignment rules and error codes are pws_border_keep's; PWS_EINVAL also for radius outside 1 .. 15 and a range that
+ * does not satisfy 0 <= start <= stop <= n.  One launch (and a 4 (stop - start) byte clear); the traffic is the fields once plus the
+ * uncovered samples and their donors, not the frames. */
+int pws_border_mosaic_u8(unsigned char *frames_hwc, const float *field, int *unfilled, int n, int start, int stop, int radius, int h, int w,
+                         int fh, int fw, int align_corners, int bicubic, pws_stream_t stream);
+int pws_border_mosaic_yuv_u8(unsigned char *frames, const float *field, int *unfilled, int n, int start, int stop, int radius, int h, int w,
+                             int fh, int fw, int layout, int chroma, int align_corners, int bicubic, pws_stream_t stream);
+int pws_border_mosaic_yuv_u16(unsigned short *frames, const float *field, int *unfilled, int n, int start, int stop, int radius, int h, int w,
+                              int fh, int fw, int layout, int chroma, int align_corners, int bicubic, pws_stream_t stream);
 
 /* The automatic crop of the reference's video loop (main_new.py:484-606, a block it keeps inside a string literal), per frame
  * (csrc/homography.hip): field[n,fh,fw,2] resized to the h0 x w0 source frame as pws_upsample_bilinear_ac does is sampled on the

@@ -144,7 +144,7 @@ PIXEL_FORMATS = ("bgr24", "nv12", "i420")
 YUV420_LAYOUT = {"nv12": 0, "i420": 1}
 PIXEL_FORMATS_16 = ("p010", "i010")
 YUV420_16_LAYOUT = {"p010": 0, "i010": 1}
-BORDERS = ("black", "keep")
+BORDERS = ("black", "keep", "mosaic")
 
 
 CHROMA_SHIFTS = ((1, 1), (1, 0), (0, 0))   # (cx, cy) of chroma 0 (4:2:0), 1 (4:2:2), 2 (4:4:4): a chroma plane is (H >> cy) x (W >> cx)
@@ -232,6 +232,11 @@ class FrameFormat(collections.namedtuple("FrameFormat", "name dtype packed layou
     @property
     def keep_entry(self):
         return "pws_border_keep_" + self.suffix
+
+    @property
+    def mosaic_entry(self):
+        """The format's mosaic pass: one entry per sample size for every packed YUV format (``chroma`` is always passed), one for BGR."""
+        return "pws_border_mosaic_" + ("u8" if not self.packed else "yuv_u16" if self.dtype == torch.uint16 else "yuv_u8")
 
 
 FRAME_FORMATS = {f.name: f for f in (
@@ -446,6 +451,50 @@ def keep_borders_(warped, field, initial, pixel_format="bgr24", initial_is_sourc
     A.check(getattr(A.lib(), fn)(A.ptr(warped), A.ptr(field), A.ptr(initial), int(bool(initial_is_source)), n, h, w, field.shape[1],
                                  field.shape[2], *fmt.args(swap_rb), _ac(align_corners), int(mode == "bicubic"), A.current_stream()), fn)
     return warped
+
+
+MOSAIC_MAX_RADIUS = 15   # (one window bit per frame, 2 radius + 1 of them in a 32-bit register)
+
+
+def mosaic_borders_(warped, field, radius, start=0, stop=None, pixel_format="bgr24", align_corners=None, mode="bilinear", return_unfilled=False,
+                    _unfilled=None):
+    """Mosaic borders for the integer fused warps, IN PLACE on ``warped``: n consecutive frames of one scene as the black-border warp wrote
+    them (``keep_borders_``' shapes and formats; contiguous) and the ``field`` (n, fh, fw, 2) that warped them.  Planes, source positions and
+    coverage are ``keep_borders_``': a position is covered iff ``m <= ix <= W-1-m`` and ``m <= iy <= H-1-m``, m = 0 for mode "bilinear", 1 for
+    "bicubic"; NaN is not covered.  Frames ``[start, stop)`` (``stop=None``: n) are filled, all n frames are donors: an uncovered position p of
+    frame t takes the sample of the temporally nearest frame that covers p -- k = 1 .. ``radius``, frame t-k first (the past wins a tie), then
+    frame t+k, inside [0, n).  Without a donor within ``radius`` (1 .. 15) the warp's blend with the pad colour stays, and the position counts
+    as unfilled.  Covered samples are never modified and donors are read only where they are covered, so the result for [start, stop)
+    depends on frames [start-radius, stop+radius) alone and chunked calls give the bytes of one call.  One launch (csrc/border_mosaic.hip).
+    Float frames are a ValueError.  Returns ``warped``, or with ``return_unfilled`` ``(warped, unfilled)``: (stop - start,) int32 on the
+    device, per frame the Y-plane (BGR: pixel) positions without a donor."""
+    if mode not in INTERPOLATIONS:
+        raise ValueError("mode must be one of %s, got %r" % (INTERPOLATIONS, mode))
+    if not isinstance(warped, torch.Tensor) or warped.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError("mosaic_borders_: frames must be uint8 or uint16 (the integer pixel formats), got %s" % (getattr(warped, "dtype", type(warped)),))
+    fmt = lookup_format(pixel_format) or _packed_format(pixel_format, torch.uint8)   # (an unknown format is a ValueError)
+    if fmt.hwc and (warped.dtype != torch.uint8 or warped.dim() != 4 or warped.shape[3] != 3):
+        raise ValueError("mosaic_borders_: bgr24 frames must be uint8 (T,H,W,3), got %s %s" % (warped.dtype, tuple(warped.shape)))
+    n, h, w = fmt.frame_shape(warped)   # (packed frames: a tensor of the other depth's dtype is a ValueError)
+    radius, start, stop = int(radius), int(start), n if stop is None else int(stop)
+    if not 1 <= radius <= MOSAIC_MAX_RADIUS:
+        raise ValueError("mosaic_borders_: radius must be 1 .. %d (one window bit per frame), got %d" % (MOSAIC_MAX_RADIUS, radius))
+    if not 0 <= start <= stop <= n:
+        raise ValueError("mosaic_borders_: the range must satisfy 0 <= start <= stop <= %d, got [%d, %d)" % (n, start, stop))
+    fn = fmt.mosaic_entry
+    A.require_cuda(field)
+    A.require_cuda(warped, dtype=warped.dtype)
+    if not warped.is_contiguous():
+        raise ValueError("mosaic_borders_: frames are modified in place and must be contiguous")
+    if field.dim() != 4 or field.shape[0] != n or field.shape[3] != 2:
+        raise ValueError("mosaic_borders_: field must be (%d, fh, fw, 2), got %s" % (n, tuple(field.shape)))
+    field = field.contiguous()
+    # (_unfilled, the stabiliser's: the contiguous (stop - start,) int32 slice of its per-clip counts to write into)
+    unfilled = _unfilled if _unfilled is not None else torch.empty(stop - start, dtype=torch.int32, device=warped.device)
+    fargs = (fmt.layout, fmt.chroma) if fmt.packed else ()
+    A.check(getattr(A.lib(), fn)(A.ptr(warped), A.ptr(field), A.ptr(unfilled), n, start, stop, radius, h, w, field.shape[1], field.shape[2], *fargs,
+                                 _ac(align_corners), int(mode == "bicubic"), A.current_stream()), fn)
+    return (warped, unfilled) if return_unfilled else warped
 
 
 def _zoom_windows(windows, n, frame_hw, what="zoom_fields"):

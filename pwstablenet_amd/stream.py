@@ -377,7 +377,8 @@ def _windows(gray_padded, start, count, period):
 
 
 class VideoStabilizer:
-    def __init__(self, netG, batch=32, period=30, device=None, swap_rb=False, interpolation="bilinear", borders="black", rigidity=0.0):
+    def __init__(self, netG, batch=32, period=30, device=None, swap_rb=False, interpolation="bilinear", borders="black", rigidity=0.0,
+                 mosaic_radius=8):
         self.net = netG
         # how far run / run_video pull each frame's field towards the homography fitted to it (functional.rigid_fields): 0 = the field as the
         # generator regressed it (no fit, no launch), 1 = every frame warped by its homography alone -- no local distortion, and no parallax
@@ -387,7 +388,15 @@ class VideoStabilizer:
             raise ValueError("borders must be one of %s, got %r" % (PF.BORDERS, borders))
         # what run / run_video show where a frame's field samples outside the source: the warp's pad colour, or -- "keep", vid.stab's
         # crop=keep -- the previous output frame of the scene (functional.keep_borders_, one more launch per batch and scene)
+        # "mosaic": the temporally nearest stabilised frame of the scene that covers the pixel, at most mosaic_radius frames into the past or
+        # the future (functional.mosaic_borders_, one launch per scene piece once the neighbours are warped).  8 is a judgement -- about a
+        # quarter second at 30 fps -- that no footage here can fit.
         self.borders = borders
+        self.mosaic_radius = int(mosaic_radius)
+        if not 1 <= self.mosaic_radius <= PF.MOSAIC_MAX_RADIUS:
+            raise ValueError("mosaic_radius must be 1 .. %d (the kernel keeps one window bit per frame), got %r" % (PF.MOSAIC_MAX_RADIUS, mosaic_radius))
+        self.mosaic_unfilled = None   # borders="mosaic": per frame of the last run / run_video, the Y (BGR: pixel) positions no frame within the
+        #                               radius covers: (T,) int32 on the device; None for the other border modes
         if interpolation not in PF.INTERPOLATIONS:
             raise ValueError("interpolation must be one of %s, got %r" % (PF.INTERPOLATIONS, interpolation))
         self.interpolation = interpolation   # how run / run_video make an output pixel: 4 taps, or grid_sample(mode="bicubic")'s 16
@@ -457,7 +466,7 @@ class VideoStabilizer:
 
     @torch.no_grad()
     def run(self, gray, frames, halo_left=0, halo_right=0, out=None, pixel_format="bgr24", scene_cuts=None, keep_from=None, _keep_wait=None,
-            zoom=None, _zoom_unc=None, _rigid_stats=None):
+            zoom=None, _zoom_unc=None, _rigid_stats=None, _mosaic_pad=None):
         """gray: (T + halo_left + halo_right, 256, 256) float32 in [-1,1] (``x/255*2-1`` as the reference, :650) for the T
         frames to stabilise plus whatever real neighbours exist on either side (up to period//2); frames: (T, C, H, W)
         float32 0..255, or (T, H, W, 3) uint8 as OpenCV delivers them (then the warp runs in the uint8 kernel: 4x less
@@ -482,6 +491,13 @@ class VideoStabilizer:
         batch's field goes through ``zoom_fields`` after the generator and before the warp, so the output shows that window of the stabilised
         frame at the full frame size, still resampled once.  The windows are left in ``self.zoom_windows``, the per-frame counts of field
         nodes that sample outside the source in ``self.zoom_uncovered``.  Not with borders="keep" (ValueError).
+        borders="mosaic" (integer frames only; float frames are a ValueError): the call's own frames are the only donors.  Every batch is
+        warped with black borders into one device buffer, the fields that warped them (after rigidity) are kept beside it, and once every
+        batch is warped ``functional.mosaic_borders_`` runs once per scene piece (slices along dim 0, cut at ``scene_cuts``) with
+        ``self.mosaic_radius``; then the frames are copied out.  Halo frames are never warped and so are no donors: a shard's first and last
+        ``mosaic_radius`` frames do not promise the unsharded clip's bytes inside the wedges.  ``self.mosaic_unfilled`` (T,) int32 is left on
+        the device (no synchronisation).  Not with a zoom (ValueError).  (_mosaic_pad, run_video's: the buffers get that many spare frames at
+        either end and are returned unfilled, (warped, fields), instead of the output.)
         VideoStabilizer(rigidity=r), r > 0: each batch's field is fitted (``field_homography``) and blended towards its homography
         (``functional.rigid_fields``, into a fresh tensor: the generator's output may be a graph's static buffer) right after the generator;
         the zoom, the warp and borders="keep" all see the adjusted field.  Nothing here depends on other frames, so halos are fine; frames
@@ -490,8 +506,15 @@ class VideoStabilizer:
         half = self.period // 2
         keep = self.borders == "keep"
         rigid = self.rigidity > 0.0
+        mosaic = self.borders == "mosaic"
         if zoom is not None and keep:
             raise ValueError("run: zoom removes the wedges that borders=\"keep\" fills: choose one")
+        if zoom is not None and mosaic:
+            raise ValueError("run: zoom removes the wedges that borders=\"mosaic\" fills: choose one")
+        if mosaic and frames.dtype not in (torch.uint8, torch.uint16):
+            raise ValueError("run: borders=\"mosaic\" is for the integer pixel formats (uint8 / uint16 frames), got %s" % (frames.dtype,))
+        if _mosaic_pad is None:
+            self.mosaic_unfilled = torch.empty((frames.shape[0],), device=self.device, dtype=torch.int32) if mosaic else None
         if keep and frames.dtype not in (torch.uint8, torch.uint16):
             raise ValueError("run: borders=\"keep\" is for the integer pixel formats (uint8 / uint16 frames), got %s" % (frames.dtype,))
         fmt = PF.frame_format(pixel_format, frames, "run", float_frames=True)   # (from here on the format is this record)
@@ -530,6 +553,7 @@ class VideoStabilizer:
         nxt = fetch(0)
         pending = []
         cutset, prev = set(cuts or ()), None
+        pad, wall, fall = _mosaic_pad or 0, None, None   # borders="mosaic": the call's warped frames and fields, `pad` spare frames at either end
         for k, (s, e, start) in enumerate(batches):
             cur, ev = nxt
             if k + 1 < len(batches):
@@ -549,6 +573,16 @@ class VideoStabilizer:
                 field = field.contiguous()
                 field = PF._field_zoom(field, zcoef[s:e], frame_hw, self.align_corners, self.interpolation, torch.empty_like(field),
                                        self.zoom_uncovered[s:e])
+            if mosaic:   # black borders into the call's buffer; the fill needs every batch
+                if wall is None:
+                    wall = torch.empty((T + 2 * pad,) + tuple(frames.shape[1:]), device=dev, dtype=frames.dtype)
+                    fall = torch.empty((T + 2 * pad,) + tuple(field.shape[1:]), device=dev, dtype=torch.float32)
+                PF.warp(cur.contiguous(), field, fmt, swap_rb=self.swap_rb, align_corners=self.align_corners, out=wall[pad + s:pad + e],
+                        mode=self.interpolation)
+                fall[pad + s:pad + e].copy_(field)
+                if on_host:
+                    cur.record_stream(compute)
+                continue
             warped = PF.warp(cur.contiguous(), field, fmt, swap_rb=self.swap_rb, align_corners=self.align_corners, mode=self.interpolation)
             if keep:
                 if (s + halo_left) in cutset or (s == 0 and keep_from is None):
@@ -574,6 +608,22 @@ class VideoStabilizer:
                 pending.append(warped)
             else:
                 out[s:e].copy_(warped)
+        if mosaic:
+            if _mosaic_pad is not None:
+                return wall, fall
+            edges = [0] + [c - halo_left for c in (cuts or ()) if 0 < c - halo_left < T] + [T]
+            for a, b in zip(edges[:-1], edges[1:]):   # one scene piece per call: donors never cross a cut
+                PF.mosaic_borders_(wall[a:b], fall[a:b], self.mosaic_radius, pixel_format=pixel_format, align_corners=self.align_corners,
+                                   mode=self.interpolation, _unfilled=self.mosaic_unfilled[a:b])
+            if on_host:
+                done = torch.cuda.Event()
+                done.record(compute)
+                with torch.cuda.stream(d2h):
+                    d2h.wait_event(done)
+                    out.copy_(wall, non_blocking=True)
+                wall.record_stream(d2h)
+            else:
+                out.copy_(wall)
         if on_host:
             d2h.synchronize()
         return out
@@ -644,6 +694,17 @@ class VideoStabilizer:
         output_size, half_size_output, halos and host or device input work as before; a shard with halo_left > 0 has no history, starts its
         first frame from that frame's source and does not promise the unsharded clip's bytes in its wedges; crop="auto" is a ValueError
         (it removes what "keep" fills).
+        VideoStabilizer(borders="mosaic", mosaic_radius=R): an uncovered pixel takes its value from the temporally nearest stabilised frame of
+        its scene that covers it, at most R frames into the past or the FUTURE (functional.mosaic_borders_ has the definition): nothing is
+        older than R frames, and chunking does not change a byte.  A chunk is finished one chunk late: chunk c is warped with black borders
+        and its fields are kept; then chunk c-1 is filled -- its donors are the last R warped frames of chunk c-2 and the first R of chunk c,
+        copied beside it into one buffer, each call cut at the scene limits -- and goes through the output resize, the crop and the copy out
+        as usual; the last chunk is finished after the loop.  About two chunks plus 2 R frames and their fields stay on the device.
+        scene_cuts (a list or "auto": a chunk's cuts are known before it is issued), output_size, half_size_output, an explicit crop,
+        rigidity (coverage uses the field that warped), every integer pixel_format, both interpolations, halos and host or device input work
+        as with "black"; a shard's first and last R frames do not promise the unsharded clip's bytes in their wedges (halo frames are not
+        warped).  ``self.mosaic_unfilled`` (T,) int32 stays on the device.  ValueError: zoom or crop="auto" (they remove what it fills),
+        chunk < R (adjacent chunks must suffice), in_flight > 1 (the one-chunk delay across two lanes needs an event design of its own).
         zoom: zoom to fill (vid.stab's ``zoom`` / ``optzoom``) -- the third answer to the wedges: the output keeps the size that was asked for,
         and shows a window of the stabilised frame enlarged to it.  The zoom is composed into each frame's FIELD (functional.zoom_fields, one
         small launch per batch) and the warp that follows resamples the source once, as without a zoom; windows are fractional, also for the
@@ -704,11 +765,21 @@ class VideoStabilizer:
             if halo_left or halo_right:
                 raise ValueError("run_video: crop=\"auto\" needs the whole clip (a shard cannot see the clip's crop recurrence): gather "
                                  "the shards' field_homography bounds and pass crop=auto_crop_window(...)")
-            if self.borders == "keep":
-                raise ValueError("run_video: crop=\"auto\" removes the wedges that borders=\"keep\" fills: choose one")
+            if self.borders in ("keep", "mosaic"):
+                raise ValueError("run_video: crop=\"auto\" removes the wedges that borders=\"%s\" fills: choose one" % self.borders)
             _check_lattice(h, w)
         self.zoom_windows = self.zoom_uncovered = None
         self.rigid_residual = self.rigid_unfit = None
+        self.mosaic_unfilled = None
+        mosaic, radius = self.borders == "mosaic", self.mosaic_radius
+        if mosaic:
+            if frames.dtype not in (torch.uint8, torch.uint16):
+                raise ValueError("run_video: borders=\"mosaic\" is for the integer pixel formats (uint8 / uint16 frames), got %s" % (frames.dtype,))
+            if max(1, int(in_flight)) > 1:
+                raise ValueError("run_video: borders=\"mosaic\" finishes a chunk one chunk late, which across two lanes needs an event design of "
+                                 "its own: use in_flight=1")
+            if int(chunk) < radius:
+                raise ValueError("run_video: chunk=%d is shorter than mosaic_radius=%d: a chunk's donors must lie in the adjacent chunks" % (chunk, radius))
         rigid = self.rigidity > 0.0
         if rigid:
             _check_lattice(h, w, "rigidity > 0")
@@ -716,8 +787,8 @@ class VideoStabilizer:
         if zoom is not None:
             if crop is not None:
                 raise ValueError("run_video: zoom fills the frame that a crop would cut: give zoom or crop, not both")
-            if self.borders == "keep":
-                raise ValueError("run_video: zoom removes the wedges that borders=\"keep\" fills: choose one")
+            if self.borders in ("keep", "mosaic"):
+                raise ValueError("run_video: zoom removes the wedges that borders=\"%s\" fills: choose one" % self.borders)
             if isinstance(zoom, str):
                 if zoom not in ("auto", "adaptive"):
                     raise ValueError("zoom must be None, a fraction in (0, 1], \"auto\" or \"adaptive\", got %r" % (zoom,))
@@ -843,6 +914,41 @@ class VideoStabilizer:
                 warped.record_stream(down)
             else:
                 out[s:e].copy_(warped)
+        pend = None   # borders="mosaic": the chunk that waits for its successor -- (warped, fields, cs, ce, buf, valid frames of the head pad)
+        if mosaic:
+            unf = torch.empty((T,), device=dev, dtype=torch.int32)
+
+        def mosaic_step(new, lane):
+            """chunk `new` = (warped, fields, cs, ce, buf), both buffers with `radius` spare frames at either end, has been warped (None: the
+            clip is over): the waiting chunk takes its first frames as donors, is filled scene by scene and finished; `new` takes the
+            waiting chunk's last frames and waits in its turn.  (Filled frames are as good donors as the warp's own.)"""
+            nonlocal pend
+            R = radius
+            if pend is not None:
+                pw, pf, ps, pe, pbuf, nt = pend
+                nh = 0
+                if new is not None:
+                    nh = min(R, new[3] - new[2])
+                    pw[R + pe - ps:R + pe - ps + nh].copy_(new[0][R:R + nh])
+                    pf[R + pe - ps:R + pe - ps + nh].copy_(new[1][R:R + nh])
+                lo, hi, off = ps - nt, pe + nh, R - ps   # the frames the buffer holds (index space of `frames`); frame g is at g + off
+                edges = [halo_left] + [t for t in cuts if halo_left < t < halo_left + T] + [halo_left + T]
+                for a, b in zip(edges[:-1], edges[1:]):
+                    fa, fb = max(a, ps), min(b, pe)
+                    if fa < fb:
+                        da, db = max(a, lo), min(b, hi)
+                        PF.mosaic_borders_(pw[da + off:db + off], pf[da + off:db + off], R, fa - da, fb - da, pixel_format=pixel_format,
+                                           align_corners=self.align_corners, mode=self.interpolation, _unfilled=unf[fa - halo_left:fb - halo_left])
+                finish(pw[R:R + pe - ps], pbuf, ps - halo_left, pe - halo_left, lane)
+            if new is not None:
+                nt = 0
+                if pend is not None:
+                    nt = min(R, pe - ps)
+                    new[0][R - nt:R].copy_(pw[R + pe - ps - nt:R + pe - ps])
+                    new[1][R - nt:R].copy_(pf[R + pe - ps - nt:R + pe - ps])
+                pend = tuple(new) + (nt,)
+            else:
+                pend = None
         staged, uploaded = {}, 0
         keep = self.borders == "keep"
         carry, carried = None, None   # borders="keep": the last warped (pre-resize) frame so far, and the event behind the pass that made it
@@ -879,6 +985,11 @@ class VideoStabilizer:
                             PF._field_rigid(fields[cs:ce], hom[cs:ce], (h, w), self.rigidity, fields[cs:ce], rres[cs:ce], runf[cs:ce])
                         continue
                     rstats = (rres[cs - halo_left:ce - halo_left], runf[cs - halo_left:ce - halo_left]) if rigid else None
+                    if mosaic:   # warped with black borders; the chunk before it is filled and finished
+                        wall, fall = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr, pixel_format=pixel_format,
+                                              scene_cuts=sc, _rigid_stats=rstats, _mosaic_pad=radius)
+                        mosaic_step((wall, fall, cs, ce, buf), lane)
+                        continue
                     if zmode is not None:   # ("fixed": the one window, in the single pass)
                         warped = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr, pixel_format=pixel_format,
                                           scene_cuts=sc, zoom=zwin, _zoom_unc=zunc[cs - halo_left:ce - halo_left], _rigid_stats=rstats)
@@ -891,6 +1002,9 @@ class VideoStabilizer:
                             carried = torch.cuda.Event()
                             carried.record(lane)
                     finish(warped, buf, cs - halo_left, ce - halo_left, lane)
+            if mosaic:
+                mosaic_step(None, compute)   # the last chunk
+                self.mosaic_unfilled = unf
         finally:
             if restore is not None:
                 for lane in lanes[1:]:
