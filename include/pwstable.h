@@ -42,6 +42,7 @@
  *   pws_upsample_grid_sample_bicubic_*  the fused path with grid_sample(mode="bicubic") (no counterpart in the reference)
  *   pws_border_keep_*             out[t] = covered ? warped[t] : out[t-1] over a scene's warped frames (no counterpart in the reference)
  *   pws_border_mosaic_*           uncovered pixels from the nearest covering frame within a radius, past or future (no counterpart in the reference)
+ *   pws_border_edge_*             uncovered pixels from the source frame itself, clamped or mirrored beyond its rim (no counterpart in the reference)
  *   pws_adam_step                 optim.Adam(...).step()           main_new.py:63,216
  *   pws_field_homography          the automatic crop's per-frame findHomography + perspectiveTransform  main_new.py:550-603
  *   pws_scene_change              the window's end clamp, applied at hard cuts too (cut score)          main_new.py:627-633
@@ -522,6 +523,28 @@ int pws_border_mosaic_yuv_u8(unsigned char *frames, const float *field, int *unf
                              int fh, int fw, int layout, int chroma, int align_corners, int bicubic, pws_stream_t stream);
 int pws_border_mosaic_yuv_u16(unsigned short *frames, const float *field, int *unfilled, int n, int start, int stop, int radius, int h, int w,
                               int fh, int fw, int layout, int chroma, int align_corners, int bicubic, pws_stream_t stream);
+
+/* Edge modes for the fused integer warps (csrc/border_edge.hip; no counterpart in the reference): `frames` holds n contiguous WARPED frames
+ * as the black-border warps above wrote them, `source` the n SOURCE frames they were warped from (same shape and layout) and `field` the n
+ * fields that warped them.  Planes, source positions and coverage are pws_border_keep's (per plane: its own size and field resize; m = 0, or
+ * 1 with `bicubic`; NaN is outside).  A covered sample and one with a non-finite coordinate stay as they are.  Every other sample is
+ * replaced whole by the source plane sampled at (ix, iy) with the plane continued beyond its rim:
+ *   Q( sum_i sum_j wy_i wx_j v(fold(y0 + i, h), fold(x0 + j, w)) ),  x0 = floor(ix), y0 = floor(iy); taps 0, 1 with weights (1 - t, t), or
+ *   with `bicubic` taps -1 .. 2 with the Keys weights (A = -0.75) of the bicubic warps;
+ *   edge 1 (clamp):  fold(i, n) = min(max(i, 0), n - 1)                          -- torch's padding_mode="border", OpenCV's BORDER_REPLICATE;
+ *   edge 2 (mirror): k = i mod 2 (n - 1); fold = k < n ? k : 2 (n - 1) - k; 0 when n == 1  -- "reflection", BORDER_REFLECT_101;
+ *   v: the source sample under the warps' read rules (swap_rb; P010 word >> 6; I010 min(word, 1023)); Q: clamp to 0 .. 255 / 0 .. 1023, then
+ *   truncate, written as the warps write it (P010: v10 << 6).
+ * Taps that all hold one value give that value exactly; every finite coordinate is defined (floor is bounded before the conversion, the fold
+ * is integer arithmetic).  No other frame is read.  `source` must not overlap `frames` (PWS_EINVAL); edge other than 1 or 2 is PWS_EINVAL.
+ * `chroma` is 0 / 1 / 2 for 4:2:0 / 4:2:2 / 4:4:4 and is always passed.  Shapes, layouts, alignment rules (they hold for `source` too) and
+ * error codes are pws_border_keep's.  One launch; the traffic is the fields plus the uncovered samples and their taps, not the frames. */
+int pws_border_edge_u8(unsigned char *frames_hwc, const unsigned char *source_hwc, const float *field, int n, int h, int w, int fh, int fw,
+                       int swap_rb, int align_corners, int bicubic, int edge, pws_stream_t stream);
+int pws_border_edge_yuv_u8(unsigned char *frames, const unsigned char *source, const float *field, int n, int h, int w, int fh, int fw, int layout,
+                           int chroma, int align_corners, int bicubic, int edge, pws_stream_t stream);
+int pws_border_edge_yuv_u16(unsigned short *frames, const unsigned short *source, const float *field, int n, int h, int w, int fh, int fw,
+                            int layout, int chroma, int align_corners, int bicubic, int edge, pws_stream_t stream);
 
 /* The automatic crop of the reference's video loop (main_new.py:484-606, a block it keeps inside a string literal), per frame
  * (csrc/homography.hip): field[n,fh,fw,2] resized to the h0 x w0 source frame as pws_upsample_bilinear_ac does is sampled on the

@@ -144,7 +144,8 @@ PIXEL_FORMATS = ("bgr24", "nv12", "i420")
 YUV420_LAYOUT = {"nv12": 0, "i420": 1}
 PIXEL_FORMATS_16 = ("p010", "i010")
 YUV420_16_LAYOUT = {"p010": 0, "i010": 1}
-BORDERS = ("black", "keep", "mosaic")
+BORDERS = ("black", "keep", "mosaic")   # which FRAMES may fill a wedge
+EDGES = ("pad", "clamp", "mirror")       # how the SOURCE continues beyond its rim (the C entries' `edge`: the index)
 
 
 CHROMA_SHIFTS = ((1, 1), (1, 0), (0, 0))   # (cx, cy) of chroma 0 (4:2:0), 1 (4:2:2), 2 (4:4:4): a chroma plane is (H >> cy) x (W >> cx)
@@ -237,6 +238,11 @@ class FrameFormat(collections.namedtuple("FrameFormat", "name dtype packed layou
     def mosaic_entry(self):
         """The format's mosaic pass: one entry per sample size for every packed YUV format (``chroma`` is always passed), one for BGR."""
         return "pws_border_mosaic_" + ("u8" if not self.packed else "yuv_u16" if self.dtype == torch.uint16 else "yuv_u8")
+
+    @property
+    def edge_entry(self):
+        """The format's edge pass: as ``mosaic_entry``, one entry per sample size for every packed YUV format, one for BGR."""
+        return "pws_border_edge_" + ("u8" if not self.packed else "yuv_u16" if self.dtype == torch.uint16 else "yuv_u8")
 
 
 FRAME_FORMATS = {f.name: f for f in (
@@ -495,6 +501,49 @@ def mosaic_borders_(warped, field, radius, start=0, stop=None, pixel_format="bgr
     A.check(getattr(A.lib(), fn)(A.ptr(warped), A.ptr(field), A.ptr(unfilled), n, start, stop, radius, h, w, field.shape[1], field.shape[2], *fargs,
                                  _ac(align_corners), int(mode == "bicubic"), A.current_stream()), fn)
     return (warped, unfilled) if return_unfilled else warped
+
+
+def edge_borders_(warped, source, field, edge, pixel_format="bgr24", swap_rb=False, align_corners=None, mode="bilinear"):
+    """Edge modes for the integer fused warps, IN PLACE on ``warped``: n frames as the black-border warp wrote them (``keep_borders_``' shapes
+    and formats; contiguous), the n ``source`` frames they were warped from (same shape and dtype, not overlapping ``warped``) and the
+    ``field`` (n, fh, fw, 2) that warped them.  Planes, source positions and coverage are ``keep_borders_``': a position is covered iff
+    ``m <= ix <= W-1-m`` and ``m <= iy <= H-1-m``, m = 0 for mode "bilinear", 1 for "bicubic"; NaN is not covered.  A covered sample keeps the
+    warp's bytes, and so does one with a non-finite coordinate.  Every other sample is replaced whole by the source plane sampled at
+    (ix, iy) with ``mode``'s taps (2 x 2, or 4 x 4 with the Keys weights, A = -0.75) and the plane continued beyond its rim: ``edge`` "clamp"
+    repeats the edge sample (tap index ``min(max(i, 0), n-1)``: torch's ``padding_mode="border"``, OpenCV's BORDER_REPLICATE), "mirror"
+    reflects about it without repeating it (``k = i mod 2(n-1)``, ``k < n ? k : 2(n-1) - k``: "reflection" with align_corners=True,
+    BORDER_REFLECT_101).  Source samples are read as the warp reads them (``swap_rb``; P010 ``word >> 6``; I010 ``min(word, 1023)``), the
+    fp32 blend is clamped to the sample range, truncated and written as the warp writes it.  Taps that all hold one value give that value
+    exactly, and every finite coordinate is defined.  "pad" returns ``warped`` as it is, without a launch.  No other frame is read.  One
+    launch (csrc/border_edge.hip).  Float frames, a non-contiguous ``warped``, a ``source`` of another shape or dtype and an unknown ``edge``
+    or ``mode`` are ValueErrors.  Returns ``warped``."""
+    if mode not in INTERPOLATIONS:
+        raise ValueError("mode must be one of %s, got %r" % (INTERPOLATIONS, mode))
+    if not isinstance(edge, str) or edge not in EDGES:
+        raise ValueError("edge must be one of %s, got %r" % (EDGES, edge))
+    if not isinstance(warped, torch.Tensor) or warped.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError("edge_borders_: frames must be uint8 or uint16 (the integer pixel formats), got %s" % (getattr(warped, "dtype", type(warped)),))
+    fmt = lookup_format(pixel_format) or _packed_format(pixel_format, torch.uint8)   # (an unknown format is a ValueError)
+    if fmt.hwc and (warped.dtype != torch.uint8 or warped.dim() != 4 or warped.shape[3] != 3):
+        raise ValueError("edge_borders_: bgr24 frames must be uint8 (T,H,W,3), got %s %s" % (warped.dtype, tuple(warped.shape)))
+    n, h, w = fmt.frame_shape(warped)   # (packed frames: a tensor of the other depth's dtype is a ValueError)
+    if not isinstance(source, torch.Tensor) or source.dtype != warped.dtype or tuple(source.shape) != tuple(warped.shape):
+        raise ValueError("edge_borders_: source must be the warped frames' sources, %s %s, got %s %s"
+                         % (warped.dtype, tuple(warped.shape), getattr(source, "dtype", type(source)), tuple(getattr(source, "shape", ()))))
+    if not warped.is_contiguous():
+        raise ValueError("edge_borders_: frames are modified in place and must be contiguous")
+    if edge == "pad":
+        return warped
+    fn = fmt.edge_entry
+    A.require_cuda(field)
+    A.require_cuda(warped, source, dtype=warped.dtype)
+    if field.dim() != 4 or field.shape[0] != n or field.shape[3] != 2:
+        raise ValueError("edge_borders_: field must be (%d, fh, fw, 2), got %s" % (n, tuple(field.shape)))
+    field, source = field.contiguous(), source.contiguous()
+    fargs = (fmt.layout, fmt.chroma) if fmt.packed else (int(bool(swap_rb)),)
+    A.check(getattr(A.lib(), fn)(A.ptr(warped), A.ptr(source), A.ptr(field), n, h, w, field.shape[1], field.shape[2], *fargs, _ac(align_corners),
+                                 int(mode == "bicubic"), EDGES.index(edge), A.current_stream()), fn)
+    return warped
 
 
 def _zoom_windows(windows, n, frame_hw, what="zoom_fields"):

@@ -257,6 +257,9 @@ SIGNATURES = {
     "pws_border_mosaic_u8": (_I, [_P, _P, _P] + [_I] * 10 + [_P]),
     "pws_border_mosaic_yuv_u8": (_I, [_P, _P, _P] + [_I] * 12 + [_P]),
     "pws_border_mosaic_yuv_u16": (_I, [_P, _P, _P] + [_I] * 12 + [_P]),
+    "pws_border_edge_u8": (_I, [_P, _P, _P] + [_I] * 9 + [_P]),
+    "pws_border_edge_yuv_u8": (_I, [_P, _P, _P] + [_I] * 10 + [_P]),
+    "pws_border_edge_yuv_u16": (_I, [_P, _P, _P] + [_I] * 10 + [_P]),
     "pws_field_homography": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "pws_scene_change": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "pws_field_zoom": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P]),

@@ -378,7 +378,7 @@ def _windows(gray_padded, start, count, period):
 
 class VideoStabilizer:
     def __init__(self, netG, batch=32, period=30, device=None, swap_rb=False, interpolation="bilinear", borders="black", rigidity=0.0,
-                 mosaic_radius=8):
+                 mosaic_radius=8, edge="pad"):
         self.net = netG
         # how far run / run_video pull each frame's field towards the homography fitted to it (functional.rigid_fields): 0 = the field as the
         # generator regressed it (no fit, no launch), 1 = every frame warped by its homography alone -- no local distortion, and no parallax
@@ -392,6 +392,14 @@ class VideoStabilizer:
         # the future (functional.mosaic_borders_, one launch per scene piece once the neighbours are warped).  8 is a judgement -- about a
         # quarter second at 30 fps -- that no footage here can fit.
         self.borders = borders
+        # how the SOURCE continues beyond its rim where a wedge still shows it ("black", and what "mosaic" finds no donor for): "pad" -- the
+        # warp's blend with the pad colour, every path as it was -- or "clamp" / "mirror": functional.edge_borders_ right after each warp,
+        # from the batch's own source frames and the field that warped them (one more launch per batch; no other frame is read)
+        if edge not in PF.EDGES:
+            raise ValueError("edge must be one of %s, got %r" % (PF.EDGES, edge))
+        if edge != "pad" and borders == "keep":
+            raise ValueError("edge=%r has nothing to fill with borders=\"keep\", which never shows the pad colour: choose one" % (edge,))
+        self.edge = edge
         self.mosaic_radius = int(mosaic_radius)
         if not 1 <= self.mosaic_radius <= PF.MOSAIC_MAX_RADIUS:
             raise ValueError("mosaic_radius must be 1 .. %d (the kernel keeps one window bit per frame), got %r" % (PF.MOSAIC_MAX_RADIUS, mosaic_radius))
@@ -502,7 +510,11 @@ class VideoStabilizer:
         (``functional.rigid_fields``, into a fresh tensor: the generator's output may be a graph's static buffer) right after the generator;
         the zoom, the warp and borders="keep" all see the adjusted field.  Nothing here depends on other frames, so halos are fine; frames
         below the fit's 600 x 300 lattice are a ValueError.  ``self.rigid_residual`` (T,) float32 and ``self.rigid_unfit`` (T,) int32 are left on
-        the device (None at rigidity 0, which takes no new path)."""
+        the device (None at rigidity 0, which takes no new path).
+        VideoStabilizer(edge="clamp" | "mirror") (integer frames only; float frames are a ValueError): right after each batch's warp
+        ``functional.edge_borders_`` samples every uncovered pixel again from the batch's own source frames, continued beyond their rim, with
+        the field that warped (after rigidity and zoom); with borders="mosaic" on the batch's slice of the buffer, before the mosaic pass,
+        so donors still win and the unfilled positions show the edge fill.  Nothing crosses a frame: halos, cuts and shards change nothing."""
         half = self.period // 2
         keep = self.borders == "keep"
         rigid = self.rigidity > 0.0
@@ -517,6 +529,9 @@ class VideoStabilizer:
             self.mosaic_unfilled = torch.empty((frames.shape[0],), device=self.device, dtype=torch.int32) if mosaic else None
         if keep and frames.dtype not in (torch.uint8, torch.uint16):
             raise ValueError("run: borders=\"keep\" is for the integer pixel formats (uint8 / uint16 frames), got %s" % (frames.dtype,))
+        edging = self.edge != "pad"
+        if edging and frames.dtype not in (torch.uint8, torch.uint16):
+            raise ValueError("run: edge=%r is for the integer pixel formats (uint8 / uint16 frames), got %s" % (self.edge, frames.dtype))
         fmt = PF.frame_format(pixel_format, frames, "run", float_frames=True)   # (from here on the format is this record)
         if not (0 <= halo_left <= half and 0 <= halo_right <= half):
             raise ValueError("halo must be within [0, %d]" % half)
@@ -579,11 +594,17 @@ class VideoStabilizer:
                     fall = torch.empty((T + 2 * pad,) + tuple(field.shape[1:]), device=dev, dtype=torch.float32)
                 PF.warp(cur.contiguous(), field, fmt, swap_rb=self.swap_rb, align_corners=self.align_corners, out=wall[pad + s:pad + e],
                         mode=self.interpolation)
+                if edging:   # before the mosaic pass: donors are read only where they are covered, so exactly the unfilled positions show it
+                    PF.edge_borders_(wall[pad + s:pad + e], cur.contiguous(), field, self.edge, pixel_format, swap_rb=self.swap_rb,
+                                     align_corners=self.align_corners, mode=self.interpolation)
                 fall[pad + s:pad + e].copy_(field)
                 if on_host:
                     cur.record_stream(compute)
                 continue
             warped = PF.warp(cur.contiguous(), field, fmt, swap_rb=self.swap_rb, align_corners=self.align_corners, mode=self.interpolation)
+            if edging:
+                PF.edge_borders_(warped, cur.contiguous(), field, self.edge, pixel_format, swap_rb=self.swap_rb, align_corners=self.align_corners,
+                                 mode=self.interpolation)
             if keep:
                 if (s + halo_left) in cutset or (s == 0 and keep_from is None):
                     init, src = cur.contiguous()[0], True   # a scene's first frame: its own source, as the warp would write it
@@ -729,6 +750,15 @@ class VideoStabilizer:
         largest distance in source pixels between the generator's field and its homography: the number to choose the setting by -- and
         ``self.rigid_unfit`` (T,) int32 -- the nodes that kept the raw field because no homography applied to them -- are left on the device
         (no synchronisation: read them when you need them); both are None at rigidity 0, which takes no new path.
+        VideoStabilizer(edge="clamp" | "mirror"): where a frame's field samples outside the source, the source itself is continued beyond its
+        rim -- the edge sample repeated, or the picture reflected about it (functional.edge_borders_ has the definition; ffmpeg deshake's
+        ``edge``, OpenCV's BORDER_REPLICATE / BORDER_REFLECT_101) -- instead of blended towards the pad colour.  One more launch behind every
+        warp, before the output resize and the crop, reading the chunk's own source frames and the field that warped; no other frame is read,
+        so in_flight, halos (a shard needs no history: given the same fields its bytes are the unsharded clip's, as with "pad"), scene_cuts,
+        zoom, explicit and automatic crops, rigidity and every integer pixel_format work as with edge="pad", the default, under which every
+        path is as it was.  With borders="mosaic" the pass runs
+        before the mosaic fill: donors win, and exactly the positions ``mosaic_unfilled`` counts show the edge fill.  borders="keep" with an
+        edge is a ValueError at construction (keep never shows the pad colour); float frames are a ValueError.
         Returns (T, H, W, 3) -- or (T, H/2, W/2, 3) / (T, height, width, 3), or the crop window of it -- uint8 on the inputs' side; for YUV
         (T, oh * 3 // 2, ow) of the output (or crop window) size oh x ow."""
         half = self.period // 2
@@ -771,6 +801,8 @@ class VideoStabilizer:
         self.zoom_windows = self.zoom_uncovered = None
         self.rigid_residual = self.rigid_unfit = None
         self.mosaic_unfilled = None
+        if self.edge != "pad" and frames.dtype not in (torch.uint8, torch.uint16):
+            raise ValueError("run_video: edge=%r is for the integer pixel formats (uint8 / uint16 frames), got %s" % (self.edge, frames.dtype))
         mosaic, radius = self.borders == "mosaic", self.mosaic_radius
         if mosaic:
             if frames.dtype not in (torch.uint8, torch.uint16):
@@ -1046,6 +1078,9 @@ class VideoStabilizer:
                 if zmode is not None:
                     fld = PF._field_zoom(fld, zcoef[s:e], (h, w), self.align_corners, self.interpolation, torch.empty_like(fld), zunc[s:e])
                 warped = PF.warp(buf.contiguous(), fld, fmt, swap_rb=self.swap_rb, align_corners=self.align_corners, mode=self.interpolation)
+                if self.edge != "pad":
+                    PF.edge_borders_(warped, buf.contiguous(), fld, self.edge, pixel_format, swap_rb=self.swap_rb, align_corners=self.align_corners,
+                                     mode=self.interpolation)
                 finish(warped, buf, s, e, compute)
         if on_host:
             down.synchronize()
