@@ -46,6 +46,7 @@
  *   pws_adam_step                 optim.Adam(...).step()           main_new.py:63,216
  *   pws_field_homography          the automatic crop's per-frame findHomography + perspectiveTransform  main_new.py:550-603
  *   pws_scene_change              the window's end clamp, applied at hard cuts too (cut score)          main_new.py:627-633
+ *   pws_block_motion / pws_motion_fit  global motion between consecutive window planes: the stability metric (no counterpart in the reference)
  *   pws_field_zoom                the warp field resampled over a per-frame window: zoom to fill (no counterpart in the reference)
  *   pws_field_rigid               the warp field blended towards its fitted homography: rigid warp mode (no counterpart in the reference)
  *   pws_pack_* / pws_netg_pack_weights   state_dict (OIHW / IOHW) -> kernel layout; main_new.py:60,471
@@ -608,6 +609,42 @@ int pws_field_rigid(const float *field, int n, int fh, int fw, const double *m, 
  * sad:  (n) uint32 -- sad[0] = 0, sad[t] = sum over the 512 counters |hist[t] - hist[t-1]|.
  * Integer arithmetic after the bin: exact, the same bits on every run.  planes and sad 4-byte aligned, hist 8-byte aligned. */
 int pws_scene_change(const float *planes, int n, int h, int w, unsigned *hist, unsigned *sad, pws_stream_t stream);
+
+/* Block motion between consecutive planes (csrc/motion.hip): the measurement behind the stability metric.  The generator regresses a warp
+ * and never measures motion; this does, on the planes the stabiliser already keeps.
+ * planes: (n, h, w) fp32 contiguous, nominally in [-1, 1] (window_planes).  radius R: 1 .. 16.
+ * Samples are quantised once, q = min(255, max(0, floor((v + 1) * 127.5 + 0.5))) in fp32 with one rounding per step (no contraction), 0 for
+ * NaN; everything after q is integer arithmetic: exact, the same bits on every run and under any schedule.
+ * Blocks are 16 x 16: nby = (h - 2R) / 16, nbx = (w - 2R) / 16 (both >= 1), block (by, bx) has its top-left at (R + 16 by, R + 16 bx); a
+ * remainder strip is not covered.  For t >= 1 and every block, S(dx, dy) = sum over the block of |q[t][y, x] - q[t-1][y + dy, x + dx]|, dx and
+ * dy in [-R, R] (the block of the current frame is searched in the previous one); the best candidate minimises S * 2048 + rank, rank = the
+ * candidate's position in the order sorted by (dx^2 + dy^2, dy, dx): ties go to the shorter vector, and a flat block gets (0, 0).
+ * mv:       (n, nby, nbx, 2) int16 = (dx, dy).
+ * sad:      (n, nby, nbx, 5) int32 = S at the best candidate and at its x-1, x+1, y-1, y+1 neighbours; -1 for a neighbour outside the range.
+ * activity: (n, nby, nbx) int32 = sum over the block of |q[y, x+1] - q[y, x]| (16 x 15 pairs) + |q[y+1, x] - q[y, x]| (15 x 16 pairs), every
+ *           frame, frame 0 included.
+ * Row 0 of mv and sad is zero.  n == 0 returns PWS_OK and launches nothing.  PWS_EINVAL: a bad shape, a radius outside 1 .. 16, a plane
+ * without a block, more than 2^20 blocks, a NULL pointer, a pointer that is not 4-byte aligned.  One launch (per 32768 frames). */
+int pws_block_motion(const float *planes, int n, int h, int w, int radius, short *mv, int *sad, int *activity, pws_stream_t stream);
+
+/* The similarity that the block vectors of each frame pair agree on, in fp64 (csrc/motion.hip).  mv, sad, activity: as pws_block_motion
+ * wrote them for (n, h, w) planes and this radius.
+ * A block is VALID if activity[t] >= min_activity, |dx| < R and |dy| < R (a best match on the rim of the search range means the motion
+ * lies outside it), and the match is sharp: 2 ((l - 2c + h)_x + (l - 2c + h)_y) >= activity[t], in integers.  Around a true match S rises
+ * like the block's summed gradient, so the two second differences together reach about the activity; a block whose content is not in the
+ * window (motion beyond the range) settles on a chance match, around which S is flat (measured 0.10 .. 0.41 of the activity on noise, against
+ * 0.95 .. 2.2 at true matches).  Its sub-pixel vector d adds, per axis, off = 0.5 (l - h) / (l - 2c + h) from S at the best candidate (c) and its two
+ * neighbours (l, h) when both exist, the denominator is positive and c > 0 (an exact match keeps its whole-pixel vector), else 0, clipped
+ * to +-0.5.
+ * A block centre p, relative to the plane centre ((w-1)/2, (h-1)/2), maps to p + d in the previous frame; p' = [[a, -b], [b, a]] p + (tx, ty)
+ * is fitted by least squares (the 4 x 4 normal system, solved in closed form).  Three rounds: round 0 uses all valid blocks; rounds 1 and 2
+ * the valid blocks whose squared residual under the previous round's fit is at most max(1.0, 4 * the mean squared residual of the blocks
+ * that round used).  Fewer than 8 blocks in any round: a NaN row with inliers 0.
+ * motion:  (n, 4) fp64 = (a, b, tx, ty), in plane pixels.   inliers: (n) int32, the blocks of the last round.
+ * Row 0 is (1, 0, 0, 0) with inliers 0.  The sums are taken in one fixed order: the same bits on every run.
+ * PWS_EINVAL: as pws_block_motion, and motion not 8-byte aligned.  One launch. */
+int pws_motion_fit(const short *mv, const int *sad, const int *activity, int n, int h, int w, int radius, int min_activity, double *motion,
+                   int *inliers, pws_stream_t stream);
 
 /* Adam (no weight decay / amsgrad) on a flat fp32 buffer, in place; step counts from 1. */
 int pws_adam_step(float *p, const float *g, float *m, float *v, size_t count, float lr, float beta1,

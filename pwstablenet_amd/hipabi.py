@@ -262,6 +262,8 @@ SIGNATURES = {
     "pws_border_edge_yuv_u16": (_I, [_P, _P, _P] + [_I] * 10 + [_P]),
     "pws_field_homography": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "pws_scene_change": (_I, [_P, _I, _I, _I, _P, _P, _P]),
+    "pws_block_motion": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "pws_motion_fit": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "pws_field_zoom": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "pws_field_rigid": (_I, [_P, _I, _I, _I, _P, _F, _I, _I, _P, _P, _P, _P]),
     "pws_bn_ws_bytes": (_S, [_I]),

@@ -239,6 +239,103 @@ def scene_scores(planes, return_counts=False):
     return (scores, hist, sad) if return_counts else scores
 
 
+def _motion_planes(planes, radius, what):
+    if not isinstance(planes, torch.Tensor) or planes.dim() != 3 or planes.dtype != torch.float32 or not planes.is_contiguous():
+        raise ValueError("%s: planes must be a contiguous (T, h, w) float32 tensor" % what)
+    A.require_cuda(planes)
+    radius = int(radius)
+    t, h, w = planes.shape
+    if not 1 <= radius <= 16:
+        raise ValueError("%s: radius must be 1 .. 16, got %r" % (what, radius))
+    if h - 2 * radius < 16 or w - 2 * radius < 16:
+        raise ValueError("%s: a %d x %d plane holds no 16 x 16 block inside a margin of %d" % (what, h, w, radius))
+    return t, h, w, radius
+
+
+def block_motion(planes, radius=16):
+    """Block motion between consecutive window planes (csrc/motion.hip; include/pwstable.h pws_block_motion has the definition): ``planes``
+    (T, h, w) float32 on the device, contiguous (``window_planes``: 256 x 256, 14 x 14 blocks at the default radius).  The samples are
+    quantised to bytes once; every 16 x 16 block of frame t is searched in frame t-1 over dx, dy in [-radius, radius] by its sum of absolute
+    differences, ties going to the shorter vector.  Returns mv (T, nby, nbx, 2) int16 = (dx, dy), sad (T, nby, nbx, 5) int32 (the best
+    candidate's and its four neighbours', -1 outside the range) and activity (T, nby, nbx) int32 (the block's summed absolute gradients),
+    on the device; row 0 of mv and sad is zero.  Integer arithmetic after the quantisation: the same bits on every run.  A tensor that is
+    not contiguous float32 (T, h, w), a radius outside 1 .. 16 or a plane without a block is a ValueError."""
+    t, h, w, radius = _motion_planes(planes, radius, "block_motion")
+    nby, nbx = (h - 2 * radius) // 16, (w - 2 * radius) // 16
+    mv = torch.empty((t, nby, nbx, 2), device=planes.device, dtype=torch.int16)
+    sad = torch.empty((t, nby, nbx, 5), device=planes.device, dtype=torch.int32)
+    act = torch.empty((t, nby, nbx), device=planes.device, dtype=torch.int32)
+    A.check(A.lib().pws_block_motion(A.ptr(planes), t, h, w, radius, A.ptr(mv), A.ptr(sad), A.ptr(act), A.current_stream()), "pws_block_motion")
+    return mv, sad, act
+
+
+def global_motion(planes, radius=16, min_activity=2000, return_blocks=False):
+    """The similarity between consecutive window planes: ``block_motion``, then per pair the least-squares fit, in fp64, of ``p' = [[a, -b],
+    [b, a]] p + (tx, ty)`` -- a block centre p of frame t, relative to the plane centre, lies at p' in frame t-1 -- to the blocks' sub-pixel
+    vectors, in three rounds that drop outliers (pws_motion_fit has the definition).  A block counts if its activity is at least
+    ``min_activity``, its vector lies inside the search range and its match is sharp (S rises around it by at least half the activity: a
+    block whose content has left the search window settles on a chance match, around which S is flat).  The default 2000 is a judgement: a flat block measures 0, the blocks of the
+    tests' synthetic texture a few thousand, and no real footage was available to fit the value to.  Returns motion (T, 4) float64 = (a, b,
+    tx, ty) in plane pixels and inliers (T,) int32 [, mv, sad, activity], all on the device, no synchronisation; row 0 is (1, 0, 0, 0) with
+    0 inliers, and a pair with fewer than 8 usable blocks in any round is a NaN row with 0 inliers.  Fixed summation order: the same bits on
+    every run.  ValueError as for ``block_motion``."""
+    t, h, w, radius = _motion_planes(planes, radius, "global_motion")
+    mv, sad, act = block_motion(planes, radius)
+    motion = torch.empty((t, 4), device=planes.device, dtype=torch.float64)
+    inliers = torch.empty((t,), device=planes.device, dtype=torch.int32)
+    A.check(A.lib().pws_motion_fit(A.ptr(mv), A.ptr(sad), A.ptr(act), t, h, w, radius, int(min_activity), A.ptr(motion), A.ptr(inliers),
+                                   A.current_stream()), "pws_motion_fit")
+    return (motion, inliers, mv, sad, act) if return_blocks else (motion, inliers)
+
+
+def _signal_score(v):
+    """One signal's stability score over a scene of m frames; v[k] is the motion of pair k (v[0] is not read)."""
+    import numpy as np
+    m = len(v)
+    p = np.zeros(m, np.float64)
+    for k in range(1, m):
+        p[k] = p[k - 1] + v[k]
+    p = p - (p[0] + (p[m - 1] - p[0]) * (np.arange(m, dtype=np.float64) / float(m - 1)))
+    e = np.abs(np.fft.fft(p)) ** 2
+    e = e[1:m // 2]
+    total = float(e.sum())
+    return 1.0 if total == 0.0 else float(e[:5].sum()) / total
+
+
+def stability_scores(motion, scene_cuts=None):
+    """The PWStableNet paper's stability metric over a clip's per-pair motion (``global_motion``; (T, 4) = (a, b, tx, ty), a tensor on either
+    side or an array; host arithmetic, float64).  Per scene -- ``scene_cuts``: sorted indices at which a new scene starts; the pair at a cut
+    does not count -- three signals are scored, tx, ty and theta = atan2(b, a): the path p[0] = 0, p[k] = p[k-1] + v[k] over the scene's m
+    frames, minus the straight line through its two end points; E = |FFT(p)|^2 over bins 1 .. m//2 - 1; the score is the first five bins
+    over all of them (1.0 when the total is 0: a still camera).  The published definition takes the FFT of the raw path, under which a steady
+    pan's own ramp hides the shake (INTEGRATION.md has the figures); the line is the one deviation.  A scene of fewer than 24 frames, or with
+    a NaN pair, scores NaN.  Returns {"stability", "translation", "rotation": the clip's values -- the frame-weighted mean of the scored
+    scenes, NaN without any -- and "scenes": [{"start", "end", "translation" = min(score x, score y), "rotation", "stability" = the smaller
+    of the two}]}.  The scores are pinned on synthetic clips only; no real footage or trained weights were available to validate them."""
+    import numpy as np
+    if isinstance(motion, torch.Tensor):
+        motion = motion.detach().to("cpu", torch.float64).numpy()
+    motion = np.asarray(motion, np.float64)
+    if motion.ndim != 2 or motion.shape[1] != 4:
+        raise ValueError("stability_scores: motion must be (T, 4): a, b, tx, ty")
+    T = motion.shape[0]
+    cuts = _check_cuts(scene_cuts, T, "stability_scores") if scene_cuts is not None and len(scene_cuts) else []
+    nan, scenes = float("nan"), []
+    for a, b in _scenes(T, cuts):
+        rows = motion[a:b]
+        if b - a < 24 or not np.isfinite(rows[1:]).all():
+            tr = ro = nan
+        else:
+            tr = min(_signal_score(rows[:, 2]), _signal_score(rows[:, 3]))
+            ro = _signal_score(np.arctan2(rows[:, 1], rows[:, 0]))
+        scenes.append({"start": a, "end": b, "translation": tr, "rotation": ro, "stability": min(tr, ro) if tr == tr else nan})
+
+    def clip(key):
+        ok = [s for s in scenes if s[key] == s[key]]
+        return sum(s[key] * (s["end"] - s["start"]) for s in ok) / sum(s["end"] - s["start"] for s in ok) if ok else nan
+    return {"stability": clip("stability"), "translation": clip("translation"), "rotation": clip("rotation"), "scenes": scenes}
+
+
 def find_scene_cuts(scores, threshold=0.25, min_scene=16):
     """The cut rule over a clip's ``scene_scores`` (a tensor on either side, an array or a sequence; host arithmetic): the sorted indices t,
     1 <= t < T, at which a new scene starts.  t is a cut if ``score[t] > threshold`` and t lies at least ``min_scene`` frames after the
@@ -378,8 +475,14 @@ def _windows(gray_padded, start, count, period):
 
 class VideoStabilizer:
     def __init__(self, netG, batch=32, period=30, device=None, swap_rb=False, interpolation="bilinear", borders="black", rigidity=0.0,
-                 mosaic_radius=8, edge="pad"):
+                 mosaic_radius=8, edge="pad", metrics=False):
         self.net = netG
+        # run_video measures the clip it stabilises: the global motion of the input and of the output planes (global_motion), and from it
+        # and the per-frame homographies the paper's three metrics (stability_report).  False: no launch, no allocation, every path as it was
+        self.metrics = bool(metrics)
+        self.motion_in = self.motion_out = None                    # metrics: (T, 4) float64 = (a, b, tx, ty) per pair of the last run_video's
+        self.motion_inliers_in = self.motion_inliers_out = None    # input / output planes and (T,) int32 inlier counts, on the device
+        self._report = None
         # how far run / run_video pull each frame's field towards the homography fitted to it (functional.rigid_fields): 0 = the field as the
         # generator regressed it (no fit, no launch), 1 = every frame warped by its homography alone -- no local distortion, and no parallax
         # correction either
@@ -474,7 +577,7 @@ class VideoStabilizer:
 
     @torch.no_grad()
     def run(self, gray, frames, halo_left=0, halo_right=0, out=None, pixel_format="bgr24", scene_cuts=None, keep_from=None, _keep_wait=None,
-            zoom=None, _zoom_unc=None, _rigid_stats=None, _mosaic_pad=None):
+            zoom=None, _zoom_unc=None, _rigid_stats=None, _mosaic_pad=None, _hom_out=None):
         """gray: (T + halo_left + halo_right, 256, 256) float32 in [-1,1] (``x/255*2-1`` as the reference, :650) for the T
         frames to stabilise plus whatever real neighbours exist on either side (up to period//2); frames: (T, C, H, W)
         float32 0..255, or (T, H, W, 3) uint8 as OpenCV delivers them (then the warp runs in the uint8 kernel: 4x less
@@ -544,7 +647,7 @@ class VideoStabilizer:
         gray_d = gray.to(dev, non_blocking=True) if not gray.is_cuda else gray  # 256 KB per frame: copied once
         if out is None:
             out = torch.empty_like(frames, pin_memory=on_host) if on_host else torch.empty_like(frames)
-        if zoom is not None or rigid:
+        if zoom is not None or rigid or _hom_out is not None:
             frame_hw = fmt.frame_shape(frames)[1:]
         if rigid:
             _check_lattice(int(frame_hw[0]), int(frame_hw[1]), "rigidity > 0")
@@ -577,7 +680,13 @@ class VideoStabilizer:
                 compute.wait_event(ev)
             win = _windows(gp, start, e - s, self.period)
             field = self.net(win, False)
-            if rigid:
+            if _hom_out is not None:   # run_video(metrics=True): the raw field's fit is kept, (T, 9) and (T, 4) slices of this call's frames
+                field = field.contiguous()
+                hom = _hom_out[0][s:e]
+                _field_homography(field, int(frame_hw[0]), int(frame_hw[1]), hom, _hom_out[1][s:e])
+                if rigid:
+                    field = PF._field_rigid(field, hom, frame_hw, self.rigidity, torch.empty_like(field), rres[s:e], runf[s:e])
+            elif rigid:
                 field = field.contiguous()
                 hom = torch.empty((e - s, 9), device=dev, dtype=torch.float64)
                 _field_homography(field, int(frame_hw[0]), int(frame_hw[1]), hom, torch.empty((e - s, 4), device=dev, dtype=torch.float32))
@@ -652,7 +761,7 @@ class VideoStabilizer:
     @torch.no_grad()
     def run_video(self, frames, chunk=32, half_size_output=False, frames_are_rgb=False, halo_left=0, halo_right=0, crop=None,
                   output_size=None, in_flight=1, pixel_format="bgr24", scene_cuts=None, scene_threshold=0.25, scene_min_len=16, zoom=None,
-                  zoom_speed=0.002, zoom_min=0.5):
+                  zoom_speed=0.002, zoom_min=0.5, metrics=None):
         """The whole device side of the reference's ``process()`` loop for one decoded clip: ``frames`` (T, H, W, 3) uint8 as
         cv2 delivers them, in (pinned) host memory or on the device.  Per chunk of ``chunk`` frames: H2D on a side stream,
         gray + INTER_AREA 256x256 window planes computed there from the uploaded frames (so nothing but the uint8 frames
@@ -759,6 +868,15 @@ class VideoStabilizer:
         path is as it was.  With borders="mosaic" the pass runs
         before the mosaic fill: donors win, and exactly the positions ``mosaic_unfilled`` counts show the edge fill.  borders="keep" with an
         edge is a ValueError at construction (keep never shows the pad colour); float frames are a ValueError.
+        metrics (None: what VideoStabilizer(metrics=) said; True / False for this call): measure the clip.  The window planes of every WARPED
+        chunk -- what the viewer sees: after keep, mosaic, edge, zoom and rigidity, before the output resize and the crop, in the output's own
+        channel order -- are computed on the chunk's lane into one (T, 256, 256) buffer (256 KB per frame, as much again as the input planes);
+        once every lane has joined, ``global_motion`` runs once over the input planes of the T core frames and once over the output planes.
+        A source of at least 600 x 300 also keeps every frame's raw ``field_homography`` fit (the two-pass paths and rigidity > 0 have it
+        already; otherwise one small launch per batch).  Left on the device, no synchronisation: ``self.motion_in`` / ``self.motion_out`` (T, 4)
+        float64 and ``self.motion_inliers_in`` / ``self.motion_inliers_out`` (T,) int32; None without metrics.  ``stability_report()`` turns
+        them into the paper's stability, cropping and distortion.  The frames are those of metrics=False bit for bit; halos (a shard reports
+        its own T frames), scene_cuts, in_flight, every pixel_format, interpolation, borders, edge, zoom and crop mode work as without it.
         Returns (T, H, W, 3) -- or (T, H/2, W/2, 3) / (T, height, width, 3), or the crop window of it -- uint8 on the inputs' side; for YUV
         (T, oh * 3 // 2, ow) of the output (or crop window) size oh x ow."""
         half = self.period // 2
@@ -801,6 +919,8 @@ class VideoStabilizer:
         self.zoom_windows = self.zoom_uncovered = None
         self.rigid_residual = self.rigid_unfit = None
         self.mosaic_unfilled = None
+        self.motion_in = self.motion_out = self.motion_inliers_in = self.motion_inliers_out = self._report = None
+        metrics = self.metrics if metrics is None else bool(metrics)
         if self.edge != "pad" and frames.dtype not in (torch.uint8, torch.uint16):
             raise ValueError("run_video: edge=%r is for the integer pixel formats (uint8 / uint16 frames), got %s" % (self.edge, frames.dtype))
         mosaic, radius = self.borders == "mosaic", self.mosaic_radius
@@ -874,6 +994,13 @@ class VideoStabilizer:
         if rigid:   # (before the lanes fork from the caller's stream: every lane writes its chunks' slices)
             rres = torch.empty((T,), device=dev, dtype=torch.float32)
             runf = torch.empty((T,), device=dev, dtype=torch.int32)
+        mhom = mbounds = None
+        if metrics:   # (also before the fork) the output planes; below the fit's lattice size cropping and distortion are not reported
+            planes_out = torch.empty((T, 256, 256), device=dev, dtype=torch.float32)
+            out_rgb = (bool(frames_are_rgb) != self.swap_rb) if not yuv else False   # the warp's swap_rb turns the channel order round
+            if h >= 300 and w >= 600 and not (auto or zmode in ("auto", "adaptive")):   # (the two-pass paths keep their own fit)
+                mhom = torch.empty((T, 9), device=dev, dtype=torch.float64)
+                mbounds = torch.empty((T, 4), device=dev, dtype=torch.float32)
         # (the lanes live as long as this object: the generator keeps an arena / a graph per STREAM, and torch's allocator a pool per stream)
         # The caller's stream is lane 0: the runtime deals streams to a handful of hardware queues, and a lane that shares its queue with
         # the upload or the download stream waits behind their copies (two NEW lanes beside up / down: 1 744 -> 1 291 frames/s).
@@ -932,6 +1059,8 @@ class VideoStabilizer:
 
         def finish(warped, buf, s, e, lane):
             """output resize + crop of the warped core frames s .. e-1 (output positions) on `lane`, and their way to `out`"""
+            if metrics:   # the planes of what the viewer sees, at the warp's size
+                _window_planes(warped, fmt, 256, planes_out[s:e], "run_video", out_rgb)
             if (oh, ow) != (h, w):
                 warped = _output_resize(warped, fmt, (ow, oh), half_size_output)
             if crop is not None:
@@ -1017,17 +1146,18 @@ class VideoStabilizer:
                             PF._field_rigid(fields[cs:ce], hom[cs:ce], (h, w), self.rigidity, fields[cs:ce], rres[cs:ce], runf[cs:ce])
                         continue
                     rstats = (rres[cs - halo_left:ce - halo_left], runf[cs - halo_left:ce - halo_left]) if rigid else None
+                    mh = (mhom[cs - halo_left:ce - halo_left], mbounds[cs - halo_left:ce - halo_left]) if mhom is not None else None
                     if mosaic:   # warped with black borders; the chunk before it is filled and finished
                         wall, fall = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr, pixel_format=pixel_format,
-                                              scene_cuts=sc, _rigid_stats=rstats, _mosaic_pad=radius)
+                                              scene_cuts=sc, _rigid_stats=rstats, _mosaic_pad=radius, _hom_out=mh)
                         mosaic_step((wall, fall, cs, ce, buf), lane)
                         continue
                     if zmode is not None:   # ("fixed": the one window, in the single pass)
                         warped = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr, pixel_format=pixel_format,
-                                          scene_cuts=sc, zoom=zwin, _zoom_unc=zunc[cs - halo_left:ce - halo_left], _rigid_stats=rstats)
+                                          scene_cuts=sc, zoom=zwin, _zoom_unc=zunc[cs - halo_left:ce - halo_left], _rigid_stats=rstats, _hom_out=mh)
                     else:
                         warped = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr, pixel_format=pixel_format, scene_cuts=sc,
-                                          keep_from=carry, _keep_wait=carried, _rigid_stats=rstats)
+                                          keep_from=carry, _keep_wait=carried, _rigid_stats=rstats, _hom_out=mh)
                     if keep:   # the next chunk's pass (on the other lane, if any) starts from this chunk's last frame: no copy, one event
                         carry = warped[-1]
                         if len(lanes) > 1:
@@ -1082,6 +1212,74 @@ class VideoStabilizer:
                     PF.edge_borders_(warped, buf.contiguous(), fld, self.edge, pixel_format, swap_rb=self.swap_rb, align_corners=self.align_corners,
                                      mode=self.interpolation)
                 finish(warped, buf, s, e, compute)
+        if metrics:   # every lane has joined the caller's stream, and every chunk's planes are behind an event it has waited for
+            core = gray_all[halo_left:halo_left + T]
+            self.motion_in, self.motion_inliers_in = global_motion(core)
+            self.motion_out, self.motion_inliers_out = global_motion(planes_out)
+            if two_pass and h >= 300 and w >= 600:
+                mhom, mbounds = hom, bounds
+            self._report = {"frames": T, "frame_hw": (h, w), "hom": mhom, "bounds": mbounds,
+                            "cuts": [c - halo_left for c in cuts if 0 < c - halo_left < T]}
         if on_host:
             down.synchronize()
+        return out
+
+    def stability_report(self):
+        """The paper's three metrics for the last ``run_video(metrics=True)``; synchronises the device.  Returns a dict:
+        ``stability_in`` / ``stability_out``: ``stability_scores`` of ``motion_in`` / ``motion_out`` under the call's scene cuts -- the clip's
+        "stability", "translation" and "rotation" and the per-scene list "scenes"; steadier is closer to 1.
+        ``cropping``: {"per_frame", "mean", "min"} -- per frame, the share of the frame that the raw fit's ``bounds`` rectangle (top, bottom,
+        left, right: ``field_homography``), clipped to the frame, leaves.
+        ``distortion``: {"per_frame", "mean", "min"} -- per frame, sigma_min / sigma_max of the Jacobian of the fitted homography M at the frame
+        centre, expressed in pixels rather than in normalised coordinates -- output pixels per source pixel, under the generator's
+        coordinate convention -- so that a 16:9 frame's aspect does not count as distortion.
+        The paper takes the ratio of the affine part's eigenvalues; singular values are used here because a shear has both eigenvalues
+        equal to 1 and would pass as undistorted.  1 = a similarity.
+        Both are None for a source below the fit's 600 x 300 lattice size; a frame without a fit is NaN in "per_frame" and is left out of
+        "mean" and "min" (NaN when no frame has one).
+        ``unfit_pairs_in`` / ``unfit_pairs_out``: the pairs inside a scene (the pair at a cut does not count) that ``global_motion`` could
+        not fit -- NaN rows.
+        The scores are pinned on synthetic clips only: no real footage or trained weights were available to validate them."""
+        import numpy as np
+        rep = self._report
+        if rep is None:
+            raise RuntimeError("stability_report: the last run_video did not run with metrics=True")
+        torch.cuda.synchronize(self.device)
+        T, (h, w), cuts = rep["frames"], rep["frame_hw"], rep["cuts"]
+        out = {}
+        for side, motion in (("in", self.motion_in), ("out", self.motion_out)):
+            m = motion.cpu().numpy()
+            out["stability_" + side] = stability_scores(m, cuts or None)
+            counted = np.ones(T, bool)
+            counted[[0] + cuts] = False
+            out["unfit_pairs_" + side] = int((np.isnan(m).any(1) & counted).sum())
+
+        def summary(v):
+            ok = v[np.isfinite(v)]
+            return {"per_frame": v.tolist(), "mean": float(ok.mean()) if len(ok) else float("nan"), "min": float(ok.min()) if len(ok) else float("nan")}
+        if rep["hom"] is None:
+            out["cropping"] = out["distortion"] = None
+            return out
+        b = rep["bounds"].to("cpu", torch.float64).numpy()
+        hh = np.clip(np.minimum(b[:, 1], float(h)) - np.maximum(b[:, 0], 0.0), 0.0, None)
+        ww = np.clip(np.minimum(b[:, 3], float(w)) - np.maximum(b[:, 2], 0.0), 0.0, None)
+        out["cropping"] = summary(hh * ww / float(h * w))
+        M = rep["hom"].cpu().numpy().reshape(T, 3, 3)
+        # a unit of the field's value in source pixels, under the generator's coordinate convention (the warp's: x = ((v + 1) w - 1) / 2, or
+        # (v + 1) (w - 1) / 2 with align_corners); M's own output is u = 2x/w - 1
+        sx, sy = (0.5 * (w - 1), 0.5 * (h - 1)) if self.align_corners else (0.5 * w, 0.5 * h)
+        ratio = np.full(T, np.nan)
+        for t in range(T):
+            m = M[t]
+            if not np.isfinite(m).all() or m[2, 2] == 0.0:
+                continue
+            # the Jacobian at the centre (0, 0) of the map (x, y) -> (m0 x + m1 y + m2, m3 x + m4 y + m5) / (m6 x + m7 y + m8), then from
+            # normalised coordinates to pixels on both sides
+            d = m[2, 2]
+            J = (m[:2, :2] - np.outer(m[:2, 2], m[2, :2]) / d) / d
+            J = np.diag([0.5 * w, 0.5 * h]) @ J @ np.diag([1.0 / sx, 1.0 / sy])
+            sv = np.linalg.svd(J, compute_uv=False)
+            if np.isfinite(sv).all() and sv[0] > 0.0:
+                ratio[t] = sv[1] / sv[0]
+        out["distortion"] = summary(ratio)
         return out
