@@ -49,6 +49,7 @@
  *   pws_block_motion / pws_motion_fit  global motion between consecutive window planes: the stability metric (no counterpart in the reference)
  *   pws_field_zoom                the warp field resampled over a per-frame window: zoom to fill (no counterpart in the reference)
  *   pws_field_rigid               the warp field blended towards its fitted homography: rigid warp mode (no counterpart in the reference)
+ *   pws_motion_fit_scaled / pws_path_smooth / pws_field_compose  path smoothing: the measured camera path, low-passed, folded into the warp fields (no counterpart in the reference)
  *   pws_pack_* / pws_netg_pack_weights   state_dict (OIHW / IOHW) -> kernel layout; main_new.py:60,471
  *
  * Layouts.  Frames / images: NCHW fp32 as in the reference.  Warp fields: N,H,W,2 fp32 (x then y,
@@ -645,6 +646,55 @@ int pws_block_motion(const float *planes, int n, int h, int w, int radius, short
  * PWS_EINVAL: as pws_block_motion, and motion not 8-byte aligned.  One launch. */
 int pws_motion_fit(const short *mv, const int *sad, const int *activity, int n, int h, int w, int radius, int min_activity, double *motion,
                    int *inliers, pws_stream_t stream);
+
+/* pws_motion_fit in FRAME pixels (csrc/motion.hip).  The planes are a resize of the frame, non-uniform unless the source is square: a
+ * rotation of a 16:9 frame is no similarity between its 256 x 256 planes, and the plane-space fit mis-reads it.  (sx, sy) = frame pixels per
+ * plane pixel, (W0 / w, H0 / h): every block centre p and every sub-pixel vector d is multiplied by (sx, sy), component by component, before
+ * the normal sums; the fit, the residuals and motion = (a, b, tx, ty) are then in frame pixels, relative to the frame centre.  The outlier
+ * threshold's floor, one squared plane pixel, becomes sx * sy: max(sx * sy, 4 * the mean squared residual).  Validity, the three rounds, the
+ * summation order and the NaN rule are pws_motion_fit's.  A product with 1.0 is exact: (1, 1) returns pws_motion_fit's bits.
+ * PWS_EINVAL: as pws_motion_fit, and sx or sy not in (0, 1e6] (NaN included).  One launch. */
+int pws_motion_fit_scaled(const short *mv, const int *sad, const int *activity, int n, int h, int w, int radius, int min_activity, double sx,
+                          double sy, double *motion, int *inliers, pws_stream_t stream);
+
+/* Path smoothing (csrc/path_smooth.hip; no counterpart in the reference): the camera path of ONE scene of n frames from its per-pair
+ * motion, the path's Gaussian low-pass, and per frame the correction from the measured path to the smooth one.  All fp64, in DEVICE
+ * memory, no synchronisation.
+ * motion: (n, 4) = (a, b, tx, ty) as pws_motion_fit[_scaled] writes it: row k maps a point of frame k to frame k-1.  Row 0 is not read; a
+ *   row with an entry that is not finite counts as (1, 0, 0, 0).
+ * path:   (n, 4) = P[k] = (lambda, theta, cx, cy), the pose C_k = C_{k-1} o motion[k] of frame k in frame 0's coordinates: P[0] = 0 and, with
+ *   s = exp(lambda[k-1]), c = cos(theta[k-1]), sn = sin(theta[k-1]):  cx[k] = cx[k-1] + s (c tx - sn ty),  cy[k] = cy[k-1] + s (sn tx + c ty),
+ *   lambda[k] = lambda[k-1] + log(hypot(a, b)),  theta[k] = theta[k-1] + atan2(b, a).
+ * Smoothing: Re = min(ceil(3 sigma), n-1), g(j) = exp(-0.5 (j / sigma)^2), P^[k] = (sum_{j=-Re..Re} g(j) P*(k+j)) / (sum_j g(j)), both sums in
+ *   ascending j, per component; P*(i) = P[i] inside the scene, 2 P[0] - P[-i] before it, 2 P[n-1] - P[2(n-1) - i] behind it (odd reflection:
+ *   a constant velocity is its own average at every frame, the ends included).
+ * d:      (n, 6) = D[k] = C_k^-1 o C^_k, row-major 2 x 3: the linear part exp(lambda^ - lambda) Rot(theta^ - theta), the translation
+ *   exp(-lambda) Rot(-theta) (c^ - c).  It maps a position of the smoothed frame to the position of the measured frame that shows the same
+ *   point, both relative to the frame centre, in the pixels of `motion` (pws_field_compose takes it as it is).
+ * Products and sums are rounded once each, in one fixed order: the same bits on every run.  n == 1 gives the identity; n == 0 returns
+ * PWS_OK and launches nothing.  PWS_EINVAL: n < 0 or above 2^24, sigma outside (0, 256] (NaN included), a NULL pointer, a pointer that is
+ * not 8-byte aligned.  motion, path and d must not overlap.  One launch of one workgroup (the scan is sequential). */
+int pws_path_smooth(const double *motion, int n, double sigma, double *path, double *d, pws_stream_t stream);
+
+/* Field composition (csrc/field_compose.hip; no counterpart in the reference): a per-frame affine correction of the OUTPUT frame folded
+ * into the warp field; the warp that follows is untouched and still resamples the source once.
+ * field[n,fh,fw,2] -> out[n,fh,fw,2]; d[n,6] fp64 in DEVICE memory = D of frame t, row-major 2 x 3, in frame pixels relative to the frame
+ * centre ((w0-1)/2, (h0-1)/2), as pws_path_smooth writes it.  For node (i, j) of frame t, in fp64:
+ *   x = j (w0-1)/(fw-1) - (w0-1)/2, y = i (h0-1)/(fh-1) - (h0-1)/2 (the frame pixel at which the warps' align_corners=True resize reads
+ *   exactly this node); x' = d0 x + d1 y + d2, y' = d3 x + d4 y + d5; sx = (x' + (w0-1)/2) (fw-1)/(w0-1), sy alike, each rounded ONCE to fp32.
+ *   x0 = clamp(floor(sx), 0, fw-2), lx = sx - x0 (fp32, NOT clamped), hx = 1 - lx; y0, ly, hy alike;
+ *   out[t,i,j,c] = fma(ly, fma(lx, F[y0+1,x0+1], hx * F[y0+1,x0]), hy * fma(lx, F[y0,x0+1], hx * F[y0,x0])) (the warps' field interpolation).
+ *   Outside the lattice the field is continued linearly from its rim cell: an affine field composes exactly, and the wedges the
+ *   correction opens reach the warp as out-of-range coordinates rather than as a smeared rim.
+ * A frame whose six coefficients are exactly (1, 0, 0, 0, 1, 0) is copied bit for bit; a node whose sx or sy is not finite (NaN or
+ * overflowing coefficients) keeps F[i,j].  floor(sx) is bounded as a float before it becomes an integer: no d can make the kernel read
+ * outside field[t].
+ * uncovered (n, int32; may be NULL): pws_field_zoom's count, rule and clearing, on out[t].  align_corners and margin are read only then.
+ * Any fh, fw >= 2; n == 0 returns PWS_OK and launches nothing.  PWS_EINVAL: NULL field / d / out, fh or fw < 2, h0 or w0 < 2, margin < 0
+ * with `uncovered`, field / out / d not 8-byte aligned, out overlapping field (the same pointer included).  One launch (and a 4 n byte
+ * clear of `uncovered`). */
+int pws_field_compose(const float *field, int n, int fh, int fw, const double *d, float *out, int h0, int w0, int align_corners, int margin,
+                      int *uncovered, pws_stream_t stream);
 
 /* Adam (no weight decay / amsgrad) on a flat fp32 buffer, in place; step counts from 1. */
 int pws_adam_step(float *p, const float *g, float *m, float *v, size_t count, float lr, float beta1,

@@ -1,0 +1,127 @@
+// Field composition (functional.compose_fields): a per-frame affine correction D of the OUTPUT frame folded into the warp field, so that the
+// fused warps (grid_sample.hip, warp_bicubic.hip) produce the corrected frame in their single resampling pass.  Path smoothing
+// (path_smooth.hip) is its user: D moves a frame from the measured camera path onto the smooth one.  No counterpart in the reference.
+//
+// Definition (restated in tests/path_ref.py; include/pwstable.h pws_field_compose has it in full).  d[t] = D row-major 2 x 3, fp64, in
+// frame pixels relative to the frame centre.  Node (i, j) of out[t] stands for frame pixel x = j (w0-1)/(fw-1), y alike (the warps resize the
+// field with align_corners=True); (x', y') = D (x - cx, y - cy) + (cx, cy) is where the uncorrected output shows what the corrected one shows
+// there, in fp64; on the field's lattice that is sx = x' (fw-1)/(w0-1), sy alike, each rounded ONCE to fp32.  The node takes the field there,
+// with the warps' own field_lerp on the cell x0 = clamp(floor(sx), 0, fw-2), lx = sx - x0 NOT clamped: outside the lattice the field is
+// continued linearly, so an affine field composes exactly and the correction's wedges reach the warp as out-of-range coordinates.
+// A frame whose D is exactly the identity is copied; a node whose sx or sy is not finite keeps F[i, j].
+//
+// Launch shape: field_zoom.hip's -- a wave owns 128 consecutive nodes of one row of one frame, a lane 2 adjacent ones (one 16-byte store), a
+// workgroup is 4 waves = 4 rows; the count reduction is that kernel's too.  Under a rotation the cell differs per lane in both axes: per
+// node two 16-byte loads, columns x0 and x0 + 1 of rows y0 and y0 + 1.  The fp64 work is the 2 x 3 product and two scalings per node.
+#include "common.h"
+#include "warp_common.h"
+
+namespace pws {
+namespace {
+
+constexpr int FC_PER_LANE = 2, FC_CHUNK = kWave * FC_PER_LANE, FC_ROWS = 4;   // nodes per lane / per wave, rows (waves) per workgroup
+
+typedef float F32x4a8 __attribute__((ext_vector_type(4), aligned(8)));   // 16 bytes at the field's 8-byte alignment (rows of odd width)
+
+struct Geo {   // host-computed, fp64: the node's frame pixel, the frame centre, the lattice coordinate of a frame pixel
+    double kx, ky, cx, cy, ikx, iky;
+};
+
+__global__ void __launch_bounds__(kWave *FC_ROWS) field_compose_kernel(const float *__restrict__ field, const double *__restrict__ d,
+                                                                        float *__restrict__ out, int fh, int fw, unsigned nrg, Geo geo, int h0,
+                                                                        int w0, int align_corners, float m, int *__restrict__ uncovered) {
+    __shared__ int cnt[FC_ROWS];
+    const unsigned t = blockIdx.x / nrg, rg = blockIdx.x - t * nrg;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63u);
+    const int i = (int)rg * FC_ROWS + wave, j0 = (int)blockIdx.y * FC_CHUNK + lane * FC_PER_LANE;
+    int unc = 0;
+    if (i < fh && j0 < fw) {
+        const double *dt = d + (size_t)t * 6;
+        const double d0 = dt[0], d1 = dt[1], d2 = dt[2], d3 = dt[3], d4 = dt[4], d5 = dt[5];
+        const bool same = d0 == 1.0 && d1 == 0.0 && d2 == 0.0 && d3 == 0.0 && d4 == 1.0 && d5 == 0.0;   // (uniform over the workgroup)
+        const double y = (double)i * geo.ky - geo.cy;
+        const float *ft = field + (size_t)t * fh * fw * 2;
+        const bool ac = align_corners != 0;
+        const float xhi = (float)(w0 - 1) - m, yhi = (float)(h0 - 1) - m;
+        float g[FC_PER_LANE][2];
+#pragma unroll
+        for (int q = 0; q < FC_PER_LANE; ++q) {
+            const int j = min(j0 + q, fw - 1);   // (a row of odd width: the last lane's second node repeats its first, and is dropped)
+            const double x = (double)j * geo.kx - geo.cx;
+            const float sx = (float)(((d0 * x + d1 * y + d2) + geo.cx) * geo.ikx), sy = (float)(((d3 * x + d4 * y + d5) + geo.cy) * geo.iky);
+            const bool keep = same || !(isfinite(sx) && isfinite(sy));   // the node keeps F[i, j]: its own cell, picked below
+            // the cell, bounded as a FLOAT before it becomes an integer: in [0, fw-2] x [0, fh-2] whatever d holds
+            const float fx = keep ? (float)min(j, fw - 2) : fminf(fmaxf(floorf(sx), 0.f), (float)(fw - 2));
+            const float fy = keep ? (float)min(i, fh - 2) : fminf(fmaxf(floorf(sy), 0.f), (float)(fh - 2));
+            const int x0 = (int)fx, y0 = (int)fy;
+            const float *f0 = ft + ((size_t)y0 * fw + x0) * 2;
+            const F32x4a8 r0 = *reinterpret_cast<const F32x4a8 *>(f0), r1 = *reinterpret_cast<const F32x4a8 *>(f0 + (size_t)fw * 2);
+            if (keep) {
+                const F32x4a8 r = i == y0 ? r0 : r1;
+                g[q][0] = j == x0 ? r.x : r.z, g[q][1] = j == x0 ? r.y : r.w;
+            } else {
+                const float lx = sx - fx, hx = 1.f - lx, ly = sy - fy, hy = 1.f - ly;   // (not clamped: linear continuation outside the lattice)
+                g[q][0] = field_lerp(hy, ly, hx, lx, r0.x, r0.z, r1.x, r1.z);
+                g[q][1] = field_lerp(hy, ly, hx, lx, r0.y, r0.w, r1.y, r1.w);
+            }
+            if (uncovered && j0 + q < fw) {
+                const float ix = unnormalize(g[q][0], w0, ac), iy = unnormalize(g[q][1], h0, ac);
+                const bool covered = ix >= m && ix <= xhi && iy >= m && iy <= yhi;   // (false for NaN)
+                unc += covered ? 0 : 1;
+            }
+        }
+        float *o = out + (((size_t)t * fh + i) * fw + j0) * 2;
+        if (j0 + 1 < fw) *reinterpret_cast<F32x4a8 *>(o) = F32x4a8{g[0][0], g[0][1], g[1][0], g[1][1]};
+        else *reinterpret_cast<float2 *>(o) = make_float2(g[0][0], g[0][1]);
+    }
+    if (uncovered) {   // (kernel argument: uniform, every thread of the workgroup arrives)
+        int s = unc;
+#pragma unroll
+        for (int o = kWave / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
+        if (lane == 0) cnt[wave] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int tot = 0;
+#pragma unroll
+            for (int w = 0; w < FC_ROWS; ++w) tot += cnt[w];
+            if (tot != 0) atomicAdd(uncovered + t, tot);
+        }
+    }
+}
+
+}  // namespace
+}  // namespace pws
+
+using namespace pws;
+
+extern "C" int pws_field_compose(const float *field, int n, int fh, int fw, const double *d, float *out, int h0, int w0, int align_corners, int margin,
+                                 int *uncovered, pws_stream_t stream) {
+    PWS_REQUIRE(n >= 0, "pws_field_compose: bad shape");
+    PWS_REQUIRE(fh >= 2 && fw >= 2, "pws_field_compose: the field needs at least 2 x 2 nodes (got %d x %d)", fw, fh);
+    PWS_REQUIRE(h0 >= 2 && w0 >= 2, "pws_field_compose: the frame must be at least 2 x 2 pixels (got %d x %d)", w0, h0);
+    PWS_REQUIRE(!uncovered || margin >= 0, "pws_field_compose: bad margin %d for the uncovered count", margin);
+    if (n == 0) return PWS_OK;
+    PWS_REQUIRE(field && d && out, "pws_field_compose: NULL pointer");
+    PWS_REQUIRE(((reinterpret_cast<size_t>(field) | reinterpret_cast<size_t>(out) | reinterpret_cast<size_t>(d)) & 7) == 0 &&
+                    (reinterpret_cast<size_t>(uncovered) & 3) == 0,
+                "pws_field_compose: field, out and d must be 8-byte aligned, uncovered 4-byte aligned");
+    const size_t bytes = (size_t)n * fh * fw * 2 * sizeof(float);
+    const char *fb = reinterpret_cast<const char *>(field), *ob = reinterpret_cast<const char *>(out);
+    PWS_REQUIRE(ob + bytes <= fb || fb + bytes <= ob, "pws_field_compose: out must not overlap field");
+    const unsigned nrg = (unsigned)((fh + FC_ROWS - 1) / FC_ROWS), chunks = (unsigned)((fw + FC_CHUNK - 1) / FC_CHUNK);
+    PWS_REQUIRE((size_t)n * nrg < (1u << 31) && chunks < 65536, "pws_field_compose: field or batch too large");
+    if (uncovered) {
+        const hipError_t e = hipMemsetAsync(uncovered, 0, (size_t)n * sizeof(int), as_stream(stream));
+        if (e != hipSuccess) {
+            set_error("pws_field_compose: clearing uncovered: %s", hipGetErrorString(e));
+            return PWS_EHIP;
+        }
+    }
+    Geo geo;
+    geo.kx = (double)(w0 - 1) / (double)(fw - 1), geo.ky = (double)(h0 - 1) / (double)(fh - 1);
+    geo.cx = 0.5 * (double)(w0 - 1), geo.cy = 0.5 * (double)(h0 - 1);
+    geo.ikx = (double)(fw - 1) / (double)(w0 - 1), geo.iky = (double)(fh - 1) / (double)(h0 - 1);
+    hipLaunchKernelGGL(field_compose_kernel, dim3((unsigned)n * nrg, chunks, 1), dim3(kWave * FC_ROWS), 0, as_stream(stream), field, d, out, fh, fw, nrg,
+                       geo, h0, w0, align_corners, (float)margin, uncovered);
+    return check_launch("field_compose_kernel");
+}

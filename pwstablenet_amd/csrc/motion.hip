@@ -13,6 +13,8 @@
 //   motion_fit_kernel     one workgroup per frame: a similarity p' = [[a, -b], [b, a]] p + t fitted in fp64 to the blocks' sub-pixel vectors
 //                         in three rounds (all valid blocks; then twice the blocks within max(1, 4 x mean squared residual) of the previous
 //                         fit).  Every sum is taken in one fixed order: a lane's blocks in index order, then a fixed butterfly.
+//                         pws_motion_fit_scaled: the same kernel with the blocks' centres and vectors multiplied by (sx, sy) first -- the fit
+//                         in FRAME pixels, of which the planes are a non-uniform resize -- and the floor 1 replaced by sx sy; (1, 1) is exact.
 // No global atomics; all stores are plain vector stores.
 #include "common.h"
 
@@ -165,7 +167,7 @@ struct Blk {
 };
 
 __device__ __forceinline__ Blk load_block(const short *__restrict__ mv, const int *__restrict__ sad, const int *__restrict__ activity, size_t o,
-                                          int i, int nbx, int R, int min_activity, double cx0, double cy0) {
+                                          int i, int nbx, int R, int min_activity, double cx0, double cy0, double sx, double sy) {
     Blk b;
     const int dxi = mv[o * 2], dyi = mv[o * 2 + 1];
     // a best match on the rim of the search range means that the motion lies outside the range
@@ -186,8 +188,10 @@ __device__ __forceinline__ Blk load_block(const short *__restrict__ mv, const in
         const double f = (c0 > 0 && lo >= 0 && hi >= 0 && den > 0) ? 0.5 * (double)(lo - hi) / (double)den : 0.0;
         off[ax] = f > 0.5 ? 0.5 : (f < -0.5 ? -0.5 : f);
     }
-    b.dx = (double)dxi + off[0], b.dy = (double)dyi + off[1];
-    b.x = ((double)(R + MO_B * (i % nbx)) + 7.5) - cx0, b.y = ((double)(R + MO_B * (i / nbx)) + 7.5) - cy0;
+    // (sx, sy): the plane is a resize of the frame, non-uniform for any source that is not square; centres and vectors go to frame pixels
+    // here, before the sums.  A product with 1.0 is exact: at (1, 1) every sum below has the bits it had without the factors.
+    b.dx = ((double)dxi + off[0]) * sx, b.dy = ((double)dyi + off[1]) * sy;
+    b.x = (((double)(R + MO_B * (i % nbx)) + 7.5) - cx0) * sx, b.y = (((double)(R + MO_B * (i / nbx)) + 7.5) - cy0) * sy;
     return b;
 }
 
@@ -198,7 +202,8 @@ __device__ __forceinline__ double residual2(const Sim &f, const Blk &b) {
 
 __global__ void __launch_bounds__(MO_THREADS) motion_fit_kernel(const short *__restrict__ mv, const int *__restrict__ sad,
                                                                 const int *__restrict__ activity, int h, int w, int R, int nby, int nbx,
-                                                                int min_activity, double *__restrict__ motion, int *__restrict__ inliers) {
+                                                                int min_activity, double sx, double sy, double *__restrict__ motion,
+                                                                int *__restrict__ inliers) {
     __shared__ double part[MO_WAVES][8];
     const int tid = threadIdx.x, t = blockIdx.x;
     double *mo = motion + (size_t)t * 4;
@@ -215,7 +220,7 @@ __global__ void __launch_bounds__(MO_THREADS) motion_fit_kernel(const short *__r
     for (int round = 0; round < 3 && ok; ++round) {   // (uniform: the sums are the same in every thread, so every thread takes every barrier)
         double s[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // N, Sx, Sy, S(x^2 + y^2), Sdx, Sdy, S(x dx + y dy), S(x dy - y dx)
         for (int i = tid; i < nb; i += MO_THREADS) {
-            const Blk b = load_block(mv, sad, activity, (size_t)t * nb + i, i, nbx, R, min_activity, cx0, cy0);
+            const Blk b = load_block(mv, sad, activity, (size_t)t * nb + i, i, nbx, R, min_activity, cx0, cy0, sx, sy);
             if (!b.valid || (round > 0 && !(residual2(prev, b) <= thr))) continue;
             s[0] += 1.0, s[1] += b.x, s[2] += b.y, s[3] += b.x * b.x + b.y * b.y, s[4] += b.dx, s[5] += b.dy;
             s[6] += b.x * b.dx + b.y * b.dy, s[7] += b.x * b.dy - b.y * b.dx;
@@ -235,13 +240,14 @@ __global__ void __launch_bounds__(MO_THREADS) motion_fit_kernel(const short *__r
         if (round == 2) break;
         double q[1] = {0.0};   // the squared residuals of the blocks this round used, under this round's fit
         for (int i = tid; i < nb; i += MO_THREADS) {
-            const Blk b = load_block(mv, sad, activity, (size_t)t * nb + i, i, nbx, R, min_activity, cx0, cy0);
+            const Blk b = load_block(mv, sad, activity, (size_t)t * nb + i, i, nbx, R, min_activity, cx0, cy0, sx, sy);
             if (!b.valid || (round > 0 && !(residual2(prev, b) <= thr))) continue;
             q[0] += residual2(fit, b);
         }
         block_sum<1>(q, part);
         const double m4 = 4.0 * (q[0] / s[0]);
-        thr = m4 > 1.0 ? m4 : 1.0;
+        const double floor2 = sx * sy;   // one squared plane pixel, in frame pixels
+        thr = m4 > floor2 ? m4 : floor2;
         prev = fit;
     }
     if (tid == 0) {
@@ -280,20 +286,30 @@ extern "C" int pws_block_motion(const float *planes, int n, int h, int w, int ra
     return PWS_OK;
 }
 
-extern "C" int pws_motion_fit(const short *mv, const int *sad, const int *activity, int n, int h, int w, int radius, int min_activity, double *motion,
-                              int *inliers, pws_stream_t stream) {
-    PWS_REQUIRE(n >= 0 && h > 0 && w > 0, "pws_motion_fit: bad shape (n %d, h %d, w %d)", n, h, w);
-    PWS_REQUIRE(radius >= 1 && radius <= MO_RMAX, "pws_motion_fit: radius must be 1 .. %d, got %d", MO_RMAX, radius);
+static int motion_fit(const char *what, const short *mv, const int *sad, const int *activity, int n, int h, int w, int radius, int min_activity,
+                      double sx, double sy, double *motion, int *inliers, pws_stream_t stream) {
+    PWS_REQUIRE(n >= 0 && h > 0 && w > 0, "%s: bad shape (n %d, h %d, w %d)", what, n, h, w);
+    PWS_REQUIRE(radius >= 1 && radius <= MO_RMAX, "%s: radius must be 1 .. %d, got %d", what, MO_RMAX, radius);
     const long long nby = ((long long)h - 2 * radius) / MO_B, nbx = ((long long)w - 2 * radius) / MO_B;
-    PWS_REQUIRE(h - 2 * radius >= MO_B && w - 2 * radius >= MO_B, "pws_motion_fit: a %d x %d plane holds no 16 x 16 block inside a margin of %d", h, w,
-                radius);
-    PWS_REQUIRE(nby * nbx <= (1 << 20), "pws_motion_fit: %lld x %lld blocks per plane, at most 2^20", nby, nbx);
+    PWS_REQUIRE(h - 2 * radius >= MO_B && w - 2 * radius >= MO_B, "%s: a %d x %d plane holds no 16 x 16 block inside a margin of %d", what, h, w, radius);
+    PWS_REQUIRE(nby * nbx <= (1 << 20), "%s: %lld x %lld blocks per plane, at most 2^20", what, nby, nbx);
+    PWS_REQUIRE(sx > 0.0 && sy > 0.0 && sx <= 1e6 && sy <= 1e6, "%s: the pixel scale must be positive and finite, got (%g, %g)", what, sx, sy);
     if (n == 0) return PWS_OK;
-    PWS_REQUIRE(mv && sad && activity && motion && inliers, "pws_motion_fit: NULL pointer");
+    PWS_REQUIRE(mv && sad && activity && motion && inliers, "%s: NULL pointer", what);
     PWS_REQUIRE(((reinterpret_cast<size_t>(mv) | reinterpret_cast<size_t>(sad) | reinterpret_cast<size_t>(activity) | reinterpret_cast<size_t>(inliers)) & 3) == 0 &&
                     (reinterpret_cast<size_t>(motion) & 7) == 0,
-                "pws_motion_fit: mv, sad, activity and inliers must be 4-byte aligned, motion 8-byte aligned");
+                "%s: mv, sad, activity and inliers must be 4-byte aligned, motion 8-byte aligned", what);
     hipLaunchKernelGGL(motion_fit_kernel, dim3((unsigned)n), dim3(MO_THREADS), 0, as_stream(stream), mv, sad, activity, h, w, radius, (int)nby, (int)nbx,
-                       min_activity, motion, inliers);
+                       min_activity, sx, sy, motion, inliers);
     return check_launch("motion_fit_kernel");
+}
+
+extern "C" int pws_motion_fit(const short *mv, const int *sad, const int *activity, int n, int h, int w, int radius, int min_activity, double *motion,
+                              int *inliers, pws_stream_t stream) {
+    return motion_fit("pws_motion_fit", mv, sad, activity, n, h, w, radius, min_activity, 1.0, 1.0, motion, inliers, stream);
+}
+
+extern "C" int pws_motion_fit_scaled(const short *mv, const int *sad, const int *activity, int n, int h, int w, int radius, int min_activity, double sx,
+                                     double sy, double *motion, int *inliers, pws_stream_t stream) {
+    return motion_fit("pws_motion_fit_scaled", mv, sad, activity, n, h, w, radius, min_activity, sx, sy, motion, inliers, stream);
 }

@@ -1,0 +1,91 @@
+// Path smoothing (stream.smooth_path): the camera path that a scene's per-pair global motion (motion.hip) adds up to, its Gaussian low-pass,
+// and per frame the correction that moves the frame from the measured path onto the smooth one.  No counterpart in the reference.
+//
+// Definition (restated in tests/path_ref.py; include/pwstable.h pws_path_smooth has it in full).  motion[k] = (a, b, tx, ty) maps a point
+// of frame k to frame k-1.  The pose C_k = C_{k-1} o motion[k] maps frame k to frame 0; it is kept as P[k] = (lambda, theta, cx, cy): log
+// scale, angle, translation.  P^[k] is the normalised Gaussian average of P over k-Re .. k+Re, with P continued beyond the scene's ends by
+// odd reflection, so that a constant velocity is its own average at every frame.  D[k] = C_k^-1 o C^_k, row-major 2 x 3, maps a position
+// of the smoothed frame to the position of the measured frame that shows the same point.
+//
+// One workgroup, one launch: lane 0 walks the scan (strictly sequential; a scene is thousands of frames at most), then the workgroup's
+// threads take the frames in turn; the Gaussian's Re + 1 weights are in LDS.  Every sum has one fixed order: the same bits on every run.
+#include "common.h"
+
+namespace pws {
+namespace {
+
+constexpr int PS_THREADS = 256, PS_RMAX = 768;   // Re <= ceil(3 * 256)
+
+#pragma clang fp contract(off)   // every product and every sum rounded once, as the float64 restatement does
+
+__device__ __forceinline__ bool finite4(const double *v) {
+    return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]) && isfinite(v[3]);
+}
+
+// P*(j), component c: P inside the scene, its odd reflection about the first / last frame outside (Re <= n-1 keeps both inside)
+__device__ __forceinline__ double path_at(const double *path, int n, int j, int c) {
+    if (j < 0) return 2.0 * path[c] - path[(size_t)(-j) * 4 + c];
+    if (j > n - 1) return 2.0 * path[(size_t)(n - 1) * 4 + c] - path[(size_t)(2 * (n - 1) - j) * 4 + c];
+    return path[(size_t)j * 4 + c];
+}
+
+__global__ void __launch_bounds__(PS_THREADS) path_smooth_kernel(const double *__restrict__ motion, int n, double sigma, int Re, double *path,
+                                                                 double *__restrict__ d) {
+    __shared__ double g[PS_RMAX + 1];
+    const int tid = threadIdx.x;
+    for (int k = tid; k <= Re; k += PS_THREADS) {
+        const double r = (double)k / sigma;
+        g[k] = exp(-0.5 * (r * r));
+    }
+    if (tid == 0) {
+        double lam = 0.0, th = 0.0, cx = 0.0, cy = 0.0;
+        path[0] = 0.0, path[1] = 0.0, path[2] = 0.0, path[3] = 0.0;
+        for (int k = 1; k < n; ++k) {
+            const double *m = motion + (size_t)k * 4;
+            const bool ok = finite4(m);
+            const double a = ok ? m[0] : 1.0, b = ok ? m[1] : 0.0, tx = ok ? m[2] : 0.0, ty = ok ? m[3] : 0.0;
+            const double s = exp(lam), c = cos(th), sn = sin(th);
+            cx = cx + s * (c * tx - sn * ty);
+            cy = cy + s * (sn * tx + c * ty);
+            lam = lam + log(hypot(a, b));
+            th = th + atan2(b, a);
+            double *p = path + (size_t)k * 4;
+            p[0] = lam, p[1] = th, p[2] = cx, p[3] = cy;
+        }
+    }
+    __syncthreads();   // (the path is in global memory: written by this workgroup, read by this workgroup)
+    for (int k = tid; k < n; k += PS_THREADS) {
+        double acc[4] = {0.0, 0.0, 0.0, 0.0}, wsum = 0.0;
+        for (int dl = -Re; dl <= Re; ++dl) {
+            const double w = g[dl < 0 ? -dl : dl];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) acc[c] = acc[c] + w * path_at(path, n, k + dl, c);
+            wsum = wsum + w;
+        }
+        const double *p = path + (size_t)k * 4;
+        const double lam = p[0], th = p[1];
+        const double dlam = acc[0] / wsum - lam, dth = acc[1] / wsum - th, ux = acc[2] / wsum - p[2], uy = acc[3] / wsum - p[3];
+        const double s = exp(dlam), e = exp(-lam), c = cos(th), sn = sin(th);
+        double *o = d + (size_t)k * 6;
+        o[0] = s * cos(dth), o[1] = 0.0 - s * sin(dth), o[2] = e * (c * ux + sn * uy);
+        o[3] = s * sin(dth), o[4] = s * cos(dth), o[5] = e * (c * uy - sn * ux);
+    }
+}
+
+}  // namespace
+}  // namespace pws
+
+using namespace pws;
+
+extern "C" int pws_path_smooth(const double *motion, int n, double sigma, double *path, double *d, pws_stream_t stream) {
+    PWS_REQUIRE(n >= 0, "pws_path_smooth: bad shape (n %d)", n);
+    PWS_REQUIRE(sigma > 0.0 && sigma <= 256.0, "pws_path_smooth: sigma must lie in (0, 256], got %g", sigma);
+    if (n == 0) return PWS_OK;
+    PWS_REQUIRE(motion && path && d, "pws_path_smooth: NULL pointer");
+    PWS_REQUIRE(((reinterpret_cast<size_t>(motion) | reinterpret_cast<size_t>(path) | reinterpret_cast<size_t>(d)) & 7) == 0,
+                "pws_path_smooth: motion, path and d must be 8-byte aligned");
+    PWS_REQUIRE(n <= (1 << 24), "pws_path_smooth: a scene of %d frames, at most 2^24", n);
+    const int r3 = (int)ceil(3.0 * sigma), Re = r3 < n - 1 ? r3 : n - 1;
+    hipLaunchKernelGGL(path_smooth_kernel, dim3(1), dim3(PS_THREADS), 0, as_stream(stream), motion, n, sigma, Re, path, d);
+    return check_launch("path_smooth_kernel");
+}

@@ -622,6 +622,50 @@ def zoom_fields(field, windows, frame_hw, align_corners=False, mode="bilinear", 
     return (out, unc) if return_uncovered else out
 
 
+def _field_compose(field, d, frame_hw, align_corners, mode, out, uncovered):
+    """pws_field_compose on device tensors: ``d`` (T, 6) float64, ``uncovered`` (T,) int32 or None."""
+    A.check(A.lib().pws_field_compose(A.ptr(field), field.shape[0], field.shape[1], field.shape[2], A.ptr(d), A.ptr(out), int(frame_hw[0]),
+                                      int(frame_hw[1]), _ac(align_corners), int(mode == "bicubic"), A.ptr(uncovered), A.current_stream()),
+            "pws_field_compose")
+    return out
+
+
+def compose_fields(field, d, frame_hw, align_corners=False, mode="bilinear", out=None, return_uncovered=False):
+    """A per-frame affine correction of the output frame, composed into the field: ``field`` (T, fh, fw, 2) as ``netG(window, False)``
+    returns it, ``d`` (T, 6) float64 on the device -- D of frame t, row-major 2 x 3, in pixels of the ``frame_hw`` = (H0, W0) frame relative
+    to its centre, as ``stream.smooth_path`` returns it: output position p shows what the uncorrected output shows at D p.  A fused warp
+    given the result produces that frame in its single resampling pass: node (i, j) takes the field at D of its own frame pixel, with the
+    warps' own field interpolation; outside the lattice the field is continued linearly, so an affine field composes exactly and the
+    wedges the correction opens reach the warp as out-of-range coordinates.  A frame whose D is exactly (1, 0, 0, 0, 1, 0) is copied bit for
+    bit; a node that D sends to a position that is not finite keeps its value.  As with ``zoom_fields`` the result is the warp of the
+    RESAMPLED field, not the exact composition.  One launch (csrc/field_compose.hip; include/pwstable.h has the definition); ``out`` must
+    not overlap ``field``.
+    return_uncovered: also a (T,) int32 device tensor, ``zoom_fields``' count on the composed field (``align_corners`` and ``mode`` the warp's).
+    ValueError: shapes or dtypes other than these, a host tensor, a frame below 2 x 2 pixels, an unknown mode."""
+    if mode not in INTERPOLATIONS:
+        raise ValueError("mode must be one of %s, got %r" % (INTERPOLATIONS, mode))
+    for name, t, dtype in (("field", field, torch.float32), ("d", d, torch.float64)) + ((("out", out, torch.float32),) if out is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
+            raise ValueError("compose_fields: %s must be a %s tensor on the device, got %s" % (
+                name, dtype, "%s on %s" % (t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t)))
+    if field.dim() != 4 or field.shape[3] != 2 or field.shape[1] < 2 or field.shape[2] < 2:
+        raise ValueError("compose_fields: field must be (T, fh, fw, 2) with fh, fw >= 2, got %s" % (tuple(field.shape),))
+    n = field.shape[0]
+    if tuple(d.shape) != (n, 6):
+        raise ValueError("compose_fields: d must be (%d, 6), got %s" % (n, tuple(d.shape)))
+    h0, w0 = int(frame_hw[0]), int(frame_hw[1])
+    if h0 < 2 or w0 < 2:
+        raise ValueError("compose_fields: the frame must be at least 2 x 2 pixels, got %d x %d" % (w0, h0))
+    field, d = field.contiguous(), d.contiguous()
+    if out is None:
+        out = torch.empty_like(field)
+    if tuple(out.shape) != tuple(field.shape) or not out.is_contiguous():
+        raise ValueError("compose_fields: out must be a contiguous %s float32 tensor" % (tuple(field.shape),))
+    unc = torch.empty((n,), device=field.device, dtype=torch.int32) if return_uncovered else None
+    _field_compose(field, d, (h0, w0), align_corners, mode, out, unc)
+    return (out, unc) if return_uncovered else out
+
+
 def _check_rigidity(rigidity, what):
     """``rigidity`` as a float in [0, 1]; ValueError otherwise (NaN included)."""
     try:

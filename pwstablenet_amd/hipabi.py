@@ -134,6 +134,7 @@ class PwsProfRecord(ctypes.Structure):
 
 _I, _S, _P = ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p
 _F = ctypes.c_float
+_D = ctypes.c_double
 # name -> (restype, argtypes); must list every symbol declared in include/pwstable.h
 SIGNATURES = {
     "pws_version": (_I, []),
@@ -264,6 +265,9 @@ SIGNATURES = {
     "pws_scene_change": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "pws_block_motion": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "pws_motion_fit": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "pws_motion_fit_scaled": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _D, _D, _P, _P, _P]),
+    "pws_path_smooth": (_I, [_P, _I, _D, _P, _P, _P]),
+    "pws_field_compose": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "pws_field_zoom": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "pws_field_rigid": (_I, [_P, _I, _I, _I, _P, _F, _I, _I, _P, _P, _P, _P]),
     "pws_bn_ws_bytes": (_S, [_I]),

@@ -269,7 +269,7 @@ def block_motion(planes, radius=16):
     return mv, sad, act
 
 
-def global_motion(planes, radius=16, min_activity=2000, return_blocks=False):
+def global_motion(planes, radius=16, min_activity=2000, return_blocks=False, pixel_scale=None):
     """The similarity between consecutive window planes: ``block_motion``, then per pair the least-squares fit, in fp64, of ``p' = [[a, -b],
     [b, a]] p + (tx, ty)`` -- a block centre p of frame t, relative to the plane centre, lies at p' in frame t-1 -- to the blocks' sub-pixel
     vectors, in three rounds that drop outliers (pws_motion_fit has the definition).  A block counts if its activity is at least
@@ -278,14 +278,65 @@ def global_motion(planes, radius=16, min_activity=2000, return_blocks=False):
     tests' synthetic texture a few thousand, and no real footage was available to fit the value to.  Returns motion (T, 4) float64 = (a, b,
     tx, ty) in plane pixels and inliers (T,) int32 [, mv, sad, activity], all on the device, no synchronisation; row 0 is (1, 0, 0, 0) with
     0 inliers, and a pair with fewer than 8 usable blocks in any round is a NaN row with 0 inliers.  Fixed summation order: the same bits on
-    every run.  ValueError as for ``block_motion``."""
+    every run.  ValueError as for ``block_motion``.
+    pixel_scale = (sx, sy): frame pixels per plane pixel, (W0 / w, H0 / h).  The planes are a non-uniform resize of any frame that is not
+    square, under which a frame's rotation is no similarity; the fit then runs in FRAME pixels, relative to the frame centre
+    (pws_motion_fit_scaled: centres and vectors scaled before the sums, the outlier floor sx sy), and so does the returned motion.  None,
+    the default, is the plane-pixel fit as it was, which (1, 1) equals bit for bit; anything but two positive finite numbers is a
+    ValueError."""
     t, h, w, radius = _motion_planes(planes, radius, "global_motion")
+    if pixel_scale is not None:
+        try:
+            sx, sy = (float(v) for v in pixel_scale)
+        except (TypeError, ValueError):
+            raise ValueError("global_motion: pixel_scale must be None or (sx, sy), got %r" % (pixel_scale,)) from None
+        if not (0.0 < sx <= 1e6 and 0.0 < sy <= 1e6):
+            raise ValueError("global_motion: pixel_scale must be two positive finite numbers, got %r" % (pixel_scale,))
     mv, sad, act = block_motion(planes, radius)
     motion = torch.empty((t, 4), device=planes.device, dtype=torch.float64)
     inliers = torch.empty((t,), device=planes.device, dtype=torch.int32)
-    A.check(A.lib().pws_motion_fit(A.ptr(mv), A.ptr(sad), A.ptr(act), t, h, w, radius, int(min_activity), A.ptr(motion), A.ptr(inliers),
-                                   A.current_stream()), "pws_motion_fit")
+    if pixel_scale is None:
+        A.check(A.lib().pws_motion_fit(A.ptr(mv), A.ptr(sad), A.ptr(act), t, h, w, radius, int(min_activity), A.ptr(motion), A.ptr(inliers),
+                                       A.current_stream()), "pws_motion_fit")
+    else:
+        A.check(A.lib().pws_motion_fit_scaled(A.ptr(mv), A.ptr(sad), A.ptr(act), t, h, w, radius, int(min_activity), sx, sy, A.ptr(motion),
+                                              A.ptr(inliers), A.current_stream()), "pws_motion_fit_scaled")
     return (motion, inliers, mv, sad, act) if return_blocks else (motion, inliers)
+
+
+def _check_sigma(sigma, what, zero_ok=False):
+    """``sigma`` as a float in (0, 256] (or [0, 256]); ValueError otherwise (NaN included)."""
+    try:
+        s = float(sigma)
+    except (TypeError, ValueError):
+        raise ValueError("%s: sigma must be a number of frames, got %r" % (what, sigma)) from None
+    if not ((0.0 < s or (zero_ok and s == 0.0)) and s <= 256.0):
+        raise ValueError("%s: sigma must lie in %s0, 256], got %r" % (what, "[" if zero_ok else "(", sigma))
+    return s
+
+
+def smooth_path(motion, sigma, scene_cuts=None):
+    """The camera path a clip's per-pair motion adds up to, low-passed, and the per-frame corrections between the two (csrc/path_smooth.hip;
+    include/pwstable.h pws_path_smooth has the definition): ``motion`` (T, 4) float64 on the device = (a, b, tx, ty) as ``global_motion``
+    returns it -- row k maps a point of frame k to frame k-1; a NaN row counts as no motion -- and ``sigma``, the Gaussian's width in frames,
+    in (0, 256].  Per scene (``scene_cuts``: sorted indices at which a new scene starts; the pair at a cut is not read, and every scene's
+    path starts at zero) the pose of each frame in its scene's first frame, P = (log scale, angle, cx, cy), is accumulated, averaged over
+    +-min(ceil(3 sigma), n-1) frames under the Gaussian with the path continued by odd reflection beyond the scene's ends (a steady pan is
+    left alone at every frame), and D[k] = C_k^-1 o C^_k -- row-major 2 x 3 -- maps a position of the smoothed frame k to the measured
+    frame's, in ``motion``'s pixels relative to the frame centre: what ``functional.compose_fields`` takes.  Returns (D (T, 6), path (T, 4)),
+    float64 on the device, no synchronisation; one launch per scene, on slices.  Fixed order: the same bits on every run.
+    ValueError: a tensor that is not (T, 4) float64 on the device, sigma outside (0, 256], bad cuts."""
+    if not isinstance(motion, torch.Tensor) or not motion.is_cuda or motion.dtype != torch.float64 or motion.dim() != 2 or motion.shape[1] != 4:
+        raise ValueError("smooth_path: motion must be a (T, 4) float64 tensor on the device")
+    sigma = _check_sigma(sigma, "smooth_path")
+    motion = motion.contiguous()
+    T = motion.shape[0]
+    cuts = _check_cuts(scene_cuts, T, "smooth_path") if scene_cuts is not None and len(scene_cuts) else []
+    d = torch.empty((T, 6), device=motion.device, dtype=torch.float64)
+    path = torch.empty((T, 4), device=motion.device, dtype=torch.float64)
+    for a, b in (_scenes(T, cuts) if T else []):
+        A.check(A.lib().pws_path_smooth(A.ptr(motion[a:b]), b - a, sigma, A.ptr(path[a:b]), A.ptr(d[a:b]), A.current_stream()), "pws_path_smooth")
+    return d, path
 
 
 def _signal_score(v):
@@ -475,8 +526,15 @@ def _windows(gray_padded, start, count, period):
 
 class VideoStabilizer:
     def __init__(self, netG, batch=32, period=30, device=None, swap_rb=False, interpolation="bilinear", borders="black", rigidity=0.0,
-                 mosaic_radius=8, edge="pad", metrics=False):
+                 mosaic_radius=8, edge="pad", metrics=False, smooth=0.0):
         self.net = netG
+        # run_video folds the shake that the fields LEAVE in the clip back into them: the global motion of the planes as the kept fields warp
+        # them is measured, the camera path low-passed with a Gaussian of `smooth` frames (smooth_path) and every frame's correction composed
+        # into its field (functional.compose_fields) before the one warp.  0: no launch, no allocation, every path as it was
+        self.smooth = _check_sigma(smooth, "VideoStabilizer", zero_ok=True)
+        self.smooth_motion = self.smooth_inliers = None       # smooth > 0, of the last run_video, on the device: (T, 4) float64 / (T,) int32, the
+        self.smooth_path = self.smooth_correction = None      # motion the fields left (frame pixels); (T, 4) its path, (T, 6) the corrections D;
+        self.smooth_uncovered = None                          # (T,) int32, the composed fields' nodes that sample outside the source
         # run_video measures the clip it stabilises: the global motion of the input and of the output planes (global_motion), and from it
         # and the per-frame homographies the paper's three metrics (stability_report).  False: no launch, no allocation, every path as it was
         self.metrics = bool(metrics)
@@ -617,7 +675,9 @@ class VideoStabilizer:
         VideoStabilizer(edge="clamp" | "mirror") (integer frames only; float frames are a ValueError): right after each batch's warp
         ``functional.edge_borders_`` samples every uncovered pixel again from the batch's own source frames, continued beyond their rim, with
         the field that warped (after rigidity and zoom); with borders="mosaic" on the batch's slice of the buffer, before the mosaic pass,
-        so donors still win and the unfilled positions show the edge fill.  Nothing crosses a frame: halos, cuts and shards change nothing."""
+        so donors still win and the unfilled positions show the edge fill.  Nothing crosses a frame: halos, cuts and shards change nothing.
+        VideoStabilizer(smooth=sigma) does nothing here: run() does not smooth.  The path needs every field of the scene before the first
+        warp, which is run_video's two-pass route."""
         half = self.period // 2
         keep = self.borders == "keep"
         rigid = self.rigidity > 0.0
@@ -877,6 +937,20 @@ class VideoStabilizer:
         float64 and ``self.motion_inliers_in`` / ``self.motion_inliers_out`` (T,) int32; None without metrics.  ``stability_report()`` turns
         them into the paper's stability, cropping and distortion.  The frames are those of metrics=False bit for bit; halos (a shard reports
         its own T frames), scene_cuts, in_flight, every pixel_format, interpolation, borders, edge, zoom and crop mode work as without it.
+        VideoStabilizer(smooth=sigma), sigma > 0 frames: path smoothing.  Each frame's field is regressed from that frame's own window, and
+        nothing makes consecutive OUTPUT frames move smoothly; this measures what the fields leave and folds it back into them.  The call
+        takes the two-pass route, also without a crop or zoom.  Once pass 1 has joined, on the caller's stream: the T core input planes are
+        warped by the kept fields (after rigidity; ``functional.grid_sample``, one (T, 256, 256) buffer); ``global_motion(...,
+        pixel_scale=(W / 256, H / 256))`` measures the motion left between them, in frame pixels; ``smooth_path`` under the call's cuts gives
+        every frame's correction D; ``functional.compose_fields`` folds it into the kept fields chunk by chunk; and, for a source of at
+        least 600 x 300, ``field_homography`` is fitted again on the composed fields, so that the bounds, crop="auto", zoom="auto" /
+        "adaptive" and the report's cropping and distortion describe the field that warps.  Pass 2 is unchanged: one resampling of the
+        source.  With a generator that returns the identity this is a complete classical stabiliser.  Left on the device, no synchronisation,
+        None at smooth = 0: ``self.smooth_motion`` (T, 4) float64 and ``self.smooth_inliers`` (T,) int32, ``self.smooth_path`` (T, 4),
+        ``self.smooth_correction`` (T, 6) float64 and ``self.smooth_uncovered`` (T,) int32 (the composed fields' nodes that sample outside the
+        source).  A pair no similarity could be fitted to counts as no motion.  Every pixel_format, interpolation, edge, crop, zoom,
+        rigidity, in_flight and scene_cuts works as without it.  ValueError: halos (a shard cannot see the scene's path), borders="keep" or
+        "mosaic" (they have no second pass).
         Returns (T, H, W, 3) -- or (T, H/2, W/2, 3) / (T, height, width, 3), or the crop window of it -- uint8 on the inputs' side; for YUV
         (T, oh * 3 // 2, ow) of the output (or crop window) size oh x ow."""
         half = self.period // 2
@@ -958,7 +1032,15 @@ class VideoStabilizer:
                     raise ValueError("zoom: the fraction of the frame must lie in (0, 1], got %r" % (zoom,))
                 zmode = "fixed"
                 zwin = _centred_window(zk, h, w)
-        two_pass = auto or zmode in ("auto", "adaptive")   # pass 1: fields and bounds; the host's decision; pass 2: the warp
+        smoothing = self.smooth > 0.0
+        self.smooth_motion = self.smooth_inliers = self.smooth_path = self.smooth_correction = self.smooth_uncovered = None
+        if smoothing:
+            if halo_left or halo_right:
+                raise ValueError("run_video: smooth > 0 needs the whole clip (a shard cannot see the scene's path)")
+            if self.borders in ("keep", "mosaic"):
+                raise ValueError("run_video: smooth > 0 warps in a second pass, which borders=\"%s\" does not have yet" % self.borders)
+        lattice = h >= 300 and w >= 600   # the homography fit's
+        two_pass = auto or zmode in ("auto", "adaptive") or smoothing   # pass 1: fields and bounds; the host's decision; pass 2: the warp
         detect = isinstance(scene_cuts, str)
         if detect and scene_cuts != "auto":
             raise ValueError("scene_cuts must be None, \"auto\" or a sorted sequence of frame indices, got %r" % (scene_cuts,))
@@ -998,7 +1080,7 @@ class VideoStabilizer:
         if metrics:   # (also before the fork) the output planes; below the fit's lattice size cropping and distortion are not reported
             planes_out = torch.empty((T, 256, 256), device=dev, dtype=torch.float32)
             out_rgb = (bool(frames_are_rgb) != self.swap_rb) if not yuv else False   # the warp's swap_rb turns the channel order round
-            if h >= 300 and w >= 600 and not (auto or zmode in ("auto", "adaptive")):   # (the two-pass paths keep their own fit)
+            if lattice and not two_pass:   # (the two-pass paths keep their own fit)
                 mhom = torch.empty((T, 9), device=dev, dtype=torch.float64)
                 mbounds = torch.empty((T, 4), device=dev, dtype=torch.float32)
         # (the lanes live as long as this object: the generator keeps an arena / a graph per STREAM, and torch's allocator a pool per stream)
@@ -1141,7 +1223,8 @@ class VideoStabilizer:
                 with torch.cuda.stream(lane):
                     if two_pass:   # pass 1: fields and per-frame bounds only (no halos here: core frames = output positions)
                         self._fields(gray_all[cs - hl:ce + hr], hl, hr, fields[cs:ce], sc)
-                        _field_homography(fields[cs:ce], h, w, hom[cs:ce], bounds[cs:ce])
+                        if not smoothing or rigid:   # (smoothing fits the fields it composes, below; the blend needs the raw fit now)
+                            _field_homography(fields[cs:ce], h, w, hom[cs:ce], bounds[cs:ce])
                         if rigid:   # the kept fields, in place; the bounds stay the raw fit's
                             PF._field_rigid(fields[cs:ce], hom[cs:ce], (h, w), self.rigidity, fields[cs:ce], rres[cs:ce], runf[cs:ce])
                         continue
@@ -1177,11 +1260,27 @@ class VideoStabilizer:
             self.rigid_residual, self.rigid_unfit = rres, runf
         if zmode is not None:
             self.zoom_windows, self.zoom_uncovered = [zwin] * T if zmode == "fixed" else None, zunc
-        if two_pass and not auto:   # (the copy of the bounds to the host waits for pass 1)
+        if smoothing:   # every lane has joined the caller's stream: the kept fields (after rigidity) are complete
+            seen = PF.grid_sample(gray_all.unsqueeze(1), fields, align_corners=self.align_corners).squeeze(1)   # the planes as the fields warp them
+            self.smooth_motion, self.smooth_inliers = global_motion(seen, pixel_scale=(w / 256.0, h / 256.0))
+            del seen
+            self.smooth_correction, self.smooth_path = smooth_path(self.smooth_motion, self.smooth, scene_cuts=cuts or None)
+            self.smooth_uncovered = torch.empty((T,), device=dev, dtype=torch.int32)
+            scratch = torch.empty((min(int(chunk), T),) + tuple(fields.shape[1:]), device=dev, dtype=torch.float32)
+            for s in range(0, T, scratch.shape[0]):
+                e = min(T, s + scratch.shape[0])
+                PF._field_compose(fields[s:e], self.smooth_correction[s:e], (h, w), self.align_corners, self.interpolation, scratch[:e - s],
+                                  self.smooth_uncovered[s:e])
+                fields[s:e].copy_(scratch[:e - s])
+                if lattice:   # bounds, crop and zoom decisions and the report describe the field that warps
+                    _field_homography(fields[s:e], h, w, hom[s:e], bounds[s:e])
+            del scratch
+        if zmode in ("auto", "adaptive"):   # (the copy of the bounds to the host waits for pass 1)
             if zmode == "auto":
                 self.zoom_windows = [zoom_window(auto_crop_window(bounds, (h, w), None, self.period, scene_cuts=cuts or None), (h, w))] * T
             else:
                 self.zoom_windows = zoom_schedule(bounds, (h, w), zoom_speed, zoom_min, scene_cuts=cuts or None)
+        if two_pass and zmode is not None:   # (a fixed fraction under smoothing: its one window, in pass 2)
             zcoef = PF.zoom_coefficients(PF._zoom_windows(self.zoom_windows, T, (h, w), "run_video"), (h, w), fields.shape[1:3]).to(dev, non_blocking=True)
         if auto:
             crop = auto_crop_window(bounds, (h, w), (oh, ow), self.period, scene_cuts=cuts or None)   # (the copy to the host waits for pass 1)
