@@ -50,6 +50,7 @@
  *   pws_field_zoom                the warp field resampled over a per-frame window: zoom to fill (no counterpart in the reference)
  *   pws_field_rigid               the warp field blended towards its fitted homography: rigid warp mode (no counterpart in the reference)
  *   pws_motion_fit_scaled / pws_path_smooth / pws_field_compose  path smoothing: the measured camera path, low-passed, folded into the warp fields (no counterpart in the reference)
+ *   pws_shutter_rates / pws_field_compose_rows  rolling-shutter correction: per-frame camera rates, and the composition with a correction per row (no counterpart in the reference)
  *   pws_pack_* / pws_netg_pack_weights   state_dict (OIHW / IOHW) -> kernel layout; main_new.py:60,471
  *
  * Layouts.  Frames / images: NCHW fp32 as in the reference.  Warp fields: N,H,W,2 fp32 (x then y,
@@ -695,6 +696,41 @@ int pws_path_smooth(const double *motion, int n, double sigma, double *path, dou
  * clear of `uncovered`). */
 int pws_field_compose(const float *field, int n, int fh, int fw, const double *d, float *out, int h0, int w0, int align_corners, int margin,
                       int *uncovered, pws_stream_t stream);
+
+/* Rolling-shutter rates (csrc/path_smooth.hip; no counterpart in the reference): per frame of ONE scene of n frames the camera's velocity
+ * in that frame's own coordinates, per frame interval, from the scene's per-pair motion.  All fp64, in DEVICE memory, no synchronisation.
+ * motion: (n, 4) = (a, b, tx, ty) as for pws_path_smooth: row k maps a point of frame k to frame k-1.  Row 0 is not read; a row with an
+ *   entry that is not finite counts as (1, 0, 0, 0).
+ * rates:  (n, 2, 4) = (ldot, wdot, xdot, ydot) -- log scale, angle, translation -- twice per frame k:
+ *   rates[k][0], forward, from motion[k+1]:  (log hypot(a, b), atan2(b, a), tx, ty);
+ *   rates[k][1], backward, from motion[k], with s = hypot(a, b), f = atan2(b, a):
+ *     (log s, f, (cos f * tx + sin f * ty) / s, (-sin f * tx + cos f * ty) / s) -- the same velocity in frame k's coordinates instead of
+ *     frame k-1's.
+ *   The scene's first frame takes its forward row as its backward row, its last frame its backward row as its forward row; n == 1 gives
+ *   zeros.  Rates never cross a scene cut: call once per scene.
+ * Every product and sum is rounded once, nothing is summed across threads: the same bits on every run.  n == 0 returns PWS_OK and
+ * launches nothing.  PWS_EINVAL: n < 0 or above 2^24, a NULL pointer, a pointer that is not 8-byte aligned.  motion and rates must not
+ * overlap.  One launch. */
+int pws_shutter_rates(const double *motion, int n, double *rates, pws_stream_t stream);
+
+/* pws_field_compose with a rolling-shutter correction that depends on the row (csrc/field_compose.hip; no counterpart in the reference).
+ * r in [-1, 1] is the share of the frame interval that the sensor's readout takes from the top row to the bottom row (negative: bottom
+ * to top); rates[n,2,4] fp64 in DEVICE memory as pws_shutter_rates writes them.  For node (i, j) of frame t, in fp64:
+ *   p0 = D q, exactly as pws_field_compose computes (x', y'): the global-shutter answer, relative to the frame centre;
+ *   delta = r * clamp(p0.y / (h0-1), -1/2, 1/2), the time offset of the row that p0 lies on, in frame intervals;
+ *   (ldot, wdot, xdot, ydot) = rates[t][0] if delta >= 0, else rates[t][1];
+ *   p = p0 - delta * (ldot * p0 + wdot * (-p0.y, p0.x) + (xdot, ydot)): the camera's velocity field times the row's time offset, taken out.
+ * sx = (p.x + (w0-1)/2) (fw-1)/(w0-1), sy alike, each rounded ONCE to fp32; the cell, lx / ly (not clamped), the interpolation, the linear
+ * continuation, the rule for sx or sy that is not finite and `uncovered` are pws_field_compose's.
+ * Deliberate approximations: the row's time is taken from p0 (no fixed-point iteration); the model is first order in delta (exact for a
+ * translation; at |delta| <= 1/2 and 0.01 rad per frame the second-order term stays below 0.01 pixel at 720p); the path is linear between
+ * frames.  The row is that of the frame the motion was measured on.
+ * A frame is copied bit for bit only if its D is exactly the identity AND (r == 0 or all eight of its rates are zero): a steady pan has
+ * D = I and is still unskewed.  r == 0 launches pws_field_compose's kernel, and all-zero rates give its bits.
+ * PWS_EINVAL: as pws_field_compose; r outside [-1, 1] (NaN included); with n > 0, rates NULL or not 8-byte aligned.  n == 0 returns PWS_OK
+ * and launches nothing.  One launch (and a 4 n byte clear of `uncovered`). */
+int pws_field_compose_rows(const float *field, int n, int fh, int fw, const double *d, const double *rates, double r, float *out, int h0, int w0,
+                           int align_corners, int margin, int *uncovered, pws_stream_t stream);
 
 /* Adam (no weight decay / amsgrad) on a flat fp32 buffer, in place; step counts from 1. */
 int pws_adam_step(float *p, const float *g, float *m, float *v, size_t count, float lr, float beta1,

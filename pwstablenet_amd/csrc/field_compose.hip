@@ -13,6 +13,10 @@
 // Launch shape: field_zoom.hip's -- a wave owns 128 consecutive nodes of one row of one frame, a lane 2 adjacent ones (one 16-byte store), a
 // workgroup is 4 waves = 4 rows; the count reduction is that kernel's too.  Under a rotation the cell differs per lane in both axes: per
 // node two 16-byte loads, columns x0 and x0 + 1 of rows y0 and y0 + 1.  The fp64 work is the 2 x 3 product and two scalings per node.
+//
+// Rolling shutter (pws_field_compose_rows, functional.compose_fields(rates=, rolling_shutter=)): the same kernel, instantiated with a
+// row-dependent step between D and the lattice -- the camera's velocity field times the time offset of the row that D q lies on, taken out
+// of D q: a dozen fp64 FMAs per node more, no transcendental, the same loads and stores.  r = 0 launches the affine instantiation.
 #include "common.h"
 #include "warp_common.h"
 
@@ -27,9 +31,18 @@ struct Geo {   // host-computed, fp64: the node's frame pixel, the frame centre,
     double kx, ky, cx, cy, ikx, iky;
 };
 
+struct Rows {   // ROWS: the frames' rates (n, 2, 4), the readout share r (never 0 here) and 1 / (h0 - 1)
+    const double *rates;
+    double r, ih;
+};
+
+// ROWS (pws_field_compose_rows): the rolling-shutter correction between D and the lattice.  p0 = D q lies on a row exposed delta = r
+// clamp(p0.y / (h0-1), -1/2, 1/2) of a frame interval away from the centre row's instant; the camera's velocity field there -- the frame's
+// forward rates for delta >= 0, its backward rates otherwise: 8 workgroup-uniform loads -- times delta is taken out of p0, in fp64.
+template <bool ROWS>
 __global__ void __launch_bounds__(kWave *FC_ROWS) field_compose_kernel(const float *__restrict__ field, const double *__restrict__ d,
                                                                         float *__restrict__ out, int fh, int fw, unsigned nrg, Geo geo, int h0,
-                                                                        int w0, int align_corners, float m, int *__restrict__ uncovered) {
+                                                                        int w0, int align_corners, float m, int *__restrict__ uncovered, Rows rows) {
     __shared__ int cnt[FC_ROWS];
     const unsigned t = blockIdx.x / nrg, rg = blockIdx.x - t * nrg;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63u);
@@ -38,7 +51,14 @@ __global__ void __launch_bounds__(kWave *FC_ROWS) field_compose_kernel(const flo
     if (i < fh && j0 < fw) {
         const double *dt = d + (size_t)t * 6;
         const double d0 = dt[0], d1 = dt[1], d2 = dt[2], d3 = dt[3], d4 = dt[4], d5 = dt[5];
-        const bool same = d0 == 1.0 && d1 == 0.0 && d2 == 0.0 && d3 == 0.0 && d4 == 1.0 && d5 == 0.0;   // (uniform over the workgroup)
+        bool same = d0 == 1.0 && d1 == 0.0 && d2 == 0.0 && d3 == 0.0 && d4 == 1.0 && d5 == 0.0;   // (uniform over the workgroup)
+        double v[2][4] = {};
+        if constexpr (ROWS) {
+            bool still = true;   // a frame whose camera stands still has nothing to take out: it is copied like any other identity frame
+#pragma unroll
+            for (int c = 0; c < 8; ++c) v[c >> 2][c & 3] = rows.rates[(size_t)t * 8 + c], still = still && v[c >> 2][c & 3] == 0.0;
+            same = same && still;
+        }
         const double y = (double)i * geo.ky - geo.cy;
         const float *ft = field + (size_t)t * fh * fw * 2;
         const bool ac = align_corners != 0;
@@ -48,7 +68,17 @@ __global__ void __launch_bounds__(kWave *FC_ROWS) field_compose_kernel(const flo
         for (int q = 0; q < FC_PER_LANE; ++q) {
             const int j = min(j0 + q, fw - 1);   // (a row of odd width: the last lane's second node repeats its first, and is dropped)
             const double x = (double)j * geo.kx - geo.cx;
-            const float sx = (float)(((d0 * x + d1 * y + d2) + geo.cx) * geo.ikx), sy = (float)(((d3 * x + d4 * y + d5) + geo.cy) * geo.iky);
+            float sx, sy;
+            if constexpr (ROWS) {
+                const double px = d0 * x + d1 * y + d2, py = d3 * x + d4 * y + d5;   // p0 = D q: the affine kernel's, and its bits at zero rates
+                const double delta = rows.r * fmin(fmax(py * rows.ih, -0.5), 0.5);
+                const bool fwd = delta >= 0.0;
+                const double ld = fwd ? v[0][0] : v[1][0], wd = fwd ? v[0][1] : v[1][1], xd = fwd ? v[0][2] : v[1][2], yd = fwd ? v[0][3] : v[1][3];
+                const double vx = (ld * px - wd * py) + xd, vy = (ld * py + wd * px) + yd;
+                sx = (float)(((px - delta * vx) + geo.cx) * geo.ikx), sy = (float)(((py - delta * vy) + geo.cy) * geo.iky);
+            } else {
+                sx = (float)(((d0 * x + d1 * y + d2) + geo.cx) * geo.ikx), sy = (float)(((d3 * x + d4 * y + d5) + geo.cy) * geo.iky);
+            }
             const bool keep = same || !(isfinite(sx) && isfinite(sy));   // the node keeps F[i, j]: its own cell, picked below
             // the cell, bounded as a FLOAT before it becomes an integer: in [0, fw-2] x [0, fh-2] whatever d holds
             const float fx = keep ? (float)min(j, fw - 2) : fminf(fmaxf(floorf(sx), 0.f), (float)(fw - 2));
@@ -89,31 +119,27 @@ __global__ void __launch_bounds__(kWave *FC_ROWS) field_compose_kernel(const flo
     }
 }
 
-}  // namespace
-}  // namespace pws
-
-using namespace pws;
-
-extern "C" int pws_field_compose(const float *field, int n, int fh, int fw, const double *d, float *out, int h0, int w0, int align_corners, int margin,
-                                 int *uncovered, pws_stream_t stream) {
-    PWS_REQUIRE(n >= 0, "pws_field_compose: bad shape");
-    PWS_REQUIRE(fh >= 2 && fw >= 2, "pws_field_compose: the field needs at least 2 x 2 nodes (got %d x %d)", fw, fh);
-    PWS_REQUIRE(h0 >= 2 && w0 >= 2, "pws_field_compose: the frame must be at least 2 x 2 pixels (got %d x %d)", w0, h0);
-    PWS_REQUIRE(!uncovered || margin >= 0, "pws_field_compose: bad margin %d for the uncovered count", margin);
+// the checks, the clear and the launch of both exports; `rows` NULL: the affine kernel
+int compose(const char *who, const float *field, int n, int fh, int fw, const double *d, float *out, int h0, int w0, int align_corners, int margin,
+            int *uncovered, pws_stream_t stream, const Rows *rows) {
+    PWS_REQUIRE(n >= 0, "%s: bad shape", who);
+    PWS_REQUIRE(fh >= 2 && fw >= 2, "%s: the field needs at least 2 x 2 nodes (got %d x %d)", who, fw, fh);
+    PWS_REQUIRE(h0 >= 2 && w0 >= 2, "%s: the frame must be at least 2 x 2 pixels (got %d x %d)", who, w0, h0);
+    PWS_REQUIRE(!uncovered || margin >= 0, "%s: bad margin %d for the uncovered count", who, margin);
     if (n == 0) return PWS_OK;
-    PWS_REQUIRE(field && d && out, "pws_field_compose: NULL pointer");
+    PWS_REQUIRE(field && d && out, "%s: NULL pointer", who);
     PWS_REQUIRE(((reinterpret_cast<size_t>(field) | reinterpret_cast<size_t>(out) | reinterpret_cast<size_t>(d)) & 7) == 0 &&
                     (reinterpret_cast<size_t>(uncovered) & 3) == 0,
-                "pws_field_compose: field, out and d must be 8-byte aligned, uncovered 4-byte aligned");
+                "%s: field, out and d must be 8-byte aligned, uncovered 4-byte aligned", who);
     const size_t bytes = (size_t)n * fh * fw * 2 * sizeof(float);
     const char *fb = reinterpret_cast<const char *>(field), *ob = reinterpret_cast<const char *>(out);
-    PWS_REQUIRE(ob + bytes <= fb || fb + bytes <= ob, "pws_field_compose: out must not overlap field");
+    PWS_REQUIRE(ob + bytes <= fb || fb + bytes <= ob, "%s: out must not overlap field", who);
     const unsigned nrg = (unsigned)((fh + FC_ROWS - 1) / FC_ROWS), chunks = (unsigned)((fw + FC_CHUNK - 1) / FC_CHUNK);
-    PWS_REQUIRE((size_t)n * nrg < (1u << 31) && chunks < 65536, "pws_field_compose: field or batch too large");
+    PWS_REQUIRE((size_t)n * nrg < (1u << 31) && chunks < 65536, "%s: field or batch too large", who);
     if (uncovered) {
         const hipError_t e = hipMemsetAsync(uncovered, 0, (size_t)n * sizeof(int), as_stream(stream));
         if (e != hipSuccess) {
-            set_error("pws_field_compose: clearing uncovered: %s", hipGetErrorString(e));
+            set_error("%s: clearing uncovered: %s", who, hipGetErrorString(e));
             return PWS_EHIP;
         }
     }
@@ -121,7 +147,31 @@ extern "C" int pws_field_compose(const float *field, int n, int fh, int fw, cons
     geo.kx = (double)(w0 - 1) / (double)(fw - 1), geo.ky = (double)(h0 - 1) / (double)(fh - 1);
     geo.cx = 0.5 * (double)(w0 - 1), geo.cy = 0.5 * (double)(h0 - 1);
     geo.ikx = (double)(fw - 1) / (double)(w0 - 1), geo.iky = (double)(fh - 1) / (double)(h0 - 1);
-    hipLaunchKernelGGL(field_compose_kernel, dim3((unsigned)n * nrg, chunks, 1), dim3(kWave * FC_ROWS), 0, as_stream(stream), field, d, out, fh, fw, nrg,
-                       geo, h0, w0, align_corners, (float)margin, uncovered);
+    const dim3 grid((unsigned)n * nrg, chunks, 1), block(kWave * FC_ROWS);
+    if (rows) {
+        hipLaunchKernelGGL(field_compose_kernel<true>, grid, block, 0, as_stream(stream), field, d, out, fh, fw, nrg, geo, h0, w0, align_corners,
+                           (float)margin, uncovered, *rows);
+        return check_launch("field_compose_kernel<rows>");
+    }
+    hipLaunchKernelGGL(field_compose_kernel<false>, grid, block, 0, as_stream(stream), field, d, out, fh, fw, nrg, geo, h0, w0, align_corners,
+                       (float)margin, uncovered, Rows{nullptr, 0.0, 0.0});
     return check_launch("field_compose_kernel");
+}
+
+}  // namespace
+}  // namespace pws
+
+using namespace pws;
+
+extern "C" int pws_field_compose(const float *field, int n, int fh, int fw, const double *d, float *out, int h0, int w0, int align_corners, int margin,
+                                 int *uncovered, pws_stream_t stream) {
+    return compose("pws_field_compose", field, n, fh, fw, d, out, h0, w0, align_corners, margin, uncovered, stream, nullptr);
+}
+
+extern "C" int pws_field_compose_rows(const float *field, int n, int fh, int fw, const double *d, const double *rates, double r, float *out, int h0,
+                                      int w0, int align_corners, int margin, int *uncovered, pws_stream_t stream) {
+    PWS_REQUIRE(r >= -1.0 && r <= 1.0, "pws_field_compose_rows: r must lie in [-1, 1], got %g", r);   // (false for NaN)
+    PWS_REQUIRE(n <= 0 || (rates && (reinterpret_cast<size_t>(rates) & 7) == 0), "pws_field_compose_rows: rates must be non-NULL and 8-byte aligned");
+    const Rows rows{rates, r, h0 >= 2 ? 1.0 / (double)(h0 - 1) : 0.0};
+    return compose("pws_field_compose_rows", field, n, fh, fw, d, out, h0, w0, align_corners, margin, uncovered, stream, r == 0.0 ? nullptr : &rows);
 }

@@ -72,10 +72,52 @@ __global__ void __launch_bounds__(PS_THREADS) path_smooth_kernel(const double *_
     }
 }
 
+// Rolling-shutter rates (stream.shutter_rates; include/pwstable.h pws_shutter_rates has the definition, tests/shutter_ref.py restates it):
+// per frame k the camera's velocity (log scale, angle, x, y per frame interval) in frame k's own coordinates, once from the pair ahead --
+// motion[k+1], which maps frame k+1 into frame k: (log s, f, tx, ty) -- and once from the pair behind -- motion[k], which maps frame k into
+// frame k-1: the same generator seen from frame k, (log s, f, Rot(-f) (tx, ty) / s).  A scene's ends have one pair and use it twice.
+// One thread per frame, nothing summed across threads: the same bits on every run.
+__device__ __forceinline__ void rate_forward(const double *m, double *o) {
+    const bool ok = finite4(m);
+    const double a = ok ? m[0] : 1.0, b = ok ? m[1] : 0.0;
+    o[0] = log(hypot(a, b)), o[1] = atan2(b, a), o[2] = ok ? m[2] : 0.0, o[3] = ok ? m[3] : 0.0;
+}
+
+__device__ __forceinline__ void rate_backward(const double *m, double *o) {
+    const bool ok = finite4(m);
+    const double a = ok ? m[0] : 1.0, b = ok ? m[1] : 0.0, tx = ok ? m[2] : 0.0, ty = ok ? m[3] : 0.0;
+    const double s = hypot(a, b), f = atan2(b, a), c = cos(f), sn = sin(f);
+    o[0] = log(s), o[1] = f, o[2] = (c * tx + sn * ty) / s, o[3] = ((0.0 - sn) * tx + c * ty) / s;
+}
+
+__global__ void __launch_bounds__(PS_THREADS) shutter_rates_kernel(const double *__restrict__ motion, int n, double *__restrict__ rates) {
+    const int k = (int)(blockIdx.x * PS_THREADS + threadIdx.x);
+    if (k >= n) return;
+    double fwd[4] = {0.0, 0.0, 0.0, 0.0}, bwd[4] = {0.0, 0.0, 0.0, 0.0};
+    const bool ahead = k + 1 < n, behind = k >= 1;   // (row 0 of a scene is not read, as in the path)
+    if (ahead) rate_forward(motion + (size_t)(k + 1) * 4, fwd);
+    if (behind) rate_backward(motion + (size_t)k * 4, bwd);
+    double *o = rates + (size_t)k * 8;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o[c] = ahead ? fwd[c] : bwd[c], o[4 + c] = behind ? bwd[c] : fwd[c];
+}
+
 }  // namespace
 }  // namespace pws
 
 using namespace pws;
+
+extern "C" int pws_shutter_rates(const double *motion, int n, double *rates, pws_stream_t stream) {
+    PWS_REQUIRE(n >= 0, "pws_shutter_rates: bad shape (n %d)", n);
+    if (n == 0) return PWS_OK;
+    PWS_REQUIRE(motion && rates, "pws_shutter_rates: NULL pointer");
+    PWS_REQUIRE(((reinterpret_cast<size_t>(motion) | reinterpret_cast<size_t>(rates)) & 7) == 0,
+                "pws_shutter_rates: motion and rates must be 8-byte aligned");
+    PWS_REQUIRE(n <= (1 << 24), "pws_shutter_rates: a scene of %d frames, at most 2^24", n);
+    hipLaunchKernelGGL(shutter_rates_kernel, dim3((unsigned)((n + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0, as_stream(stream), motion, n,
+                       rates);
+    return check_launch("shutter_rates_kernel");
+}
 
 extern "C" int pws_path_smooth(const double *motion, int n, double sigma, double *path, double *d, pws_stream_t stream) {
     PWS_REQUIRE(n >= 0, "pws_path_smooth: bad shape (n %d)", n);

@@ -630,7 +630,26 @@ def _field_compose(field, d, frame_hw, align_corners, mode, out, uncovered):
     return out
 
 
-def compose_fields(field, d, frame_hw, align_corners=False, mode="bilinear", out=None, return_uncovered=False):
+def _field_compose_rows(field, d, rates, r, frame_hw, align_corners, mode, out, uncovered):
+    """pws_field_compose_rows on device tensors: ``rates`` (T, 2, 4) float64, ``r`` the readout share in [-1, 1]."""
+    A.check(A.lib().pws_field_compose_rows(A.ptr(field), field.shape[0], field.shape[1], field.shape[2], A.ptr(d), A.ptr(rates), float(r), A.ptr(out),
+                                           int(frame_hw[0]), int(frame_hw[1]), _ac(align_corners), int(mode == "bicubic"), A.ptr(uncovered),
+                                           A.current_stream()), "pws_field_compose_rows")
+    return out
+
+
+def _check_rolling_shutter(r, what):
+    """``rolling_shutter`` as a float in [-1, 1]; ValueError otherwise (NaN included)."""
+    try:
+        v = float(r)
+    except (TypeError, ValueError):
+        raise ValueError("%s: rolling_shutter must be a number in [-1, 1], got %r" % (what, r)) from None
+    if not -1.0 <= v <= 1.0:
+        raise ValueError("%s: rolling_shutter must lie in [-1, 1], got %r" % (what, r))
+    return v
+
+
+def compose_fields(field, d, frame_hw, align_corners=False, mode="bilinear", out=None, return_uncovered=False, rates=None, rolling_shutter=0.0):
     """A per-frame affine correction of the output frame, composed into the field: ``field`` (T, fh, fw, 2) as ``netG(window, False)``
     returns it, ``d`` (T, 6) float64 on the device -- D of frame t, row-major 2 x 3, in pixels of the ``frame_hw`` = (H0, W0) frame relative
     to its centre, as ``stream.smooth_path`` returns it: output position p shows what the uncorrected output shows at D p.  A fused warp
@@ -641,10 +660,21 @@ def compose_fields(field, d, frame_hw, align_corners=False, mode="bilinear", out
     RESAMPLED field, not the exact composition.  One launch (csrc/field_compose.hip; include/pwstable.h has the definition); ``out`` must
     not overlap ``field``.
     return_uncovered: also a (T,) int32 device tensor, ``zoom_fields``' count on the composed field (``align_corners`` and ``mode`` the warp's).
-    ValueError: shapes or dtypes other than these, a host tensor, a frame below 2 x 2 pixels, an unknown mode."""
+    rates, rolling_shutter: the rolling-shutter correction.  ``rolling_shutter`` = r in [-1, 1] is the share of the frame interval that the
+    sensor's readout takes from the top row to the bottom row (negative: bottom to top), ``rates`` (T, 2, 4) float64 on the device the
+    camera's forward and backward velocity per frame, as ``stream.shutter_rates`` returns it.  D p lies on a row exposed delta = r
+    clamp((D p).y / (H0 - 1), -1/2, 1/2) of a frame interval away from the centre row; the velocity field there (forward rates for delta >= 0,
+    backward otherwise) times delta is taken out of D p before the field is read (csrc/field_compose.hip, the kernel's second
+    instantiation; include/pwstable.h pws_field_compose_rows has the definition and its approximations).  A frame is then copied only if
+    its D is the identity and its rates are all zero.  ``rolling_shutter == 0.0`` or ``rates is None`` is the call without them, bit for
+    bit.
+    ValueError: shapes or dtypes other than these, a host tensor, a frame below 2 x 2 pixels, an unknown mode, rolling_shutter outside [-1, 1]."""
     if mode not in INTERPOLATIONS:
         raise ValueError("mode must be one of %s, got %r" % (INTERPOLATIONS, mode))
-    for name, t, dtype in (("field", field, torch.float32), ("d", d, torch.float64)) + ((("out", out, torch.float32),) if out is not None else ()):
+    r = _check_rolling_shutter(rolling_shutter, "compose_fields")
+    rows = r != 0.0 and rates is not None
+    for name, t, dtype in (("field", field, torch.float32), ("d", d, torch.float64)) + ((("out", out, torch.float32),) if out is not None else ()) + (
+            (("rates", rates, torch.float64),) if rows else ()):
         if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
             raise ValueError("compose_fields: %s must be a %s tensor on the device, got %s" % (
                 name, dtype, "%s on %s" % (t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t)))
@@ -653,6 +683,8 @@ def compose_fields(field, d, frame_hw, align_corners=False, mode="bilinear", out
     n = field.shape[0]
     if tuple(d.shape) != (n, 6):
         raise ValueError("compose_fields: d must be (%d, 6), got %s" % (n, tuple(d.shape)))
+    if rows and tuple(rates.shape) != (n, 2, 4):
+        raise ValueError("compose_fields: rates must be (%d, 2, 4), got %s" % (n, tuple(rates.shape)))
     h0, w0 = int(frame_hw[0]), int(frame_hw[1])
     if h0 < 2 or w0 < 2:
         raise ValueError("compose_fields: the frame must be at least 2 x 2 pixels, got %d x %d" % (w0, h0))
@@ -662,7 +694,10 @@ def compose_fields(field, d, frame_hw, align_corners=False, mode="bilinear", out
     if tuple(out.shape) != tuple(field.shape) or not out.is_contiguous():
         raise ValueError("compose_fields: out must be a contiguous %s float32 tensor" % (tuple(field.shape),))
     unc = torch.empty((n,), device=field.device, dtype=torch.int32) if return_uncovered else None
-    _field_compose(field, d, (h0, w0), align_corners, mode, out, unc)
+    if rows:
+        _field_compose_rows(field, d, rates.contiguous(), r, (h0, w0), align_corners, mode, out, unc)
+    else:
+        _field_compose(field, d, (h0, w0), align_corners, mode, out, unc)
     return (out, unc) if return_uncovered else out
 
 

@@ -339,6 +339,25 @@ def smooth_path(motion, sigma, scene_cuts=None):
     return d, path
 
 
+def shutter_rates(motion, scene_cuts=None):
+    """The camera's velocity at every frame of a clip, for the rolling-shutter correction (csrc/path_smooth.hip; include/pwstable.h
+    pws_shutter_rates has the definition): ``motion`` (T, 4) float64 on the device as for ``smooth_path``.  Returns (T, 2, 4) float64 on
+    the device: per frame k the rates (log scale, angle, x, y per frame interval) in frame k's own coordinates, [k, 0] from the pair ahead
+    (motion[k+1]), [k, 1] from the pair behind (motion[k]) -- what ``functional.compose_fields(rates=)`` takes.  Per scene
+    (``scene_cuts`` as for ``smooth_path``): rates never cross a cut, a scene's first and last frame use their one pair twice, a scene of
+    one frame has zero rates; a NaN row counts as no motion.  No synchronisation; one launch per scene, on slices; the same bits on every run.
+    ValueError: a tensor that is not (T, 4) float64 on the device, bad cuts."""
+    if not isinstance(motion, torch.Tensor) or not motion.is_cuda or motion.dtype != torch.float64 or motion.dim() != 2 or motion.shape[1] != 4:
+        raise ValueError("shutter_rates: motion must be a (T, 4) float64 tensor on the device")
+    motion = motion.contiguous()
+    T = motion.shape[0]
+    cuts = _check_cuts(scene_cuts, T, "shutter_rates") if scene_cuts is not None and len(scene_cuts) else []
+    rates = torch.empty((T, 2, 4), device=motion.device, dtype=torch.float64)
+    for a, b in (_scenes(T, cuts) if T else []):
+        A.check(A.lib().pws_shutter_rates(A.ptr(motion[a:b]), b - a, A.ptr(rates[a:b]), A.current_stream()), "pws_shutter_rates")
+    return rates
+
+
 def _signal_score(v):
     """One signal's stability score over a scene of m frames; v[k] is the motion of pair k (v[0] is not read)."""
     import numpy as np
@@ -526,7 +545,7 @@ def _windows(gray_padded, start, count, period):
 
 class VideoStabilizer:
     def __init__(self, netG, batch=32, period=30, device=None, swap_rb=False, interpolation="bilinear", borders="black", rigidity=0.0,
-                 mosaic_radius=8, edge="pad", metrics=False, smooth=0.0):
+                 mosaic_radius=8, edge="pad", metrics=False, smooth=0.0, rolling_shutter=0.0):
         self.net = netG
         # run_video folds the shake that the fields LEAVE in the clip back into them: the global motion of the planes as the kept fields warp
         # them is measured, the camera path low-passed with a Gaussian of `smooth` frames (smooth_path) and every frame's correction composed
@@ -535,6 +554,15 @@ class VideoStabilizer:
         self.smooth_motion = self.smooth_inliers = None       # smooth > 0, of the last run_video, on the device: (T, 4) float64 / (T,) int32, the
         self.smooth_path = self.smooth_correction = None      # motion the fields left (frame pixels); (T, 4) its path, (T, 6) the corrections D;
         self.smooth_uncovered = None                          # (T,) int32, the composed fields' nodes that sample outside the source
+        # the share of the frame interval that the sensor's readout takes from the top row to the bottom row, in [-1, 1] (negative: bottom to
+        # top); a property of the camera, which the user supplies.  Not 0: the correction that smoothing composes into each field depends on
+        # the row (shutter_rates, functional.compose_fields(rates=, rolling_shutter=)), so that the skew and wobble of a CMOS readout under
+        # shake come out with the shake.  It needs the motion that smoothing measures and the second pass that smoothing owns
+        self.rolling_shutter = PF._check_rolling_shutter(rolling_shutter, "VideoStabilizer")
+        if self.rolling_shutter != 0.0 and self.smooth == 0.0:
+            raise ValueError("VideoStabilizer: rolling_shutter=%r needs smooth > 0 (the correction uses the motion that smoothing measures and "
+                             "its second pass)" % (rolling_shutter,))
+        self.shutter_rates = None   # rolling_shutter != 0, of the last run_video, on the device: (T, 2, 4) float64, shutter_rates' rows
         # run_video measures the clip it stabilises: the global motion of the input and of the output planes (global_motion), and from it
         # and the per-frame homographies the paper's three metrics (stability_report).  False: no launch, no allocation, every path as it was
         self.metrics = bool(metrics)
@@ -951,6 +979,13 @@ class VideoStabilizer:
         source).  A pair no similarity could be fitted to counts as no motion.  Every pixel_format, interpolation, edge, crop, zoom,
         rigidity, in_flight and scene_cuts works as without it.  ValueError: halos (a shard cannot see the scene's path), borders="keep" or
         "mosaic" (they have no second pass).
+        VideoStabilizer(smooth=sigma, rolling_shutter=r), r != 0: rolling-shutter correction inside the same composition.  r in [-1, 1] is the
+        share of the frame interval that the readout from the top row to the bottom row takes (negative: bottom to top).  ``shutter_rates``
+        of the measured motion, under the call's cuts, gives every frame's forward and backward velocity; ``compose_fields(rates=,
+        rolling_shutter=r)`` takes, per field node, that velocity times the time offset of the node's row out of the position that D gives.
+        The refit, and with it crop, zoom and the report, see the corrected field.  ``self.shutter_rates`` (T, 2, 4) float64 is left on the
+        device, no synchronisation; None at r = 0.  First order in the time offset, a linear path between frames, the row taken from the
+        frame that the motion was measured on (INTEGRATION.md has the model and its caveats); not validated on real footage.
         Returns (T, H, W, 3) -- or (T, H/2, W/2, 3) / (T, height, width, 3), or the crop window of it -- uint8 on the inputs' side; for YUV
         (T, oh * 3 // 2, ow) of the output (or crop window) size oh x ow."""
         half = self.period // 2
@@ -1034,6 +1069,9 @@ class VideoStabilizer:
                 zwin = _centred_window(zk, h, w)
         smoothing = self.smooth > 0.0
         self.smooth_motion = self.smooth_inliers = self.smooth_path = self.smooth_correction = self.smooth_uncovered = None
+        self.shutter_rates = None
+        if self.rolling_shutter != 0.0 and not smoothing:   # (the attributes can be set after construction)
+            raise ValueError("run_video: rolling_shutter=%r needs smooth > 0" % (self.rolling_shutter,))
         if smoothing:
             if halo_left or halo_right:
                 raise ValueError("run_video: smooth > 0 needs the whole clip (a shard cannot see the scene's path)")
@@ -1266,11 +1304,18 @@ class VideoStabilizer:
             del seen
             self.smooth_correction, self.smooth_path = smooth_path(self.smooth_motion, self.smooth, scene_cuts=cuts or None)
             self.smooth_uncovered = torch.empty((T,), device=dev, dtype=torch.int32)
+            rs = PF._check_rolling_shutter(self.rolling_shutter, "run_video")
+            if rs != 0.0:   # the velocity at every frame, from the same measured motion and under the same cuts
+                self.shutter_rates = shutter_rates(self.smooth_motion, scene_cuts=cuts or None)
             scratch = torch.empty((min(int(chunk), T),) + tuple(fields.shape[1:]), device=dev, dtype=torch.float32)
             for s in range(0, T, scratch.shape[0]):
                 e = min(T, s + scratch.shape[0])
-                PF._field_compose(fields[s:e], self.smooth_correction[s:e], (h, w), self.align_corners, self.interpolation, scratch[:e - s],
-                                  self.smooth_uncovered[s:e])
+                if rs != 0.0:
+                    PF._field_compose_rows(fields[s:e], self.smooth_correction[s:e], self.shutter_rates[s:e], rs, (h, w), self.align_corners,
+                                           self.interpolation, scratch[:e - s], self.smooth_uncovered[s:e])
+                else:
+                    PF._field_compose(fields[s:e], self.smooth_correction[s:e], (h, w), self.align_corners, self.interpolation, scratch[:e - s],
+                                      self.smooth_uncovered[s:e])
                 fields[s:e].copy_(scratch[:e - s])
                 if lattice:   # bounds, crop and zoom decisions and the report describe the field that warps
                     _field_homography(fields[s:e], h, w, hom[s:e], bounds[s:e])
