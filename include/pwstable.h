@@ -49,6 +49,7 @@
  *   pws_block_motion / pws_motion_fit  global motion between consecutive window planes: the stability metric (no counterpart in the reference)
  *   pws_field_zoom                the warp field resampled over a per-frame window: zoom to fill (no counterpart in the reference)
  *   pws_field_rigid               the warp field blended towards its fitted homography: rigid warp mode (no counterpart in the reference)
+ *   pws_field_wobble              the warp fields' non-rigid part low-passed along time: wobble suppression (no counterpart in the reference)
  *   pws_motion_fit_scaled / pws_path_smooth / pws_field_compose  path smoothing: the measured camera path, low-passed, folded into the warp fields (no counterpart in the reference)
  *   pws_shutter_rates / pws_field_compose_rows  rolling-shutter correction: per-frame camera rates, and the composition with a correction per row (no counterpart in the reference)
  *   pws_pack_* / pws_netg_pack_weights   state_dict (OIHW / IOHW) -> kernel layout; main_new.py:60,471
@@ -601,6 +602,35 @@ int pws_field_zoom(const float *field, int n, int fh, int fw, const float *coef,
  * aligned, residual / unfit not 4-byte aligned, out overlapping field in part.  One launch (and a 4 n byte clear per statistic). */
 int pws_field_rigid(const float *field, int n, int fh, int fw, const double *m, float rigidity, int h0, int w0, float *out, float *residual,
                     int *unfit, pws_stream_t stream);
+
+/* Wobble suppression (csrc/field_wobble.hip; no counterpart in the reference).  The generator regresses every frame's field from that
+ * frame's own window, and nothing ties the NON-RIGID part of consecutive fields together: the local, per-pixel part changes from frame to
+ * frame, which reads as wobble.  This low-passes that part along time and leaves the rigid part -- the fitted homography -- as it is.
+ * One call is ONE scene of n frames (the caller slices at its cuts).  field[n,fh,fw,2] -> out[n,fh,fw,2]; m[n,9] fp64 in device memory as
+ * pws_field_homography writes it; (h0, w0) the frame; sigma in (0, 5] frames, the Gaussian's width.
+ *   R = ceil(3 sigma) (fp64), 1 .. 15: the filter looks no further than the generator's own window of +-15 frames.
+ *   g_k = exp(-k^2 / (2 sigma^2)), k = -R .. R, in fp64 on the host, each rounded to fp32; g_0 = 1.
+ *   P[t] at node (i, j), and the notions FITTED (frame) and VALID (node), are pws_field_rigid's, word for word: the adjugate in fp64,
+ *   D/Dc >= 2^-20, P rounded once to fp32 (the same device code: csrc/rigid_position.h).
+ *   A (frame, node) pair is USABLE when the frame is fitted, the node is valid and both components of F are finite.
+ *   For a usable pair E = F - P: one fp32 subtraction per component.
+ *   A node that is not usable at t: out = F bit for bit, and the node counts in unfit[t] (a node with a NaN in F included).
+ *   A node usable at t: S = sum g_k E[t+k] and W = sum g_k, both over the k, in ascending order, with 0 <= t+k < n and (t+k, node) usable;
+ *   fp32: S by fmaf(g_k, E, S) per component from 0, W by plain additions from 0; W >= 1 since k = 0 counts.  out = P[t] + S / W (one
+ *   IEEE division, one addition).  Frames outside the scene and unusable taps drop out of both sums: no reflection, no padding, and a
+ *   scene of one frame returns float32(P + (F - P)).
+ * removed (n, fp32; may be NULL): the largest max(|out_x - F_x| * (w0/2), |out_y - F_y| * (h0/2)) -- fp32: one subtraction, one product; a
+ * NaN drops out -- over the usable nodes of frame t, 0 without any: how much the filter moved the field, in source pixels; the number
+ * to choose sigma by.  unfit (n, int32; may be NULL) as above.  An integer atomic max on the bits of a non-negative float and integer
+ * counts; the sums run in a fixed order and no floating-point atomic is used: the same bits on every run.  Both are cleared by the call.
+ * The filter acts at fixed OUTPUT positions (field nodes), not along scene points: a real, fast change of parallax is smoothed too.
+ * The kernel reads neighbouring frames, so it cannot run in place.  Its time segments are PWS_WOBBLE_SEGMENT output frames long.
+ * Any fh, fw >= 2; n == 0 returns PWS_OK, launches nothing and writes nothing.  PWS_EINVAL: NULL field / m / out, n < 0, fh or fw < 2,
+ * h0 or w0 < 1, sigma outside (0, 5] or NaN, field / out / m not 8-byte aligned, removed / unfit not 4-byte aligned, out overlapping
+ * field (the same pointer included).  One launch (and a 4 n byte clear per statistic). */
+#define PWS_WOBBLE_SEGMENT 32
+int pws_field_wobble(const float *field, int n, int fh, int fw, const double *m, double sigma, int h0, int w0, float *out, float *removed,
+                     int *unfit, pws_stream_t stream);
 
 /* Scene-cut score for edited footage (csrc/scene.hip).  The reference clamps a frame's 31-plane window at the clip's first and last frame
  * only (main_new.py:627-633); the streaming stabiliser applies the same clamp at every hard cut, which it finds from the L1 distance of

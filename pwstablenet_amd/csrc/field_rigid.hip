@@ -25,6 +25,7 @@
 // hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage: 40 VGPRs, 52 SGPRs, 0 bytes of scratch, 32 bytes of LDS,
 // 8 waves per SIMD.
 #include "common.h"
+#include "rigid_position.h"
 
 namespace pws {
 namespace {
@@ -45,17 +46,8 @@ __global__ void __launch_bounds__(kWave *FR_ROWS) field_rigid_kernel(const float
     float res = 0.f;
     if (i < fh && j0 < fw) {
         // ---- wave-uniform: the adjugate, the fitted test, the row's terms
-        const double *M = m + (size_t)t * 9;
-        const double m0 = M[0], m1 = M[1], m2 = M[2], m3 = M[3], m4 = M[4], m5 = M[5], m6 = M[6], m7 = M[7], m8 = M[8];
-        const double a00 = m4 * m8 - m5 * m7, a01 = m2 * m7 - m1 * m8, a02 = m1 * m5 - m2 * m4;
-        const double a10 = m5 * m6 - m3 * m8, a11 = m0 * m8 - m2 * m6, a12 = m2 * m3 - m0 * m5;
-        const double a20 = m3 * m7 - m4 * m6, a21 = m1 * m6 - m0 * m7, a22 = m0 * m4 - m1 * m3;
-        const double det = m0 * a00 + m1 * a10 + m2 * a20;
-        bool fitted = __builtin_isfinite(det) && det != 0.0 && a22 != 0.0;
-        fitted = fitted && __builtin_isfinite(m0) && __builtin_isfinite(m1) && __builtin_isfinite(m2) && __builtin_isfinite(m3) &&
-                 __builtin_isfinite(m4) && __builtin_isfinite(m5) && __builtin_isfinite(m6) && __builtin_isfinite(m7) && __builtin_isfinite(m8);
-        const double v = (double)i * sv - 1.0;
-        const double xr = a01 * v + a02, yr = a11 * v + a12, dr = a21 * v + a22;
+        const RigidFrame frame = rigid_frame(m + (size_t)t * 9);   // (rigid_position.h: shared with field_wobble.hip)
+        const RigidRow row = rigid_row(frame, (double)i * sv - 1.0);
         // ---- the lane's two nodes
         const bool two = j0 + 1 < fw;   // (a row of odd width: its last lane holds one node)
         const float *f = field + (((size_t)t * fh + i) * fw + j0) * 2;
@@ -70,10 +62,8 @@ __global__ void __launch_bounds__(kWave *FR_ROWS) field_rigid_kernel(const float
 #pragma unroll
         for (int q = 0; q < FR_PER_LANE; ++q) {
             const float fx = q ? F.z : F.x, fy = q ? F.w : F.y;
-            const double u = (double)(j0 + q) * su - 1.0;
-            const double X = a00 * u + xr, Y = a10 * u + yr, D = a20 * u + dr;
-            const bool valid = fitted && D / a22 >= 0x1p-20;   // (false for NaN)
-            const float px = (float)(X / D), py = (float)(Y / D);   // (true fp64 divisions: the definition's quotients, rounded once)
+            float px, py;
+            const bool valid = rigid_node(frame, row, (double)(j0 + q) * su - 1.0, px, py);
             const bool live = q == 0 || two;
             if (valid) {
                 if (r == 1.f) {   // (kernel argument: uniform.  Full rigidity is the homography itself, not F + (P - F))

@@ -757,6 +757,74 @@ def rigid_fields(field, m, frame_hw, rigidity=1.0, out=None, return_stats=False)
     return (out, res, unfit) if return_stats else out
 
 
+WOBBLE_MAX_SIGMA = 5.0   # frames: R = ceil(3 sigma) <= 15, the generator's own window of +-15 frames at period 30
+WOBBLE_SEGMENT = 32      # the kernel's time segment, in output frames (include/pwstable.h PWS_WOBBLE_SEGMENT)
+
+
+def _check_wobble(sigma, what, zero_ok=False):
+    """``wobble`` / ``sigma`` as a float in (0, 5] (or [0, 5]); ValueError otherwise (NaN included)."""
+    try:
+        s = float(sigma)
+    except (TypeError, ValueError):
+        raise ValueError("%s: the wobble filter's sigma must be a number of frames, got %r" % (what, sigma)) from None
+    if not ((0.0 < s or (zero_ok and s == 0.0)) and s <= WOBBLE_MAX_SIGMA):
+        raise ValueError("%s: the wobble filter's sigma must lie in %s0, %g] frames, got %r" % (what, "[" if zero_ok else "(", WOBBLE_MAX_SIGMA, sigma))
+    return s
+
+
+def _field_wobble(field, m, frame_hw, sigma, out, removed, unfit):
+    """pws_field_wobble on device tensors, ONE scene: ``m`` (n, 9) or (n, 3, 3) float64, ``removed`` (n,) float32 / ``unfit`` (n,) int32 or None."""
+    A.check(A.lib().pws_field_wobble(A.ptr(field), field.shape[0], field.shape[1], field.shape[2], A.ptr(m), float(sigma), int(frame_hw[0]),
+                                     int(frame_hw[1]), A.ptr(out), A.ptr(removed), A.ptr(unfit), A.current_stream()), "pws_field_wobble")
+    return out
+
+
+def wobble_fields(field, m, frame_hw, sigma, scene_cuts=None, out=None, return_stats=False):
+    """Wobble suppression: the non-rigid part of a clip's fields low-passed along time.  ``field`` (T, fh, fw, 2) as ``netG(window, False)``
+    returns it, ``m`` (T, 3, 3) or (T, 9) float64 on the device, as ``stream.field_homography(field, frame_hw)`` returns them, ``frame_hw`` =
+    (H0, W0), ``sigma`` in (0, 5] frames.  Per node, P is the position the frame's homography alone would have it sample (``rigid_fields``'
+    P, FITTED frame and VALID node, word for word) and E = F - P the residual: parallax, lens correction -- and the frame-to-frame shimmer
+    of a field that is regressed from each frame's own window.  The node becomes P + sum g_k E[t+k] / sum g_k with g_k = exp(-k^2 / (2
+    sigma^2)), |k| <= ceil(3 sigma) <= 15, over the frames of its scene at which the node is usable (fitted frame, valid node, finite F):
+    taps beyond the scene's ends or at unusable nodes drop out of both sums -- no reflection, no padding.  A node that is not usable keeps
+    F bit for bit.  The rigid part is untouched: a field that is exactly its homography comes back to within P's rounding, a residual that
+    does not change in time comes back to a few ulps.  The filter acts at fixed OUTPUT positions: a real, fast change of parallax is smoothed
+    too.  ``scene_cuts``: sorted indices at which a new scene starts; taps never cross a cut.  One launch per scene, on slices
+    (csrc/field_wobble.hip; include/pwstable.h has the full definition); fixed order, no floating-point atomics: the same bits on every
+    run.  ``out`` must not overlap ``field`` (the kernel reads neighbouring frames).  Any frame size: the 600 x 300 minimum is the fit's.
+    return_stats: also removed (T,) float32 -- per frame, the largest distance in source pixels by which the filter moved a node: the number
+    to choose sigma by -- and unfit (T,) int32, the nodes that kept F because they were not usable; both on the device, no synchronisation.
+    ValueError: shapes or dtypes other than these, a host tensor, sigma outside (0, 5], bad cuts, an ``out`` that overlaps ``field``."""
+    s = _check_wobble(sigma, "wobble_fields")
+    for name, t, dtype in (("field", field, torch.float32), ("m", m, torch.float64)) + ((("out", out, torch.float32),) if out is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
+            raise ValueError("wobble_fields: %s must be a %s tensor on the device, got %s" % (
+                name, dtype, "%s on %s" % (t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t)))
+    if field.dim() != 4 or field.shape[3] != 2 or field.shape[1] < 2 or field.shape[2] < 2:
+        raise ValueError("wobble_fields: field must be (T, fh, fw, 2) with fh, fw >= 2, got %s" % (tuple(field.shape),))
+    n = field.shape[0]
+    if tuple(m.shape) not in ((n, 3, 3), (n, 9)):
+        raise ValueError("wobble_fields: m must be (%d, 3, 3) or (%d, 9), got %s" % (n, n, tuple(m.shape)))
+    h0, w0 = int(frame_hw[0]), int(frame_hw[1])
+    if h0 < 1 or w0 < 1:
+        raise ValueError("wobble_fields: bad frame size %d x %d" % (w0, h0))
+    if out is not None and (tuple(out.shape) != tuple(field.shape) or not out.is_contiguous()):
+        raise ValueError("wobble_fields: out must be a contiguous %s float32 tensor" % (tuple(field.shape),))
+    from .stream import _check_cuts, _scenes   # (stream imports this module)
+    cuts = _check_cuts(scene_cuts, n, "wobble_fields") if scene_cuts is not None and len(scene_cuts) else []
+    field, m = field.contiguous(), m.contiguous().reshape(n, 9)
+    if out is None:
+        out = torch.empty_like(field)
+    nbytes = field.numel() * 4
+    if n and out.data_ptr() < field.data_ptr() + nbytes and field.data_ptr() < out.data_ptr() + nbytes:
+        raise ValueError("wobble_fields: out must not overlap field (the filter reads neighbouring frames: it cannot run in place)")
+    removed = torch.empty((n,), device=field.device, dtype=torch.float32) if return_stats else None
+    unfit = torch.empty((n,), device=field.device, dtype=torch.int32) if return_stats else None
+    for a, b in (_scenes(n, cuts) if n else []):
+        _field_wobble(field[a:b], m[a:b], (h0, w0), s, out[a:b], removed[a:b] if return_stats else None, unfit[a:b] if return_stats else None)
+    return (out, removed, unfit) if return_stats else out
+
+
 def adam_step_(p, g, m, v, lr, beta1, beta2, eps, step):
     """In-place fused Adam on flat fp32 CUDA buffers."""
     A.require_cuda(p, g, m, v)

@@ -272,6 +272,7 @@ SIGNATURES = {
     "pws_field_compose_rows": (_I, [_P, _I, _I, _I, _P, _P, _D, _P, _I, _I, _I, _I, _P, _P]),
     "pws_field_zoom": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "pws_field_rigid": (_I, [_P, _I, _I, _I, _P, _F, _I, _I, _P, _P, _P, _P]),
+    "pws_field_wobble": (_I, [_P, _I, _I, _I, _P, _D, _I, _I, _P, _P, _P, _P]),
     "pws_bn_ws_bytes": (_S, [_I]),
     "pws_bn_train_fwd": (_I, [_P, _S, _I, _P, _P, _I, _P, _P, _P, _P, _F, _F, _I, _P, _S, _P]),
     "pws_bn_train_bwd": (_I, [_P, _P, _P, _P, _P, _I, _S, _I, _P, _P, _P, _S, _P]),

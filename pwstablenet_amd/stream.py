@@ -545,8 +545,15 @@ def _windows(gray_padded, start, count, period):
 
 class VideoStabilizer:
     def __init__(self, netG, batch=32, period=30, device=None, swap_rb=False, interpolation="bilinear", borders="black", rigidity=0.0,
-                 mosaic_radius=8, edge="pad", metrics=False, smooth=0.0, rolling_shutter=0.0):
+                 mosaic_radius=8, edge="pad", metrics=False, smooth=0.0, rolling_shutter=0.0, wobble=0.0):
         self.net = netG
+        # run_video low-passes the NON-RIGID part of the clip's fields along time: each field minus its fitted homography, under a Gaussian of
+        # `wobble` frames, in (0, 5] (functional.wobble_fields).  The generator regresses every field from that frame's own window, and the
+        # local part of consecutive fields shimmers; rigidity removes that part altogether, this keeps it and steadies it.  0: no launch, no
+        # allocation, every path as it was
+        self.wobble = PF._check_wobble(wobble, "VideoStabilizer", zero_ok=True)
+        self.wobble_removed = None   # wobble > 0, of the last run_video, on the device: (T,) float32, per frame the largest distance in source
+        self.wobble_unfit = None     # pixels by which the filter moved a node; (T,) int32, the nodes that kept their value (not usable)
         # run_video folds the shake that the fields LEAVE in the clip back into them: the global motion of the planes as the kept fields warp
         # them is measured, the camera path low-passed with a Gaussian of `smooth` frames (smooth_path) and every frame's correction composed
         # into its field (functional.compose_fields) before the one warp.  0: no launch, no allocation, every path as it was
@@ -986,6 +993,21 @@ class VideoStabilizer:
         The refit, and with it crop, zoom and the report, see the corrected field.  ``self.shutter_rates`` (T, 2, 4) float64 is left on the
         device, no synchronisation; None at r = 0.  First order in the time offset, a linear path between frames, the row taken from the
         frame that the motion was measured on (INTEGRATION.md has the model and its caveats); not validated on real footage.
+        VideoStabilizer(wobble=sigma), sigma in (0, 5] frames: wobble suppression.  The local, per-pixel part of the field changes from frame
+        to frame, which reads as wobble or "jello"; rigidity removes that part and with it the parallax and lens correction a per-pixel field
+        exists for.  This low-passes it along time instead (``functional.wobble_fields`` has the definition): per node, the field minus the
+        frame's fitted homography is averaged over +-ceil(3 sigma) frames of its scene under a Gaussian, and the homography's own position
+        is added back.  The call takes the two-pass route, also without a crop, zoom or smooth; pass 1 fits M on the raw field.  Once pass
+        1 has joined, on the caller's stream: the kept fields (after the in-place rigidity blend) are filtered under the call's cuts into a
+        second buffer that replaces them -- another 512 KB per frame for the duration of the call; ``field_homography`` is fitted again on
+        the result, so that the bounds, crop="auto", zoom="auto" / "adaptive" and the report describe the field that warps (under smooth the
+        one refit is the one behind its composition); smooth's measurement follows, so it sees the filtered fields.  Pass 2 is unchanged.
+        Left on the device, no synchronisation, None at wobble = 0: ``self.wobble_removed`` (T,) float32 -- per frame, the largest distance
+        in source pixels by which the filter moved a node: the number to choose sigma by -- and ``self.wobble_unfit`` (T,) int32, the nodes
+        that kept their value.  The filter acts at fixed output positions, so a real, fast change of parallax is smoothed too; nothing
+        was validated on real footage.  Every pixel_format, interpolation, edge, crop, zoom, rigidity, smooth, in_flight and scene_cuts
+        works as without it.  ValueError: halos, borders="keep" or "mosaic" (no second pass), a source below the fit's 600 x 300 lattice.
+        ``run()`` does not take it.
         Returns (T, H, W, 3) -- or (T, H/2, W/2, 3) / (T, height, width, 3), or the crop window of it -- uint8 on the inputs' side; for YUV
         (T, oh * 3 // 2, ow) of the output (or crop window) size oh x ow."""
         half = self.period // 2
@@ -1077,8 +1099,16 @@ class VideoStabilizer:
                 raise ValueError("run_video: smooth > 0 needs the whole clip (a shard cannot see the scene's path)")
             if self.borders in ("keep", "mosaic"):
                 raise ValueError("run_video: smooth > 0 warps in a second pass, which borders=\"%s\" does not have yet" % self.borders)
+        wob = PF._check_wobble(self.wobble, "run_video", zero_ok=True)   # (the attribute can be set after construction)
+        self.wobble_removed = self.wobble_unfit = None
+        if wob > 0.0:
+            if halo_left or halo_right:
+                raise ValueError("run_video: wobble > 0 needs the whole clip (a shard cannot see its neighbours' fields)")
+            if self.borders in ("keep", "mosaic"):
+                raise ValueError("run_video: wobble > 0 warps in a second pass, which borders=\"%s\" does not have yet" % self.borders)
+            _check_lattice(h, w, "wobble > 0")
         lattice = h >= 300 and w >= 600   # the homography fit's
-        two_pass = auto or zmode in ("auto", "adaptive") or smoothing   # pass 1: fields and bounds; the host's decision; pass 2: the warp
+        two_pass = auto or zmode in ("auto", "adaptive") or smoothing or wob > 0.0   # pass 1: fields and bounds; the host's decision; pass 2: the warp
         detect = isinstance(scene_cuts, str)
         if detect and scene_cuts != "auto":
             raise ValueError("scene_cuts must be None, \"auto\" or a sorted sequence of frame indices, got %r" % (scene_cuts,))
@@ -1261,7 +1291,8 @@ class VideoStabilizer:
                 with torch.cuda.stream(lane):
                     if two_pass:   # pass 1: fields and per-frame bounds only (no halos here: core frames = output positions)
                         self._fields(gray_all[cs - hl:ce + hr], hl, hr, fields[cs:ce], sc)
-                        if not smoothing or rigid:   # (smoothing fits the fields it composes, below; the blend needs the raw fit now)
+                        if not smoothing or rigid or wob > 0.0:   # (smoothing fits the fields it composes, below; the blend and the wobble
+                            #                                         filter need the raw fit)
                             _field_homography(fields[cs:ce], h, w, hom[cs:ce], bounds[cs:ce])
                         if rigid:   # the kept fields, in place; the bounds stay the raw fit's
                             PF._field_rigid(fields[cs:ce], hom[cs:ce], (h, w), self.rigidity, fields[cs:ce], rres[cs:ce], runf[cs:ce])
@@ -1298,7 +1329,11 @@ class VideoStabilizer:
             self.rigid_residual, self.rigid_unfit = rres, runf
         if zmode is not None:
             self.zoom_windows, self.zoom_uncovered = [zwin] * T if zmode == "fixed" else None, zunc
-        if smoothing:   # every lane has joined the caller's stream: the kept fields (after rigidity) are complete
+        if wob > 0.0:   # every lane has joined the caller's stream: the kept fields (after rigidity) are complete, and so is the cut list
+            fields, self.wobble_removed, self.wobble_unfit = PF.wobble_fields(fields, hom, (h, w), wob, scene_cuts=cuts or None, return_stats=True)
+            if not smoothing:   # bounds, crop and zoom decisions and the report describe the field that warps (smoothing fits what it composes)
+                _field_homography(fields, h, w, hom, bounds)
+        if smoothing:   # ... and it measures the filtered fields
             seen = PF.grid_sample(gray_all.unsqueeze(1), fields, align_corners=self.align_corners).squeeze(1)   # the planes as the fields warp them
             self.smooth_motion, self.smooth_inliers = global_motion(seen, pixel_scale=(w / 256.0, h / 256.0))
             del seen
