@@ -52,6 +52,7 @@
  *   pws_field_wobble              the warp fields' non-rigid part low-passed along time: wobble suppression (no counterpart in the reference)
  *   pws_motion_fit_scaled / pws_path_smooth / pws_field_compose  path smoothing: the measured camera path, low-passed, folded into the warp fields (no counterpart in the reference)
  *   pws_shutter_rates / pws_field_compose_rows  rolling-shutter correction: per-frame camera rates, and the composition with a correction per row (no counterpart in the reference)
+ *   pws_path_levels / pws_field_reach / pws_path_limit  crop-bounded smoothing: per frame the share of its correction that keeps a window covered (no counterpart in the reference)
  *   pws_pack_* / pws_netg_pack_weights   state_dict (OIHW / IOHW) -> kernel layout; main_new.py:60,471
  *
  * Layouts.  Frames / images: NCHW fp32 as in the reference.  Warp fields: N,H,W,2 fp32 (x then y,
@@ -761,6 +762,56 @@ int pws_shutter_rates(const double *motion, int n, double *rates, pws_stream_t s
  * and launches nothing.  One launch (and a 4 n byte clear of `uncovered`). */
 int pws_field_compose_rows(const float *field, int n, int fh, int fw, const double *d, const double *rates, double r, float *out, int h0, int w0,
                            int align_corners, int margin, int *uncovered, pws_stream_t stream);
+
+/* Crop-bounded smoothing, step 1 (csrc/path_limit.hip; no counterpart in the reference): the corrections of n frames scaled back to
+ * levels + 1 shares of themselves.  All fp64, in DEVICE memory, no synchronisation.
+ * d:     (n, 6) = D of frame t, row-major 2 x 3, as pws_path_smooth writes it: a SIMILARITY (d4 == d0, d1 == -d3).  Only d0, d3, d2, d5 are
+ *   read for the levels in between; any other matrix is replaced there by the similarity those four entries give.
+ * table: (n, levels+1, 6); table[t, l] = D_t(l / levels).  For a row whose six entries are finite, with ls = log(hypot(d0, d3)) and
+ *   phi = atan2(d3, d0), D(lam) has the linear part exp(lam ls) Rot(lam phi) and the translation lam (d2, d5):
+ *   s = exp(lam * ls), c = cos(lam * phi), sn = sin(lam * phi);  D(lam) = (s c, 0 - s sn, lam d2, s sn, s c, lam d5),
+ *   every product and sum rounded once.  Level 0 is exactly (1, 0, 0, 0, 1, 0); level `levels` is the row of d verbatim.  A row with an entry
+ *   that is not finite is copied to every level, level 0 included (pws_field_compose keeps such frames' nodes).
+ * Nothing is summed across threads: the same bits on every run.  n == 0 returns PWS_OK and launches nothing.  PWS_EINVAL: n < 0 or above
+ * 2^24, levels outside 1 .. 64, a NULL pointer, a pointer that is not 8-byte aligned.  d and table must not overlap.  One launch. */
+int pws_path_levels(const double *d, int n, int levels, double *table, pws_stream_t stream);
+
+/* Crop-bounded smoothing, step 2 (csrc/field_reach.hip; no counterpart in the reference): per frame and level, how many nodes of a
+ * rectangle of the lattice would sample outside the source if the field were composed with that level's correction.
+ * field[n,fh,fw,2] fp32; table[n,levels+1,6] fp64 as pws_path_levels writes it (any finite or non-finite 2 x 3 rows are accepted);
+ * counts[n,levels+1] int32; all in DEVICE memory.  counts[t, l] = the number of nodes (i, j) with i0 <= i <= i1 and j0 <= j <= j1 for
+ * which the value that pws_field_compose would write at that node of frame t for D = table[t, l] -- with rates != NULL and r != 0: the
+ * value that pws_field_compose_rows would write, rates[n,2,4] and r as there -- is uncovered by pws_field_zoom's rule: the warps' fp32
+ * un-normalisation with `align_corners`, margin <= ix <= w0-1-margin and margin <= iy <= h0-1-margin, NaN not covered.  The value is
+ * computed by the function that pws_field_compose's kernel calls (csrc/compose_node.h) -- the fp64 position, the single rounding to fp32,
+ * the cell clamp, the unclamped lx / ly, the fma chain, the linear continuation, the rule for positions that are not finite, the copy of
+ * an identity level -- and is never stored.  levels == 0 with a one-entry table counts one correction per frame.
+ * counts is cleared by the call; the integer counts are summed per workgroup and added with integer atomics: the same on every run.  The
+ * cell is bounded as a float before it becomes an integer and the rectangle is checked against the lattice: no table, rectangle or
+ * field value can make the kernel read outside field[t].
+ * Any fh, fw >= 2; n == 0 returns PWS_OK and launches nothing.  PWS_EINVAL: NULL field / table / counts, fh or fw < 2, h0 or w0 < 2,
+ * margin < 0, levels outside 0 .. 64, r outside [-1, 1] (NaN included), a rectangle that is empty (i1 < i0 or j1 < j0) or leaves the
+ * lattice (i0 < 0, i1 > fh-1, j0 < 0, j1 > fw-1), field / table / rates not 8-byte aligned, counts not 4-byte aligned.  One launch and a
+ * 4 n (levels+1) byte clear of `counts`. */
+int pws_field_reach(const float *field, int n, int fh, int fw, const double *table, int levels, const double *rates, double r, int i0, int i1,
+                    int j0, int j1, int h0, int w0, int align_corners, int margin, int *counts, pws_stream_t stream);
+
+/* Crop-bounded smoothing, step 3 (csrc/path_limit.hip; no counterpart in the reference): from pws_field_reach's counts the share of its
+ * correction that each frame of ONE scene of n frames can take, eased over time, and the corrections scaled to it.  DEVICE memory, no
+ * synchronisation.  d (n, 6) fp64 and counts (n, levels+1) int32 as above.
+ * need:     (n) int32; need[t] = the largest l such that counts[t, l'] == 0 for every l' <= l (the prefix rule: every smaller level is
+ *   feasible too), -1 if counts[t, 0] > 0 (the field alone does not cover the rectangle).  A row of d that is not finite: need[t] = levels.
+ * strength: (n) fp64; with s[t] = max(need[t], 0) / levels, the largest sequence with strength[t] <= s[t] and |strength[t] -
+ *   strength[t-1]| <= relax: a forward sweep strength[t] = min(s[t], strength[t-1] + relax), then the same sweep backward.
+ * d_out:    (n, 6) fp64; d[t] verbatim when strength[t] == 1.0, otherwise D_t(strength[t]) by pws_path_levels' formulas (exactly the
+ *   identity at 0; a row that is not finite is copied).
+ * strength[t] lies between grid levels after the sweeps, where the counts say nothing: count again with pws_field_reach(levels = 0).
+ * Strengths never relax across a scene cut: call once per scene.  One fixed order: the same bits on every run.  n == 0 returns PWS_OK
+ * and launches nothing.  PWS_EINVAL: n < 0 or above 2^24, levels outside 1 .. 64, relax outside (0, 1] (NaN included), a NULL pointer, d /
+ * strength / d_out not 8-byte aligned, counts / need not 4-byte aligned.  d_out must not overlap d.  One launch of one workgroup (the
+ * sweeps are sequential). */
+int pws_path_limit(const double *d, const int *counts, int n, int levels, double relax, int *need, double *strength, double *d_out,
+                   pws_stream_t stream);
 
 /* Adam (no weight decay / amsgrad) on a flat fp32 buffer, in place; step counts from 1. */
 int pws_adam_step(float *p, const float *g, float *m, float *v, size_t count, float lr, float beta1,

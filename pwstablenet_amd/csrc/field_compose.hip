@@ -17,28 +17,17 @@
 // Rolling shutter (pws_field_compose_rows, functional.compose_fields(rates=, rolling_shutter=)): the same kernel, instantiated with a
 // row-dependent step between D and the lattice -- the camera's velocity field times the time offset of the row that D q lies on, taken out
 // of D q: a dozen fp64 FMAs per node more, no transcendental, the same loads and stores.  r = 0 launches the affine instantiation.
-#include "common.h"
-#include "warp_common.h"
+#include "compose_node.h"
 
 namespace pws {
 namespace {
 
 constexpr int FC_PER_LANE = 2, FC_CHUNK = kWave * FC_PER_LANE, FC_ROWS = 4;   // nodes per lane / per wave, rows (waves) per workgroup
 
-typedef float F32x4a8 __attribute__((ext_vector_type(4), aligned(8)));   // 16 bytes at the field's 8-byte alignment (rows of odd width)
+typedef ComposeGeo Geo;
+typedef ComposeRows Rows;
 
-struct Geo {   // host-computed, fp64: the node's frame pixel, the frame centre, the lattice coordinate of a frame pixel
-    double kx, ky, cx, cy, ikx, iky;
-};
-
-struct Rows {   // ROWS: the frames' rates (n, 2, 4), the readout share r (never 0 here) and 1 / (h0 - 1)
-    const double *rates;
-    double r, ih;
-};
-
-// ROWS (pws_field_compose_rows): the rolling-shutter correction between D and the lattice.  p0 = D q lies on a row exposed delta = r
-// clamp(p0.y / (h0-1), -1/2, 1/2) of a frame interval away from the centre row's instant; the camera's velocity field there -- the frame's
-// forward rates for delta >= 0, its backward rates otherwise: 8 workgroup-uniform loads -- times delta is taken out of p0, in fp64.
+// The node itself -- position, rounding, cell, interpolation, the ROWS step -- is compose_node.h's compose_node, shared with field_reach.hip.
 template <bool ROWS>
 __global__ void __launch_bounds__(kWave *FC_ROWS) field_compose_kernel(const float *__restrict__ field, const double *__restrict__ d,
                                                                         float *__restrict__ out, int fh, int fw, unsigned nrg, Geo geo, int h0,
@@ -50,15 +39,9 @@ __global__ void __launch_bounds__(kWave *FC_ROWS) field_compose_kernel(const flo
     int unc = 0;
     if (i < fh && j0 < fw) {
         const double *dt = d + (size_t)t * 6;
-        const double d0 = dt[0], d1 = dt[1], d2 = dt[2], d3 = dt[3], d4 = dt[4], d5 = dt[5];
-        bool same = d0 == 1.0 && d1 == 0.0 && d2 == 0.0 && d3 == 0.0 && d4 == 1.0 && d5 == 0.0;   // (uniform over the workgroup)
         double v[2][4] = {};
-        if constexpr (ROWS) {
-            bool still = true;   // a frame whose camera stands still has nothing to take out: it is copied like any other identity frame
-#pragma unroll
-            for (int c = 0; c < 8; ++c) v[c >> 2][c & 3] = rows.rates[(size_t)t * 8 + c], still = still && v[c >> 2][c & 3] == 0.0;
-            same = same && still;
-        }
+        const bool still = compose_still<ROWS>(ROWS ? rows.rates + (size_t)t * 8 : nullptr, v);
+        const bool same = compose_identity(dt) && still;   // (uniform over the workgroup)
         const double y = (double)i * geo.ky - geo.cy;
         const float *ft = field + (size_t)t * fh * fw * 2;
         const bool ac = align_corners != 0;
@@ -67,38 +50,8 @@ __global__ void __launch_bounds__(kWave *FC_ROWS) field_compose_kernel(const flo
 #pragma unroll
         for (int q = 0; q < FC_PER_LANE; ++q) {
             const int j = min(j0 + q, fw - 1);   // (a row of odd width: the last lane's second node repeats its first, and is dropped)
-            const double x = (double)j * geo.kx - geo.cx;
-            float sx, sy;
-            if constexpr (ROWS) {
-                const double px = d0 * x + d1 * y + d2, py = d3 * x + d4 * y + d5;   // p0 = D q: the affine kernel's, and its bits at zero rates
-                const double delta = rows.r * fmin(fmax(py * rows.ih, -0.5), 0.5);
-                const bool fwd = delta >= 0.0;
-                const double ld = fwd ? v[0][0] : v[1][0], wd = fwd ? v[0][1] : v[1][1], xd = fwd ? v[0][2] : v[1][2], yd = fwd ? v[0][3] : v[1][3];
-                const double vx = (ld * px - wd * py) + xd, vy = (ld * py + wd * px) + yd;
-                sx = (float)(((px - delta * vx) + geo.cx) * geo.ikx), sy = (float)(((py - delta * vy) + geo.cy) * geo.iky);
-            } else {
-                sx = (float)(((d0 * x + d1 * y + d2) + geo.cx) * geo.ikx), sy = (float)(((d3 * x + d4 * y + d5) + geo.cy) * geo.iky);
-            }
-            const bool keep = same || !(isfinite(sx) && isfinite(sy));   // the node keeps F[i, j]: its own cell, picked below
-            // the cell, bounded as a FLOAT before it becomes an integer: in [0, fw-2] x [0, fh-2] whatever d holds
-            const float fx = keep ? (float)min(j, fw - 2) : fminf(fmaxf(floorf(sx), 0.f), (float)(fw - 2));
-            const float fy = keep ? (float)min(i, fh - 2) : fminf(fmaxf(floorf(sy), 0.f), (float)(fh - 2));
-            const int x0 = (int)fx, y0 = (int)fy;
-            const float *f0 = ft + ((size_t)y0 * fw + x0) * 2;
-            const F32x4a8 r0 = *reinterpret_cast<const F32x4a8 *>(f0), r1 = *reinterpret_cast<const F32x4a8 *>(f0 + (size_t)fw * 2);
-            if (keep) {
-                const F32x4a8 r = i == y0 ? r0 : r1;
-                g[q][0] = j == x0 ? r.x : r.z, g[q][1] = j == x0 ? r.y : r.w;
-            } else {
-                const float lx = sx - fx, hx = 1.f - lx, ly = sy - fy, hy = 1.f - ly;   // (not clamped: linear continuation outside the lattice)
-                g[q][0] = field_lerp(hy, ly, hx, lx, r0.x, r0.z, r1.x, r1.z);
-                g[q][1] = field_lerp(hy, ly, hx, lx, r0.y, r0.w, r1.y, r1.w);
-            }
-            if (uncovered && j0 + q < fw) {
-                const float ix = unnormalize(g[q][0], w0, ac), iy = unnormalize(g[q][1], h0, ac);
-                const bool covered = ix >= m && ix <= xhi && iy >= m && iy <= yhi;   // (false for NaN)
-                unc += covered ? 0 : 1;
-            }
+            compose_node<ROWS>(ft, fh, fw, i, j, y, dt, same, geo, rows, v, g[q][0], g[q][1]);
+            if (uncovered && j0 + q < fw) unc += compose_covered(g[q][0], g[q][1], h0, w0, ac, m, xhi, yhi) ? 0 : 1;
         }
         float *o = out + (((size_t)t * fh + i) * fw + j0) * 2;
         if (j0 + 1 < fw) *reinterpret_cast<F32x4a8 *>(o) = F32x4a8{g[0][0], g[0][1], g[1][0], g[1][1]};
@@ -143,10 +96,7 @@ int compose(const char *who, const float *field, int n, int fh, int fw, const do
             return PWS_EHIP;
         }
     }
-    Geo geo;
-    geo.kx = (double)(w0 - 1) / (double)(fw - 1), geo.ky = (double)(h0 - 1) / (double)(fh - 1);
-    geo.cx = 0.5 * (double)(w0 - 1), geo.cy = 0.5 * (double)(h0 - 1);
-    geo.ikx = (double)(fw - 1) / (double)(w0 - 1), geo.iky = (double)(fh - 1) / (double)(h0 - 1);
+    const Geo geo = compose_geo(fh, fw, h0, w0);
     const dim3 grid((unsigned)n * nrg, chunks, 1), block(kWave * FC_ROWS);
     if (rows) {
         hipLaunchKernelGGL(field_compose_kernel<true>, grid, block, 0, as_stream(stream), field, d, out, fh, fw, nrg, geo, h0, w0, align_corners,

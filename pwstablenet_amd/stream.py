@@ -358,6 +358,130 @@ def shutter_rates(motion, scene_cuts=None):
     return rates
 
 
+def _check_limit(max_crop, levels, relax, sigma, what):
+    """(max_crop or None, levels, relax) checked: max_crop in [0, 0.5] (NaN is a ValueError), levels an int in 1 .. 64, relax in (0, 1] --
+    None: 1 / ceil(3 sigma), the strength recovers from 0 to 1 over the Gaussian's own reach (1.0 at sigma 0, where nothing is limited)."""
+    if max_crop is not None:
+        try:
+            c = float(max_crop)
+        except (TypeError, ValueError):
+            raise ValueError("%s: max_crop must be None or a share of the frame in [0, 0.5], got %r" % (what, max_crop)) from None
+        if not 0.0 <= c <= 0.5:   # (False for NaN)
+            raise ValueError("%s: max_crop must lie in [0, 0.5], got %r" % (what, max_crop))
+        max_crop = c
+    try:
+        lv = int(levels)
+        if lv != levels:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError("%s: limit_levels must be an integer in 1 .. 64, got %r" % (what, levels)) from None
+    if not 1 <= lv <= 64:
+        raise ValueError("%s: limit_levels must lie in 1 .. 64, got %r" % (what, levels))
+    if relax is None:
+        rx = 1.0 / max(1, int(math.ceil(3.0 * float(sigma))))
+    else:
+        try:
+            rx = float(relax)
+        except (TypeError, ValueError):
+            raise ValueError("%s: limit_relax must be None or a number in (0, 1], got %r" % (what, relax)) from None
+        if not 0.0 < rx <= 1.0:   # (False for NaN)
+            raise ValueError("%s: limit_relax must lie in (0, 1], got %r" % (what, relax))
+    return max_crop, lv, rx
+
+
+def limit_rectangle(fraction, frame_hw, field_hw):
+    """The nodes (i0, i1, j0, j1), inclusive, of every field cell that the centred window of ``fraction`` of the frame touches: with the
+    window's (Ax, Bx, Ay, By) from ``functional.zoom_coefficients`` -- the float32 values that a later zoom to that window samples the field
+    with -- j0 = floor(Ax), j1 = ceil(fmaf(Bx, fw - 1, Ax)), i0 and i1 alike, clamped to the lattice.  (The float64 sum Bx (fw-1) + Ax of
+    float32 operands is exact at these magnitudes, so its one rounding to float32 is fmaf's.)"""
+    import numpy as np
+    h, w = int(frame_hw[0]), int(frame_hw[1])
+    fh, fw = int(field_hw[0]), int(field_hw[1])
+    win = PF._zoom_windows(_centred_window(float(fraction), h, w), 1, (h, w), "limit_path")
+    ax, bx, ay, by = (float(v) for v in PF.zoom_coefficients(win, (h, w), (fh, fw))[0].tolist())
+
+    def span(a, b, n):
+        lo = int(math.floor(a))
+        hi = int(math.ceil(float(np.float32(b * (n - 1) + a))))
+        return min(max(lo, 0), n - 1), min(max(hi, 0), n - 1)
+    i0, i1 = span(ay, by, fh)
+    j0, j1 = span(ax, bx, fw)
+    return i0, i1, j0, j1
+
+
+def limit_path(d, fields, frame_hw, fraction, levels=16, relax=1.0, scene_cuts=None, rates=None, rolling_shutter=0.0, align_corners=False,
+               mode="bilinear"):
+    """Crop-bounded smoothing, the step on its own (csrc/path_limit.hip, csrc/field_reach.hip; include/pwstable.h pws_path_levels,
+    pws_field_reach and pws_path_limit have the definitions): per frame, as much of the smoothing correction as keeps a window of the
+    output covered by the source, eased over time.  ``d`` (T, 6) float64 on the device as ``smooth_path`` returns it (similarities);
+    ``fields`` (T, fh, fw, 2) float32 on the device, the fields that ``functional.compose_fields`` will fold d into, read in place;
+    ``fraction`` = k in (0, 1]: the protected window is the centred window of that fraction of the ``frame_hw`` = (H0, W0) frame
+    (``_centred_window``: the one ``run_video(zoom=k)`` shows).
+    D_t(lam) is the correction scaled back along (log scale, angle, translation): exp(lam ls) Rot(lam phi), lam (d2, d5).  For lam = l /
+    levels, l = 0 .. levels, ``pws_field_reach`` counts the nodes of ``limit_rectangle`` -- every node of every field cell the window
+    touches -- whose composed value would sample outside the source (``compose_fields``' own node function and ``zoom_fields``' coverage
+    rule with ``align_corners`` and ``mode``; with ``rates`` and ``rolling_shutter`` the row-dependent composition).  need[t] is the
+    largest level up to which every count is zero (-1: the field alone leaves the window uncovered), the raw strength max(need, 0) /
+    levels; inside each scene (``scene_cuts`` as for ``smooth_path``) the strength is the largest sequence below it that changes by at
+    most ``relax`` per frame (``zoom_schedule``'s two sweeps; never across a cut); d_limited[t] is d[t] verbatim at strength 1, else
+    D_t(strength[t]).  The source rectangle is convex and the warps interpolate the field linearly between nodes, so zero uncovered
+    nodes in the rectangle means that zoom=k shows no wedge.  After the sweeps a strength lies between grid levels, where feasibility is
+    not proven: the last value returned counts the rectangle's uncovered nodes under d_limited itself.
+    Returns (d_limited (T, 6) float64, strength (T,) float64, need (T,) int32, counts (T,) int32), on the device, no synchronisation;
+    3 + (number of scenes) launches and two small clears.  Integer counts and one fixed order: the same bits on every run.
+    ValueError: tensors other than these, fraction outside (0, 1], levels outside 1 .. 64, relax outside (0, 1], rolling_shutter outside
+    [-1, 1], an unknown mode, bad cuts, a frame below 2 x 2 pixels."""
+    if mode not in PF.INTERPOLATIONS:
+        raise ValueError("mode must be one of %s, got %r" % (PF.INTERPOLATIONS, mode))
+    r = PF._check_rolling_shutter(rolling_shutter, "limit_path")
+    rows = r != 0.0 and rates is not None
+    for name, t, dtype in (("d", d, torch.float64), ("fields", fields, torch.float32)) + ((("rates", rates, torch.float64),) if rows else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
+            raise ValueError("limit_path: %s must be a %s tensor on the device" % (name, dtype))
+    if fields.dim() != 4 or fields.shape[3] != 2 or fields.shape[1] < 2 or fields.shape[2] < 2:
+        raise ValueError("limit_path: fields must be (T, fh, fw, 2) with fh, fw >= 2, got %s" % (tuple(fields.shape),))
+    T, fh, fw = fields.shape[:3]
+    if tuple(d.shape) != (T, 6):
+        raise ValueError("limit_path: d must be (%d, 6), got %s" % (T, tuple(d.shape)))
+    if rows and tuple(rates.shape) != (T, 2, 4):
+        raise ValueError("limit_path: rates must be (%d, 2, 4), got %s" % (T, tuple(rates.shape)))
+    h0, w0 = int(frame_hw[0]), int(frame_hw[1])
+    if h0 < 2 or w0 < 2:
+        raise ValueError("limit_path: the frame must be at least 2 x 2 pixels, got %d x %d" % (w0, h0))
+    try:
+        k = float(fraction)
+    except (TypeError, ValueError):
+        raise ValueError("limit_path: fraction must be a number in (0, 1], got %r" % (fraction,)) from None
+    if not 0.0 < k <= 1.0:
+        raise ValueError("limit_path: fraction must lie in (0, 1], got %r" % (fraction,))
+    _, levels, relax = _check_limit(None, levels, relax, 0.0, "limit_path")
+    cuts = _check_cuts(scene_cuts, T, "limit_path") if scene_cuts is not None and len(scene_cuts) else []
+    d, fields = d.contiguous(), fields.contiguous()
+    rates = rates.contiguous() if rows else None
+    dev = d.device
+    d_out = torch.empty((T, 6), device=dev, dtype=torch.float64)
+    strength = torch.empty((T,), device=dev, dtype=torch.float64)
+    need = torch.empty((T,), device=dev, dtype=torch.int32)
+    left = torch.empty((T, 1), device=dev, dtype=torch.int32)
+    if T == 0:
+        return d_out, strength, need, left.reshape(0)
+    i0, i1, j0, j1 = limit_rectangle(k, (h0, w0), (fh, fw))
+    L, stream = A.lib(), A.current_stream()
+    table = torch.empty((T, levels + 1, 6), device=dev, dtype=torch.float64)
+    counts = torch.empty((T, levels + 1), device=dev, dtype=torch.int32)
+
+    def reach(tab, lv, out):
+        A.check(L.pws_field_reach(A.ptr(fields), T, fh, fw, A.ptr(tab), lv, A.ptr(rates), r if rows else 0.0, i0, i1, j0, j1, h0, w0,
+                                  PF._ac(align_corners), int(mode == "bicubic"), A.ptr(out), stream), "pws_field_reach")
+    A.check(L.pws_path_levels(A.ptr(d), T, levels, A.ptr(table), stream), "pws_path_levels")
+    reach(table, levels, counts)
+    for a, b in _scenes(T, cuts):
+        A.check(L.pws_path_limit(A.ptr(d[a:b]), A.ptr(counts[a:b]), b - a, levels, relax, A.ptr(need[a:b]), A.ptr(strength[a:b]),
+                                 A.ptr(d_out[a:b]), stream), "pws_path_limit")
+    reach(d_out, 0, left)   # (T, 6) is a (T, 1, 6) table
+    return d_out, strength, need, left.reshape(T)
+
+
 def _signal_score(v):
     """One signal's stability score over a scene of m frames; v[k] is the motion of pair k (v[0] is not read)."""
     import numpy as np
@@ -545,7 +669,8 @@ def _windows(gray_padded, start, count, period):
 
 class VideoStabilizer:
     def __init__(self, netG, batch=32, period=30, device=None, swap_rb=False, interpolation="bilinear", borders="black", rigidity=0.0,
-                 mosaic_radius=8, edge="pad", metrics=False, smooth=0.0, rolling_shutter=0.0, wobble=0.0):
+                 mosaic_radius=8, edge="pad", metrics=False, smooth=0.0, rolling_shutter=0.0, wobble=0.0, max_crop=None, limit_levels=16,
+                 limit_relax=None):
         self.net = netG
         # run_video low-passes the NON-RIGID part of the clip's fields along time: each field minus its fitted homography, under a Gaussian of
         # `wobble` frames, in (0, 5] (functional.wobble_fields).  The generator regresses every field from that frame's own window, and the
@@ -570,6 +695,18 @@ class VideoStabilizer:
             raise ValueError("VideoStabilizer: rolling_shutter=%r needs smooth > 0 (the correction uses the motion that smoothing measures and "
                              "its second pass)" % (rolling_shutter,))
         self.shutter_rates = None   # rolling_shutter != 0, of the last run_video, on the device: (T, 2, 4) float64, shutter_rates' rows
+        # the crop budget of smoothing: the share of the frame, per axis, that the viewer is prepared to lose, in [0, 0.5].  Each frame takes
+        # as much of its correction as keeps the centred window of the fraction 1 - max_crop covered by the source (limit_path: the share is
+        # searched on limit_levels + 1 grid levels, on the fields themselves) and the share changes by at most limit_relax per frame.
+        # limit_relax=None: 1 / ceil(3 smooth), the strength recovers from 0 to 1 over the Gaussian's own reach -- a judgement that no
+        # footage here can fit, like zoom_speed.  None: no launch, no allocation, every path as it was
+        self.max_crop, self.limit_levels, relax = _check_limit(max_crop, limit_levels, limit_relax, self.smooth, "VideoStabilizer")
+        self.limit_relax = None if limit_relax is None else relax   # (None is resolved against the call's smooth in run_video)
+        if self.max_crop is not None and self.smooth == 0.0:
+            raise ValueError("VideoStabilizer: max_crop=%r needs smooth > 0 (it bounds the correction that smoothing composes)" % (max_crop,))
+        self.limit_strength = self.limit_need = None          # max_crop, of the last run_video, on the device: (T,) float64 in [0, 1]; (T,) int32, the
+        self.limit_uncovered = None                           # raw level (-1: the field alone leaves the window uncovered); (T,) int32, the window's
+        self.smooth_correction_unlimited = None               # nodes still outside under the D that was composed; (T, 6), what smooth_path returned
         # run_video measures the clip it stabilises: the global motion of the input and of the output planes (global_motion), and from it
         # and the per-frame homographies the paper's three metrics (stability_report).  False: no launch, no allocation, every path as it was
         self.metrics = bool(metrics)
@@ -1008,6 +1145,21 @@ class VideoStabilizer:
         was validated on real footage.  Every pixel_format, interpolation, edge, crop, zoom, rigidity, smooth, in_flight and scene_cuts
         works as without it.  ValueError: halos, borders="keep" or "mosaic" (no second pass), a source below the fit's 600 x 300 lattice.
         ``run()`` does not take it.
+        VideoStabilizer(smooth=sigma, max_crop=c, limit_levels=16, limit_relax=None), c in [0, 0.5]: crop-bounded smoothing (vid.stab's
+        ``maxshift`` / ``maxangle``, OpenCV videostab's trim ratio, Warp Stabilizer's "crop less / smooth more").  c is the share of the
+        frame, per axis, that the viewer is prepared to lose: the centred window of the fraction 1 - c -- the one zoom=1 - c shows -- stays
+        covered by the source.  Between ``smooth_path`` (and ``shutter_rates``) and the composition, on the caller's stream, ``limit_path``
+        reads the kept fields in place (after rigidity and wobble), finds per frame the largest of limit_levels + 1 shares of the correction
+        under which no node of the window's cells samples outside the source -- ``compose_fields``' own node function, so it holds for
+        per-pixel fields and the rolling-shutter composition alike -- and eases the share by at most limit_relax per frame inside each
+        scene (None: 1 / ceil(3 sigma), a judgement that no footage here can fit, like zoom_speed; never across a cut).  What is composed,
+        refitted, cropped and zoomed is the limited correction.  Left on the device, no synchronisation, None at max_crop=None, which
+        takes no new path: ``self.limit_strength`` (T,) float64 in [0, 1], ``self.limit_need`` (T,) int32 (the raw level; -1: the field
+        alone does not cover the window), ``self.limit_uncovered`` (T,) int32 (the window's nodes that still sample outside under the
+        correction that was composed: the eased share lies between grid levels, where feasibility is not proven -- read it),
+        ``self.smooth_correction_unlimited`` (T, 6), what ``smooth_path`` returned; ``self.smooth_correction`` is then the limited D.  It
+        bounds the correction and nothing else -- not the generator's own field -- and works with every pixel_format, interpolation,
+        edge, crop, zoom, rigidity, wobble, rolling_shutter, in_flight, scene_cuts and metrics.  ValueError: max_crop without smooth > 0.
         Returns (T, H, W, 3) -- or (T, H/2, W/2, 3) / (T, height, width, 3), or the crop window of it -- uint8 on the inputs' side; for YUV
         (T, oh * 3 // 2, ow) of the output (or crop window) size oh x ow."""
         half = self.period // 2
@@ -1094,6 +1246,10 @@ class VideoStabilizer:
         self.shutter_rates = None
         if self.rolling_shutter != 0.0 and not smoothing:   # (the attributes can be set after construction)
             raise ValueError("run_video: rolling_shutter=%r needs smooth > 0" % (self.rolling_shutter,))
+        max_crop, limit_levels, limit_relax = _check_limit(self.max_crop, self.limit_levels, self.limit_relax, self.smooth, "run_video")
+        self.limit_strength = self.limit_need = self.limit_uncovered = self.smooth_correction_unlimited = None
+        if max_crop is not None and not smoothing:   # (the attributes can be set after construction)
+            raise ValueError("run_video: max_crop=%r needs smooth > 0" % (self.max_crop,))
         if smoothing:
             if halo_left or halo_right:
                 raise ValueError("run_video: smooth > 0 needs the whole clip (a shard cannot see the scene's path)")
@@ -1342,6 +1498,11 @@ class VideoStabilizer:
             rs = PF._check_rolling_shutter(self.rolling_shutter, "run_video")
             if rs != 0.0:   # the velocity at every frame, from the same measured motion and under the same cuts
                 self.shutter_rates = shutter_rates(self.smooth_motion, scene_cuts=cuts or None)
+            if max_crop is not None:   # the crop budget: every frame's share of its correction, decided on the kept fields, read in place
+                self.smooth_correction_unlimited = self.smooth_correction
+                self.smooth_correction, self.limit_strength, self.limit_need, self.limit_uncovered = limit_path(
+                    self.smooth_correction, fields, (h, w), 1.0 - max_crop, levels=limit_levels, relax=limit_relax, scene_cuts=cuts or None,
+                    rates=self.shutter_rates, rolling_shutter=rs, align_corners=self.align_corners, mode=self.interpolation)
             scratch = torch.empty((min(int(chunk), T),) + tuple(fields.shape[1:]), device=dev, dtype=torch.float32)
             for s in range(0, T, scratch.shape[0]):
                 e = min(T, s + scratch.shape[0])

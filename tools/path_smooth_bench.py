@@ -35,9 +35,10 @@ from pwstablenet_amd import hipabi as A  # noqa: E402
 from pwstablenet_amd import synth  # noqa: E402
 
 
-def textured_clip(T, H, W, seed=3, sigma=3.0):
+def textured_clip(T, H, W, seed=3, sigma=3.0, jolt=None):
     """A shaky textured clip, BGR and NV12: twelve sinusoids of 14 to 90 pixels under a pan of (1.0, 0.4) pixel a frame plus Gaussian jitter of
-    sigma pixels (the GPU tests' texture: busy enough for global_motion's activity threshold, which synth.smooth_frames_u8 is not)."""
+    sigma pixels (the GPU tests' texture: busy enough for global_motion's activity threshold, which synth.smooth_frames_u8 is not).
+    jolt = (frame, pixels): that one frame is displaced by so many pixels in x on top (tools/path_limit_bench.py); the draws are unchanged."""
     rs = np.random.RandomState(seed)
     k = 12
     wl, ang, ph = rs.uniform(14.0, 90.0, k), rs.uniform(0, 2 * np.pi, k), rs.uniform(0, 2 * np.pi, k)
@@ -47,6 +48,8 @@ def textured_clip(T, H, W, seed=3, sigma=3.0):
     sa, ca = np.sin(a), np.cos(a)
     t = np.arange(T)
     tx, ty = 1.0 * t + rs.normal(0, sigma, T), 0.4 * t + rs.normal(0, sigma, T)
+    if jolt is not None:
+        tx[int(jolt[0])] += float(jolt[1])
     phi = kx[None] * tx[:, None] + ky[None] * ty[:, None]
     v = np.cos(phi).astype(np.float32) @ sa + np.sin(phi).astype(np.float32) @ ca
     base = np.clip(np.rint(127.5 + 127.5 * 0.13 * v), 0, 255).astype(np.uint8).reshape(T, H, W)
