@@ -52,6 +52,7 @@
  *   pws_field_wobble              the warp fields' non-rigid part low-passed along time: wobble suppression (no counterpart in the reference)
  *   pws_motion_fit_scaled / pws_path_smooth / pws_field_compose  path smoothing: the measured camera path, low-passed, folded into the warp fields (no counterpart in the reference)
  *   pws_shutter_rates / pws_field_compose_rows  rolling-shutter correction: per-frame camera rates, and the composition with a correction per row (no counterpart in the reference)
+ *   pws_shutter_terms / pws_shutter_estimate  rolling-shutter estimate: the readout share r from the block vectors smoothing has measured (no counterpart in the reference)
  *   pws_path_levels / pws_field_reach / pws_path_limit  crop-bounded smoothing: per frame the share of its correction that keeps a window covered (no counterpart in the reference)
  *   pws_pack_* / pws_netg_pack_weights   state_dict (OIHW / IOHW) -> kernel layout; main_new.py:60,471
  *
@@ -762,6 +763,40 @@ int pws_shutter_rates(const double *motion, int n, double *rates, pws_stream_t s
  * and launches nothing.  One launch (and a 4 n byte clear of `uncovered`). */
 int pws_field_compose_rows(const float *field, int n, int fh, int fw, const double *d, const double *rates, double r, float *out, int h0, int w0,
                            int align_corners, int margin, int *uncovered, pws_stream_t stream);
+
+/* Rolling-shutter estimate, step 1 (csrc/shutter_estimate.hip; no counterpart in the reference): per pair of ONE scene of n frames what
+ * the pair's block vectors say about r, the share of the frame interval that the readout takes from the top row to the bottom row (signed).
+ * All in DEVICE memory, no synchronisation.
+ * mv, sad, activity: the scene's rows as pws_block_motion wrote them for (n, h, w) planes and this radius.  motion (n, 4) as
+ *   pws_motion_fit[_scaled] returned it for these blocks with this min_activity and (sx, sy); rates (n, 2, 4) as pws_shutter_rates returns
+ *   it for this scene.  (sx, sy): the pixel scale of the fit, (1, 1) for pws_motion_fit.  h0: the frame height in motion's pixels (h at
+ *   scale 1, the frame's own height for the scaled fit).
+ * Pair k is USABLE when 2 <= k <= n - 2 and rows k-1, k, k+1 of motion are finite: both velocity differences below then come from real
+ *   pairs, never from a scene end's duplicated rate.  Every other pair writes a zero row.
+ * Blocks: those that pass pws_motion_fit's validity rule (one shared device function, csrc/motion_blocks.h), each with its centre p = (x, y)
+ *   relative to the centre and its sub-pixel vector v, both times (sx, sy).  Fewer than 8: a zero row.  With f = (motion[k][0] - 1,
+ *   motion[k][1..3]) and res2 pws_motion_fit's squared residual, the KEPT blocks are those with res2 <= max(sx sy, 4 * the mean of res2 over
+ *   the valid blocks): the rule of the fit's own rounds.  Fewer than 8 kept blocks, or centres that span no area: a zero row.
+ * Per kept block: c = clamp(y / (h0 - 1), -1/2, 1/2); (dl, dw, dx, dy) = rates[k][s] - rates[k-1][s] with s = 0 where c >= 0, else 1;
+ *   z = c (dl p + dw (-y, x) + (dx, dy)), as (c * ((dl x - dw y) + dx), c * ((dl y + dw x) + dy)).
+ *   e = v - (the least-squares similarity fitted to v over the kept blocks), z_perp = z - (the one fitted to z): pws_motion_fit's closed
+ *   form, a block's residual taken as u - ((a1 x - b y) + tx), u' - ((b x + a1 y) + ty).
+ * terms: (n, 4) fp64; terms[k] = (sum e . z_perp, sum z_perp . z_perp, sum e . e, the number of kept blocks).
+ * Every product and sum is rounded once; the sums are pws_motion_fit's: a lane's blocks in index order, then a fixed butterfly.  The same
+ * bits on every run; no atomics.  n == 0 returns PWS_OK and launches nothing; n < 4 writes zero rows.  PWS_EINVAL: as pws_motion_fit_scaled;
+ * h0 outside (1, 1e9] (NaN included); n above 2^24; motion, rates or terms not 8-byte aligned.  One launch, one workgroup per pair. */
+int pws_shutter_terms(const short *mv, const int *sad, const int *activity, const double *motion, const double *rates, int n, int h, int w,
+                      int radius, int min_activity, double sx, double sy, double h0, double *terms, pws_stream_t stream);
+
+/* Rolling-shutter estimate, step 2 (csrc/shutter_estimate.hip): the clip's estimate from the terms of all its pairs (every scene's rows, n in
+ * all).  N, D, E, cnt = the four column sums over the rows in index order; m = the rows whose count is positive.
+ * out4: (4) fp64 = (r_hat, se, D, cnt), r_hat = N / D, se = sqrt(max(0, E - r_hat N) / (2 cnt - 4 m - 1) / D); (NaN, +inf, D, cnt) when D or
+ *   the degrees of freedom 2 cnt - 4 m - 1 are not positive (n == 0 included).
+ * se is the least-squares standard error under independent, unbiased block errors.  The real errors -- a first-order model, correlated
+ * sub-pixel bias -- are systematic and several times larger: se tells a clip with information from one without (a tripod, a steady pan);
+ * it is NOT an error bar.  PWS_EINVAL: n < 0 or above 2^24, NULL out4 (terms with n > 0), a pointer that is not 8-byte aligned.  One launch
+ * of one workgroup. */
+int pws_shutter_estimate(const double *terms, int n, double *out4, pws_stream_t stream);
 
 /* Crop-bounded smoothing, step 1 (csrc/path_limit.hip; no counterpart in the reference): the corrections of n frames scaled back to
  * levels + 1 shares of themselves.  All fp64, in DEVICE memory, no synchronisation.

@@ -270,6 +270,8 @@ SIGNATURES = {
     "pws_field_compose": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "pws_shutter_rates": (_I, [_P, _I, _P, _P]),
     "pws_field_compose_rows": (_I, [_P, _I, _I, _I, _P, _P, _D, _P, _I, _I, _I, _I, _P, _P]),
+    "pws_shutter_terms": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _D, _D, _P, _P]),
+    "pws_shutter_estimate": (_I, [_P, _I, _P, _P]),
     "pws_path_levels": (_I, [_P, _I, _I, _P, _P]),
     "pws_field_reach": (_I, [_P, _I, _I, _I, _P, _I, _P, _D, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "pws_path_limit": (_I, [_P, _P, _I, _I, _D, _P, _P, _P, _P]),

@@ -269,6 +269,17 @@ def block_motion(planes, radius=16):
     return mv, sad, act
 
 
+def _check_pixel_scale(pixel_scale, what):
+    """``pixel_scale`` as (sx, sy), two floats in (0, 1e6]; ValueError otherwise (NaN included)."""
+    try:
+        sx, sy = (float(v) for v in pixel_scale)
+    except (TypeError, ValueError):
+        raise ValueError("%s: pixel_scale must be None or (sx, sy), got %r" % (what, pixel_scale)) from None
+    if not (0.0 < sx <= 1e6 and 0.0 < sy <= 1e6):
+        raise ValueError("%s: pixel_scale must be two positive finite numbers, got %r" % (what, pixel_scale))
+    return sx, sy
+
+
 def global_motion(planes, radius=16, min_activity=2000, return_blocks=False, pixel_scale=None):
     """The similarity between consecutive window planes: ``block_motion``, then per pair the least-squares fit, in fp64, of ``p' = [[a, -b],
     [b, a]] p + (tx, ty)`` -- a block centre p of frame t, relative to the plane centre, lies at p' in frame t-1 -- to the blocks' sub-pixel
@@ -286,12 +297,7 @@ def global_motion(planes, radius=16, min_activity=2000, return_blocks=False, pix
     ValueError."""
     t, h, w, radius = _motion_planes(planes, radius, "global_motion")
     if pixel_scale is not None:
-        try:
-            sx, sy = (float(v) for v in pixel_scale)
-        except (TypeError, ValueError):
-            raise ValueError("global_motion: pixel_scale must be None or (sx, sy), got %r" % (pixel_scale,)) from None
-        if not (0.0 < sx <= 1e6 and 0.0 < sy <= 1e6):
-            raise ValueError("global_motion: pixel_scale must be two positive finite numbers, got %r" % (pixel_scale,))
+        sx, sy = _check_pixel_scale(pixel_scale, "global_motion")
     mv, sad, act = block_motion(planes, radius)
     motion = torch.empty((t, 4), device=planes.device, dtype=torch.float64)
     inliers = torch.empty((t,), device=planes.device, dtype=torch.int32)
@@ -356,6 +362,83 @@ def shutter_rates(motion, scene_cuts=None):
     for a, b in (_scenes(T, cuts) if T else []):
         A.check(A.lib().pws_shutter_rates(A.ptr(motion[a:b]), b - a, A.ptr(rates[a:b]), A.current_stream()), "pws_shutter_rates")
     return rates
+
+
+def estimate_rolling_shutter(motion, mv, sad, activity, plane_hw, radius=16, min_activity=2000, pixel_scale=None, scene_cuts=None,
+                             frame_height=None, return_terms=False):
+    """The rolling-shutter share r of a clip, estimated from what ``global_motion(..., return_blocks=True)`` measured on it
+    (csrc/shutter_estimate.hip; include/pwstable.h pws_shutter_terms / pws_shutter_estimate have the definition): ``motion`` (T, 4) float64
+    and ``mv``, ``sad``, ``activity`` as that call returned them for (T, h, w) planes, ``plane_hw`` = (h, w), and the ``radius``,
+    ``min_activity`` and ``pixel_scale`` that the call was given.  ``frame_height``: the frame's height in ``motion``'s pixels -- None: h
+    times the scale's sy, which is h for the plane-pixel fit.  A rolling shutter leaves in the block vectors a displacement that no
+    similarity absorbs: the block's share c of the readout (its row over the frame height, in [-1/2, 1/2]) times the change of the camera's
+    velocity from the pair behind to this pair (``shutter_rates`` under ``scene_cuts``, computed here).  r is the least-squares coefficient
+    of that regressor, over the blocks that the fit kept, of every pair with a real pair on both sides -- none within 2 frames of a cut or
+    of the clip's ends, none next to a NaN row -- after the vectors and the regressor have each had their own similarity taken out.
+    Returns a (4,) float64 device tensor (r_hat, se, D, n) [, terms (T, 4): per pair (sum e . z, sum z . z, sum e . e, blocks)], no
+    synchronisation; one launch per scene and one for the estimate; fixed order, the same bits on every run.  D is the regressor's
+    energy, n the blocks used; (NaN, inf, D, n) when D or the degrees of freedom are not positive (a still clip, T below 4).
+    se is the formal least-squares standard error.  It tells a clip that holds information -- one with acceleration -- from one that
+    does not (a tripod, a steady pan); it is NOT an error bar: the real errors are systematic (a first-order model, correlated sub-pixel
+    bias) and measured several times larger on the analytic clips of tests/shutter_est_ref.py.  Not validated on real footage.
+    ValueError: tensors other than these, on the device; shapes that do not fit (T, plane_hw, radius); a bad radius, pixel_scale,
+    frame_height or cuts."""
+    what = "estimate_rolling_shutter"
+    if not isinstance(motion, torch.Tensor) or not motion.is_cuda or motion.dtype != torch.float64 or motion.dim() != 2 or motion.shape[1] != 4:
+        raise ValueError("%s: motion must be a (T, 4) float64 tensor on the device" % what)
+    try:
+        h, w = (int(v) for v in plane_hw)
+    except (TypeError, ValueError):
+        raise ValueError("%s: plane_hw must be (h, w), got %r" % (what, plane_hw)) from None
+    radius = int(radius)
+    if not 1 <= radius <= 16:
+        raise ValueError("%s: radius must be 1 .. 16, got %r" % (what, radius))
+    if h - 2 * radius < 16 or w - 2 * radius < 16:
+        raise ValueError("%s: a %d x %d plane holds no 16 x 16 block inside a margin of %d" % (what, h, w, radius))
+    T = motion.shape[0]
+    nby, nbx = (h - 2 * radius) // 16, (w - 2 * radius) // 16
+    for name, x, dtype, shape in (("mv", mv, torch.int16, (T, nby, nbx, 2)), ("sad", sad, torch.int32, (T, nby, nbx, 5)),
+                                  ("activity", activity, torch.int32, (T, nby, nbx))):
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != dtype or tuple(x.shape) != shape or not x.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous %s %s tensor on the device, as block_motion returns it for %d planes of %d x %d at "
+                             "radius %d" % (what, name, shape, str(dtype).replace("torch.", ""), T, h, w, radius))
+    sx, sy = (1.0, 1.0) if pixel_scale is None else _check_pixel_scale(pixel_scale, what)
+    try:
+        h0 = h * sy if frame_height is None else float(frame_height)
+    except (TypeError, ValueError):
+        raise ValueError("%s: frame_height must be None or a number of pixels, got %r" % (what, frame_height)) from None
+    if not 1.0 < h0 <= 1e9:
+        raise ValueError("%s: frame_height must lie in (1, 1e9], got %r" % (what, frame_height))
+    motion = motion.contiguous()
+    cuts = _check_cuts(scene_cuts, T, what) if scene_cuts is not None and len(scene_cuts) else []
+    rates = shutter_rates(motion, scene_cuts=cuts or None)
+    terms = torch.empty((T, 4), device=motion.device, dtype=torch.float64)
+    for a, b in (_scenes(T, cuts) if T else []):
+        A.check(A.lib().pws_shutter_terms(A.ptr(mv[a:b]), A.ptr(sad[a:b]), A.ptr(activity[a:b]), A.ptr(motion[a:b]), A.ptr(rates[a:b]), b - a, h, w,
+                                          radius, int(min_activity), sx, sy, h0, A.ptr(terms[a:b]), A.current_stream()), "pws_shutter_terms")
+    est = torch.empty((4,), device=motion.device, dtype=torch.float64)
+    A.check(A.lib().pws_shutter_estimate(A.ptr(terms), T, A.ptr(est), A.current_stream()), "pws_shutter_estimate")
+    return (est, terms) if return_terms else est
+
+
+def _check_shutter(r, what):
+    """``rolling_shutter`` as VideoStabilizer takes it: a float in [-1, 1] or "auto"; ValueError otherwise."""
+    if isinstance(r, str):
+        if r != "auto":
+            raise ValueError("%s: rolling_shutter must be a number in [-1, 1] or \"auto\", got %r" % (what, r))
+        return r
+    return PF._check_rolling_shutter(r, what)
+
+
+def _check_max_se(v, what):
+    """``shutter_max_se`` as a float >= 0; ValueError otherwise (NaN included)."""
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        raise ValueError("%s: shutter_max_se must be a number >= 0, got %r" % (what, v)) from None
+    if not f >= 0.0:
+        raise ValueError("%s: shutter_max_se must be a number >= 0, got %r" % (what, v))
+    return f
 
 
 def _check_limit(max_crop, levels, relax, sigma, what):
@@ -670,7 +753,7 @@ def _windows(gray_padded, start, count, period):
 class VideoStabilizer:
     def __init__(self, netG, batch=32, period=30, device=None, swap_rb=False, interpolation="bilinear", borders="black", rigidity=0.0,
                  mosaic_radius=8, edge="pad", metrics=False, smooth=0.0, rolling_shutter=0.0, wobble=0.0, max_crop=None, limit_levels=16,
-                 limit_relax=None):
+                 limit_relax=None, shutter_max_se=0.02):
         self.net = netG
         # run_video low-passes the NON-RIGID part of the clip's fields along time: each field minus its fitted homography, under a Gaussian of
         # `wobble` frames, in (0, 5] (functional.wobble_fields).  The generator regresses every field from that frame's own window, and the
@@ -690,7 +773,15 @@ class VideoStabilizer:
         # top); a property of the camera, which the user supplies.  Not 0: the correction that smoothing composes into each field depends on
         # the row (shutter_rates, functional.compose_fields(rates=, rolling_shutter=)), so that the skew and wobble of a CMOS readout under
         # shake come out with the shake.  It needs the motion that smoothing measures and the second pass that smoothing owns
-        self.rolling_shutter = PF._check_rolling_shutter(rolling_shutter, "VideoStabilizer")
+        # "auto": run_video estimates it from the block vectors that smoothing measures (estimate_rolling_shutter) and uses the estimate,
+        # clamped to [-1, 1], when it is finite and its formal standard error is at most shutter_max_se; otherwise 0.0, no correction.  The
+        # standard error is a gate against clips without information (a tripod, a steady pan), not an error bar; 0.02 is a judgement that
+        # no footage here can fit, like zoom_speed: the analytic clips of tests/shutter_est_ref.py measure 0.005 .. 0.010 where the estimate
+        # is good to 0.07, and 0.78 on a steady pan
+        self.rolling_shutter = _check_shutter(rolling_shutter, "VideoStabilizer")
+        self.shutter_max_se = _check_max_se(shutter_max_se, "VideoStabilizer")
+        self.shutter_estimate = None        # rolling_shutter="auto", of the last run_video: (4,) float64 on the device = (r_hat, se, D, blocks),
+        self.rolling_shutter_used = None    # and the r that the gate let through, a float
         if self.rolling_shutter != 0.0 and self.smooth == 0.0:
             raise ValueError("VideoStabilizer: rolling_shutter=%r needs smooth > 0 (the correction uses the motion that smoothing measures and "
                              "its second pass)" % (rolling_shutter,))
@@ -1130,6 +1221,14 @@ class VideoStabilizer:
         The refit, and with it crop, zoom and the report, see the corrected field.  ``self.shutter_rates`` (T, 2, 4) float64 is left on the
         device, no synchronisation; None at r = 0.  First order in the time offset, a linear path between frames, the row taken from the
         frame that the motion was measured on (INTEGRATION.md has the model and its caveats); not validated on real footage.
+        VideoStabilizer(smooth=sigma, rolling_shutter="auto", shutter_max_se=0.02): r estimated from the clip.  The measurement keeps its
+        blocks, ``estimate_rolling_shutter`` regresses their vectors on the row share times the camera's acceleration under the call's
+        cuts, and the four numbers (r_hat, se, D, blocks) are read to the host: one 32-byte read, under "auto" only, at which the host
+        waits for pass 1.  r = clamp(r_hat, -1, 1) when r_hat is finite and se <= shutter_max_se, else 0.0 (no correction: a still clip,
+        a steady pan, fewer than 4 frames); from there on everything is the fixed-r path with that number, bit for bit.  se is a gate,
+        not an error bar, and 0.02 a judgement that no footage here can fit.  ``self.shutter_estimate`` (4,) float64 on the device and
+        ``self.rolling_shutter_used``, a float; both None otherwise.  The vectors are measured on the planes as the fields warp them:
+        what the generator's field already took out of the skew is not seen.
         VideoStabilizer(wobble=sigma), sigma in (0, 5] frames: wobble suppression.  The local, per-pixel part of the field changes from frame
         to frame, which reads as wobble or "jello"; rigidity removes that part and with it the parallax and lens correction a per-pixel field
         exists for.  This low-passes it along time instead (``functional.wobble_fields`` has the definition): per node, the field minus the
@@ -1243,8 +1342,10 @@ class VideoStabilizer:
                 zwin = _centred_window(zk, h, w)
         smoothing = self.smooth > 0.0
         self.smooth_motion = self.smooth_inliers = self.smooth_path = self.smooth_correction = self.smooth_uncovered = None
-        self.shutter_rates = None
-        if self.rolling_shutter != 0.0 and not smoothing:   # (the attributes can be set after construction)
+        self.shutter_rates = self.shutter_estimate = self.rolling_shutter_used = None
+        rs = _check_shutter(self.rolling_shutter, "run_video")   # (the attributes can be set after construction)
+        max_se = _check_max_se(self.shutter_max_se, "run_video")
+        if rs != 0.0 and not smoothing:
             raise ValueError("run_video: rolling_shutter=%r needs smooth > 0" % (self.rolling_shutter,))
         max_crop, limit_levels, limit_relax = _check_limit(self.max_crop, self.limit_levels, self.limit_relax, self.smooth, "run_video")
         self.limit_strength = self.limit_need = self.limit_uncovered = self.smooth_correction_unlimited = None
@@ -1491,11 +1592,19 @@ class VideoStabilizer:
                 _field_homography(fields, h, w, hom, bounds)
         if smoothing:   # ... and it measures the filtered fields
             seen = PF.grid_sample(gray_all.unsqueeze(1), fields, align_corners=self.align_corners).squeeze(1)   # the planes as the fields warp them
-            self.smooth_motion, self.smooth_inliers = global_motion(seen, pixel_scale=(w / 256.0, h / 256.0))
+            if rs == "auto":   # the blocks behind the fit are kept for the estimate: the same launches, the same motion
+                self.smooth_motion, self.smooth_inliers, mv, sad, act = global_motion(seen, pixel_scale=(w / 256.0, h / 256.0), return_blocks=True)
+                self.shutter_estimate = estimate_rolling_shutter(self.smooth_motion, mv, sad, act, tuple(seen.shape[1:]),
+                                                                 pixel_scale=(w / 256.0, h / 256.0), scene_cuts=cuts or None, frame_height=h)
+                del mv, sad, act
+                r_hat, se = self.shutter_estimate.tolist()[:2]   # the one read of "auto": 32 bytes, and the host waits for pass 1 here
+                rs = min(1.0, max(-1.0, r_hat)) if math.isfinite(r_hat) and se <= max_se else 0.0
+                self.rolling_shutter_used = rs
+            else:
+                self.smooth_motion, self.smooth_inliers = global_motion(seen, pixel_scale=(w / 256.0, h / 256.0))
             del seen
             self.smooth_correction, self.smooth_path = smooth_path(self.smooth_motion, self.smooth, scene_cuts=cuts or None)
             self.smooth_uncovered = torch.empty((T,), device=dev, dtype=torch.int32)
-            rs = PF._check_rolling_shutter(self.rolling_shutter, "run_video")
             if rs != 0.0:   # the velocity at every frame, from the same measured motion and under the same cuts
                 self.shutter_rates = shutter_rates(self.smooth_motion, scene_cuts=cuts or None)
             if max_crop is not None:   # the crop budget: every frame's share of its correction, decided on the kept fields, read in place
