@@ -13,6 +13,7 @@ import collections
 import torch
 
 from . import hipabi as A
+from .scenes import _cut_list, _scenes
 
 
 def _ac(align_corners):
@@ -810,8 +811,7 @@ def wobble_fields(field, m, frame_hw, sigma, scene_cuts=None, out=None, return_s
         raise ValueError("wobble_fields: bad frame size %d x %d" % (w0, h0))
     if out is not None and (tuple(out.shape) != tuple(field.shape) or not out.is_contiguous()):
         raise ValueError("wobble_fields: out must be a contiguous %s float32 tensor" % (tuple(field.shape),))
-    from .stream import _check_cuts, _scenes   # (stream imports this module)
-    cuts = _check_cuts(scene_cuts, n, "wobble_fields") if scene_cuts is not None and len(scene_cuts) else []
+    cuts = _cut_list(scene_cuts, n, "wobble_fields")
     field, m = field.contiguous(), m.contiguous().reshape(n, 9)
     if out is None:
         out = torch.empty_like(field)

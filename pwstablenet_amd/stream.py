@@ -13,169 +13,74 @@ host<->device round trip per frame.  Here:
     and results go D2H on a third stream (hipMemcpyAsync through torch, one event per hand-off);
   * several GPUs take contiguous frame chunks with a 15-frame halo each (``distributed.shard_frames``): no collective.
 """
+import collections
 import math
 import time
 
 import torch
 
 from . import functional as PF
-from . import hipabi as A
+from .frameio import (_area_resize_yuv, _crop, _frames_shape, _output_resize, _window_planes, _yuv_crop, _yuv_format, _yuv_planes,  # noqa: F401
+                      area_half, area_resize, area_resize_yuv, area_resize_yuv16, window_planes, window_planes_yuv, window_planes_yuv16)
+from .framing import (_bounds_rows, _centred_window, _check_lattice, _field_homography, _has_lattice, auto_crop_window,  # noqa: F401
+                      field_homography, zoom_schedule, zoom_window)
+from .motion import (_check_limit, _check_max_se, _check_shutter, _check_sigma, block_motion, estimate_rolling_shutter,  # noqa: F401
+                     global_motion, limit_path, limit_rectangle, scene_scores, shutter_rates, smooth_path, stability_scores)
+from .scenes import _check_cuts, _cut_rule, _scenes, find_scene_cuts  # noqa: F401
 
 
-def _window_planes(frames, fmt, size, out, what, frames_are_rgb=False):
-    """The window planes of frames in the format ``fmt`` (functional.FrameFormat) in one launch: what window_planes, window_planes_yuv and
-    window_planes_yuv16 document.  The format's shape rules (ValueError, width a multiple of 2) come before host tensors or a wrong dtype."""
-    t, h, w = fmt.frame_shape(frames, w_multiple=2)
-    A.require_cuda(frames, dtype=fmt.dtype)
-    if fmt.hwc and frames.shape[3] != 3:
-        raise ValueError("%s: frames must be (T, H, W, 3) uint8, got %s" % (what, tuple(frames.shape),))
-    frames = frames.contiguous()
-    if out is None:
-        out = torch.empty((t, size, size), device=frames.device, dtype=torch.float32)
-    A.require_cuda(out)
-    if tuple(out.shape) != (t, size, size) or not out.is_contiguous():
-        raise ValueError("%s: out must be a contiguous (T, %d, %d) float32 tensor" % (what, size, size))
-    A.check(getattr(A.lib(), fmt.window_planes)(A.ptr(frames), A.ptr(out), t, h, w, size, size, 1, *fmt.args(frames_are_rgb), A.current_stream()),
-            fmt.window_planes)
-    return out
+def _check_integer_frames(frames, what, feature):
+    """``feature`` -- borders="keep", borders="mosaic", an edge mode -- reads and writes integer samples; ValueError for other frames."""
+    if frames.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError("%s: %s is for the integer pixel formats (uint8 / uint16 frames), got %s" % (what, feature, frames.dtype))
 
 
-def window_planes(frames_hwc, size=256, frames_are_rgb=False, out=None):
-    """``cv2.resize(cv2.cvtColor(frame, COLOR_BGR2GRAY), (size, size), INTER_AREA) / 255 * 2 - 1`` for a batch of decoded
-    frames (reference main_new.py:639-643,653-667) on the device: (T, H, W, 3) uint8 -> (T, size, size) float32."""
-    A.require_cuda(frames_hwc, dtype=torch.uint8)
-    if frames_hwc.dim() != 4:
-        raise ValueError("window_planes: frames must be (T, H, W, 3) uint8, got %s" % (tuple(frames_hwc.shape),))
-    return _window_planes(frames_hwc, PF.FRAME_FORMATS["bgr24"], size, out, "window_planes", frames_are_rgb)
+def _crop_window(fmt, oh, ow, crop):
+    """(cy0, cy1, cx0, cx1): the window that ``crop`` = None or (x_start, x_end, y_start, y_end[, threshold]) cuts out of the oh x ow output
+    frame in the format ``fmt``; ValueError for a window that does not lie inside it or, for packed frames, off the format's multiples."""
+    cy0, cy1, cx0, cx1 = 0, oh, 0, ow
+    if crop is not None:
+        if len(crop) not in (4, 5):
+            raise ValueError("crop must be (x_start, x_end, y_start, y_end[, threshold])")
+        th = int(crop[4]) if len(crop) == 5 else 0
+        cx0, cx1, cy0, cy1 = int(crop[0]) + th, int(crop[1]) - th, int(crop[2]) + th, int(crop[3]) - th
+        if not (0 <= cx0 < cx1 <= ow and 0 <= cy0 < cy1 <= oh):
+            raise ValueError("crop window x [%d, %d) y [%d, %d) does not lie inside the %d x %d output frame" % (cx0, cx1, cy0, cy1, ow, oh))
+        mx, my = fmt.multiples if fmt.packed else (1, 1)
+        if (cx0 | cx1) % mx or (cy0 | cy1) % my:
+            if fmt.chroma == 0:
+                raise ValueError("crop window x [%d, %d) y [%d, %d) of %s frames must have even edges" % (cx0, cx1, cy0, cy1, fmt.name))
+            raise ValueError("crop window x [%d, %d) y [%d, %d) of %s frames must have edges that are multiples of %d (x) and %d (y)"
+                             % (cx0, cx1, cy0, cy1, fmt.name, mx, my))
+    return cy0, cy1, cx0, cx1
 
 
-def area_half(frames_hwc, swap_rb=False):
-    """``cv2.cvtColor(cv2.resize(frame, (W/2, H/2), INTER_AREA), COLOR_BGR2RGB)`` of the output frames (main_new.py:723-725;
-    the swap is optional): (T, H, W, 3) uint8 -> (T, H/2, W/2, 3) uint8."""
-    A.require_cuda(frames_hwc, dtype=torch.uint8)
-    frames_hwc = frames_hwc.contiguous()
-    t, h, w, _ = frames_hwc.shape
-    out = torch.empty((t, h // 2, w // 2, 3), device=frames_hwc.device, dtype=torch.uint8)
-    A.check(A.lib().pws_area_half_u8(A.ptr(frames_hwc), A.ptr(out), t, h, w, int(bool(swap_rb)), A.current_stream()),
-            "pws_area_half_u8")
-    return out
+def _hand_over(warped, dest, lane, down):
+    """``warped``, finished on the stream ``lane``, into ``dest``: host frames go down on the stream ``down`` behind one event; device frames
+    (down None) are copied in place."""
+    if down is None:
+        dest.copy_(warped)
+        return
+    done = torch.cuda.Event()
+    done.record(lane)
+    with torch.cuda.stream(down):
+        down.wait_event(done)
+        dest.copy_(warped, non_blocking=True)
+    warped.record_stream(down)
 
 
-def area_resize(frames_hwc, size, swap_rb=False):
-    """``cv2.resize(frame, size, interpolation=cv2.INTER_AREA)`` for any down-scaling ratio, ``size`` = (width, height) as cv2 takes
-    it (main_new.py:723: ``cv2.resize(samples, (640, 360), interpolation=cv2.INTER_AREA)``): (T, H, W, 3) uint8 -> (T, height, width, 3)."""
-    A.require_cuda(frames_hwc, dtype=torch.uint8)
-    frames_hwc = frames_hwc.contiguous()
-    t, h, w, _ = frames_hwc.shape
-    ow, oh = int(size[0]), int(size[1])
-    out = torch.empty((t, oh, ow, 3), device=frames_hwc.device, dtype=torch.uint8)
-    A.check(A.lib().pws_area_resize_u8(A.ptr(frames_hwc), A.ptr(out), t, h, w, oh, ow, int(bool(swap_rb)), A.current_stream()),
-            "pws_area_resize_u8")
-    return out
-
-
-def window_planes_yuv(frames, pixel_format, size=256, out=None):
-    """window_planes of the BGR frames ``cv2.cvtColor(frame, COLOR_YUV2BGR_NV12 / COLOR_YUV2BGR_I420)`` would give, straight from packed
-    4:2:0 frames (T, H * 3 // 2, W) uint8 in one launch (BT.601 limited range, OpenCV 4.x's 8-bit fixed point): the same planes bit for
-    bit, so a YUV clip gets the fields of its BGR decode.  H and W even.  -> (T, size, size) float32."""
-    A.require_cuda(frames, dtype=torch.uint8)   # (wins over the format's name and shape rules here, as it always has)
-    return _window_planes(frames, _yuv_format(pixel_format, torch.uint8), size, out, "window_planes_yuv")
-
-
-def _yuv_format(pixel_format, dtype):
-    """The record of a packed YUV format of that sample dtype: a 4:2:0 name, or -- the 4:2:0 wrappers' ValueError for any other name staying
-    word for word -- one of the 4:2:2 / 4:4:4 names of functional.CHROMA_FORMATS."""
-    fmt = PF.lookup_format(pixel_format)
-    if fmt is not None and fmt.packed and fmt.dtype == dtype:
-        return fmt
-    return PF._packed_format(pixel_format, dtype)
-
-
-def _yuv_planes(x, h, w, pixel_format):
-    """Views of the planes of packed frames x (T, packed rows of h, w) (FrameFormat.planes): [Y (T, h, w), UV (T, h/2, w)] for NV12, [Y, U
-    (T, h/2, w/2), V (T, h/2, w/2)] for I420; P010 as NV12 and I010 as I420, in 16-bit words; chroma planes of h x w/2 for the 4:2:2 formats
-    and h x w for 4:4:4."""
-    return PF.lookup_format(pixel_format).planes(x, h, w)
-
-
-def _area_resize_yuv(frames, fmt, size, what):
-    """INTER_AREA plane by plane for packed frames in the format ``fmt``: what area_resize_yuv and area_resize_yuv16 document.  The output
-    size is a multiple of the format's subsampling per axis (4:2:0: both even; 4:2:2: the width; 4:4:4: free)."""
-    t, h, w = fmt.frame_shape(frames, w_multiple=2)
-    A.require_cuda(frames, dtype=fmt.dtype)
-    ow, oh = int(size[0]), int(size[1])
-    (cx, cy), (mx, my) = fmt.shifts, fmt.multiples
-    if ow % mx or oh % my or not (0 < ow <= w and 0 < oh <= h):
-        if fmt.chroma == 0:
-            raise ValueError("%s: output size %s must be even and within the %d x %d source" % (what, tuple(size), w, h))
-        raise ValueError("%s: %s output size %s must be a multiple of %d x %d and within the %d x %d source" % (what, fmt.name, tuple(size), mx, my, w, h))
-    frames = frames.contiguous()
-    out = torch.empty(_frames_shape(fmt, t, oh, ow), device=frames.device, dtype=fmt.dtype)
-    fs, os_ = frames[0].numel(), out[0].numel()   # (in samples)
-    ch_, cw_, qh_, qw_ = h >> cy, w >> cx, oh >> cy, ow >> cx   # the chroma planes, source and output
-    geo = [(1, h, w, oh, ow)] + ([(2, ch_, cw_, qh_, qw_)] if fmt.layout == 0 else [(1, ch_, cw_, qh_, qw_)] * 2)
-    placement = (fmt.layout,) if fmt.dtype == torch.uint16 else ()   # (the 16-bit entry also takes where the 10 bits sit in a word)
-    for (c, ph, pw, qh, qw), src, dst in zip(geo, _yuv_planes(frames, h, w, fmt.name), _yuv_planes(out, oh, ow, fmt.name)):
-        A.check(getattr(A.lib(), fmt.plane_resize)(A.ptr(src), fs, A.ptr(dst), os_, t, ph, pw, c, qh, qw, *placement, A.current_stream()),
-                fmt.plane_resize)
-    return out
-
-
-def area_resize_yuv(frames, pixel_format, size):
-    """area_resize for packed 4:2:0 frames, plane by plane: Y to (height, width), the chroma to (height/2, width/2) (NV12's interleaved UV
-    as a 2-channel image, I420's U and V as 1-channel images); ``size`` = (width, height), both even.  (T, H * 3 // 2, W) uint8 ->
-    (T, height * 3 // 2, width)."""
-    A.require_cuda(frames, dtype=torch.uint8)   # (wins over the format's name and shape rules here, as it always has)
-    return _area_resize_yuv(frames, _yuv_format(pixel_format, torch.uint8), size, "area_resize_yuv")
-
-
-def window_planes_yuv16(frames, pixel_format, size=256, out=None):
-    """window_planes_yuv for 10-bit frames (T, H * 3 // 2, W) uint16, "p010" or "i010": the generator was trained on 8-bit gray, so the plane
-    of a 10-bit frame is by definition the plane of its 8-bit reduction ``v8 = min(255, (v10 + 2) >> 2)``, fused into the kernel's loads (no
-    8-bit copy of the frames): a P010 / I010 clip gets the fields of the NV12 / I420 clip of its reduced samples bit for bit.  H and W even.
-    -> (T, size, size) float32."""
-    return _window_planes(frames, _yuv_format(pixel_format, torch.uint16), size, out, "window_planes_yuv16")
-
-
-def area_resize_yuv16(frames, pixel_format, size):
-    """area_resize_yuv for 10-bit frames, INTER_AREA plane by plane on the 10-bit values (P010's interleaved UV as a 2-channel image),
-    clamped to 0..1023 and stored in the format's placement; ``size`` = (width, height), both even.  (T, H * 3 // 2, W) uint16 ->
-    (T, height * 3 // 2, width)."""
-    return _area_resize_yuv(frames, _yuv_format(pixel_format, torch.uint16), size, "area_resize_yuv16")
-
-
-def _yuv_crop(x, h, w, pixel_format, cy0, cy1, cx0, cx1):
-    """The window [cy0, cy1) x [cx0, cx1) of packed frames (edges: multiples of the format's subsampling per axis -- even for 4:2:0), packed
-    again on the device: Y [cy0:cy1, cx0:cx1], chroma [cy0 >> cy:cy1 >> cy, cx0 >> cx:cx1 >> cx]."""
-    fmt = PF.lookup_format(pixel_format)
-    cx, cy = fmt.shifts
-    ch, cw = cy1 - cy0, cx1 - cx0
-    out = torch.empty(_frames_shape(fmt, x.shape[0], ch, cw), device=x.device, dtype=x.dtype)
-    src, dst = fmt.planes(x, h, w), fmt.planes(out, ch, cw)
-    dst[0].copy_(src[0][:, cy0:cy1, cx0:cx1])
-    if len(src) == 2:
-        dst[1].copy_(src[1][:, cy0 >> cy:cy1 >> cy, cx0:cx1])   # (U V interleaved, cx = 1: chroma columns cx0/2 .. are samples cx0 ..)
-    else:
-        for k in (1, 2):
-            dst[k].copy_(src[k][:, cy0 >> cy:cy1 >> cy, cx0 >> cx:cx1 >> cx])
-    return out
-
-
-def _output_resize(frames, fmt, size, half):
-    """run_video's resize of warped frames to ``size`` = (width, height); half: BGR's 2 x 2 kernel (the YUV planes take the general one)."""
-    if fmt.packed:
-        return _area_resize_yuv(frames, fmt, size, "run_video")
-    return area_half(frames) if half else area_resize(frames, size)
-
-
-def _frames_shape(fmt, n, h, w):
-    """The shape of n integer frames of h x w pixels in the format ``fmt``."""
-    return (n, fmt.packed_rows(h), w) if fmt.packed else (n, h, w, 3)
-
-
-def _crop(frames, fmt, h, w, cy0, cy1, cx0, cx1):
-    """The window [cy0, cy1) x [cx0, cx1) of h x w frames, packed on the device: only the window crosses PCIe."""
-    return _yuv_crop(frames, h, w, fmt.name, cy0, cy1, cx0, cx1) if fmt.packed else frames[:, cy0:cy1, cx0:cx1, :].contiguous()
+class StreamPlan(collections.namedtuple("StreamPlan", "fmt h w oh ow T n_all halo_left halo_right chunk chunks in_flight on_host half_size_output "
+                                        "frames_are_rgb crop zmode zwin zoom_speed zoom_min two_pass mosaic radius keep rigid edge metrics lattice "
+                                        "smooth shutter max_se wobble max_crop limit_levels limit_relax detect cuts scene_threshold scene_min_len")):
+    """Everything that run_video decides from its arguments and the stabiliser's options before it touches the device (VideoStabilizer._plan):
+    the format record ``fmt``; the source ``h`` x ``w`` and the output ``oh`` x ``ow`` before the crop; the ``T`` frames to stabilise of the
+    ``n_all`` given, the halos, ``chunk`` and the ``chunks`` [(start, stop)] in the index space of the frames (the first / last chunk carry
+    the halo frames with them), ``in_flight`` lanes, ``on_host`` input; ``crop``: None, the window (cy0, cy1, cx0, cx1) of an explicit crop,
+    or "auto"; ``zmode``: None, "fixed" (``zwin``, the one window), "auto" or "adaptive" (``zoom_speed``, ``zoom_min``); ``two_pass``: pass 1
+    keeps fields and bounds, the host decides, pass 2 warps; ``mosaic`` and its ``radius``, ``keep``, ``rigid``, the ``edge`` mode,
+    ``metrics``, ``lattice`` (the frame holds the homography fit's); ``smooth`` (sigma, 0: off), ``shutter`` (a float or "auto") and ``max_se``, ``wobble`` (sigma, 0: off), ``max_crop`` (None: off) with ``limit_levels`` and the resolved ``limit_relax``; ``detect``
+    (scene_cuts="auto") with its thresholds, and ``cuts``, the checked list the call starts from."""
+    __slots__ = ()
 
 
 def _prefetch(frames, s, e, stream, dev):
@@ -187,558 +92,6 @@ def _prefetch(frames, s, e, stream, dev):
         ev = torch.cuda.Event()
         ev.record(stream)
     return buf, ev
-
-
-def _field_homography(field, h0, w0, m_out, bounds_out, pts_out=None):
-    A.check(A.lib().pws_field_homography(A.ptr(field), field.shape[0], field.shape[1], field.shape[2], h0, w0, A.ptr(m_out),
-                                         A.ptr(bounds_out), A.ptr(pts_out), A.current_stream()), "pws_field_homography")
-
-
-def _check_lattice(h0, w0, what="automatic crop"):
-    """``what``: the feature that asked for the fit, for the message."""
-    if h0 < 300 or w0 < 600:
-        raise ValueError("%s: the homography fit's 20 x 20 sampling lattice needs a frame of at least 600 x 300 pixels, got %d x %d" % (what, w0, h0))
-
-
-def field_homography(field, frame_hw, return_points=False):
-    """The per-frame half of the reference's automatic crop (main_new.py:550-574) on the device: ``field`` (N, fh, fw, 2) as
-    ``netG(window, False)`` returns it, ``frame_hw`` = (H0, W0) of the source frames it warps.  The field resized to H0 x W0 as the warp
-    resizes it is sampled on a 20 x 20 lattice (p1), the homography M (m33 = 1) from p1 to the lattice's own positions in [-1, 1] is
-    fitted in fp64 (least squares on the reprojection error: cv2.findHomography's result when every sample is an inlier), and the
-    corners mapped through it give the frame's bounds in source pixels.  Returns M (N, 3, 3) float64 and bounds (N, 4) float32 = (top,
-    bottom, left, right) [and p1 (N, 400, 2) float32], all on the device; a frame without a well-defined fit has NaN M and bounds."""
-    A.require_cuda(field)
-    if field.dim() != 4 or field.shape[3] != 2:
-        raise ValueError("field_homography: field must be (N, fh, fw, 2), got %s" % (tuple(field.shape),))
-    h0, w0 = int(frame_hw[0]), int(frame_hw[1])
-    _check_lattice(h0, w0)
-    field = field.contiguous()
-    n = field.shape[0]
-    m = torch.empty((n, 3, 3), device=field.device, dtype=torch.float64)
-    bounds = torch.empty((n, 4), device=field.device, dtype=torch.float32)
-    pts = torch.empty((n, 400, 2), device=field.device, dtype=torch.float32) if return_points else None
-    _field_homography(field, h0, w0, m, bounds, pts)
-    return (m, bounds, pts) if return_points else (m, bounds)
-
-
-def scene_scores(planes, return_counts=False):
-    """The cut score of consecutive window planes (csrc/scene.hip): ``planes`` (T, h, w) float32 on the device, contiguous, h and w
-    multiples of 4 (``window_planes``: 256 x 256).  Every plane is summarised by the 32-bin histograms of its 4 x 4 blocks (512 counters; the
-    bin of a sample v is ``min(31, int((v + 1) * 16))``, 0 below -1 and for NaN); ``score[t] = sum |hist[t] - hist[t-1]| / (2 h w)`` lies in
-    [0, 1] (0: the same block histograms, which a shaky shot nearly keeps; 1: no sample of any block kept its bin), ``score[0] = 0``.  The
-    counters are exact integers and the division is torch's on them: the same bits on every run.  Returns (T,) float32 on the device
-    [, hist (T, 16, 32) int32, sad (T,) int32].  A tensor that is not contiguous float32 (T, h, w) is a ValueError."""
-    if not isinstance(planes, torch.Tensor) or planes.dim() != 3 or planes.dtype != torch.float32 or not planes.is_contiguous():
-        raise ValueError("scene_scores: planes must be a contiguous (T, h, w) float32 tensor")
-    A.require_cuda(planes)
-    t, h, w = planes.shape
-    hist = torch.empty((t, 16, 32), device=planes.device, dtype=torch.int32)
-    sad = torch.empty((t,), device=planes.device, dtype=torch.int32)
-    A.check(A.lib().pws_scene_change(A.ptr(planes), t, h, w, A.ptr(hist), A.ptr(sad), A.current_stream()), "pws_scene_change")
-    scores = sad.to(torch.float32) / float(2 * h * w)
-    return (scores, hist, sad) if return_counts else scores
-
-
-def _motion_planes(planes, radius, what):
-    if not isinstance(planes, torch.Tensor) or planes.dim() != 3 or planes.dtype != torch.float32 or not planes.is_contiguous():
-        raise ValueError("%s: planes must be a contiguous (T, h, w) float32 tensor" % what)
-    A.require_cuda(planes)
-    radius = int(radius)
-    t, h, w = planes.shape
-    if not 1 <= radius <= 16:
-        raise ValueError("%s: radius must be 1 .. 16, got %r" % (what, radius))
-    if h - 2 * radius < 16 or w - 2 * radius < 16:
-        raise ValueError("%s: a %d x %d plane holds no 16 x 16 block inside a margin of %d" % (what, h, w, radius))
-    return t, h, w, radius
-
-
-def block_motion(planes, radius=16):
-    """Block motion between consecutive window planes (csrc/motion.hip; include/pwstable.h pws_block_motion has the definition): ``planes``
-    (T, h, w) float32 on the device, contiguous (``window_planes``: 256 x 256, 14 x 14 blocks at the default radius).  The samples are
-    quantised to bytes once; every 16 x 16 block of frame t is searched in frame t-1 over dx, dy in [-radius, radius] by its sum of absolute
-    differences, ties going to the shorter vector.  Returns mv (T, nby, nbx, 2) int16 = (dx, dy), sad (T, nby, nbx, 5) int32 (the best
-    candidate's and its four neighbours', -1 outside the range) and activity (T, nby, nbx) int32 (the block's summed absolute gradients),
-    on the device; row 0 of mv and sad is zero.  Integer arithmetic after the quantisation: the same bits on every run.  A tensor that is
-    not contiguous float32 (T, h, w), a radius outside 1 .. 16 or a plane without a block is a ValueError."""
-    t, h, w, radius = _motion_planes(planes, radius, "block_motion")
-    nby, nbx = (h - 2 * radius) // 16, (w - 2 * radius) // 16
-    mv = torch.empty((t, nby, nbx, 2), device=planes.device, dtype=torch.int16)
-    sad = torch.empty((t, nby, nbx, 5), device=planes.device, dtype=torch.int32)
-    act = torch.empty((t, nby, nbx), device=planes.device, dtype=torch.int32)
-    A.check(A.lib().pws_block_motion(A.ptr(planes), t, h, w, radius, A.ptr(mv), A.ptr(sad), A.ptr(act), A.current_stream()), "pws_block_motion")
-    return mv, sad, act
-
-
-def _check_pixel_scale(pixel_scale, what):
-    """``pixel_scale`` as (sx, sy), two floats in (0, 1e6]; ValueError otherwise (NaN included)."""
-    try:
-        sx, sy = (float(v) for v in pixel_scale)
-    except (TypeError, ValueError):
-        raise ValueError("%s: pixel_scale must be None or (sx, sy), got %r" % (what, pixel_scale)) from None
-    if not (0.0 < sx <= 1e6 and 0.0 < sy <= 1e6):
-        raise ValueError("%s: pixel_scale must be two positive finite numbers, got %r" % (what, pixel_scale))
-    return sx, sy
-
-
-def global_motion(planes, radius=16, min_activity=2000, return_blocks=False, pixel_scale=None):
-    """The similarity between consecutive window planes: ``block_motion``, then per pair the least-squares fit, in fp64, of ``p' = [[a, -b],
-    [b, a]] p + (tx, ty)`` -- a block centre p of frame t, relative to the plane centre, lies at p' in frame t-1 -- to the blocks' sub-pixel
-    vectors, in three rounds that drop outliers (pws_motion_fit has the definition).  A block counts if its activity is at least
-    ``min_activity``, its vector lies inside the search range and its match is sharp (S rises around it by at least half the activity: a
-    block whose content has left the search window settles on a chance match, around which S is flat).  The default 2000 is a judgement: a flat block measures 0, the blocks of the
-    tests' synthetic texture a few thousand, and no real footage was available to fit the value to.  Returns motion (T, 4) float64 = (a, b,
-    tx, ty) in plane pixels and inliers (T,) int32 [, mv, sad, activity], all on the device, no synchronisation; row 0 is (1, 0, 0, 0) with
-    0 inliers, and a pair with fewer than 8 usable blocks in any round is a NaN row with 0 inliers.  Fixed summation order: the same bits on
-    every run.  ValueError as for ``block_motion``.
-    pixel_scale = (sx, sy): frame pixels per plane pixel, (W0 / w, H0 / h).  The planes are a non-uniform resize of any frame that is not
-    square, under which a frame's rotation is no similarity; the fit then runs in FRAME pixels, relative to the frame centre
-    (pws_motion_fit_scaled: centres and vectors scaled before the sums, the outlier floor sx sy), and so does the returned motion.  None,
-    the default, is the plane-pixel fit as it was, which (1, 1) equals bit for bit; anything but two positive finite numbers is a
-    ValueError."""
-    t, h, w, radius = _motion_planes(planes, radius, "global_motion")
-    if pixel_scale is not None:
-        sx, sy = _check_pixel_scale(pixel_scale, "global_motion")
-    mv, sad, act = block_motion(planes, radius)
-    motion = torch.empty((t, 4), device=planes.device, dtype=torch.float64)
-    inliers = torch.empty((t,), device=planes.device, dtype=torch.int32)
-    if pixel_scale is None:
-        A.check(A.lib().pws_motion_fit(A.ptr(mv), A.ptr(sad), A.ptr(act), t, h, w, radius, int(min_activity), A.ptr(motion), A.ptr(inliers),
-                                       A.current_stream()), "pws_motion_fit")
-    else:
-        A.check(A.lib().pws_motion_fit_scaled(A.ptr(mv), A.ptr(sad), A.ptr(act), t, h, w, radius, int(min_activity), sx, sy, A.ptr(motion),
-                                              A.ptr(inliers), A.current_stream()), "pws_motion_fit_scaled")
-    return (motion, inliers, mv, sad, act) if return_blocks else (motion, inliers)
-
-
-def _check_sigma(sigma, what, zero_ok=False):
-    """``sigma`` as a float in (0, 256] (or [0, 256]); ValueError otherwise (NaN included)."""
-    try:
-        s = float(sigma)
-    except (TypeError, ValueError):
-        raise ValueError("%s: sigma must be a number of frames, got %r" % (what, sigma)) from None
-    if not ((0.0 < s or (zero_ok and s == 0.0)) and s <= 256.0):
-        raise ValueError("%s: sigma must lie in %s0, 256], got %r" % (what, "[" if zero_ok else "(", sigma))
-    return s
-
-
-def smooth_path(motion, sigma, scene_cuts=None):
-    """The camera path a clip's per-pair motion adds up to, low-passed, and the per-frame corrections between the two (csrc/path_smooth.hip;
-    include/pwstable.h pws_path_smooth has the definition): ``motion`` (T, 4) float64 on the device = (a, b, tx, ty) as ``global_motion``
-    returns it -- row k maps a point of frame k to frame k-1; a NaN row counts as no motion -- and ``sigma``, the Gaussian's width in frames,
-    in (0, 256].  Per scene (``scene_cuts``: sorted indices at which a new scene starts; the pair at a cut is not read, and every scene's
-    path starts at zero) the pose of each frame in its scene's first frame, P = (log scale, angle, cx, cy), is accumulated, averaged over
-    +-min(ceil(3 sigma), n-1) frames under the Gaussian with the path continued by odd reflection beyond the scene's ends (a steady pan is
-    left alone at every frame), and D[k] = C_k^-1 o C^_k -- row-major 2 x 3 -- maps a position of the smoothed frame k to the measured
-    frame's, in ``motion``'s pixels relative to the frame centre: what ``functional.compose_fields`` takes.  Returns (D (T, 6), path (T, 4)),
-    float64 on the device, no synchronisation; one launch per scene, on slices.  Fixed order: the same bits on every run.
-    ValueError: a tensor that is not (T, 4) float64 on the device, sigma outside (0, 256], bad cuts."""
-    if not isinstance(motion, torch.Tensor) or not motion.is_cuda or motion.dtype != torch.float64 or motion.dim() != 2 or motion.shape[1] != 4:
-        raise ValueError("smooth_path: motion must be a (T, 4) float64 tensor on the device")
-    sigma = _check_sigma(sigma, "smooth_path")
-    motion = motion.contiguous()
-    T = motion.shape[0]
-    cuts = _check_cuts(scene_cuts, T, "smooth_path") if scene_cuts is not None and len(scene_cuts) else []
-    d = torch.empty((T, 6), device=motion.device, dtype=torch.float64)
-    path = torch.empty((T, 4), device=motion.device, dtype=torch.float64)
-    for a, b in (_scenes(T, cuts) if T else []):
-        A.check(A.lib().pws_path_smooth(A.ptr(motion[a:b]), b - a, sigma, A.ptr(path[a:b]), A.ptr(d[a:b]), A.current_stream()), "pws_path_smooth")
-    return d, path
-
-
-def shutter_rates(motion, scene_cuts=None):
-    """The camera's velocity at every frame of a clip, for the rolling-shutter correction (csrc/path_smooth.hip; include/pwstable.h
-    pws_shutter_rates has the definition): ``motion`` (T, 4) float64 on the device as for ``smooth_path``.  Returns (T, 2, 4) float64 on
-    the device: per frame k the rates (log scale, angle, x, y per frame interval) in frame k's own coordinates, [k, 0] from the pair ahead
-    (motion[k+1]), [k, 1] from the pair behind (motion[k]) -- what ``functional.compose_fields(rates=)`` takes.  Per scene
-    (``scene_cuts`` as for ``smooth_path``): rates never cross a cut, a scene's first and last frame use their one pair twice, a scene of
-    one frame has zero rates; a NaN row counts as no motion.  No synchronisation; one launch per scene, on slices; the same bits on every run.
-    ValueError: a tensor that is not (T, 4) float64 on the device, bad cuts."""
-    if not isinstance(motion, torch.Tensor) or not motion.is_cuda or motion.dtype != torch.float64 or motion.dim() != 2 or motion.shape[1] != 4:
-        raise ValueError("shutter_rates: motion must be a (T, 4) float64 tensor on the device")
-    motion = motion.contiguous()
-    T = motion.shape[0]
-    cuts = _check_cuts(scene_cuts, T, "shutter_rates") if scene_cuts is not None and len(scene_cuts) else []
-    rates = torch.empty((T, 2, 4), device=motion.device, dtype=torch.float64)
-    for a, b in (_scenes(T, cuts) if T else []):
-        A.check(A.lib().pws_shutter_rates(A.ptr(motion[a:b]), b - a, A.ptr(rates[a:b]), A.current_stream()), "pws_shutter_rates")
-    return rates
-
-
-def estimate_rolling_shutter(motion, mv, sad, activity, plane_hw, radius=16, min_activity=2000, pixel_scale=None, scene_cuts=None,
-                             frame_height=None, return_terms=False):
-    """The rolling-shutter share r of a clip, estimated from what ``global_motion(..., return_blocks=True)`` measured on it
-    (csrc/shutter_estimate.hip; include/pwstable.h pws_shutter_terms / pws_shutter_estimate have the definition): ``motion`` (T, 4) float64
-    and ``mv``, ``sad``, ``activity`` as that call returned them for (T, h, w) planes, ``plane_hw`` = (h, w), and the ``radius``,
-    ``min_activity`` and ``pixel_scale`` that the call was given.  ``frame_height``: the frame's height in ``motion``'s pixels -- None: h
-    times the scale's sy, which is h for the plane-pixel fit.  A rolling shutter leaves in the block vectors a displacement that no
-    similarity absorbs: the block's share c of the readout (its row over the frame height, in [-1/2, 1/2]) times the change of the camera's
-    velocity from the pair behind to this pair (``shutter_rates`` under ``scene_cuts``, computed here).  r is the least-squares coefficient
-    of that regressor, over the blocks that the fit kept, of every pair with a real pair on both sides -- none within 2 frames of a cut or
-    of the clip's ends, none next to a NaN row -- after the vectors and the regressor have each had their own similarity taken out.
-    Returns a (4,) float64 device tensor (r_hat, se, D, n) [, terms (T, 4): per pair (sum e . z, sum z . z, sum e . e, blocks)], no
-    synchronisation; one launch per scene and one for the estimate; fixed order, the same bits on every run.  D is the regressor's
-    energy, n the blocks used; (NaN, inf, D, n) when D or the degrees of freedom are not positive (a still clip, T below 4).
-    se is the formal least-squares standard error.  It tells a clip that holds information -- one with acceleration -- from one that
-    does not (a tripod, a steady pan); it is NOT an error bar: the real errors are systematic (a first-order model, correlated sub-pixel
-    bias) and measured several times larger on the analytic clips of tests/shutter_est_ref.py.  Not validated on real footage.
-    ValueError: tensors other than these, on the device; shapes that do not fit (T, plane_hw, radius); a bad radius, pixel_scale,
-    frame_height or cuts."""
-    what = "estimate_rolling_shutter"
-    if not isinstance(motion, torch.Tensor) or not motion.is_cuda or motion.dtype != torch.float64 or motion.dim() != 2 or motion.shape[1] != 4:
-        raise ValueError("%s: motion must be a (T, 4) float64 tensor on the device" % what)
-    try:
-        h, w = (int(v) for v in plane_hw)
-    except (TypeError, ValueError):
-        raise ValueError("%s: plane_hw must be (h, w), got %r" % (what, plane_hw)) from None
-    radius = int(radius)
-    if not 1 <= radius <= 16:
-        raise ValueError("%s: radius must be 1 .. 16, got %r" % (what, radius))
-    if h - 2 * radius < 16 or w - 2 * radius < 16:
-        raise ValueError("%s: a %d x %d plane holds no 16 x 16 block inside a margin of %d" % (what, h, w, radius))
-    T = motion.shape[0]
-    nby, nbx = (h - 2 * radius) // 16, (w - 2 * radius) // 16
-    for name, x, dtype, shape in (("mv", mv, torch.int16, (T, nby, nbx, 2)), ("sad", sad, torch.int32, (T, nby, nbx, 5)),
-                                  ("activity", activity, torch.int32, (T, nby, nbx))):
-        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != dtype or tuple(x.shape) != shape or not x.is_contiguous():
-            raise ValueError("%s: %s must be a contiguous %s %s tensor on the device, as block_motion returns it for %d planes of %d x %d at "
-                             "radius %d" % (what, name, shape, str(dtype).replace("torch.", ""), T, h, w, radius))
-    sx, sy = (1.0, 1.0) if pixel_scale is None else _check_pixel_scale(pixel_scale, what)
-    try:
-        h0 = h * sy if frame_height is None else float(frame_height)
-    except (TypeError, ValueError):
-        raise ValueError("%s: frame_height must be None or a number of pixels, got %r" % (what, frame_height)) from None
-    if not 1.0 < h0 <= 1e9:
-        raise ValueError("%s: frame_height must lie in (1, 1e9], got %r" % (what, frame_height))
-    motion = motion.contiguous()
-    cuts = _check_cuts(scene_cuts, T, what) if scene_cuts is not None and len(scene_cuts) else []
-    rates = shutter_rates(motion, scene_cuts=cuts or None)
-    terms = torch.empty((T, 4), device=motion.device, dtype=torch.float64)
-    for a, b in (_scenes(T, cuts) if T else []):
-        A.check(A.lib().pws_shutter_terms(A.ptr(mv[a:b]), A.ptr(sad[a:b]), A.ptr(activity[a:b]), A.ptr(motion[a:b]), A.ptr(rates[a:b]), b - a, h, w,
-                                          radius, int(min_activity), sx, sy, h0, A.ptr(terms[a:b]), A.current_stream()), "pws_shutter_terms")
-    est = torch.empty((4,), device=motion.device, dtype=torch.float64)
-    A.check(A.lib().pws_shutter_estimate(A.ptr(terms), T, A.ptr(est), A.current_stream()), "pws_shutter_estimate")
-    return (est, terms) if return_terms else est
-
-
-def _check_shutter(r, what):
-    """``rolling_shutter`` as VideoStabilizer takes it: a float in [-1, 1] or "auto"; ValueError otherwise."""
-    if isinstance(r, str):
-        if r != "auto":
-            raise ValueError("%s: rolling_shutter must be a number in [-1, 1] or \"auto\", got %r" % (what, r))
-        return r
-    return PF._check_rolling_shutter(r, what)
-
-
-def _check_max_se(v, what):
-    """``shutter_max_se`` as a float >= 0; ValueError otherwise (NaN included)."""
-    try:
-        f = float(v)
-    except (TypeError, ValueError):
-        raise ValueError("%s: shutter_max_se must be a number >= 0, got %r" % (what, v)) from None
-    if not f >= 0.0:
-        raise ValueError("%s: shutter_max_se must be a number >= 0, got %r" % (what, v))
-    return f
-
-
-def _check_limit(max_crop, levels, relax, sigma, what):
-    """(max_crop or None, levels, relax) checked: max_crop in [0, 0.5] (NaN is a ValueError), levels an int in 1 .. 64, relax in (0, 1] --
-    None: 1 / ceil(3 sigma), the strength recovers from 0 to 1 over the Gaussian's own reach (1.0 at sigma 0, where nothing is limited)."""
-    if max_crop is not None:
-        try:
-            c = float(max_crop)
-        except (TypeError, ValueError):
-            raise ValueError("%s: max_crop must be None or a share of the frame in [0, 0.5], got %r" % (what, max_crop)) from None
-        if not 0.0 <= c <= 0.5:   # (False for NaN)
-            raise ValueError("%s: max_crop must lie in [0, 0.5], got %r" % (what, max_crop))
-        max_crop = c
-    try:
-        lv = int(levels)
-        if lv != levels:
-            raise ValueError
-    except (TypeError, ValueError):
-        raise ValueError("%s: limit_levels must be an integer in 1 .. 64, got %r" % (what, levels)) from None
-    if not 1 <= lv <= 64:
-        raise ValueError("%s: limit_levels must lie in 1 .. 64, got %r" % (what, levels))
-    if relax is None:
-        rx = 1.0 / max(1, int(math.ceil(3.0 * float(sigma))))
-    else:
-        try:
-            rx = float(relax)
-        except (TypeError, ValueError):
-            raise ValueError("%s: limit_relax must be None or a number in (0, 1], got %r" % (what, relax)) from None
-        if not 0.0 < rx <= 1.0:   # (False for NaN)
-            raise ValueError("%s: limit_relax must lie in (0, 1], got %r" % (what, relax))
-    return max_crop, lv, rx
-
-
-def limit_rectangle(fraction, frame_hw, field_hw):
-    """The nodes (i0, i1, j0, j1), inclusive, of every field cell that the centred window of ``fraction`` of the frame touches: with the
-    window's (Ax, Bx, Ay, By) from ``functional.zoom_coefficients`` -- the float32 values that a later zoom to that window samples the field
-    with -- j0 = floor(Ax), j1 = ceil(fmaf(Bx, fw - 1, Ax)), i0 and i1 alike, clamped to the lattice.  (The float64 sum Bx (fw-1) + Ax of
-    float32 operands is exact at these magnitudes, so its one rounding to float32 is fmaf's.)"""
-    import numpy as np
-    h, w = int(frame_hw[0]), int(frame_hw[1])
-    fh, fw = int(field_hw[0]), int(field_hw[1])
-    win = PF._zoom_windows(_centred_window(float(fraction), h, w), 1, (h, w), "limit_path")
-    ax, bx, ay, by = (float(v) for v in PF.zoom_coefficients(win, (h, w), (fh, fw))[0].tolist())
-
-    def span(a, b, n):
-        lo = int(math.floor(a))
-        hi = int(math.ceil(float(np.float32(b * (n - 1) + a))))
-        return min(max(lo, 0), n - 1), min(max(hi, 0), n - 1)
-    i0, i1 = span(ay, by, fh)
-    j0, j1 = span(ax, bx, fw)
-    return i0, i1, j0, j1
-
-
-def limit_path(d, fields, frame_hw, fraction, levels=16, relax=1.0, scene_cuts=None, rates=None, rolling_shutter=0.0, align_corners=False,
-               mode="bilinear"):
-    """Crop-bounded smoothing, the step on its own (csrc/path_limit.hip, csrc/field_reach.hip; include/pwstable.h pws_path_levels,
-    pws_field_reach and pws_path_limit have the definitions): per frame, as much of the smoothing correction as keeps a window of the
-    output covered by the source, eased over time.  ``d`` (T, 6) float64 on the device as ``smooth_path`` returns it (similarities);
-    ``fields`` (T, fh, fw, 2) float32 on the device, the fields that ``functional.compose_fields`` will fold d into, read in place;
-    ``fraction`` = k in (0, 1]: the protected window is the centred window of that fraction of the ``frame_hw`` = (H0, W0) frame
-    (``_centred_window``: the one ``run_video(zoom=k)`` shows).
-    D_t(lam) is the correction scaled back along (log scale, angle, translation): exp(lam ls) Rot(lam phi), lam (d2, d5).  For lam = l /
-    levels, l = 0 .. levels, ``pws_field_reach`` counts the nodes of ``limit_rectangle`` -- every node of every field cell the window
-    touches -- whose composed value would sample outside the source (``compose_fields``' own node function and ``zoom_fields``' coverage
-    rule with ``align_corners`` and ``mode``; with ``rates`` and ``rolling_shutter`` the row-dependent composition).  need[t] is the
-    largest level up to which every count is zero (-1: the field alone leaves the window uncovered), the raw strength max(need, 0) /
-    levels; inside each scene (``scene_cuts`` as for ``smooth_path``) the strength is the largest sequence below it that changes by at
-    most ``relax`` per frame (``zoom_schedule``'s two sweeps; never across a cut); d_limited[t] is d[t] verbatim at strength 1, else
-    D_t(strength[t]).  The source rectangle is convex and the warps interpolate the field linearly between nodes, so zero uncovered
-    nodes in the rectangle means that zoom=k shows no wedge.  After the sweeps a strength lies between grid levels, where feasibility is
-    not proven: the last value returned counts the rectangle's uncovered nodes under d_limited itself.
-    Returns (d_limited (T, 6) float64, strength (T,) float64, need (T,) int32, counts (T,) int32), on the device, no synchronisation;
-    3 + (number of scenes) launches and two small clears.  Integer counts and one fixed order: the same bits on every run.
-    ValueError: tensors other than these, fraction outside (0, 1], levels outside 1 .. 64, relax outside (0, 1], rolling_shutter outside
-    [-1, 1], an unknown mode, bad cuts, a frame below 2 x 2 pixels."""
-    if mode not in PF.INTERPOLATIONS:
-        raise ValueError("mode must be one of %s, got %r" % (PF.INTERPOLATIONS, mode))
-    r = PF._check_rolling_shutter(rolling_shutter, "limit_path")
-    rows = r != 0.0 and rates is not None
-    for name, t, dtype in (("d", d, torch.float64), ("fields", fields, torch.float32)) + ((("rates", rates, torch.float64),) if rows else ()):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
-            raise ValueError("limit_path: %s must be a %s tensor on the device" % (name, dtype))
-    if fields.dim() != 4 or fields.shape[3] != 2 or fields.shape[1] < 2 or fields.shape[2] < 2:
-        raise ValueError("limit_path: fields must be (T, fh, fw, 2) with fh, fw >= 2, got %s" % (tuple(fields.shape),))
-    T, fh, fw = fields.shape[:3]
-    if tuple(d.shape) != (T, 6):
-        raise ValueError("limit_path: d must be (%d, 6), got %s" % (T, tuple(d.shape)))
-    if rows and tuple(rates.shape) != (T, 2, 4):
-        raise ValueError("limit_path: rates must be (%d, 2, 4), got %s" % (T, tuple(rates.shape)))
-    h0, w0 = int(frame_hw[0]), int(frame_hw[1])
-    if h0 < 2 or w0 < 2:
-        raise ValueError("limit_path: the frame must be at least 2 x 2 pixels, got %d x %d" % (w0, h0))
-    try:
-        k = float(fraction)
-    except (TypeError, ValueError):
-        raise ValueError("limit_path: fraction must be a number in (0, 1], got %r" % (fraction,)) from None
-    if not 0.0 < k <= 1.0:
-        raise ValueError("limit_path: fraction must lie in (0, 1], got %r" % (fraction,))
-    _, levels, relax = _check_limit(None, levels, relax, 0.0, "limit_path")
-    cuts = _check_cuts(scene_cuts, T, "limit_path") if scene_cuts is not None and len(scene_cuts) else []
-    d, fields = d.contiguous(), fields.contiguous()
-    rates = rates.contiguous() if rows else None
-    dev = d.device
-    d_out = torch.empty((T, 6), device=dev, dtype=torch.float64)
-    strength = torch.empty((T,), device=dev, dtype=torch.float64)
-    need = torch.empty((T,), device=dev, dtype=torch.int32)
-    left = torch.empty((T, 1), device=dev, dtype=torch.int32)
-    if T == 0:
-        return d_out, strength, need, left.reshape(0)
-    i0, i1, j0, j1 = limit_rectangle(k, (h0, w0), (fh, fw))
-    L, stream = A.lib(), A.current_stream()
-    table = torch.empty((T, levels + 1, 6), device=dev, dtype=torch.float64)
-    counts = torch.empty((T, levels + 1), device=dev, dtype=torch.int32)
-
-    def reach(tab, lv, out):
-        A.check(L.pws_field_reach(A.ptr(fields), T, fh, fw, A.ptr(tab), lv, A.ptr(rates), r if rows else 0.0, i0, i1, j0, j1, h0, w0,
-                                  PF._ac(align_corners), int(mode == "bicubic"), A.ptr(out), stream), "pws_field_reach")
-    A.check(L.pws_path_levels(A.ptr(d), T, levels, A.ptr(table), stream), "pws_path_levels")
-    reach(table, levels, counts)
-    for a, b in _scenes(T, cuts):
-        A.check(L.pws_path_limit(A.ptr(d[a:b]), A.ptr(counts[a:b]), b - a, levels, relax, A.ptr(need[a:b]), A.ptr(strength[a:b]),
-                                 A.ptr(d_out[a:b]), stream), "pws_path_limit")
-    reach(d_out, 0, left)   # (T, 6) is a (T, 1, 6) table
-    return d_out, strength, need, left.reshape(T)
-
-
-def _signal_score(v):
-    """One signal's stability score over a scene of m frames; v[k] is the motion of pair k (v[0] is not read)."""
-    import numpy as np
-    m = len(v)
-    p = np.zeros(m, np.float64)
-    for k in range(1, m):
-        p[k] = p[k - 1] + v[k]
-    p = p - (p[0] + (p[m - 1] - p[0]) * (np.arange(m, dtype=np.float64) / float(m - 1)))
-    e = np.abs(np.fft.fft(p)) ** 2
-    e = e[1:m // 2]
-    total = float(e.sum())
-    return 1.0 if total == 0.0 else float(e[:5].sum()) / total
-
-
-def stability_scores(motion, scene_cuts=None):
-    """The PWStableNet paper's stability metric over a clip's per-pair motion (``global_motion``; (T, 4) = (a, b, tx, ty), a tensor on either
-    side or an array; host arithmetic, float64).  Per scene -- ``scene_cuts``: sorted indices at which a new scene starts; the pair at a cut
-    does not count -- three signals are scored, tx, ty and theta = atan2(b, a): the path p[0] = 0, p[k] = p[k-1] + v[k] over the scene's m
-    frames, minus the straight line through its two end points; E = |FFT(p)|^2 over bins 1 .. m//2 - 1; the score is the first five bins
-    over all of them (1.0 when the total is 0: a still camera).  The published definition takes the FFT of the raw path, under which a steady
-    pan's own ramp hides the shake (INTEGRATION.md has the figures); the line is the one deviation.  A scene of fewer than 24 frames, or with
-    a NaN pair, scores NaN.  Returns {"stability", "translation", "rotation": the clip's values -- the frame-weighted mean of the scored
-    scenes, NaN without any -- and "scenes": [{"start", "end", "translation" = min(score x, score y), "rotation", "stability" = the smaller
-    of the two}]}.  The scores are pinned on synthetic clips only; no real footage or trained weights were available to validate them."""
-    import numpy as np
-    if isinstance(motion, torch.Tensor):
-        motion = motion.detach().to("cpu", torch.float64).numpy()
-    motion = np.asarray(motion, np.float64)
-    if motion.ndim != 2 or motion.shape[1] != 4:
-        raise ValueError("stability_scores: motion must be (T, 4): a, b, tx, ty")
-    T = motion.shape[0]
-    cuts = _check_cuts(scene_cuts, T, "stability_scores") if scene_cuts is not None and len(scene_cuts) else []
-    nan, scenes = float("nan"), []
-    for a, b in _scenes(T, cuts):
-        rows = motion[a:b]
-        if b - a < 24 or not np.isfinite(rows[1:]).all():
-            tr = ro = nan
-        else:
-            tr = min(_signal_score(rows[:, 2]), _signal_score(rows[:, 3]))
-            ro = _signal_score(np.arctan2(rows[:, 1], rows[:, 0]))
-        scenes.append({"start": a, "end": b, "translation": tr, "rotation": ro, "stability": min(tr, ro) if tr == tr else nan})
-
-    def clip(key):
-        ok = [s for s in scenes if s[key] == s[key]]
-        return sum(s[key] * (s["end"] - s["start"]) for s in ok) / sum(s["end"] - s["start"] for s in ok) if ok else nan
-    return {"stability": clip("stability"), "translation": clip("translation"), "rotation": clip("rotation"), "scenes": scenes}
-
-
-def find_scene_cuts(scores, threshold=0.25, min_scene=16):
-    """The cut rule over a clip's ``scene_scores`` (a tensor on either side, an array or a sequence; host arithmetic): the sorted indices t,
-    1 <= t < T, at which a new scene starts.  t is a cut if ``score[t] > threshold`` and t lies at least ``min_scene`` frames after the
-    previous accepted cut (or after frame 0); a candidate closer than that is dropped and does not restart the count (a photo flash gives two
-    high scores a frame or two apart, and one cut at most).  The rule is causal -- nothing after t is read -- so run_video can apply it
-    chunk by chunk while the clip is still uploading."""
-    if isinstance(scores, torch.Tensor):
-        scores = scores.detach().to("cpu", torch.float32).tolist()
-    cuts, last = [], 0
-    for t, v in enumerate(scores):
-        if t >= 1 and float(v) > threshold and t - last >= min_scene:
-            cuts.append(t)
-            last = t
-    return cuts
-
-
-def _check_cuts(cuts, n, what):
-    """scene_cuts as a list of ints: sorted, unique, within 1 .. n-1 (ValueError otherwise)."""
-    if isinstance(cuts, torch.Tensor):
-        cuts = cuts.tolist()
-    try:
-        cuts = [int(c) for c in cuts]
-    except (TypeError, ValueError):
-        raise ValueError("%s: scene_cuts must be a sequence of frame indices" % what) from None
-    if any(not 1 <= c < n for c in cuts) or any(c2 <= c1 for c1, c2 in zip(cuts, cuts[1:])):
-        raise ValueError("%s: scene_cuts must be sorted, unique and within 1 .. %d, got %r" % (what, n - 1, cuts))
-    return cuts
-
-
-def _scenes(n, cuts):
-    """The scenes [a, b) that the cuts split 0 .. n into."""
-    edges = [0] + list(cuts) + [n]
-    return list(zip(edges[:-1], edges[1:]))
-
-
-def _bounds_rows(bounds, what):
-    """Per-frame bounds (a tensor on either side, an array or a sequence) as T rows of 4 floats."""
-    if isinstance(bounds, torch.Tensor):
-        bounds = bounds.detach().to("cpu", torch.float64).tolist()
-    bounds = [[float(v) for v in row] for row in bounds]
-    if any(len(row) != 4 for row in bounds):
-        raise ValueError("%s: bounds must be (T, 4): top, bottom, left, right" % what)
-    return bounds
-
-
-def _centred_window(k, h, w):
-    """The window (x0, x1, y0, y1) of the fraction k of an h x w frame around its centre (float64, in this order of operations)."""
-    return (0.5 * w - 0.5 * k * w, 0.5 * w + 0.5 * k * w, 0.5 * h - 0.5 * k * h, 0.5 * h + 0.5 * k * h)
-
-
-def auto_crop_window(bounds, frame_hw, output_hw=None, period=30, scene_cuts=None):
-    """The reference's crop recurrence (main_new.py:575-603) over a clip's per-frame bounds (``field_homography``; (T, 4) top, bottom,
-    left, right in source pixels, a tensor on either side or an array): the window starts at the whole H0 x W0 frame, and each frame i
-    with period//2 < i < T - period//2 pulls every edge that lies outside the frame's bounds half way towards them, in float64.  Returns
-    (x_start, x_end, y_start, y_end), scaled to ``output_hw`` = (height, width) of the output frame when given, for run_video's ``crop``.
-    ValueError when a frame the recurrence reads has NaN bounds, or when the window is empty.
-    scene_cuts (sorted indices at which a new scene starts): the reference's end rule holds per scene -- frame i of scene [a, b) is read only
-    if a + period//2 < i < b - period//2, since the frames next to a cut see a clamped window as those at the clip's ends do -- and the one
-    window is carried from scene to scene (one output size serves the whole clip)."""
-    bounds = _bounds_rows(bounds, "auto_crop_window")
-    h0, w0 = int(frame_hw[0]), int(frame_hw[1])
-    T, half, rate = len(bounds), int(period) // 2, 0.5
-    x0, x1, y0, y1 = 0.0, float(w0), 0.0, float(h0)
-    scenes = _scenes(T, _check_cuts(scene_cuts, T, "auto_crop_window")) if scene_cuts is not None and len(scene_cuts) else [(0, T)]
-    for i in (i for a, b in scenes for i in range(a + half + 1, b - half)):
-        top, bottom, left, right = bounds[i]
-        if not all(math.isfinite(v) for v in bounds[i]):
-            raise ValueError("auto_crop_window: frame %d has no homography (bounds %r)" % (i, bounds[i]))
-        if y0 < top:
-            y0 += (top - y0) * rate
-        if y1 > bottom:
-            y1 -= (y1 - bottom) * rate
-        if x0 < left:
-            x0 += (left - x0) * rate
-        if x1 > right:
-            x1 -= (x1 - right) * rate
-    if output_hw is not None:
-        sy, sx = int(output_hw[0]) / h0, int(output_hw[1]) / w0
-        x0, x1, y0, y1 = x0 * sx, x1 * sx, y0 * sy, y1 * sy
-    if not (int(x1) > int(x0) and int(y1) > int(y0)):
-        raise ValueError("auto_crop_window: the crop window x [%g, %g) y [%g, %g) is empty" % (x0, x1, y0, y1))
-    return x0, x1, y0, y1
-
-
-def zoom_window(window, frame_hw):
-    """The largest window of the frame's aspect centred inside ``window`` = (x0, x1, y0, y1) (source-pixel edge coordinates, as
-    ``auto_crop_window(..., output_hw=None)`` returns them): with k = min((x1 - x0) / W0, (y1 - y0) / H0) and the window's centre (cx, cy),
-    (cx - k W0 / 2, cx + k W0 / 2, cy - k H0 / 2, cy + k H0 / 2), kept inside ``window`` against the last rounding.  Zooming the H0 x W0
-    frame into it scales both axes alike (vid.stab's ``zoom``).  Host arithmetic, float64."""
-    x0, x1, y0, y1 = (float(v) for v in window)
-    h0, w0 = int(frame_hw[0]), int(frame_hw[1])
-    if not (x1 > x0 and y1 > y0 and h0 > 0 and w0 > 0):
-        raise ValueError("zoom_window: the window x [%g, %g) y [%g, %g) is empty" % (x0, x1, y0, y1))
-    k = min((x1 - x0) / w0, (y1 - y0) / h0)
-    cx, cy = 0.5 * (x0 + x1), 0.5 * (y0 + y1)
-    return (max(x0, cx - 0.5 * k * w0), min(x1, cx + 0.5 * k * w0), max(y0, cy - 0.5 * k * h0), min(y1, cy + 0.5 * k * h0))
-
-
-def zoom_schedule(bounds, frame_hw, speed=0.002, min_window=0.5, scene_cuts=None):
-    """Per-frame zoom windows from a clip's per-frame bounds (``field_homography``; (T, 4) top, bottom, left, right in source pixels): vid.stab's
-    ``optzoom=2``.  Every window is centred on the frame's centre and has the frame's aspect, window t = the fraction k[t] of the frame.
-    Frame t asks for k_req[t] = min(1, 2 min(W0/2 - left, right - W0/2) / W0, 2 min(H0/2 - top, bottom - H0/2) / H0), the largest centred window
-    inside its bounds; kc = max(k_req, min_window) (a frame that asks for more zoom than 1 / min_window keeps some wedge); inside each scene
-    k[t] = min over s of kc[s] + speed |t - s|: the largest schedule that never exceeds kc and never changes by more than ``speed`` per frame
-    (two linear sweeps).  scene_cuts: sorted indices at which a new scene starts; the schedule is free to jump there.  NaN bounds are a
-    ValueError naming the frame.  Returns T windows (x0, x1, y0, y1) for ``zoom_fields`` / ``run(zoom=)``.  Host arithmetic, float64."""
-    bounds = _bounds_rows(bounds, "zoom_schedule")
-    h0, w0 = int(frame_hw[0]), int(frame_hw[1])
-    speed, min_window = float(speed), float(min_window)
-    if not (speed >= 0.0 and 0.0 < min_window <= 1.0):
-        raise ValueError("zoom_schedule: speed must be >= 0 and min_window in (0, 1], got %r and %r" % (speed, min_window))
-    T = len(bounds)
-    kc = []
-    for t, row in enumerate(bounds):
-        if not all(math.isfinite(v) for v in row):
-            raise ValueError("zoom_schedule: frame %d has no homography (bounds %r)" % (t, row))
-        top, bottom, left, right = row
-        k_req = min(1.0, 2.0 * min(0.5 * w0 - left, right - 0.5 * w0) / w0, 2.0 * min(0.5 * h0 - top, bottom - 0.5 * h0) / h0)
-        kc.append(max(k_req, min_window))
-    k = list(kc)
-    for a, b in (_scenes(T, _check_cuts(scene_cuts, T, "zoom_schedule")) if scene_cuts is not None and len(scene_cuts) else [(0, T)]):
-        for t in range(a + 1, b):
-            k[t] = min(k[t], k[t - 1] + speed)
-        for t in range(b - 2, a - 1, -1):
-            k[t] = min(k[t], k[t + 1] + speed)
-    return [_centred_window(v, h0, w0) for v in k]
 
 
 def _windows(gray_padded, start, count, period):
@@ -897,8 +250,7 @@ class VideoStabilizer:
             out[s:e].copy_(self.net(_windows(gp, start, e - s, self.period), False))
 
     @torch.no_grad()
-    def run(self, gray, frames, halo_left=0, halo_right=0, out=None, pixel_format="bgr24", scene_cuts=None, keep_from=None, _keep_wait=None,
-            zoom=None, _zoom_unc=None, _rigid_stats=None, _mosaic_pad=None, _hom_out=None):
+    def run(self, gray, frames, halo_left=0, halo_right=0, out=None, pixel_format="bgr24", scene_cuts=None, keep_from=None, zoom=None):
         """gray: (T + halo_left + halo_right, 256, 256) float32 in [-1,1] (``x/255*2-1`` as the reference, :650) for the T
         frames to stabilise plus whatever real neighbours exist on either side (up to period//2); frames: (T, C, H, W)
         float32 0..255, or (T, H, W, 3) uint8 as OpenCV delivers them (then the warp runs in the uint8 kernel: 4x less
@@ -928,8 +280,7 @@ class VideoStabilizer:
         batch is warped ``functional.mosaic_borders_`` runs once per scene piece (slices along dim 0, cut at ``scene_cuts``) with
         ``self.mosaic_radius``; then the frames are copied out.  Halo frames are never warped and so are no donors: a shard's first and last
         ``mosaic_radius`` frames do not promise the unsharded clip's bytes inside the wedges.  ``self.mosaic_unfilled`` (T,) int32 is left on
-        the device (no synchronisation).  Not with a zoom (ValueError).  (_mosaic_pad, run_video's: the buffers get that many spare frames at
-        either end and are returned unfilled, (warped, fields), instead of the output.)
+        the device (no synchronisation).  Not with a zoom (ValueError).
         VideoStabilizer(rigidity=r), r > 0: each batch's field is fitted (``field_homography``) and blended towards its homography
         (``functional.rigid_fields``, into a fresh tensor: the generator's output may be a graph's static buffer) right after the generator;
         the zoom, the warp and borders="keep" all see the adjusted field.  Nothing here depends on other frames, so halos are fine; frames
@@ -949,137 +300,139 @@ class VideoStabilizer:
             raise ValueError("run: zoom removes the wedges that borders=\"keep\" fills: choose one")
         if zoom is not None and mosaic:
             raise ValueError("run: zoom removes the wedges that borders=\"mosaic\" fills: choose one")
-        if mosaic and frames.dtype not in (torch.uint8, torch.uint16):
-            raise ValueError("run: borders=\"mosaic\" is for the integer pixel formats (uint8 / uint16 frames), got %s" % (frames.dtype,))
-        if _mosaic_pad is None:
-            self.mosaic_unfilled = torch.empty((frames.shape[0],), device=self.device, dtype=torch.int32) if mosaic else None
-        if keep and frames.dtype not in (torch.uint8, torch.uint16):
-            raise ValueError("run: borders=\"keep\" is for the integer pixel formats (uint8 / uint16 frames), got %s" % (frames.dtype,))
-        edging = self.edge != "pad"
-        if edging and frames.dtype not in (torch.uint8, torch.uint16):
-            raise ValueError("run: edge=%r is for the integer pixel formats (uint8 / uint16 frames), got %s" % (self.edge, frames.dtype))
+        if mosaic:
+            _check_integer_frames(frames, "run", "borders=\"mosaic\"")
+        if keep:
+            _check_integer_frames(frames, "run", "borders=\"keep\"")
+        if self.edge != "pad":
+            _check_integer_frames(frames, "run", "edge=%r" % (self.edge,))
         fmt = PF.frame_format(pixel_format, frames, "run", float_frames=True)   # (from here on the format is this record)
         if not (0 <= halo_left <= half and 0 <= halo_right <= half):
             raise ValueError("halo must be within [0, %d]" % half)
         T = frames.shape[0]
         if gray.shape[0] != T + halo_left + halo_right:
             raise ValueError("gray has %d frames, expected %d + %d + %d" % (gray.shape[0], T, halo_left, halo_right))
-        on_host = not frames.is_cuda
-        dev = self.device
         cuts = _check_cuts(scene_cuts, gray.shape[0], "run") if scene_cuts is not None else None
-        gray_d = gray.to(dev, non_blocking=True) if not gray.is_cuda else gray  # 256 KB per frame: copied once
-        if out is None:
-            out = torch.empty_like(frames, pin_memory=on_host) if on_host else torch.empty_like(frames)
-        if zoom is not None or rigid or _hom_out is not None:
+        if zoom is not None or rigid:
             frame_hw = fmt.frame_shape(frames)[1:]
         if rigid:
             _check_lattice(int(frame_hw[0]), int(frame_hw[1]), "rigidity > 0")
-        if _rigid_stats is not None:   # run_video's, a slice per chunk: it publishes the whole tensors itself, once every chunk is issued
-            rres, runf = _rigid_stats
-        else:
-            rres, runf = (torch.empty((T,), device=dev, dtype=torch.float32), torch.empty((T,), device=dev, dtype=torch.int32)) if rigid else (None, None)
-            self.rigid_residual, self.rigid_unfit = rres, runf
+        windows = PF._zoom_windows(zoom, T, frame_hw, "run") if zoom is not None else None
+        # every check has passed: from here on the previous call's results go
+        on_host = not frames.is_cuda
+        dev = self.device
+        self.mosaic_unfilled = torch.empty((T,), device=dev, dtype=torch.int32) if mosaic else None
+        gray_d = gray.to(dev, non_blocking=True) if not gray.is_cuda else gray  # 256 KB per frame: copied once
+        if out is None:
+            out = torch.empty_like(frames, pin_memory=on_host) if on_host else torch.empty_like(frames)
+        rres, runf = (torch.empty((T,), device=dev, dtype=torch.float32), torch.empty((T,), device=dev, dtype=torch.int32)) if rigid else (None, None)
+        self.rigid_residual, self.rigid_unfit = rres, runf
         if zoom is not None:
-            self.zoom_windows = PF._zoom_windows(zoom, T, frame_hw, "run")
-            self.zoom_uncovered = _zoom_unc if _zoom_unc is not None else torch.empty((T,), device=dev, dtype=torch.int32)
-            zcoef = None   # (the field's size is the generator's to say: formed at the first batch, uploaded once)
+            self.zoom_windows, self.zoom_uncovered = windows, torch.empty((T,), device=dev, dtype=torch.int32)
         if T == 0:
             return out
-        gp, batches = self._layout(gray_d.contiguous(), halo_left, halo_right, T, cuts)
-        compute = torch.cuda.current_stream(dev)
-        h2d, d2h = (torch.cuda.Stream(dev), torch.cuda.Stream(dev)) if on_host else (None, None)
+        copies = (torch.cuda.Stream(dev), torch.cuda.Stream(dev)) if on_host else (None, None)
+        wall, fall = self._batches(fmt, gray_d, frames, halo_left, halo_right, cuts, out, copies, pad=0 if mosaic else None, keep_from=keep_from,
+                                   zoom=(windows, self.zoom_uncovered) if zoom is not None else None, rigid_stats=(rres, runf))
+        if mosaic:
+            for a, b in _scenes(halo_left + T, cuts or (), halo_left):   # one scene piece per call: donors never cross a cut
+                a, b = a - halo_left, b - halo_left
+                PF.mosaic_borders_(wall[a:b], fall[a:b], self.mosaic_radius, pixel_format=pixel_format, align_corners=self.align_corners,
+                                   mode=self.interpolation, _unfilled=self.mosaic_unfilled[a:b])
+            _hand_over(wall, out, torch.cuda.current_stream(dev), copies[1])
+            if on_host:
+                copies[1].synchronize()
+        return out
 
-        def fetch(k):
-            return _prefetch(frames, batches[k][0], batches[k][1], h2d, dev)
-        nxt = fetch(0)
+    def _warp(self, fmt, source, field, out=None):
+        """One batch's warp -- the ``source`` frames by ``field``, into ``out`` if given -- and then the edge fill, if any: before a mosaic
+        pass, where donors are read only where they are covered, so that exactly the unfilled positions show it."""
+        source = source.contiguous()
+        warped = PF.warp(source, field, fmt, swap_rb=self.swap_rb, align_corners=self.align_corners, out=out, mode=self.interpolation)
+        if self.edge != "pad":
+            PF.edge_borders_(warped, source, field, self.edge, fmt.name, swap_rb=self.swap_rb, align_corners=self.align_corners,
+                             mode=self.interpolation)
+        return warped
+
+    def _batches(self, fmt, gray, frames, halo_left, halo_right, cuts, out, copies=(None, None), pad=None, keep_from=None, keep_wait=None,
+                 zoom=None, rigid_stats=(None, None), hom_out=None):
+        """The batch loop of run() and of run_video's single pass, arguments checked: ``gray`` on the device, ``frames`` (T > 0 of them) in the
+        format ``fmt``, ``cuts`` a checked list in gray's index space or None.  Per batch: the generator, [the fit and the rigidity blend,]
+        [the zoom,] the warp [and the edge fill], [the keep pass,] and frames s .. e-1 on their way to out[s:e].
+        copies: the (upload, download) streams of host frames; the download stream has been waited for on return.
+        keep_wait: the event behind the pass that wrote ``keep_from``, when another stream did (run_video's other lane).
+        zoom = (windows, uncovered): the T checked windows and the (T,) counts to fill.
+        rigid_stats = (residual, unfit) and hom_out = (M (T, 9), bounds (T, 4)): tensors of the T frames to fill -- run_video's, a slice
+        per chunk, which it publishes itself once every chunk is issued; hom_out: the raw field's fit is kept (run_video(metrics=True)).
+        pad (borders="mosaic"): nothing goes to ``out``.  The frames are warped with black borders into one buffer with ``pad`` spare frames at
+        either end, and the fields that warped them are kept beside it, for the caller to fill.
+        Returns (warped, fields): those two buffers, or (None, None) without ``pad``."""
+        T, dev = frames.shape[0], self.device
+        keep, rigid, mosaic = self.borders == "keep", self.rigidity > 0.0, pad is not None
+        on_host = not frames.is_cuda
+        h2d, d2h = copies
+        rres, runf = rigid_stats
+        if zoom is not None or rigid or hom_out is not None:
+            frame_hw = fmt.frame_shape(frames)[1:]
+        zcoef = None   # (the field's size is the generator's to say: formed at the first batch, uploaded once)
+        gp, batches = self._layout(gray.contiguous(), halo_left, halo_right, T, cuts)
+        compute = torch.cuda.current_stream(dev)
+        nxt = _prefetch(frames, batches[0][0], batches[0][1], h2d, dev)
         pending = []
         cutset, prev = set(cuts or ()), None
-        pad, wall, fall = _mosaic_pad or 0, None, None   # borders="mosaic": the call's warped frames and fields, `pad` spare frames at either end
+        wall, fall = None, None   # borders="mosaic": the call's warped frames and fields
         for k, (s, e, start) in enumerate(batches):
             cur, ev = nxt
             if k + 1 < len(batches):
-                nxt = fetch(k + 1)  # overlaps with this batch's compute
+                nxt = _prefetch(frames, batches[k + 1][0], batches[k + 1][1], h2d, dev)  # overlaps with this batch's compute
             if ev is not None:
                 compute.wait_event(ev)
             win = _windows(gp, start, e - s, self.period)
             field = self.net(win, False)
-            if _hom_out is not None:   # run_video(metrics=True): the raw field's fit is kept, (T, 9) and (T, 4) slices of this call's frames
+            if hom_out is not None or rigid:
                 field = field.contiguous()
-                hom = _hom_out[0][s:e]
-                _field_homography(field, int(frame_hw[0]), int(frame_hw[1]), hom, _hom_out[1][s:e])
+                if hom_out is not None:
+                    hom, bounds = hom_out[0][s:e], hom_out[1][s:e]
+                else:
+                    hom, bounds = torch.empty((e - s, 9), device=dev, dtype=torch.float64), torch.empty((e - s, 4), device=dev, dtype=torch.float32)
+                _field_homography(field, int(frame_hw[0]), int(frame_hw[1]), hom, bounds)
                 if rigid:
                     field = PF._field_rigid(field, hom, frame_hw, self.rigidity, torch.empty_like(field), rres[s:e], runf[s:e])
-            elif rigid:
-                field = field.contiguous()
-                hom = torch.empty((e - s, 9), device=dev, dtype=torch.float64)
-                _field_homography(field, int(frame_hw[0]), int(frame_hw[1]), hom, torch.empty((e - s, 4), device=dev, dtype=torch.float32))
-                field = PF._field_rigid(field, hom, frame_hw, self.rigidity, torch.empty_like(field), rres[s:e], runf[s:e])
             if zoom is not None:
                 if zcoef is None:
-                    zcoef = PF.zoom_coefficients(self.zoom_windows, frame_hw, field.shape[1:3]).to(dev, non_blocking=True)
+                    zcoef = PF.zoom_coefficients(zoom[0], frame_hw, field.shape[1:3]).to(dev, non_blocking=True)
                 field = field.contiguous()
-                field = PF._field_zoom(field, zcoef[s:e], frame_hw, self.align_corners, self.interpolation, torch.empty_like(field),
-                                       self.zoom_uncovered[s:e])
+                field = PF._field_zoom(field, zcoef[s:e], frame_hw, self.align_corners, self.interpolation, torch.empty_like(field), zoom[1][s:e])
             if mosaic:   # black borders into the call's buffer; the fill needs every batch
                 if wall is None:
                     wall = torch.empty((T + 2 * pad,) + tuple(frames.shape[1:]), device=dev, dtype=frames.dtype)
                     fall = torch.empty((T + 2 * pad,) + tuple(field.shape[1:]), device=dev, dtype=torch.float32)
-                PF.warp(cur.contiguous(), field, fmt, swap_rb=self.swap_rb, align_corners=self.align_corners, out=wall[pad + s:pad + e],
-                        mode=self.interpolation)
-                if edging:   # before the mosaic pass: donors are read only where they are covered, so exactly the unfilled positions show it
-                    PF.edge_borders_(wall[pad + s:pad + e], cur.contiguous(), field, self.edge, pixel_format, swap_rb=self.swap_rb,
-                                     align_corners=self.align_corners, mode=self.interpolation)
+                self._warp(fmt, cur, field, wall[pad + s:pad + e])
                 fall[pad + s:pad + e].copy_(field)
                 if on_host:
                     cur.record_stream(compute)
                 continue
-            warped = PF.warp(cur.contiguous(), field, fmt, swap_rb=self.swap_rb, align_corners=self.align_corners, mode=self.interpolation)
-            if edging:
-                PF.edge_borders_(warped, cur.contiguous(), field, self.edge, pixel_format, swap_rb=self.swap_rb, align_corners=self.align_corners,
-                                 mode=self.interpolation)
+            warped = self._warp(fmt, cur, field)
             if keep:
                 if (s + halo_left) in cutset or (s == 0 and keep_from is None):
                     init, src = cur.contiguous()[0], True   # a scene's first frame: its own source, as the warp would write it
                 elif prev is not None:
                     init, src = prev, False
                 else:   # the caller's history: possibly written on another stream (run_video's other lane)
-                    if _keep_wait is not None:
-                        compute.wait_event(_keep_wait)
+                    if keep_wait is not None:
+                        compute.wait_event(keep_wait)
                     keep_from.record_stream(compute)
                     init, src = keep_from, False
-                PF.keep_borders_(warped, field, init, pixel_format, initial_is_source=src, swap_rb=self.swap_rb, align_corners=self.align_corners,
+                PF.keep_borders_(warped, field, init, fmt.name, initial_is_source=src, swap_rb=self.swap_rb, align_corners=self.align_corners,
                                  mode=self.interpolation)
                 prev = warped[-1]   # (a view: keeps the batch alive until the next one has read it)
+            _hand_over(warped, out[s:e], compute, d2h)
             if on_host:
-                done = torch.cuda.Event()
-                done.record(compute)
-                with torch.cuda.stream(d2h):
-                    d2h.wait_event(done)
-                    out[s:e].copy_(warped, non_blocking=True)
-                warped.record_stream(d2h)
                 cur.record_stream(compute)
                 pending.append(warped)
-            else:
-                out[s:e].copy_(warped)
-        if mosaic:
-            if _mosaic_pad is not None:
-                return wall, fall
-            edges = [0] + [c - halo_left for c in (cuts or ()) if 0 < c - halo_left < T] + [T]
-            for a, b in zip(edges[:-1], edges[1:]):   # one scene piece per call: donors never cross a cut
-                PF.mosaic_borders_(wall[a:b], fall[a:b], self.mosaic_radius, pixel_format=pixel_format, align_corners=self.align_corners,
-                                   mode=self.interpolation, _unfilled=self.mosaic_unfilled[a:b])
-            if on_host:
-                done = torch.cuda.Event()
-                done.record(compute)
-                with torch.cuda.stream(d2h):
-                    d2h.wait_event(done)
-                    out.copy_(wall, non_blocking=True)
-                wall.record_stream(d2h)
-            else:
-                out.copy_(wall)
-        if on_host:
+        if on_host and not mosaic:
             d2h.synchronize()
-        return out
+        return wall, fall
 
     @torch.no_grad()
     def run_video(self, frames, chunk=32, half_size_output=False, frames_are_rgb=False, halo_left=0, halo_right=0, crop=None,
@@ -1261,6 +614,36 @@ class VideoStabilizer:
         edge, crop, zoom, rigidity, wobble, rolling_shutter, in_flight, scene_cuts and metrics.  ValueError: max_crop without smooth > 0.
         Returns (T, H, W, 3) -- or (T, H/2, W/2, 3) / (T, height, width, 3), or the crop window of it -- uint8 on the inputs' side; for YUV
         (T, oh * 3 // 2, ow) of the output (or crop window) size oh x ow."""
+        plan = self._plan(frames, chunk, half_size_output, frames_are_rgb, halo_left, halo_right, crop, output_size, in_flight, pixel_format,
+                          scene_cuts, scene_threshold, scene_min_len, zoom, zoom_speed, zoom_min, metrics)
+        self._reset(plan)
+        call = _Call(self, plan, frames)
+        if plan.T == 0:
+            return call.out
+        call.open()   # buffers and lanes
+        try:
+            for c in range(len(plan.chunks)):
+                call.chunk(c)   # pass 1, or the single pass
+            call.drain()
+        finally:
+            call.join()
+        call.publish()
+        if plan.two_pass:
+            call.between_passes()
+            call.pass2()
+        if plan.metrics:
+            call.measure()
+        if plan.on_host:
+            call.down.synchronize()
+        return call.out
+
+    def _plan(self, frames, chunk=32, half_size_output=False, frames_are_rgb=False, halo_left=0, halo_right=0, crop=None, output_size=None,
+              in_flight=1, pixel_format="bgr24", scene_cuts=None, scene_threshold=0.25, scene_min_len=16, zoom=None, zoom_speed=0.002,
+              zoom_min=0.5, metrics=None):
+        """run_video's arguments and this object's options resolved into a StreamPlan, or the ValueError they deserve: every check that
+        needs no data from the device, in one fixed order (when two rules are violated the earlier one speaks).  Host arithmetic on
+        ``frames``' shape, dtype and side only: no device call, no allocation, nothing of ``self`` changes, and a CPU or "meta" tensor
+        will do.  What depends on the clip -- the automatic crop, the zoom windows, an empty even window -- is run_video's to raise."""
         half = self.period // 2
         if not (0 <= halo_left <= half and 0 <= halo_right <= half):
             raise ValueError("halo must be within [0, %d]" % half)
@@ -1268,8 +651,6 @@ class VideoStabilizer:
         T = n_all - halo_left - halo_right
         if T < 0:
             raise ValueError("frames holds %d frames, fewer than the halos %d + %d" % (n_all, halo_left, halo_right))
-        on_host = not frames.is_cuda
-        dev = self.device
         fmt = PF.frame_format(pixel_format, frames, "run_video")   # (from here on the format is this record)
         yuv = fmt.packed   # output sizes and crop edges: multiples of the subsampling per axis (4:2:0: even)
         mx, my = fmt.multiples if yuv else (1, 1)
@@ -1288,27 +669,24 @@ class VideoStabilizer:
             if fmt.chroma == 0:
                 raise ValueError("run_video: the %s output size %d x %d must be even" % (pixel_format, ow, oh))
             raise ValueError("run_video: the %s output size %d x %d must be a multiple of %d x %d" % (pixel_format, ow, oh, mx, my))
+        halos = bool(halo_left or halo_right)
+        second_pass = self.borders not in ("keep", "mosaic")   # (they finish every frame in the single pass)
         auto = isinstance(crop, str)
         if auto:
             if crop != "auto":
                 raise ValueError("crop must be None, \"auto\" or (x_start, x_end, y_start, y_end[, threshold])")
-            if halo_left or halo_right:
+            if halos:
                 raise ValueError("run_video: crop=\"auto\" needs the whole clip (a shard cannot see the clip's crop recurrence): gather "
                                  "the shards' field_homography bounds and pass crop=auto_crop_window(...)")
-            if self.borders in ("keep", "mosaic"):
+            if not second_pass:
                 raise ValueError("run_video: crop=\"auto\" removes the wedges that borders=\"%s\" fills: choose one" % self.borders)
             _check_lattice(h, w)
-        self.zoom_windows = self.zoom_uncovered = None
-        self.rigid_residual = self.rigid_unfit = None
-        self.mosaic_unfilled = None
-        self.motion_in = self.motion_out = self.motion_inliers_in = self.motion_inliers_out = self._report = None
         metrics = self.metrics if metrics is None else bool(metrics)
-        if self.edge != "pad" and frames.dtype not in (torch.uint8, torch.uint16):
-            raise ValueError("run_video: edge=%r is for the integer pixel formats (uint8 / uint16 frames), got %s" % (self.edge, frames.dtype))
+        if self.edge != "pad":
+            _check_integer_frames(frames, "run_video", "edge=%r" % (self.edge,))
         mosaic, radius = self.borders == "mosaic", self.mosaic_radius
         if mosaic:
-            if frames.dtype not in (torch.uint8, torch.uint16):
-                raise ValueError("run_video: borders=\"mosaic\" is for the integer pixel formats (uint8 / uint16 frames), got %s" % (frames.dtype,))
+            _check_integer_frames(frames, "run_video", "borders=\"mosaic\"")
             if max(1, int(in_flight)) > 1:
                 raise ValueError("run_video: borders=\"mosaic\" finishes a chunk one chunk late, which across two lanes needs an event design of "
                                  "its own: use in_flight=1")
@@ -1317,16 +695,16 @@ class VideoStabilizer:
         rigid = self.rigidity > 0.0
         if rigid:
             _check_lattice(h, w, "rigidity > 0")
-        zmode = None
+        zmode = zwin = None
         if zoom is not None:
             if crop is not None:
                 raise ValueError("run_video: zoom fills the frame that a crop would cut: give zoom or crop, not both")
-            if self.borders in ("keep", "mosaic"):
+            if not second_pass:
                 raise ValueError("run_video: zoom removes the wedges that borders=\"%s\" fills: choose one" % self.borders)
             if isinstance(zoom, str):
                 if zoom not in ("auto", "adaptive"):
                     raise ValueError("zoom must be None, a fraction in (0, 1], \"auto\" or \"adaptive\", got %r" % (zoom,))
-                if halo_left or halo_right:
+                if halos:
                     raise ValueError("run_video: zoom=%r needs the whole clip (a shard cannot see the clip's bounds): gather the shards' "
                                      "field_homography bounds and pass windows to run(zoom=)" % (zoom,))
                 _check_lattice(h, w, "zoom=%r" % (zoom,))
@@ -1341,337 +719,53 @@ class VideoStabilizer:
                 zmode = "fixed"
                 zwin = _centred_window(zk, h, w)
         smoothing = self.smooth > 0.0
-        self.smooth_motion = self.smooth_inliers = self.smooth_path = self.smooth_correction = self.smooth_uncovered = None
-        self.shutter_rates = self.shutter_estimate = self.rolling_shutter_used = None
         rs = _check_shutter(self.rolling_shutter, "run_video")   # (the attributes can be set after construction)
         max_se = _check_max_se(self.shutter_max_se, "run_video")
         if rs != 0.0 and not smoothing:
             raise ValueError("run_video: rolling_shutter=%r needs smooth > 0" % (self.rolling_shutter,))
         max_crop, limit_levels, limit_relax = _check_limit(self.max_crop, self.limit_levels, self.limit_relax, self.smooth, "run_video")
-        self.limit_strength = self.limit_need = self.limit_uncovered = self.smooth_correction_unlimited = None
         if max_crop is not None and not smoothing:   # (the attributes can be set after construction)
             raise ValueError("run_video: max_crop=%r needs smooth > 0" % (self.max_crop,))
         if smoothing:
-            if halo_left or halo_right:
+            if halos:
                 raise ValueError("run_video: smooth > 0 needs the whole clip (a shard cannot see the scene's path)")
-            if self.borders in ("keep", "mosaic"):
+            if not second_pass:
                 raise ValueError("run_video: smooth > 0 warps in a second pass, which borders=\"%s\" does not have yet" % self.borders)
         wob = PF._check_wobble(self.wobble, "run_video", zero_ok=True)   # (the attribute can be set after construction)
-        self.wobble_removed = self.wobble_unfit = None
         if wob > 0.0:
-            if halo_left or halo_right:
+            if halos:
                 raise ValueError("run_video: wobble > 0 needs the whole clip (a shard cannot see its neighbours' fields)")
-            if self.borders in ("keep", "mosaic"):
+            if not second_pass:
                 raise ValueError("run_video: wobble > 0 warps in a second pass, which borders=\"%s\" does not have yet" % self.borders)
             _check_lattice(h, w, "wobble > 0")
-        lattice = h >= 300 and w >= 600   # the homography fit's
         two_pass = auto or zmode in ("auto", "adaptive") or smoothing or wob > 0.0   # pass 1: fields and bounds; the host's decision; pass 2: the warp
         detect = isinstance(scene_cuts, str)
         if detect and scene_cuts != "auto":
             raise ValueError("scene_cuts must be None, \"auto\" or a sorted sequence of frame indices, got %r" % (scene_cuts,))
-        cuts = [] if detect or scene_cuts is None else _check_cuts(scene_cuts, n_all, "run_video")
-        self.scene_cuts = cuts
+        cuts = () if detect or scene_cuts is None else tuple(_check_cuts(scene_cuts, n_all, "run_video"))
+        window = crop if auto or crop is None else _crop_window(fmt, oh, ow, crop)
+        # chunk bounds in the index space of `frames`: the first / last chunk carry the halo frames with them.  (An empty clip has none, and
+        # returns before anything reads ``chunk`` or ``in_flight``: whatever they hold is no error there, as it never was)
+        chunks = tuple((s if s > halo_left else 0, min(halo_left + T, s + chunk) if s + chunk < halo_left + T else n_all)
+                       for s in range(halo_left, halo_left + T, chunk)) if T > 0 else ()
+        return StreamPlan(fmt, h, w, oh, ow, T, n_all, halo_left, halo_right, chunk, chunks, max(1, int(in_flight)) if T > 0 else 1, not frames.is_cuda,
+                          bool(half_size_output), bool(frames_are_rgb), window, zmode, zwin, zoom_speed, zoom_min, bool(two_pass), mosaic, radius,
+                          self.borders == "keep", rigid, self.edge, metrics, _has_lattice(h, w), self.smooth, rs, max_se, wob, max_crop, limit_levels,
+                          limit_relax, detect, cuts, scene_threshold, scene_min_len)
 
-        def crop_window(crop):
-            cy0, cy1, cx0, cx1 = 0, oh, 0, ow
-            if crop is not None:
-                if len(crop) not in (4, 5):
-                    raise ValueError("crop must be (x_start, x_end, y_start, y_end[, threshold])")
-                th = int(crop[4]) if len(crop) == 5 else 0
-                cx0, cx1, cy0, cy1 = int(crop[0]) + th, int(crop[1]) - th, int(crop[2]) + th, int(crop[3]) - th
-                if not (0 <= cx0 < cx1 <= ow and 0 <= cy0 < cy1 <= oh):
-                    raise ValueError("crop window x [%d, %d) y [%d, %d) does not lie inside the %d x %d output frame" % (cx0, cx1, cy0, cy1, ow, oh))
-                if yuv and ((cx0 | cx1) % mx or (cy0 | cy1) % my):
-                    if fmt.chroma == 0:
-                        raise ValueError("crop window x [%d, %d) y [%d, %d) of %s frames must have even edges" % (cx0, cx1, cy0, cy1, pixel_format))
-                    raise ValueError("crop window x [%d, %d) y [%d, %d) of %s frames must have edges that are multiples of %d (x) and %d (y)"
-                                     % (cx0, cx1, cy0, cy1, pixel_format, mx, my))
-            return cy0, cy1, cx0, cx1
-
-        def alloc_out():
-            oshape = _frames_shape(fmt, T, cy1 - cy0, cx1 - cx0)
-            return torch.empty(oshape, dtype=frames.dtype, pin_memory=True) if on_host else torch.empty(oshape, dtype=frames.dtype, device=dev)
-        cy0, cy1, cx0, cx1 = crop_window(None if auto else crop)
-        out = None if auto and T > 0 else alloc_out()
-        if T == 0:
-            return out
-        compute = torch.cuda.current_stream(dev)
-        up, down = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
-        in_flight = max(1, int(in_flight))
-        if rigid:   # (before the lanes fork from the caller's stream: every lane writes its chunks' slices)
-            rres = torch.empty((T,), device=dev, dtype=torch.float32)
-            runf = torch.empty((T,), device=dev, dtype=torch.int32)
-        mhom = mbounds = None
-        if metrics:   # (also before the fork) the output planes; below the fit's lattice size cropping and distortion are not reported
-            planes_out = torch.empty((T, 256, 256), device=dev, dtype=torch.float32)
-            out_rgb = (bool(frames_are_rgb) != self.swap_rb) if not yuv else False   # the warp's swap_rb turns the channel order round
-            if lattice and not two_pass:   # (the two-pass paths keep their own fit)
-                mhom = torch.empty((T, 9), device=dev, dtype=torch.float64)
-                mbounds = torch.empty((T, 4), device=dev, dtype=torch.float32)
-        # (the lanes live as long as this object: the generator keeps an arena / a graph per STREAM, and torch's allocator a pool per stream)
-        # The caller's stream is lane 0: the runtime deals streams to a handful of hardware queues, and a lane that shares its queue with
-        # the upload or the download stream waits behind their copies (two NEW lanes beside up / down: 1 744 -> 1 291 frames/s).
-        while len(self._lanes) < in_flight - 1:
-            self._lanes.append(torch.cuda.Stream(dev))
-        lanes = [compute] + self._lanes[:in_flight - 1]
-        mod = getattr(self.net, "module", self.net)
-        restore = None
-        if in_flight > 1:
-            restore = (mod._graph_mode, mod._graph_alias, getattr(mod, "_graph_per_stream", False), mod.two_queues)
-            mod.two_queues = False   # two forwards that both fork into the device's one side queue would serialise there
-            if mod._graph_mode:
-                mod.enable_graph(True, mod._graph_alias, per_stream=True)
-            for lane in lanes[1:]:
-                lane.wait_stream(compute)
-        gray_all = torch.empty((n_all, 256, 256), device=dev, dtype=torch.float32)
-        if zmode is not None:
-            zunc = torch.empty((T,), device=dev, dtype=torch.int32)
-        if two_pass:
-            fields = torch.empty((T, 256, 256, 2), device=dev, dtype=torch.float32)
-            hom = torch.empty((T, 9), device=dev, dtype=torch.float64)
-            bounds = torch.empty((T, 4), device=dev, dtype=torch.float32)
-        # chunk bounds in the index space of `frames`: the first / last chunk carry the halo frames with them
-        chunks = [(s if s > halo_left else 0, min(halo_left + T, s + chunk) if s + chunk < halo_left + T else n_all)
-                  for s in range(halo_left, halo_left + T, chunk)]
-        up.wait_stream(compute)   # gray_all was allocated on the compute stream
-
-        def upload(c):
-            s, e = chunks[c]
-            with torch.cuda.stream(up):
-                buf = frames[s:e].to(dev, non_blocking=True) if on_host else frames[s:e]
-                _window_planes(buf, fmt, 256, gray_all[s:e], "run_video", frames_are_rgb)
-                ev = torch.cuda.Event()
-                ev.record(up)
-                if detect:   # same stream: ordered behind the planes (and behind the previous chunk's, whose last plane it reads)
-                    s0 = max(s - 1, 0)
-                    scores_h[s:e].copy_(scene_scores(gray_all[s0:e])[s - s0:], non_blocking=True)
-                    scored[c] = torch.cuda.Event()
-                    scored[c].record(up)
-            return buf, ev
-
-        def detect_cuts(need):
-            """extends the cut list over the planes 0 .. need-1 (the host waits for the upload that scored plane need-1)"""
-            nonlocal decided
-            k = next(k for k, (s, e) in enumerate(chunks) if e >= need)
-            t0 = time.perf_counter()
-            scored[k].synchronize()
-            self.scene_wait_s += time.perf_counter() - t0
-            last = cuts[-1] if cuts else 0
-            first = max(decided, 1)
-            for t, v in enumerate(scores_h[first:need].tolist(), first):
-                if v > scene_threshold and t - last >= scene_min_len:   # find_scene_cuts' rule, continued
-                    cuts.append(t)
-                    last = t
-            decided = max(decided, need)
-
-        def finish(warped, buf, s, e, lane):
-            """output resize + crop of the warped core frames s .. e-1 (output positions) on `lane`, and their way to `out`"""
-            if metrics:   # the planes of what the viewer sees, at the warp's size
-                _window_planes(warped, fmt, 256, planes_out[s:e], "run_video", out_rgb)
-            if (oh, ow) != (h, w):
-                warped = _output_resize(warped, fmt, (ow, oh), half_size_output)
-            if crop is not None:
-                warped = _crop(warped, fmt, oh, ow, cy0, cy1, cx0, cx1)
-            if on_host:
-                buf.record_stream(lane)
-                done = torch.cuda.Event()
-                done.record(lane)
-                with torch.cuda.stream(down):
-                    down.wait_event(done)
-                    out[s:e].copy_(warped, non_blocking=True)
-                warped.record_stream(down)
-            else:
-                out[s:e].copy_(warped)
-        pend = None   # borders="mosaic": the chunk that waits for its successor -- (warped, fields, cs, ce, buf, valid frames of the head pad)
-        if mosaic:
-            unf = torch.empty((T,), device=dev, dtype=torch.int32)
-
-        def mosaic_step(new, lane):
-            """chunk `new` = (warped, fields, cs, ce, buf), both buffers with `radius` spare frames at either end, has been warped (None: the
-            clip is over): the waiting chunk takes its first frames as donors, is filled scene by scene and finished; `new` takes the
-            waiting chunk's last frames and waits in its turn.  (Filled frames are as good donors as the warp's own.)"""
-            nonlocal pend
-            R = radius
-            if pend is not None:
-                pw, pf, ps, pe, pbuf, nt = pend
-                nh = 0
-                if new is not None:
-                    nh = min(R, new[3] - new[2])
-                    pw[R + pe - ps:R + pe - ps + nh].copy_(new[0][R:R + nh])
-                    pf[R + pe - ps:R + pe - ps + nh].copy_(new[1][R:R + nh])
-                lo, hi, off = ps - nt, pe + nh, R - ps   # the frames the buffer holds (index space of `frames`); frame g is at g + off
-                edges = [halo_left] + [t for t in cuts if halo_left < t < halo_left + T] + [halo_left + T]
-                for a, b in zip(edges[:-1], edges[1:]):
-                    fa, fb = max(a, ps), min(b, pe)
-                    if fa < fb:
-                        da, db = max(a, lo), min(b, hi)
-                        PF.mosaic_borders_(pw[da + off:db + off], pf[da + off:db + off], R, fa - da, fb - da, pixel_format=pixel_format,
-                                           align_corners=self.align_corners, mode=self.interpolation, _unfilled=unf[fa - halo_left:fb - halo_left])
-                finish(pw[R:R + pe - ps], pbuf, ps - halo_left, pe - halo_left, lane)
-            if new is not None:
-                nt = 0
-                if pend is not None:
-                    nt = min(R, pe - ps)
-                    new[0][R - nt:R].copy_(pw[R + pe - ps - nt:R + pe - ps])
-                    new[1][R - nt:R].copy_(pf[R + pe - ps - nt:R + pe - ps])
-                pend = tuple(new) + (nt,)
-            else:
-                pend = None
-        staged, uploaded = {}, 0
-        keep = self.borders == "keep"
-        carry, carried = None, None   # borders="keep": the last warped (pre-resize) frame so far, and the event behind the pass that made it
-        if detect:
-            scores_h = torch.empty((n_all,), dtype=torch.float32, pin_memory=True)
-            scored, decided = {}, 0
-            self.scene_wait_s = 0.0   # host time spent in those waits (tools/scene_cuts_bench.py)
-        try:
-            for c, (s, e) in enumerate(chunks):
-                lane = lanes[c % len(lanes)]
-                # a chunk's windows reach `half` frames past its end: every chunk that holds one of those frames must be on the
-                # device (and its planes computed) first; one chunk further ahead keeps the upload stream busy during this compute
-                need = min(n_all, e + half)
-                while uploaded < len(chunks) and (chunks[uploaded][0] < need or uploaded <= c + 1):
-                    staged[uploaded] = upload(uploaded)
-                    uploaded += 1
-                for k in range(c, uploaded):
-                    if chunks[k][0] < need:
-                        lane.wait_event(staged[k][1])
-                # (planes of EARLIER chunks that this one's windows reach back into were produced before staged[c]'s event on the same stream)
-                buf, ev = staged.pop(c)
-                # core frames of this chunk (the halo frames at the clip's ends are uploaded with it but not stabilised)
-                cs, ce = max(s, halo_left), min(e, halo_left + T)
-                hl, hr = min(half, cs), min(half, n_all - ce)
-                if detect:
-                    detect_cuts(ce + hr)
-                # the cuts inside this chunk's slice of the planes, in the slice's index space (None without cuts: the path as it was)
-                sc = [t - (cs - hl) for t in cuts if cs - hl < t < ce + hr] or None
-                with torch.cuda.stream(lane):
-                    if two_pass:   # pass 1: fields and per-frame bounds only (no halos here: core frames = output positions)
-                        self._fields(gray_all[cs - hl:ce + hr], hl, hr, fields[cs:ce], sc)
-                        if not smoothing or rigid or wob > 0.0:   # (smoothing fits the fields it composes, below; the blend and the wobble
-                            #                                         filter need the raw fit)
-                            _field_homography(fields[cs:ce], h, w, hom[cs:ce], bounds[cs:ce])
-                        if rigid:   # the kept fields, in place; the bounds stay the raw fit's
-                            PF._field_rigid(fields[cs:ce], hom[cs:ce], (h, w), self.rigidity, fields[cs:ce], rres[cs:ce], runf[cs:ce])
-                        continue
-                    rstats = (rres[cs - halo_left:ce - halo_left], runf[cs - halo_left:ce - halo_left]) if rigid else None
-                    mh = (mhom[cs - halo_left:ce - halo_left], mbounds[cs - halo_left:ce - halo_left]) if mhom is not None else None
-                    if mosaic:   # warped with black borders; the chunk before it is filled and finished
-                        wall, fall = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr, pixel_format=pixel_format,
-                                              scene_cuts=sc, _rigid_stats=rstats, _mosaic_pad=radius, _hom_out=mh)
-                        mosaic_step((wall, fall, cs, ce, buf), lane)
-                        continue
-                    if zmode is not None:   # ("fixed": the one window, in the single pass)
-                        warped = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr, pixel_format=pixel_format,
-                                          scene_cuts=sc, zoom=zwin, _zoom_unc=zunc[cs - halo_left:ce - halo_left], _rigid_stats=rstats, _hom_out=mh)
-                    else:
-                        warped = self.run(gray_all[cs - hl:ce + hr], buf[cs - s:ce - s], halo_left=hl, halo_right=hr, pixel_format=pixel_format, scene_cuts=sc,
-                                          keep_from=carry, _keep_wait=carried, _rigid_stats=rstats, _hom_out=mh)
-                    if keep:   # the next chunk's pass (on the other lane, if any) starts from this chunk's last frame: no copy, one event
-                        carry = warped[-1]
-                        if len(lanes) > 1:
-                            carried = torch.cuda.Event()
-                            carried.record(lane)
-                    finish(warped, buf, cs - halo_left, ce - halo_left, lane)
-            if mosaic:
-                mosaic_step(None, compute)   # the last chunk
-                self.mosaic_unfilled = unf
-        finally:
-            if restore is not None:
-                for lane in lanes[1:]:
-                    compute.wait_stream(lane)   # the caller's stream sees every chunk; gray_all and the outputs may be freed behind it
-                mod.two_queues = restore[3]
-                mod.enable_graph(restore[0], restore[1], per_stream=restore[2])
-        if rigid:
-            self.rigid_residual, self.rigid_unfit = rres, runf
-        if zmode is not None:
-            self.zoom_windows, self.zoom_uncovered = [zwin] * T if zmode == "fixed" else None, zunc
-        if wob > 0.0:   # every lane has joined the caller's stream: the kept fields (after rigidity) are complete, and so is the cut list
-            fields, self.wobble_removed, self.wobble_unfit = PF.wobble_fields(fields, hom, (h, w), wob, scene_cuts=cuts or None, return_stats=True)
-            if not smoothing:   # bounds, crop and zoom decisions and the report describe the field that warps (smoothing fits what it composes)
-                _field_homography(fields, h, w, hom, bounds)
-        if smoothing:   # ... and it measures the filtered fields
-            seen = PF.grid_sample(gray_all.unsqueeze(1), fields, align_corners=self.align_corners).squeeze(1)   # the planes as the fields warp them
-            if rs == "auto":   # the blocks behind the fit are kept for the estimate: the same launches, the same motion
-                self.smooth_motion, self.smooth_inliers, mv, sad, act = global_motion(seen, pixel_scale=(w / 256.0, h / 256.0), return_blocks=True)
-                self.shutter_estimate = estimate_rolling_shutter(self.smooth_motion, mv, sad, act, tuple(seen.shape[1:]),
-                                                                 pixel_scale=(w / 256.0, h / 256.0), scene_cuts=cuts or None, frame_height=h)
-                del mv, sad, act
-                r_hat, se = self.shutter_estimate.tolist()[:2]   # the one read of "auto": 32 bytes, and the host waits for pass 1 here
-                rs = min(1.0, max(-1.0, r_hat)) if math.isfinite(r_hat) and se <= max_se else 0.0
-                self.rolling_shutter_used = rs
-            else:
-                self.smooth_motion, self.smooth_inliers = global_motion(seen, pixel_scale=(w / 256.0, h / 256.0))
-            del seen
-            self.smooth_correction, self.smooth_path = smooth_path(self.smooth_motion, self.smooth, scene_cuts=cuts or None)
-            self.smooth_uncovered = torch.empty((T,), device=dev, dtype=torch.int32)
-            if rs != 0.0:   # the velocity at every frame, from the same measured motion and under the same cuts
-                self.shutter_rates = shutter_rates(self.smooth_motion, scene_cuts=cuts or None)
-            if max_crop is not None:   # the crop budget: every frame's share of its correction, decided on the kept fields, read in place
-                self.smooth_correction_unlimited = self.smooth_correction
-                self.smooth_correction, self.limit_strength, self.limit_need, self.limit_uncovered = limit_path(
-                    self.smooth_correction, fields, (h, w), 1.0 - max_crop, levels=limit_levels, relax=limit_relax, scene_cuts=cuts or None,
-                    rates=self.shutter_rates, rolling_shutter=rs, align_corners=self.align_corners, mode=self.interpolation)
-            scratch = torch.empty((min(int(chunk), T),) + tuple(fields.shape[1:]), device=dev, dtype=torch.float32)
-            for s in range(0, T, scratch.shape[0]):
-                e = min(T, s + scratch.shape[0])
-                if rs != 0.0:
-                    PF._field_compose_rows(fields[s:e], self.smooth_correction[s:e], self.shutter_rates[s:e], rs, (h, w), self.align_corners,
-                                           self.interpolation, scratch[:e - s], self.smooth_uncovered[s:e])
-                else:
-                    PF._field_compose(fields[s:e], self.smooth_correction[s:e], (h, w), self.align_corners, self.interpolation, scratch[:e - s],
-                                      self.smooth_uncovered[s:e])
-                fields[s:e].copy_(scratch[:e - s])
-                if lattice:   # bounds, crop and zoom decisions and the report describe the field that warps
-                    _field_homography(fields[s:e], h, w, hom[s:e], bounds[s:e])
-            del scratch
-        if zmode in ("auto", "adaptive"):   # (the copy of the bounds to the host waits for pass 1)
-            if zmode == "auto":
-                self.zoom_windows = [zoom_window(auto_crop_window(bounds, (h, w), None, self.period, scene_cuts=cuts or None), (h, w))] * T
-            else:
-                self.zoom_windows = zoom_schedule(bounds, (h, w), zoom_speed, zoom_min, scene_cuts=cuts or None)
-        if two_pass and zmode is not None:   # (a fixed fraction under smoothing: its one window, in pass 2)
-            zcoef = PF.zoom_coefficients(PF._zoom_windows(self.zoom_windows, T, (h, w), "run_video"), (h, w), fields.shape[1:3]).to(dev, non_blocking=True)
-        if auto:
-            crop = auto_crop_window(bounds, (h, w), (oh, ow), self.period, scene_cuts=cuts or None)   # (the copy to the host waits for pass 1)
-            if yuv:   # the BGR path's window, rounded inward to the format's multiples (4:2:0: even edges; 4:4:4: as it is)
-                x0, x1, y0, y1 = int(crop[0]), int(crop[1]), int(crop[2]), int(crop[3])
-                crop = (x0 + (-x0) % mx, x1 - x1 % mx, y0 + (-y0) % my, y1 - y1 % my)
-                if not (crop[1] > crop[0] and crop[3] > crop[2]):
-                    raise ValueError("run_video: the even crop window x [%d, %d) y [%d, %d) is empty" % crop)
-            cy0, cy1, cx0, cx1 = crop_window(crop)
-            out = alloc_out()
-        if two_pass:
-            # pass 2: [zoom +] warp + output resize + crop with the kept fields; chunk k+1 uploads while chunk k computes
-
-            def fetch(c):
-                return _prefetch(frames, chunks[c][0], chunks[c][1], up, dev)
-            nxt = fetch(0)
-            for c, (s, e) in enumerate(chunks):
-                buf, ev = nxt
-                if c + 1 < len(chunks):
-                    nxt = fetch(c + 1)
-                if ev is not None:
-                    compute.wait_event(ev)
-                fld = fields[s:e]
-                if zmode is not None:
-                    fld = PF._field_zoom(fld, zcoef[s:e], (h, w), self.align_corners, self.interpolation, torch.empty_like(fld), zunc[s:e])
-                warped = PF.warp(buf.contiguous(), fld, fmt, swap_rb=self.swap_rb, align_corners=self.align_corners, mode=self.interpolation)
-                if self.edge != "pad":
-                    PF.edge_borders_(warped, buf.contiguous(), fld, self.edge, pixel_format, swap_rb=self.swap_rb, align_corners=self.align_corners,
-                                     mode=self.interpolation)
-                finish(warped, buf, s, e, compute)
-        if metrics:   # every lane has joined the caller's stream, and every chunk's planes are behind an event it has waited for
-            core = gray_all[halo_left:halo_left + T]
-            self.motion_in, self.motion_inliers_in = global_motion(core)
-            self.motion_out, self.motion_inliers_out = global_motion(planes_out)
-            if two_pass and h >= 300 and w >= 600:
-                mhom, mbounds = hom, bounds
-            self._report = {"frames": T, "frame_hw": (h, w), "hom": mhom, "bounds": mbounds,
-                            "cuts": [c - halo_left for c in cuts if 0 < c - halo_left < T]}
-        if on_host:
-            down.synchronize()
-        return out
+    def _reset(self, plan):
+        """What the previous run_video left goes, in one place, once the plan stands: every result is None until this call sets it."""
+        self.zoom_windows = self.zoom_uncovered = None
+        self.rigid_residual = self.rigid_unfit = None
+        self.mosaic_unfilled = None
+        self.motion_in = self.motion_out = self.motion_inliers_in = self.motion_inliers_out = self._report = None
+        self.smooth_motion = self.smooth_inliers = self.smooth_path = self.smooth_correction = self.smooth_uncovered = None
+        self.shutter_rates = self.shutter_estimate = self.rolling_shutter_used = None
+        self.limit_strength = self.limit_need = self.limit_uncovered = self.smooth_correction_unlimited = None
+        self.wobble_removed = self.wobble_unfit = None
+        self.scene_cuts = list(plan.cuts)   # scene_cuts="auto" extends it chunk by chunk
+        if plan.detect:
+            self.scene_wait_s = 0.0   # host time spent waiting for scores (tools/scene_cuts_bench.py)
 
     def stability_report(self):
         """The paper's three metrics for the last ``run_video(metrics=True)``; synchronises the device.  Returns a dict:
@@ -1732,3 +826,319 @@ class VideoStabilizer:
                 ratio[t] = sv[1] / sv[0]
         out["distortion"] = summary(ratio)
         return out
+
+
+class _Call:
+    """One run_video call in flight: the plan, the streams and lanes, the clip's buffers, and what one step leaves for the next -- the staged
+    uploads, the cut detection's scores, the mosaic's waiting chunk, the keep pass's last frame.  run_video names the steps in their order."""
+
+    def __init__(self, vs, plan, frames):
+        self.vs, self.plan, self.frames = vs, plan, frames
+        self.cuts = vs.scene_cuts   # (the one list: what detection appends, the stabiliser shows)
+        self.cropping = plan.crop is not None
+        self.window = plan.crop if isinstance(plan.crop, tuple) else (0, plan.oh, 0, plan.ow)   # (cy0, cy1, cx0, cx1); "auto": after pass 1
+        self.out = None if plan.crop == "auto" and plan.T > 0 else self.alloc_out()
+
+    def alloc_out(self):
+        p = self.plan
+        cy0, cy1, cx0, cx1 = self.window
+        oshape = _frames_shape(p.fmt, p.T, cy1 - cy0, cx1 - cx0)
+        if p.on_host:
+            return torch.empty(oshape, dtype=self.frames.dtype, pin_memory=True)
+        return torch.empty(oshape, dtype=self.frames.dtype, device=self.vs.device)
+
+    def open(self):
+        """The streams, the lanes and every buffer that lives as long as the call."""
+        vs, p, dev = self.vs, self.plan, self.vs.device
+        T = p.T
+        self.compute = compute = torch.cuda.current_stream(dev)
+        self.up, self.down = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+        self.rres = self.runf = None
+        if p.rigid:   # (before the lanes fork from the caller's stream: every lane writes its chunks' slices)
+            self.rres = torch.empty((T,), device=dev, dtype=torch.float32)
+            self.runf = torch.empty((T,), device=dev, dtype=torch.int32)
+        self.mhom = self.mbounds = None
+        if p.metrics:   # (also before the fork) the output planes; below the fit's lattice size cropping and distortion are not reported
+            self.planes_out = torch.empty((T, 256, 256), device=dev, dtype=torch.float32)
+            self.out_rgb = (p.frames_are_rgb != vs.swap_rb) if not p.fmt.packed else False   # the warp's swap_rb turns the channel order round
+            if p.lattice and not p.two_pass:   # (the two-pass paths keep their own fit)
+                self.mhom = torch.empty((T, 9), device=dev, dtype=torch.float64)
+                self.mbounds = torch.empty((T, 4), device=dev, dtype=torch.float32)
+        # (the lanes live as long as the stabiliser: the generator keeps an arena / a graph per STREAM, and torch's allocator a pool per stream)
+        # The caller's stream is lane 0: the runtime deals streams to a handful of hardware queues, and a lane that shares its queue with
+        # the upload or the download stream waits behind their copies (two NEW lanes beside up / down: 1 744 -> 1 291 frames/s).
+        while len(vs._lanes) < p.in_flight - 1:
+            vs._lanes.append(torch.cuda.Stream(dev))
+        self.lanes = [compute] + vs._lanes[:p.in_flight - 1]
+        self.mod = mod = getattr(vs.net, "module", vs.net)
+        self.restore = None
+        if p.in_flight > 1:
+            self.restore = (mod._graph_mode, mod._graph_alias, getattr(mod, "_graph_per_stream", False), mod.two_queues)
+            mod.two_queues = False   # two forwards that both fork into the device's one side queue would serialise there
+            if mod._graph_mode:
+                mod.enable_graph(True, mod._graph_alias, per_stream=True)
+            for lane in self.lanes[1:]:
+                lane.wait_stream(compute)
+        self.gray_all = torch.empty((p.n_all, 256, 256), device=dev, dtype=torch.float32)
+        if p.zmode is not None:
+            self.zunc = torch.empty((T,), device=dev, dtype=torch.int32)
+        if p.two_pass:
+            self.fields = torch.empty((T, 256, 256, 2), device=dev, dtype=torch.float32)
+            self.hom = torch.empty((T, 9), device=dev, dtype=torch.float64)
+            self.bounds = torch.empty((T, 4), device=dev, dtype=torch.float32)
+        self.up.wait_stream(compute)   # gray_all was allocated on the compute stream
+        self.pend = None   # borders="mosaic": the chunk that waits for its successor -- (warped, fields, cs, ce, buf, valid frames of the head pad)
+        if p.mosaic:
+            self.unf = torch.empty((T,), device=dev, dtype=torch.int32)
+        self.staged, self.uploaded = {}, 0
+        self.carry, self.carried = None, None   # borders="keep": the last warped (pre-resize) frame so far, and the event behind the pass that made it
+        if p.detect:
+            self.scores_h = torch.empty((p.n_all,), dtype=torch.float32, pin_memory=True)
+            self.scored, self.decided = {}, 0
+
+    def upload(self, c):
+        p = self.plan
+        s, e = p.chunks[c]
+        with torch.cuda.stream(self.up):
+            buf = self.frames[s:e].to(self.vs.device, non_blocking=True) if p.on_host else self.frames[s:e]
+            _window_planes(buf, p.fmt, 256, self.gray_all[s:e], "run_video", p.frames_are_rgb)
+            ev = torch.cuda.Event()
+            ev.record(self.up)
+            if p.detect:   # same stream: ordered behind the planes (and behind the previous chunk's, whose last plane it reads)
+                s0 = max(s - 1, 0)
+                self.scores_h[s:e].copy_(scene_scores(self.gray_all[s0:e])[s - s0:], non_blocking=True)
+                self.scored[c] = torch.cuda.Event()
+                self.scored[c].record(self.up)
+        return buf, ev
+
+    def detect_cuts(self, need):
+        """extends the cut list over the planes 0 .. need-1 (the host waits for the upload that scored plane need-1)"""
+        p = self.plan
+        k = next(k for k, (s, e) in enumerate(p.chunks) if e >= need)
+        t0 = time.perf_counter()
+        self.scored[k].synchronize()
+        self.vs.scene_wait_s += time.perf_counter() - t0
+        first = max(self.decided, 1)
+        self.cuts.extend(_cut_rule(self.scores_h[first:need].tolist(), first, self.cuts[-1] if self.cuts else 0, p.scene_threshold, p.scene_min_len))
+        self.decided = max(self.decided, need)
+
+    def chunk(self, c):
+        """Chunk c on its lane: the uploads it needs, its cuts, and pass 1 or the single pass."""
+        vs, p = self.vs, self.plan
+        half = vs.period // 2
+        s, e = p.chunks[c]
+        lane = self.lanes[c % len(self.lanes)]
+        # a chunk's windows reach `half` frames past its end: every chunk that holds one of those frames must be on the
+        # device (and its planes computed) first; one chunk further ahead keeps the upload stream busy during this compute
+        need = min(p.n_all, e + half)
+        while self.uploaded < len(p.chunks) and (p.chunks[self.uploaded][0] < need or self.uploaded <= c + 1):
+            self.staged[self.uploaded] = self.upload(self.uploaded)
+            self.uploaded += 1
+        for k in range(c, self.uploaded):
+            if p.chunks[k][0] < need:
+                lane.wait_event(self.staged[k][1])
+        # (planes of EARLIER chunks that this one's windows reach back into were produced before staged[c]'s event on the same stream)
+        buf, ev = self.staged.pop(c)
+        # core frames of this chunk (the halo frames at the clip's ends are uploaded with it but not stabilised)
+        cs, ce = max(s, p.halo_left), min(e, p.halo_left + p.T)
+        hl, hr = min(half, cs), min(half, p.n_all - ce)
+        if p.detect:
+            self.detect_cuts(ce + hr)
+        # the cuts inside this chunk's slice of the planes, in the slice's index space (None without cuts: the path as it was)
+        sc = [t - (cs - hl) for t in self.cuts if cs - hl < t < ce + hr] or None
+        gray = self.gray_all[cs - hl:ce + hr]
+        with torch.cuda.stream(lane):
+            if p.two_pass:
+                self.pass1(gray, hl, hr, cs, ce, sc)
+            else:
+                self.single_pass(gray, hl, hr, cs, ce, sc, buf, s, lane)
+
+    def pass1(self, gray, hl, hr, cs, ce, sc):
+        """fields and per-frame bounds only (no halos here: core frames = output positions)"""
+        vs, p = self.vs, self.plan
+        fields, hom = self.fields[cs:ce], self.hom[cs:ce]
+        vs._fields(gray, hl, hr, fields, sc)
+        if not p.smooth > 0.0 or p.rigid or p.wobble > 0.0:   # (smoothing fits the fields it composes, between the passes; the blend and the
+            #                                                     wobble filter need the raw fit)
+            _field_homography(fields, p.h, p.w, hom, self.bounds[cs:ce])
+        if p.rigid:   # the kept fields, in place; the bounds stay the raw fit's
+            PF._field_rigid(fields, hom, (p.h, p.w), vs.rigidity, fields, self.rres[cs:ce], self.runf[cs:ce])
+
+    def single_pass(self, gray, hl, hr, cs, ce, sc, buf, s, lane):
+        """the chunk's core frames buf[cs - s:ce - s] through the batch loop and on to ``out``"""
+        vs, p = self.vs, self.plan
+        a, b = cs - p.halo_left, ce - p.halo_left   # (output positions)
+        core = buf[cs - s:ce - s]
+        fill = {"rigid_stats": (self.rres[a:b], self.runf[a:b]) if p.rigid else (None, None),
+                "hom_out": (self.mhom[a:b], self.mbounds[a:b]) if self.mhom is not None else None}
+        if p.mosaic:   # warped with black borders; the chunk before it is filled and finished
+            wall, fall = vs._batches(p.fmt, gray, core, hl, hr, sc, None, pad=p.radius, **fill)
+            self.mosaic_step((wall, fall, cs, ce, buf), lane)
+            return
+        warped = torch.empty_like(core)
+        # ("fixed": the one window, in the single pass)
+        zoom = (PF._zoom_windows(p.zwin, ce - cs, (p.h, p.w), "run"), self.zunc[a:b]) if p.zmode is not None else None
+        vs._batches(p.fmt, gray, core, hl, hr, sc, warped, zoom=zoom, keep_from=self.carry, keep_wait=self.carried, **fill)
+        if p.keep:   # the next chunk's pass (on the other lane, if any) starts from this chunk's last frame: no copy, one event
+            self.carry = warped[-1]
+            if len(self.lanes) > 1:
+                self.carried = torch.cuda.Event()
+                self.carried.record(lane)
+        self.finish(warped, buf, a, b, lane)
+
+    def finish(self, warped, buf, s, e, lane):
+        """output resize + crop of the warped core frames s .. e-1 (output positions) on `lane`, and their way to `out`"""
+        p = self.plan
+        if p.metrics:   # the planes of what the viewer sees, at the warp's size
+            _window_planes(warped, p.fmt, 256, self.planes_out[s:e], "run_video", self.out_rgb)
+        if (p.oh, p.ow) != (p.h, p.w):
+            warped = _output_resize(warped, p.fmt, (p.ow, p.oh), p.half_size_output)
+        if self.cropping:
+            warped = _crop(warped, p.fmt, p.oh, p.ow, *self.window)
+        if p.on_host:
+            buf.record_stream(lane)
+        _hand_over(warped, self.out[s:e], lane, self.down if p.on_host else None)
+
+    def mosaic_step(self, new, lane):
+        """chunk `new` = (warped, fields, cs, ce, buf), both buffers with `radius` spare frames at either end, has been warped (None: the
+        clip is over): the waiting chunk takes its first frames as donors, is filled scene by scene and finished; `new` takes the
+        waiting chunk's last frames and waits in its turn.  (Filled frames are as good donors as the warp's own.)"""
+        vs, p = self.vs, self.plan
+        R, pend = p.radius, self.pend
+        if pend is not None:
+            pw, pf, ps, pe, pbuf, nt = pend
+            nh = 0
+            if new is not None:
+                nh = min(R, new[3] - new[2])
+                pw[R + pe - ps:R + pe - ps + nh].copy_(new[0][R:R + nh])
+                pf[R + pe - ps:R + pe - ps + nh].copy_(new[1][R:R + nh])
+            lo, hi, off = ps - nt, pe + nh, R - ps   # the frames the buffer holds (index space of `frames`); frame g is at g + off
+            for a, b in _scenes(p.halo_left + p.T, self.cuts, p.halo_left):
+                fa, fb = max(a, ps), min(b, pe)
+                if fa < fb:
+                    da, db = max(a, lo), min(b, hi)
+                    PF.mosaic_borders_(pw[da + off:db + off], pf[da + off:db + off], R, fa - da, fb - da, pixel_format=p.fmt.name,
+                                       align_corners=vs.align_corners, mode=vs.interpolation, _unfilled=self.unf[fa - p.halo_left:fb - p.halo_left])
+            self.finish(pw[R:R + pe - ps], pbuf, ps - p.halo_left, pe - p.halo_left, lane)
+        if new is not None:
+            nt = 0
+            if pend is not None:
+                nt = min(R, pe - ps)
+                new[0][R - nt:R].copy_(pw[R + pe - ps - nt:R + pe - ps])
+                new[1][R - nt:R].copy_(pf[R + pe - ps - nt:R + pe - ps])
+            self.pend = tuple(new) + (nt,)
+        else:
+            self.pend = None
+
+    def drain(self):
+        """Every chunk is issued: borders="mosaic" finishes the last one."""
+        if self.plan.mosaic:
+            self.mosaic_step(None, self.compute)
+            self.vs.mosaic_unfilled = self.unf
+
+    def join(self):
+        """The lanes join the caller's stream and the generator gets its settings back, whatever happened."""
+        if self.restore is not None:
+            for lane in self.lanes[1:]:
+                self.compute.wait_stream(lane)   # the caller's stream sees every chunk; gray_all and the outputs may be freed behind it
+            self.mod.two_queues = self.restore[3]
+            self.mod.enable_graph(self.restore[0], self.restore[1], per_stream=self.restore[2])
+
+    def publish(self):
+        """The per-frame results that the chunks filled slice by slice."""
+        vs, p = self.vs, self.plan
+        if p.rigid:
+            vs.rigid_residual, vs.rigid_unfit = self.rres, self.runf
+        if p.zmode is not None:
+            vs.zoom_windows, vs.zoom_uncovered = [p.zwin] * p.T if p.zmode == "fixed" else None, self.zunc
+
+    def between_passes(self):
+        """Every lane has joined the caller's stream: the kept fields (after rigidity) are complete, and so is the cut list.  On that stream,
+        in this order: wobble, the measurement, the "auto" shutter estimate and its one host read, smooth_path, shutter_rates, limit_path,
+        the composition and refit per chunk, the zoom windows, the automatic crop and the output's allocation."""
+        vs, p, dev = self.vs, self.plan, self.vs.device
+        h, w, T = p.h, p.w, p.T
+        cuts = self.cuts or None
+        rs = p.shutter
+        if p.wobble > 0.0:
+            self.fields, vs.wobble_removed, vs.wobble_unfit = PF.wobble_fields(self.fields, self.hom, (h, w), p.wobble, scene_cuts=cuts, return_stats=True)
+            if not p.smooth > 0.0:   # bounds, crop and zoom decisions and the report describe the field that warps (smoothing fits what it composes)
+                _field_homography(self.fields, h, w, self.hom, self.bounds)
+        fields = self.fields
+        if p.smooth > 0.0:   # ... and it measures the filtered fields
+            scale = (w / 256.0, h / 256.0)   # frame pixels per plane pixel
+            seen = PF.grid_sample(self.gray_all.unsqueeze(1), fields, align_corners=vs.align_corners).squeeze(1)   # the planes as the fields warp them
+            if rs == "auto":   # the blocks behind the fit are kept for the estimate: the same launches, the same motion
+                vs.smooth_motion, vs.smooth_inliers, mv, sad, act = global_motion(seen, pixel_scale=scale, return_blocks=True)
+                vs.shutter_estimate = estimate_rolling_shutter(vs.smooth_motion, mv, sad, act, tuple(seen.shape[1:]), pixel_scale=scale,
+                                                               scene_cuts=cuts, frame_height=h)
+                del mv, sad, act
+                r_hat, se = vs.shutter_estimate.tolist()[:2]   # the one read of "auto": 32 bytes, and the host waits for pass 1 here
+                rs = min(1.0, max(-1.0, r_hat)) if math.isfinite(r_hat) and se <= p.max_se else 0.0
+                vs.rolling_shutter_used = rs
+            else:
+                vs.smooth_motion, vs.smooth_inliers = global_motion(seen, pixel_scale=scale)
+            del seen
+            vs.smooth_correction, vs.smooth_path = smooth_path(vs.smooth_motion, p.smooth, scene_cuts=cuts)
+            vs.smooth_uncovered = torch.empty((T,), device=dev, dtype=torch.int32)
+            if rs != 0.0:   # the velocity at every frame, from the same measured motion and under the same cuts
+                vs.shutter_rates = shutter_rates(vs.smooth_motion, scene_cuts=cuts)
+            if p.max_crop is not None:   # the crop budget: every frame's share of its correction, decided on the kept fields, read in place
+                vs.smooth_correction_unlimited = vs.smooth_correction
+                vs.smooth_correction, vs.limit_strength, vs.limit_need, vs.limit_uncovered = limit_path(
+                    vs.smooth_correction, fields, (h, w), 1.0 - p.max_crop, levels=p.limit_levels, relax=p.limit_relax, scene_cuts=cuts,
+                    rates=vs.shutter_rates, rolling_shutter=rs, align_corners=vs.align_corners, mode=vs.interpolation)
+            scratch = torch.empty((min(int(p.chunk), T),) + tuple(fields.shape[1:]), device=dev, dtype=torch.float32)
+            for s in range(0, T, scratch.shape[0]):
+                e = min(T, s + scratch.shape[0])
+                if rs != 0.0:
+                    PF._field_compose_rows(fields[s:e], vs.smooth_correction[s:e], vs.shutter_rates[s:e], rs, (h, w), vs.align_corners,
+                                           vs.interpolation, scratch[:e - s], vs.smooth_uncovered[s:e])
+                else:
+                    PF._field_compose(fields[s:e], vs.smooth_correction[s:e], (h, w), vs.align_corners, vs.interpolation, scratch[:e - s],
+                                      vs.smooth_uncovered[s:e])
+                fields[s:e].copy_(scratch[:e - s])
+                if p.lattice:   # bounds, crop and zoom decisions and the report describe the field that warps
+                    _field_homography(fields[s:e], h, w, self.hom[s:e], self.bounds[s:e])
+            del scratch
+        if p.zmode == "auto":   # (the copy of the bounds to the host waits for pass 1)
+            vs.zoom_windows = [zoom_window(auto_crop_window(self.bounds, (h, w), None, vs.period, scene_cuts=cuts), (h, w))] * T
+        elif p.zmode == "adaptive":
+            vs.zoom_windows = zoom_schedule(self.bounds, (h, w), p.zoom_speed, p.zoom_min, scene_cuts=cuts)
+        if p.zmode is not None:   # (a fixed fraction under smoothing: its one window, in pass 2)
+            self.zcoef = PF.zoom_coefficients(PF._zoom_windows(vs.zoom_windows, T, (h, w), "run_video"), (h, w), fields.shape[1:3]).to(dev, non_blocking=True)
+        if p.crop == "auto":
+            crop = auto_crop_window(self.bounds, (h, w), (p.oh, p.ow), vs.period, scene_cuts=cuts)   # (the copy to the host waits for pass 1)
+            if p.fmt.packed:   # the BGR path's window, rounded inward to the format's multiples (4:2:0: even edges; 4:4:4: as it is)
+                mx, my = p.fmt.multiples
+                x0, x1, y0, y1 = int(crop[0]), int(crop[1]), int(crop[2]), int(crop[3])
+                crop = (x0 + (-x0) % mx, x1 - x1 % mx, y0 + (-y0) % my, y1 - y1 % my)
+                if not (crop[1] > crop[0] and crop[3] > crop[2]):
+                    raise ValueError("run_video: the even crop window x [%d, %d) y [%d, %d) is empty" % crop)
+            self.window = _crop_window(p.fmt, p.oh, p.ow, crop)
+            self.out = self.alloc_out()
+
+    def pass2(self):
+        """[zoom +] warp + output resize + crop with the kept fields; chunk k+1 uploads while chunk k computes"""
+        vs, p = self.vs, self.plan
+        nxt = _prefetch(self.frames, p.chunks[0][0], p.chunks[0][1], self.up, vs.device)
+        for c, (s, e) in enumerate(p.chunks):
+            buf, ev = nxt
+            if c + 1 < len(p.chunks):
+                nxt = _prefetch(self.frames, p.chunks[c + 1][0], p.chunks[c + 1][1], self.up, vs.device)
+            if ev is not None:
+                self.compute.wait_event(ev)
+            fld = self.fields[s:e]
+            if p.zmode is not None:
+                fld = PF._field_zoom(fld, self.zcoef[s:e], (p.h, p.w), vs.align_corners, vs.interpolation, torch.empty_like(fld), self.zunc[s:e])
+            self.finish(vs._warp(p.fmt, buf, fld), buf, s, e, self.compute)
+
+    def measure(self):
+        """metrics: every lane has joined the caller's stream, and every chunk's planes are behind an event it has waited for"""
+        vs, p = self.vs, self.plan
+        core = self.gray_all[p.halo_left:p.halo_left + p.T]
+        vs.motion_in, vs.motion_inliers_in = global_motion(core)
+        vs.motion_out, vs.motion_inliers_out = global_motion(self.planes_out)
+        hom, bounds = (self.hom, self.bounds) if p.two_pass and p.lattice else (self.mhom, self.mbounds)
+        vs._report = {"frames": p.T, "frame_hw": (p.h, p.w), "hom": hom, "bounds": bounds,
+                      "cuts": [c - p.halo_left for c in self.cuts if 0 < c - p.halo_left < p.T]}
