@@ -3,12 +3,9 @@
 // warps' field_lerp and the rule for positions that are not finite.  field_compose.hip stores the value; field_reach.hip only classifies
 // it.  Both include this one function, so that what is counted is what would be written, bit for bit.
 #pragma once
-#include "common.h"
-#include "warp_common.h"
+#include "field_lattice.h"
 
 namespace pws {
-
-typedef float F32x4a8 __attribute__((ext_vector_type(4), aligned(8)));   // 16 bytes at the field's 8-byte alignment (rows of odd width)
 
 struct ComposeGeo {   // host-computed, fp64: the node's frame pixel, the frame centre, the lattice coordinate of a frame pixel
     double kx, ky, cx, cy, ikx, iky;
@@ -78,12 +75,6 @@ __device__ __forceinline__ void compose_node(const float *ft, int fh, int fw, in
         gx = field_lerp(hy, ly, hx, lx, r0.x, r0.z, r1.x, r1.z);
         gy = field_lerp(hy, ly, hx, lx, r0.y, r0.w, r1.y, r1.w);
     }
-}
-
-// pws_field_zoom's coverage rule at one value: the warps' fp32 un-normalisation, the margin, NaN not covered
-__device__ __forceinline__ bool compose_covered(float gx, float gy, int h0, int w0, bool ac, float m, float xhi, float yhi) {
-    const float ix = unnormalize(gx, w0, ac), iy = unnormalize(gy, h0, ac);
-    return ix >= m && ix <= xhi && iy >= m && iy <= yhi;   // (false for NaN)
 }
 
 }  // namespace pws

@@ -10,9 +10,9 @@
 // continued linearly, so an affine field composes exactly and the correction's wedges reach the warp as out-of-range coordinates.
 // A frame whose D is exactly the identity is copied; a node whose sx or sy is not finite keeps F[i, j].
 //
-// Launch shape: field_zoom.hip's -- a wave owns 128 consecutive nodes of one row of one frame, a lane 2 adjacent ones (one 16-byte store), a
-// workgroup is 4 waves = 4 rows; the count reduction is that kernel's too.  Under a rotation the cell differs per lane in both axes: per
-// node two 16-byte loads, columns x0 and x0 + 1 of rows y0 and y0 + 1.  The fp64 work is the 2 x 3 product and two scalings per node.
+// Launch shape: field_lattice.h's, 4 rows per workgroup, with its exact workgroup sum for the count.  Under a rotation the cell differs per
+// lane in both axes: per node two 16-byte loads, columns x0 and x0 + 1 of rows y0 and y0 + 1.  The fp64 work is the 2 x 3 product and two
+// scalings per node.
 //
 // Rolling shutter (pws_field_compose_rows, functional.compose_fields(rates=, rolling_shutter=)): the same kernel, instantiated with a
 // row-dependent step between D and the lattice -- the camera's velocity field times the time offset of the row that D q lies on, taken out
@@ -22,7 +22,7 @@
 namespace pws {
 namespace {
 
-constexpr int FC_PER_LANE = 2, FC_CHUNK = kWave * FC_PER_LANE, FC_ROWS = 4;   // nodes per lane / per wave, rows (waves) per workgroup
+constexpr int FC_ROWS = 4;   // rows (waves) per workgroup
 
 typedef ComposeGeo Geo;
 typedef ComposeRows Rows;
@@ -33,9 +33,9 @@ __global__ void __launch_bounds__(kWave *FC_ROWS) field_compose_kernel(const flo
                                                                         float *__restrict__ out, int fh, int fw, unsigned nrg, Geo geo, int h0,
                                                                         int w0, int align_corners, float m, int *__restrict__ uncovered, Rows rows) {
     __shared__ int cnt[FC_ROWS];
-    const unsigned t = blockIdx.x / nrg, rg = blockIdx.x - t * nrg;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63u);
-    const int i = (int)rg * FC_ROWS + wave, j0 = (int)blockIdx.y * FC_CHUNK + lane * FC_PER_LANE;
+    const LatticePos p = lattice_pos<FC_ROWS>(nrg);
+    const unsigned t = p.t;
+    const int i = p.i, j0 = p.j0;
     int unc = 0;
     if (i < fh && j0 < fw) {
         const double *dt = d + (size_t)t * 6;
@@ -46,56 +46,32 @@ __global__ void __launch_bounds__(kWave *FC_ROWS) field_compose_kernel(const flo
         const float *ft = field + (size_t)t * fh * fw * 2;
         const bool ac = align_corners != 0;
         const float xhi = (float)(w0 - 1) - m, yhi = (float)(h0 - 1) - m;
-        float g[FC_PER_LANE][2];
+        float g[kLaneNodes][2];
 #pragma unroll
-        for (int q = 0; q < FC_PER_LANE; ++q) {
+        for (int q = 0; q < kLaneNodes; ++q) {
             const int j = min(j0 + q, fw - 1);   // (a row of odd width: the last lane's second node repeats its first, and is dropped)
             compose_node<ROWS>(ft, fh, fw, i, j, y, dt, same, geo, rows, v, g[q][0], g[q][1]);
-            if (uncovered && j0 + q < fw) unc += compose_covered(g[q][0], g[q][1], h0, w0, ac, m, xhi, yhi) ? 0 : 1;
+            if (uncovered && j0 + q < fw) unc += node_covered(g[q][0], g[q][1], h0, w0, ac, m, xhi, yhi) ? 0 : 1;
         }
-        float *o = out + (((size_t)t * fh + i) * fw + j0) * 2;
-        if (j0 + 1 < fw) *reinterpret_cast<F32x4a8 *>(o) = F32x4a8{g[0][0], g[0][1], g[1][0], g[1][1]};
-        else *reinterpret_cast<float2 *>(o) = make_float2(g[0][0], g[0][1]);
+        store_pair(out + (((size_t)t * fh + i) * fw + j0) * 2, j0 + 1 < fw, F32x4a8{g[0][0], g[0][1], g[1][0], g[1][1]});
     }
-    if (uncovered) {   // (kernel argument: uniform, every thread of the workgroup arrives)
-        int s = unc;
-#pragma unroll
-        for (int o = kWave / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, kWave);
-        if (lane == 0) cnt[wave] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int tot = 0;
-#pragma unroll
-            for (int w = 0; w < FC_ROWS; ++w) tot += cnt[w];
-            if (tot != 0) atomicAdd(uncovered + t, tot);
-        }
-    }
+    if (uncovered) block_sum<FC_ROWS>(p, unc, cnt, uncovered);   // (kernel argument: uniform, every thread of the workgroup arrives)
 }
 
 // the checks, the clear and the launch of both exports; `rows` NULL: the affine kernel
 int compose(const char *who, const float *field, int n, int fh, int fw, const double *d, float *out, int h0, int w0, int align_corners, int margin,
             int *uncovered, pws_stream_t stream, const Rows *rows) {
-    PWS_REQUIRE(n >= 0, "%s: bad shape", who);
-    PWS_REQUIRE(fh >= 2 && fw >= 2, "%s: the field needs at least 2 x 2 nodes (got %d x %d)", who, fw, fh);
+    if (int rc = lattice_shape(who, n, fh, fw)) return rc;
     PWS_REQUIRE(h0 >= 2 && w0 >= 2, "%s: the frame must be at least 2 x 2 pixels (got %d x %d)", who, w0, h0);
     PWS_REQUIRE(!uncovered || margin >= 0, "%s: bad margin %d for the uncovered count", who, margin);
     if (n == 0) return PWS_OK;
-    PWS_REQUIRE(field && d && out, "%s: NULL pointer", who);
-    PWS_REQUIRE(((reinterpret_cast<size_t>(field) | reinterpret_cast<size_t>(out) | reinterpret_cast<size_t>(d)) & 7) == 0 &&
-                    (reinterpret_cast<size_t>(uncovered) & 3) == 0,
-                "%s: field, out and d must be 8-byte aligned, uncovered 4-byte aligned", who);
-    const size_t bytes = (size_t)n * fh * fw * 2 * sizeof(float);
-    const char *fb = reinterpret_cast<const char *>(field), *ob = reinterpret_cast<const char *>(out);
-    PWS_REQUIRE(ob + bytes <= fb || fb + bytes <= ob, "%s: out must not overlap field", who);
-    const unsigned nrg = (unsigned)((fh + FC_ROWS - 1) / FC_ROWS), chunks = (unsigned)((fw + FC_CHUNK - 1) / FC_CHUNK);
-    PWS_REQUIRE((size_t)n * nrg < (1u << 31) && chunks < 65536, "%s: field or batch too large", who);
-    if (uncovered) {
-        const hipError_t e = hipMemsetAsync(uncovered, 0, (size_t)n * sizeof(int), as_stream(stream));
-        if (e != hipSuccess) {
-            set_error("%s: clearing uncovered: %s", who, hipGetErrorString(e));
-            return PWS_EHIP;
-        }
-    }
+    if (int rc = lattice_pointers(who, field && d && out, addr(field) | addr(out) | addr(d), addr(uncovered),
+                                  "field, out and d must be 8-byte aligned, uncovered 4-byte aligned"))
+        return rc;
+    if (int rc = lattice_overlap(who, field, out, n, fh, fw, false)) return rc;
+    unsigned nrg, chunks;
+    if (int rc = lattice_grid(who, fh, fw, FC_ROWS, (size_t)n, 1, "batch", nrg, chunks)) return rc;
+    if (int rc = lattice_clear(who, "uncovered", (size_t)n * sizeof(int), as_stream(stream), uncovered)) return rc;
     const Geo geo = compose_geo(fh, fw, h0, w0);
     const dim3 grid((unsigned)n * nrg, chunks, 1), block(kWave * FC_ROWS);
     if (rows) {

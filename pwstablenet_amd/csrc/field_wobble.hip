@@ -12,9 +12,8 @@
 // padding.  removed[t] = the largest max(|out_x - F_x| w0/2, |out_y - F_y| h0/2) over the usable nodes of t (fmaxf: a NaN drops out), 0
 // without any.
 //
-// Launch shape: a time-walking kernel.  A wave owns 128 consecutive nodes of ONE row, a lane 2 adjacent ones (16-byte loads and stores,
-// field_rigid.hip's row and lane layout); a workgroup is 2 waves = 2 rows.  Segments in time supply the parallelism that the 512 waves
-// of a 256 x 256 field lack: blockIdx.z is a segment of FW_L = 32 output frames, and a lane walks its 32 + 2R input frames once:
+// Launch shape: a time-walking kernel on field_lattice.h's rows and lanes (16-byte loads and stores); a workgroup is 2 waves = 2 rows and
+// the grid is (row groups, chunks, segments).  Segments in time supply the parallelism that the 512 waves of a 256 x 256 field lack: blockIdx.z is a segment of FW_L = 32 output frames, and a lane walks its 32 + 2R input frames once:
 //   load F[tin], evaluate P[tin] (three fp64 divisions per node: ONCE per frame the lane visits, not once per tap), E[tin] into the ring;
 //   then frame tout = tin - R has all its taps in the ring: sum, divide, store.
 // The ring of the last 2R+1 residuals lives in REGISTERS: the kernel is a template on R and the walk is unrolled by the ring length 2R+1 --
@@ -24,8 +23,8 @@
 // lane that wrote it: no barrier); F[tout] is read again from memory (a second read of the field, mostly from L2 / MALL).
 // Re-read factor of the field and of the fp64 work: (L + 2R) / L = 1.06 (R = 1) .. 1.38 (sigma 2, R = 6) .. 1.94 (sigma 5, R = 15), plus the
 // second read of F.  A scene of n <= 32 frames is one segment: 512 waves at 256 x 256.
-// Statistics: per output frame and wave a shuffle reduction, then lane 0 adds the count if it is not 0 and raises the maximum -- an integer
-// atomic max on the bits of a non-negative float, attempted only when a relaxed load shows a smaller value (the value only grows, so a stale
+// Statistics: per output frame and wave field_lattice.h's shuffle reduction, then lane 0 adds the count if it is not 0 and raises the
+// maximum -- an integer atomic max on the bits of a non-negative float, attempted only when a relaxed load shows a smaller value (the value only grows, so a stale
 // read costs one needless atomic at worst).  Exact, and the same on every run.  No floating-point atomics anywhere.
 //
 // Measured on an MI355X (profiles/wobble_bench.json), 128 x 256 x 256 nodes (64 MB in, 64 MB out): sigma 2 takes 61 us (0.48 us per frame),
@@ -41,7 +40,7 @@
 //   R 11: 172 / 2 / 24576    R 12: 185 / 2 / 26624    R 13: 194 / 2 / 28672    R 14: 205 / 2 / 30720    R 15: 215 / 2 / 32768
 // (An earlier form, `#pragma unroll` over the ring slots, was left rolled by the optimiser from R = 13 on and put the ring in scratch, 448 ..
 // 512 bytes per lane: hence the template steps.)
-#include "common.h"
+#include "field_lattice.h"
 #include "rigid_position.h"
 
 #include <cmath>
@@ -50,11 +49,9 @@
 namespace pws {
 namespace {
 
-constexpr int FW_PER_LANE = 2, FW_CHUNK = kWave * FW_PER_LANE, FW_ROWS = 2;   // nodes per lane / per wave, rows (waves) per workgroup
-constexpr int FW_L = PWS_WOBBLE_SEGMENT;                                     // output frames per segment
-constexpr int FW_MAX_R = 15;                                                  // sigma <= 5
-
-typedef float F32x4a8 __attribute__((ext_vector_type(4), aligned(8)));   // 16 bytes at the field's 8-byte alignment (rows of odd width)
+constexpr int FW_ROWS = 2;                   // rows (waves) per workgroup
+constexpr int FW_L = PWS_WOBBLE_SEGMENT;    // output frames per segment
+constexpr int FW_MAX_R = 15;                 // sigma <= 5
 
 struct WobbleWeights {
     float g[FW_MAX_R + 1];   // g[|k|]; g[0] = 1
@@ -82,10 +79,7 @@ struct WobbleWalk {
     int pw;                // the delay line's slot of this step's P: q mod (R+1)
 
     __device__ __forceinline__ F32x4a8 load(int t) const {
-        const float *f = field + (size_t)t * frame_stride + node;
-        if (two) return *reinterpret_cast<const F32x4a8 *>(f);
-        const float2 h = *reinterpret_cast<const float2 *>(f);
-        return F32x4a8{h.x, h.y, h.x, h.y};
+        return load_pair(field + (size_t)t * frame_stride + node, two);
     }
 
     template <int S>
@@ -153,16 +147,10 @@ struct WobbleWalk {
             } else {
                 kept += two ? 1 : 0;
             }
-            float *o = out + (size_t)tout * frame_stride + node;
-            if (two) *reinterpret_cast<F32x4a8 *>(o) = F32x4a8{o0, o1, o2, o3};
-            else *reinterpret_cast<float2 *>(o) = make_float2(o0, o1);
+            store_pair(out + (size_t)tout * frame_stride + node, two, F32x4a8{o0, o1, o2, o3});
         }
         if (removed_bits || unfit) {   // (kernel arguments: uniform)
-#pragma unroll
-            for (int d = kWave / 2; d > 0; d >>= 1) {
-                kept += __shfl_xor(kept, d, kWave);
-                big = fmaxf(big, __shfl_xor(big, d, kWave));
-            }
+            wave_sum_max(kept, big);
             if (lane == 0) {
                 if (unfit && kept != 0) atomicAdd(unfit + tout, kept);
                 // (big >= 0: its bits order as ints.  The value only grows: a stale read costs one needless atomic at worst)
@@ -185,14 +173,14 @@ __global__ void __launch_bounds__(kWave *FW_ROWS) field_wobble_kernel(const floa
                                                                        int *__restrict__ removed_bits, int *__restrict__ unfit) {
     constexpr int RING = 2 * R + 1;
     __shared__ f32x4 pline[R + 1][kWave * FW_ROWS];
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int i = (int)blockIdx.x * FW_ROWS + wave, j0 = (int)blockIdx.y * FW_CHUNK + (int)(threadIdx.x & 63u) * FW_PER_LANE;
+    const LatticePos p = lattice_rows<FW_ROWS>(0, blockIdx.x);
+    const int i = p.i, j0 = p.j0;
     WobbleWalk<R> w;
     w.field = field, w.m = m, w.out = out, w.pline = &pline[0][threadIdx.x], w.removed_bits = removed_bits, w.unfit = unfit, w.wt = wt;
     w.active = i < fh && j0 < fw, w.two = j0 + 1 < fw;   // (a row of odd width: its last lane holds one node)
     w.node = w.active ? ((size_t)i * fw + j0) * 2 : 0, w.frame_stride = (size_t)fh * fw * 2;
     w.v = (double)i * sv - 1.0, w.u0 = (double)j0 * su - 1.0, w.u1 = (double)(j0 + 1) * su - 1.0;
-    w.half_w = half_w, w.half_h = half_h, w.n = n, w.lane = (int)(threadIdx.x & 63u);
+    w.half_w = half_w, w.half_h = half_h, w.n = n, w.lane = p.lane;
     w.t0 = (int)blockIdx.z * FW_L;
     w.steps = (min(n, w.t0 + FW_L) - w.t0) + 2 * R;   // input frames t0 - R .. t1 - 1 + R, one per step; step q >= 2R also writes frame t0 + q - 2R
     w.wfull = 0.f;   // W where every tap is usable: the same ascending fp32 sum
@@ -218,36 +206,26 @@ using namespace pws;
 
 extern "C" int pws_field_wobble(const float *field, int n, int fh, int fw, const double *m, double sigma, int h0, int w0, float *out,
                                 float *removed, int *unfit, pws_stream_t stream) {
-    PWS_REQUIRE(n >= 0, "pws_field_wobble: bad shape");
-    PWS_REQUIRE(fh >= 2 && fw >= 2, "pws_field_wobble: the field needs at least 2 x 2 nodes (got %d x %d)", fw, fh);
+    const char *who = "pws_field_wobble";
+    if (int rc = lattice_shape(who, n, fh, fw)) return rc;
     PWS_REQUIRE(h0 >= 1 && w0 >= 1, "pws_field_wobble: bad frame size %d x %d", w0, h0);
     PWS_REQUIRE(sigma > 0.0 && sigma <= 5.0, "pws_field_wobble: sigma must lie in (0, 5] frames, got %g", sigma);   // (false for NaN)
     if (n == 0) return PWS_OK;
-    PWS_REQUIRE(field && m && out, "pws_field_wobble: NULL pointer");
-    PWS_REQUIRE(((reinterpret_cast<size_t>(field) | reinterpret_cast<size_t>(out) | reinterpret_cast<size_t>(m)) & 7) == 0 &&
-                    ((reinterpret_cast<size_t>(removed) | reinterpret_cast<size_t>(unfit)) & 3) == 0,
-                "pws_field_wobble: field, out and m must be 8-byte aligned, removed and unfit 4-byte aligned");
-    const size_t bytes = (size_t)n * fh * fw * 2 * sizeof(float);
-    const char *fb = reinterpret_cast<const char *>(field), *ob = reinterpret_cast<const char *>(out);
-    PWS_REQUIRE(ob + bytes <= fb || fb + bytes <= ob,
-                "pws_field_wobble: out must not overlap field (the filter reads neighbouring frames: it cannot run in place)");
-    const unsigned nrg = (unsigned)((fh + FW_ROWS - 1) / FW_ROWS), chunks = (unsigned)((fw + FW_CHUNK - 1) / FW_CHUNK);
+    if (int rc = lattice_pointers(who, field && m && out, addr(field) | addr(out) | addr(m), addr(removed) | addr(unfit),
+                                  "field, out and m must be 8-byte aligned, removed and unfit 4-byte aligned"))
+        return rc;
+    if (int rc = lattice_overlap(who, field, out, n, fh, fw, false,
+                                 "out must not overlap field (the filter reads neighbouring frames: it cannot run in place)"))
+        return rc;
     const unsigned nseg = (unsigned)((n + FW_L - 1) / FW_L);
-    PWS_REQUIRE(chunks < 65536 && nseg < 65536, "pws_field_wobble: field or scene too large");
-    void *const stats[2] = {removed, unfit};
-    for (void *stat : stats) {
-        if (!stat) continue;
-        const hipError_t e = hipMemsetAsync(stat, 0, (size_t)n * 4, as_stream(stream));   // (0.0f and 0 alike)
-        if (e != hipSuccess) {
-            set_error("pws_field_wobble: clearing the statistics: %s", hipGetErrorString(e));
-            return PWS_EHIP;
-        }
-    }
+    unsigned nrg, chunks;
+    if (int rc = lattice_grid(who, fh, fw, FW_ROWS, 1, nseg, "scene", nrg, chunks)) return rc;
+    if (int rc = lattice_clear(who, "the statistics", (size_t)n * 4, as_stream(stream), removed, unfit)) return rc;
     const int R = (int)std::ceil(3.0 * sigma);   // 1 .. 15
     WobbleWeights wt;
     for (int k = 0; k <= FW_MAX_R; ++k) wt.g[k] = k <= R ? (float)std::exp(-(double)(k * k) / (2.0 * sigma * sigma)) : 0.f;
-    // node j -> u = 2 (j (w0-1)/(fw-1)) / w0 - 1 = j su - 1; rows alike (pws_field_rigid's)
-    const double su = 2.0 * (double)(w0 - 1) / ((double)(fw - 1) * (double)w0), sv = 2.0 * (double)(h0 - 1) / ((double)(fh - 1) * (double)h0);
+    double su, sv;
+    node_scale(fh, fw, h0, w0, &su, &sv);
     const dim3 grid(nrg, chunks, nseg);
     const float half_w = 0.5f * (float)w0, half_h = 0.5f * (float)h0;
     int *const rb = reinterpret_cast<int *>(removed);

@@ -34,6 +34,11 @@ __device__ __forceinline__ RigidFrame rigid_frame(const double *__restrict__ M) 
     return f;
 }
 
+// The node-to-frame scale (host): node j stands for u = 2 (j (w0-1)/(fw-1)) / w0 - 1 = j su - 1; rows alike with sv
+inline void node_scale(int fh, int fw, int h0, int w0, double *su, double *sv) {
+    *su = 2.0 * (double)(w0 - 1) / ((double)(fw - 1) * (double)w0), *sv = 2.0 * (double)(h0 - 1) / ((double)(fh - 1) * (double)h0);
+}
+
 // v = i sv - 1 of the node's row
 __device__ __forceinline__ RigidRow rigid_row(const RigidFrame &f, double v) {
     return RigidRow{f.a01 * v + f.a02, f.a11 * v + f.a12, f.a21 * v + f.a22};

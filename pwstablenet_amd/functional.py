@@ -585,6 +585,26 @@ def zoom_coefficients(windows, frame_hw, field_hw):
     return coef.pin_memory() if torch.cuda.is_available() else coef
 
 
+def _field_operands(what, field, operands=(), name="field"):
+    """ValueError unless every (name, tensor, dtype) of ``operands`` is a tensor of that dtype on the device and ``field`` is (T, fh, fw, 2)
+    with at least 2 x 2 nodes: the first checks of every field operator, in this order."""
+    for oname, t, dtype in operands:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
+            raise ValueError("%s: %s must be a %s tensor on the device, got %s" % (
+                what, oname, dtype, "%s on %s" % (t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t)))
+    if field.dim() != 4 or field.shape[3] != 2 or field.shape[1] < 2 or field.shape[2] < 2:
+        raise ValueError("%s: %s must be (T, fh, fw, 2) with fh, fw >= 2, got %s" % (what, name, tuple(field.shape),))
+
+
+def _field_out(what, field, out, stats, *dtypes):
+    """``out`` checked against ``field`` (ValueError), or allocated, and -- ``stats`` -- one (T,) device tensor per dtype, None otherwise."""
+    if out is None:
+        out = torch.empty(field.shape, device=field.device, dtype=torch.float32)
+    elif tuple(out.shape) != tuple(field.shape) or not out.is_contiguous():
+        raise ValueError("%s: out must be a contiguous %s float32 tensor" % (what, tuple(field.shape),))
+    return [out] + [torch.empty((field.shape[0],), device=field.device, dtype=dt) if stats else None for dt in dtypes]
+
+
 def _field_zoom(field, coef, frame_hw, align_corners, mode, out, uncovered):
     """pws_field_zoom on device tensors: ``coef`` (T, 4) float32, ``uncovered`` (T,) int32 or None."""
     A.check(A.lib().pws_field_zoom(A.ptr(field), field.shape[0], field.shape[1], field.shape[2], A.ptr(coef), A.ptr(out), int(frame_hw[0]),
@@ -608,17 +628,12 @@ def zoom_fields(field, windows, frame_hw, align_corners=False, mode="bilinear", 
     if mode not in INTERPOLATIONS:
         raise ValueError("mode must be one of %s, got %r" % (INTERPOLATIONS, mode))
     A.require_cuda(field)
-    if field.dim() != 4 or field.shape[3] != 2 or field.shape[1] < 2 or field.shape[2] < 2:
-        raise ValueError("zoom_fields: field must be (T, fh, fw, 2) with fh, fw >= 2, got %s" % (tuple(field.shape),))
+    _field_operands("zoom_fields", field)
     field = field.contiguous()
     n = field.shape[0]
     coef = zoom_coefficients(_zoom_windows(windows, n, frame_hw), frame_hw, field.shape[1:3]).to(field.device, non_blocking=True)
-    if out is None:
-        out = torch.empty_like(field)
     A.require_cuda(out)
-    if tuple(out.shape) != tuple(field.shape) or not out.is_contiguous():
-        raise ValueError("zoom_fields: out must be a contiguous %s float32 tensor" % (tuple(field.shape),))
-    unc = torch.empty((n,), device=field.device, dtype=torch.int32) if return_uncovered else None
+    out, unc = _field_out("zoom_fields", field, out, return_uncovered, torch.int32)
     _field_zoom(field, coef, frame_hw, align_corners, mode, out, unc)
     return (out, unc) if return_uncovered else out
 
@@ -674,13 +689,8 @@ def compose_fields(field, d, frame_hw, align_corners=False, mode="bilinear", out
         raise ValueError("mode must be one of %s, got %r" % (INTERPOLATIONS, mode))
     r = _check_rolling_shutter(rolling_shutter, "compose_fields")
     rows = r != 0.0 and rates is not None
-    for name, t, dtype in (("field", field, torch.float32), ("d", d, torch.float64)) + ((("out", out, torch.float32),) if out is not None else ()) + (
-            (("rates", rates, torch.float64),) if rows else ()):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
-            raise ValueError("compose_fields: %s must be a %s tensor on the device, got %s" % (
-                name, dtype, "%s on %s" % (t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t)))
-    if field.dim() != 4 or field.shape[3] != 2 or field.shape[1] < 2 or field.shape[2] < 2:
-        raise ValueError("compose_fields: field must be (T, fh, fw, 2) with fh, fw >= 2, got %s" % (tuple(field.shape),))
+    _field_operands("compose_fields", field, (("field", field, torch.float32), ("d", d, torch.float64)) + (
+        (("out", out, torch.float32),) if out is not None else ()) + ((("rates", rates, torch.float64),) if rows else ()))
     n = field.shape[0]
     if tuple(d.shape) != (n, 6):
         raise ValueError("compose_fields: d must be (%d, 6), got %s" % (n, tuple(d.shape)))
@@ -690,11 +700,7 @@ def compose_fields(field, d, frame_hw, align_corners=False, mode="bilinear", out
     if h0 < 2 or w0 < 2:
         raise ValueError("compose_fields: the frame must be at least 2 x 2 pixels, got %d x %d" % (w0, h0))
     field, d = field.contiguous(), d.contiguous()
-    if out is None:
-        out = torch.empty_like(field)
-    if tuple(out.shape) != tuple(field.shape) or not out.is_contiguous():
-        raise ValueError("compose_fields: out must be a contiguous %s float32 tensor" % (tuple(field.shape),))
-    unc = torch.empty((n,), device=field.device, dtype=torch.int32) if return_uncovered else None
+    out, unc = _field_out("compose_fields", field, out, return_uncovered, torch.int32)
     if rows:
         _field_compose_rows(field, d, rates.contiguous(), r, (h0, w0), align_corners, mode, out, unc)
     else:
@@ -733,27 +739,18 @@ def rigid_fields(field, m, frame_hw, rigidity=1.0, out=None, return_stats=False)
     unfit (T,) int32, the number of nodes that kept F because no homography applied to them; both on the device.
     ValueError: shapes or dtypes other than these, a host tensor, rigidity outside [0, 1]."""
     r = _check_rigidity(rigidity, "rigid_fields")
-    for name, t, dtype in (("field", field, torch.float32), ("m", m, torch.float64)) + ((("out", out, torch.float32),) if out is not None else ()):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
-            raise ValueError("rigid_fields: %s must be a %s tensor on the device, got %s" % (
-                name, dtype, "%s on %s" % (t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t)))
-    if field.dim() != 4 or field.shape[3] != 2 or field.shape[1] < 2 or field.shape[2] < 2:
-        raise ValueError("rigid_fields: field must be (T, fh, fw, 2) with fh, fw >= 2, got %s" % (tuple(field.shape),))
+    _field_operands("rigid_fields", field, (("field", field, torch.float32), ("m", m, torch.float64)) + (
+        (("out", out, torch.float32),) if out is not None else ()))
     n = field.shape[0]
     if tuple(m.shape) not in ((n, 3, 3), (n, 9)):
         raise ValueError("rigid_fields: m must be (%d, 3, 3) or (%d, 9), got %s" % (n, n, tuple(m.shape)))
     h0, w0 = int(frame_hw[0]), int(frame_hw[1])
     if h0 < 1 or w0 < 1:
         raise ValueError("rigid_fields: bad frame size %d x %d" % (w0, h0))
-    if out is not None and (tuple(out.shape) != tuple(field.shape) or not out.is_contiguous()):
-        raise ValueError("rigid_fields: out must be a contiguous %s float32 tensor" % (tuple(field.shape),))
-    if out is not None and out.data_ptr() == field.data_ptr() and not field.is_contiguous():
+    out, res, unfit = _field_out("rigid_fields", field, out, return_stats, torch.float32, torch.int32)
+    if out.data_ptr() == field.data_ptr() and not field.is_contiguous():
         raise ValueError("rigid_fields: out=field needs a contiguous field")
     field, m = field.contiguous(), m.contiguous()
-    if out is None:
-        out = torch.empty_like(field)
-    res = torch.empty((n,), device=field.device, dtype=torch.float32) if return_stats else None
-    unfit = torch.empty((n,), device=field.device, dtype=torch.int32) if return_stats else None
     _field_rigid(field, m, (h0, w0), r, out, res, unfit)
     return (out, res, unfit) if return_stats else out
 
@@ -797,29 +794,20 @@ def wobble_fields(field, m, frame_hw, sigma, scene_cuts=None, out=None, return_s
     to choose sigma by -- and unfit (T,) int32, the nodes that kept F because they were not usable; both on the device, no synchronisation.
     ValueError: shapes or dtypes other than these, a host tensor, sigma outside (0, 5], bad cuts, an ``out`` that overlaps ``field``."""
     s = _check_wobble(sigma, "wobble_fields")
-    for name, t, dtype in (("field", field, torch.float32), ("m", m, torch.float64)) + ((("out", out, torch.float32),) if out is not None else ()):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
-            raise ValueError("wobble_fields: %s must be a %s tensor on the device, got %s" % (
-                name, dtype, "%s on %s" % (t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t)))
-    if field.dim() != 4 or field.shape[3] != 2 or field.shape[1] < 2 or field.shape[2] < 2:
-        raise ValueError("wobble_fields: field must be (T, fh, fw, 2) with fh, fw >= 2, got %s" % (tuple(field.shape),))
+    _field_operands("wobble_fields", field, (("field", field, torch.float32), ("m", m, torch.float64)) + (
+        (("out", out, torch.float32),) if out is not None else ()))
     n = field.shape[0]
     if tuple(m.shape) not in ((n, 3, 3), (n, 9)):
         raise ValueError("wobble_fields: m must be (%d, 3, 3) or (%d, 9), got %s" % (n, n, tuple(m.shape)))
     h0, w0 = int(frame_hw[0]), int(frame_hw[1])
     if h0 < 1 or w0 < 1:
         raise ValueError("wobble_fields: bad frame size %d x %d" % (w0, h0))
-    if out is not None and (tuple(out.shape) != tuple(field.shape) or not out.is_contiguous()):
-        raise ValueError("wobble_fields: out must be a contiguous %s float32 tensor" % (tuple(field.shape),))
+    out, removed, unfit = _field_out("wobble_fields", field, out, return_stats, torch.float32, torch.int32)
     cuts = _cut_list(scene_cuts, n, "wobble_fields")
     field, m = field.contiguous(), m.contiguous().reshape(n, 9)
-    if out is None:
-        out = torch.empty_like(field)
     nbytes = field.numel() * 4
     if n and out.data_ptr() < field.data_ptr() + nbytes and field.data_ptr() < out.data_ptr() + nbytes:
         raise ValueError("wobble_fields: out must not overlap field (the filter reads neighbouring frames: it cannot run in place)")
-    removed = torch.empty((n,), device=field.device, dtype=torch.float32) if return_stats else None
-    unfit = torch.empty((n,), device=field.device, dtype=torch.int32) if return_stats else None
     for a, b in (_scenes(n, cuts) if n else []):
         _field_wobble(field[a:b], m[a:b], (h0, w0), s, out[a:b], removed[a:b] if return_stats else None, unfit[a:b] if return_stats else None)
     return (out, removed, unfit) if return_stats else out

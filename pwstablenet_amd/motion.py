@@ -314,8 +314,7 @@ def limit_path(d, fields, frame_hw, fraction, levels=16, relax=1.0, scene_cuts=N
     for name, t, dtype in (("d", d, torch.float64), ("fields", fields, torch.float32)) + ((("rates", rates, torch.float64),) if rows else ()):
         if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
             raise ValueError("limit_path: %s must be a %s tensor on the device" % (name, dtype))
-    if fields.dim() != 4 or fields.shape[3] != 2 or fields.shape[1] < 2 or fields.shape[2] < 2:
-        raise ValueError("limit_path: fields must be (T, fh, fw, 2) with fh, fw >= 2, got %s" % (tuple(fields.shape),))
+    PF._field_operands("limit_path", fields, name="fields")
     T, fh, fw = fields.shape[:3]
     if tuple(d.shape) != (T, 6):
         raise ValueError("limit_path: d must be (%d, 6), got %s" % (T, tuple(d.shape)))
