@@ -43,7 +43,7 @@
  *   pws_border_keep_*             out[t] = covered ? warped[t] : out[t-1] over a scene's warped frames (no counterpart in the reference)
  *   pws_border_mosaic_*           uncovered pixels from the nearest covering frame within a radius, past or future (no counterpart in the reference)
  *   pws_border_edge_*             uncovered pixels from the source frame itself, clamped or mirrored beyond its rim (no counterpart in the reference)
- *   pws_adam_step                 optim.Adam(...).step()           main_new.py:63,216
+ *   pws_adam_step / _multi / _d   optim.Adam(...).step()           main_new.py:63,216
  *   pws_field_homography          the automatic crop's per-frame findHomography + perspectiveTransform  main_new.py:550-603
  *   pws_scene_change              the window's end clamp, applied at hard cuts too (cut score)          main_new.py:627-633
  *   pws_block_motion / pws_motion_fit  global motion between consecutive window planes: the stability metric (no counterpart in the reference)
@@ -856,6 +856,19 @@ int pws_adam_step(float *p, const float *g, float *m, float *v, size_t count, fl
  * element counts): a generator has 92 tensors, most of them small. */
 int pws_adam_step_multi(float *const *p, const float *const *g, float *const *m, float *const *v, const size_t *counts,
                         int ntensors, float lr, float beta1, float beta2, float eps, int step, pws_stream_t stream);
+
+/* pws_adam_step / pws_adam_step_multi with the hyper-parameters as the DOUBLES the caller wrote (what optim.Adam calls).  torch's
+ * formulation: m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;  p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 -
+ * beta2^step) + eps).  The host rounds beta and 1 - beta to fp32 each on its own, and forms lr / (1 - beta1^step) and 1 / sqrt(1 -
+ * beta2^step) in double; state and arithmetic on the device are fp32.  A float entry cannot do this: (float)0.999 no longer says what
+ * 1 - 0.999 was (1.f - 0.999f = 0.99998713e-3 against 1.00000005e-3: 1.3e-5 of every v, 6e-6 of every update).  The float entries above
+ * forward here with (double) of their arguments, which gives the kernels the scalars those entries always gave them.  Every element gets
+ * the same roundings whether it is updated in a float4 or alone (a ragged tail, buffers that are not 16-byte aligned).  Same errors as the float entries (PWS_EINVAL: step < 1, a NULL
+ * pointer with a non-zero count; pws_adam_step_d: buffers not 16-byte aligned with count > 256). */
+int pws_adam_step_d(float *p, const float *g, float *m, float *v, size_t count, double lr, double beta1, double beta2, double eps,
+                    int step, pws_stream_t stream);
+int pws_adam_step_multi_d(float *const *p, const float *const *g, float *const *m, float *const *v, const size_t *counts, int ntensors,
+                          double lr, double beta1, double beta2, double eps, int step, pws_stream_t stream);
 
 /* ---------------------------------------------------------------- training objective around the path
  * The per-step losses the reference's train() wraps round netG + grid_sample (main_new.py:101-118,184-212;

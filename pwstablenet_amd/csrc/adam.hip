@@ -6,31 +6,33 @@
 
 namespace pws {
 
+// One element's update, the same roundings wherever it runs: the compiler contracts `b2 * v + c2 * g * g` into one fused multiply-add
+// in the float4 bodies and into none in the scalar tails, so the same values in an aligned and an unaligned buffer got different bits
+// in v.  The fused operations are therefore spelled out -- as the float4 bodies, which update almost every element, have always had them.
+__device__ __forceinline__ void adam_update(float &p, float g, float &m, float &v, float b1, float c1, float b2, float c2, float eps,
+                                            float step_size, float inv_bc2_sqrt) {
+    m = __builtin_fmaf(b1, m, c1 * g);
+    v = __builtin_fmaf(c2 * g, g, b2 * v);
+    p = __builtin_fmaf(-step_size, m / __builtin_fmaf(sqrtf(v), inv_bc2_sqrt, eps), p);
+}
+
 __global__ void __launch_bounds__(256) adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
-                                                   float *__restrict__ v, size_t n4, size_t count, float b1, float b2,
-                                                   float eps, float step_size, float inv_bc2_sqrt) {
+                                                   float *__restrict__ v, size_t n4, size_t count, float b1, float c1,
+                                                   float b2, float c2, float eps, float step_size, float inv_bc2_sqrt) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         float4 pp = reinterpret_cast<float4 *>(p)[i], gg = reinterpret_cast<const float4 *>(g)[i];
         float4 mm = reinterpret_cast<float4 *>(m)[i], vv = reinterpret_cast<float4 *>(v)[i];
         float *P = &pp.x, *G = &gg.x, *M = &mm.x, *V = &vv.x;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            M[k] = b1 * M[k] + (1.f - b1) * G[k];
-            V[k] = b2 * V[k] + (1.f - b2) * G[k] * G[k];
-            P[k] -= step_size * (M[k] / (sqrtf(V[k]) * inv_bc2_sqrt + eps));
-        }
+        for (int k = 0; k < 4; ++k) adam_update(P[k], G[k], M[k], V[k], b1, c1, b2, c2, eps, step_size, inv_bc2_sqrt);
         reinterpret_cast<float4 *>(p)[i] = pp, reinterpret_cast<float4 *>(m)[i] = mm, reinterpret_cast<float4 *>(v)[i] = vv;
     }
     // ragged tail (count % 4) handled by the first lanes of block 0
     const size_t tail0 = n4 * 4;
     if (blockIdx.x == 0 && tail0 + threadIdx.x < count) {
         const size_t i = tail0 + threadIdx.x;
-        const float gi = g[i];
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi, v[i] = vi;
-        p[i] -= step_size * (mi / (sqrtf(vi) * inv_bc2_sqrt + eps));
+        adam_update(p[i], g[i], m[i], v[i], b1, c1, b2, c2, eps, step_size, inv_bc2_sqrt);
     }
 }
 
@@ -49,8 +51,8 @@ struct AdamMultiArgs {
 };
 static_assert(sizeof(AdamMultiArgs) <= 4096, "kernel argument block");
 
-__global__ void __launch_bounds__(256) adam_multi_kernel(const AdamMultiArgs a, float b1, float b2, float eps, float step_size,
-                                                         float inv_bc2_sqrt) {
+__global__ void __launch_bounds__(256) adam_multi_kernel(const AdamMultiArgs a, float b1, float c1, float b2, float c2, float eps,
+                                                         float step_size, float inv_bc2_sqrt) {
     int lo = 0, hi = a.ntensors - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -70,32 +72,35 @@ __global__ void __launch_bounds__(256) adam_multi_kernel(const AdamMultiArgs a, 
             float4 mm = *reinterpret_cast<float4 *>(m + e), vv = *reinterpret_cast<float4 *>(v + e);
             float *P = &pp.x, *G = &gg.x, *M = &mm.x, *V = &vv.x;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                M[k] = b1 * M[k] + (1.f - b1) * G[k];
-                V[k] = b2 * V[k] + (1.f - b2) * G[k] * G[k];
-                P[k] -= step_size * (M[k] / (sqrtf(V[k]) * inv_bc2_sqrt + eps));
-            }
+            for (int k = 0; k < 4; ++k) adam_update(P[k], G[k], M[k], V[k], b1, c1, b2, c2, eps, step_size, inv_bc2_sqrt);
             *reinterpret_cast<float4 *>(p + e) = pp, *reinterpret_cast<float4 *>(m + e) = mm, *reinterpret_cast<float4 *>(v + e) = vv;
         } else {
             for (size_t i = e; i < e + 4 && i < count; ++i) {
-                const float gi = g[i];
-                const float mi = b1 * m[i] + (1.f - b1) * gi;
-                const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-                m[i] = mi, v[i] = vi;
-                p[i] -= step_size * (mi / (sqrtf(vi) * inv_bc2_sqrt + eps));
+                adam_update(p[i], g[i], m[i], v[i], b1, c1, b2, c2, eps, step_size, inv_bc2_sqrt);
             }
         }
     }
 }
 
+// What the host works out of the caller's hyper-parameters, in double: the decay factors and THEIR complements rounded to fp32 each on
+// its own (1 - 0.999 is 1.00000005e-3 as a float; 1.f - 0.999f is 0.99998713e-3, a 1.3e-5 relative error in every v), lr over the first
+// bias correction, the reciprocal root of the second.
+struct AdamScalars {
+    float b1, c1, b2, c2, eps, step_size, inv_bc2_sqrt;
+};
+
+static AdamScalars adam_scalars(double lr, double beta1, double beta2, double eps, int step) {
+    const double bc1 = 1.0 - std::pow(beta1, step), bc2 = 1.0 - std::pow(beta2, step);
+    return {(float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)(lr / bc1), (float)(1.0 / std::sqrt(bc2))};
+}
+
 }  // namespace pws
 
-extern "C" int pws_adam_step_multi(float *const *p, const float *const *g, float *const *m, float *const *v, const size_t *counts,
-                                   int ntensors, float lr, float beta1, float beta2, float eps, int step, pws_stream_t stream) {
+extern "C" int pws_adam_step_multi_d(float *const *p, const float *const *g, float *const *m, float *const *v, const size_t *counts,
+                                     int ntensors, double lr, double beta1, double beta2, double eps, int step, pws_stream_t stream) {
     PWS_REQUIRE(step >= 1, "pws_adam_step_multi: step counts from 1 (got %d)", step);
     PWS_REQUIRE(ntensors >= 0 && (ntensors == 0 || (p && g && m && v && counts)), "pws_adam_step_multi: bad arguments");
-    const double bc1 = 1.0 - std::pow((double)beta1, step), bc2 = 1.0 - std::pow((double)beta2, step);
-    const float step_size = (float)(lr / bc1), inv_bc2_sqrt = (float)(1.0 / std::sqrt(bc2));
+    const pws::AdamScalars s = pws::adam_scalars(lr, beta1, beta2, eps, step);
     double total = 0;
     for (int i = 0; i < ntensors; ++i) total += (double)counts[i];
     pws::ProfScope prof(pws::KID_ADAM, 12.0 * total, 28.0 * total, pws::as_stream(stream));
@@ -113,22 +118,21 @@ extern "C" int pws_adam_step_multi(float *const *p, const float *const *g, float
         }
         a.ntensors = k;
         if (k == 0) continue;
-        hipLaunchKernelGGL(pws::adam_multi_kernel, dim3(nb), dim3(256), 0, pws::as_stream(stream), a, beta1, beta2, eps, step_size,
-                           inv_bc2_sqrt);
+        hipLaunchKernelGGL(pws::adam_multi_kernel, dim3(nb), dim3(256), 0, pws::as_stream(stream), a, s.b1, s.c1, s.b2, s.c2, s.eps,
+                           s.step_size, s.inv_bc2_sqrt);
     }
     return pws::check_launch("adam_multi_kernel");
 }
 
-extern "C" int pws_adam_step(float *p, const float *g, float *m, float *v, size_t count, float lr, float beta1, float beta2,
-                             float eps, int step, pws_stream_t stream) {
+extern "C" int pws_adam_step_d(float *p, const float *g, float *m, float *v, size_t count, double lr, double beta1, double beta2,
+                               double eps, int step, pws_stream_t stream) {
     PWS_REQUIRE(step >= 1, "pws_adam_step: step counts from 1 (got %d)", step);
     if (count == 0) return PWS_OK;
     PWS_REQUIRE(p && g && m && v, "pws_adam_step: NULL pointer");
     const bool al = ((reinterpret_cast<size_t>(p) | reinterpret_cast<size_t>(g) | reinterpret_cast<size_t>(m) |
                       reinterpret_cast<size_t>(v)) & 15) == 0;
     const size_t n4 = al ? count / 4 : 0;
-    const double bc1 = 1.0 - std::pow((double)beta1, step), bc2 = 1.0 - std::pow((double)beta2, step);
-    const float step_size = (float)(lr / bc1), inv_bc2_sqrt = (float)(1.0 / std::sqrt(bc2));
+    const pws::AdamScalars s = pws::adam_scalars(lr, beta1, beta2, eps, step);
     size_t blocks = (n4 + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     if (blocks == 0) blocks = 1;
@@ -137,7 +141,19 @@ extern "C" int pws_adam_step(float *p, const float *g, float *m, float *v, size_
         PWS_REQUIRE(count <= 256, "pws_adam_step: buffers must be 16-byte aligned (count %zu)", count);
     }
     pws::ProfScope prof(pws::KID_ADAM, 12.0 * count, 28.0 * count, pws::as_stream(stream));
-    hipLaunchKernelGGL(pws::adam_kernel, dim3((unsigned)blocks), dim3(256), 0, pws::as_stream(stream), p, g, m, v, n4, count,
-                       beta1, beta2, eps, step_size, inv_bc2_sqrt);
+    hipLaunchKernelGGL(pws::adam_kernel, dim3((unsigned)blocks), dim3(256), 0, pws::as_stream(stream), p, g, m, v, n4, count, s.b1, s.c1,
+                       s.b2, s.c2, s.eps, s.step_size, s.inv_bc2_sqrt);
     return pws::check_launch("adam_kernel");
+}
+
+// The float entries: the same update from fp32 hyper-parameters.  1.0 - (double)b is exact and rounds to exactly 1.f - b, and the
+// double of a float converts back to itself, so the kernels get the scalars these entries have always given them.
+extern "C" int pws_adam_step_multi(float *const *p, const float *const *g, float *const *m, float *const *v, const size_t *counts,
+                                   int ntensors, float lr, float beta1, float beta2, float eps, int step, pws_stream_t stream) {
+    return pws_adam_step_multi_d(p, g, m, v, counts, ntensors, (double)lr, (double)beta1, (double)beta2, (double)eps, step, stream);
+}
+
+extern "C" int pws_adam_step(float *p, const float *g, float *m, float *v, size_t count, float lr, float beta1, float beta2,
+                             float eps, int step, pws_stream_t stream) {
+    return pws_adam_step_d(p, g, m, v, count, (double)lr, (double)beta1, (double)beta2, (double)eps, step, stream);
 }

@@ -814,7 +814,7 @@ def wobble_fields(field, m, frame_hw, sigma, scene_cuts=None, out=None, return_s
 
 
 def adam_step_(p, g, m, v, lr, beta1, beta2, eps, step):
-    """In-place fused Adam on flat fp32 CUDA buffers."""
+    """In-place fused Adam on flat fp32 CUDA buffers; the hyper-parameters travel as doubles (pws_adam_step_d)."""
     A.require_cuda(p, g, m, v)
-    A.check(A.lib().pws_adam_step(A.ptr(p), A.ptr(g), A.ptr(m), A.ptr(v), p.numel(), lr, beta1, beta2, eps, step,
-                                  A.current_stream()), "pws_adam_step")
+    A.check(A.lib().pws_adam_step_d(A.ptr(p), A.ptr(g), A.ptr(m), A.ptr(v), p.numel(), lr, beta1, beta2, eps, step,
+                                    A.current_stream()), "pws_adam_step_d")

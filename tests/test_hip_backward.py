@@ -298,7 +298,8 @@ def test_netg_training_step_vs_reference_golden(hip, netg_golden, tag, kind, ngf
 
 def test_two_forwards_one_backward_and_adam(hip):
     """The reference's loop runs netG twice before one backward (main_new.py:101,112,214); gradients must add up.
-    Then one fused-Adam step must match torch.optim.Adam on the same gradients."""
+    Then one fused-Adam step must match torch.optim.Adam on the same gradients.
+    (tests/test_hip_adam_float64.py is where the optimiser -- p, m and v, over many steps -- is held to float64.)"""
     from pwstablenet_amd import functional as PF
     from pwstablenet_amd.optim import Adam
     net = make_net("W1", 16)

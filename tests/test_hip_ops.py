@@ -604,6 +604,7 @@ def test_upsample_and_fused_720p_golden(hip, ops_golden):
 
 
 def test_adam_golden_and_ragged(hip, oracle, ops_golden):
+    """(tests/test_hip_adam_float64.py is where the optimiser -- p, m and v, over many steps -- is held to float64.)"""
     A, g = hip, ops_golden
     p = dev(g["adam_p0"].copy())
     m, v = torch.zeros_like(p), torch.zeros_like(p)
