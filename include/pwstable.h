@@ -848,6 +848,73 @@ int pws_field_reach(const float *field, int n, int fh, int fw, const double *tab
 int pws_path_limit(const double *d, const int *counts, int n, int levels, double relax, int *need, double *strength, double *d_out,
                    pws_stream_t stream);
 
+/* Deblurring (csrc/deblur.hip; no counterpart in the reference; OpenCV videostab's WeightingDeblurer with bilinear donors): a blurred SOURCE
+ * frame borrows detail from the sharper frames of its scene around it, aligned by the clip's global motion, before the warp reads it.
+ * Three steps -- sharpness, plan, blend -- all in DEVICE memory, no synchronisation.  tests/deblur_ref.py restates them.
+ *
+ * Sharpness.  S[t] = sum over the interior 1 <= x <= w-2, 1 <= y <= h-2 of (I[y,x+1] - I[y,x-1])^2 + (I[y+1,x] - I[y-1,x])^2, with I an
+ * integer intensity, accumulated in 64-bit integers into sharpness (n) int64, which the entry zeroes itself.  Exact integer arithmetic:
+ * workgroup partials are added with vector 64-bit atomics, and the result does not depend on their order -- the same bits on every run.
+ *   pws_frame_sharpness_u8:  frames (n, h, w, 3) bytes, I = (29 c0 + 150 c1 + 77 c2 + 128) >> 8 (BGR order; rgb != 0 swaps the 29 and the 77).
+ *   pws_plane_sharpness_u8:  a plane of h x w bytes per frame, frame t at planes + t * frame_stride (in samples; the Y plane of a packed
+ *     frame with its packed size as the stride), I = the byte.
+ *   pws_plane_sharpness_u16: the same for 16-bit words; layout 0: I = word >> 6 (P010, P210), 1: I = min(word, 1023) (I010, I210, I410).
+ * h, w >= 3.  n == 0 returns PWS_OK and launches nothing.  PWS_EINVAL: n < 0 or above 65535, h or w below 3, h w >= 2^31, a stride smaller
+ * than the plane, a layout other than 0 / 1, a NULL pointer, sharpness not 8-byte aligned, 16-bit planes or their stride not 2-byte
+ * aligned.  One memset and one launch. */
+int pws_frame_sharpness_u8(const unsigned char *frames_hwc, int n, int h, int w, int rgb, long long *sharpness, pws_stream_t stream);
+int pws_plane_sharpness_u8(const unsigned char *planes, size_t frame_stride, int n, int h, int w, long long *sharpness, pws_stream_t stream);
+int pws_plane_sharpness_u16(const unsigned short *planes, size_t frame_stride, int n, int h, int w, int layout, long long *sharpness,
+                            pws_stream_t stream);
+
+/* The deblurring plan of ONE scene of n frames (call once per scene, as pws_path_smooth).
+ * motion:    (n, 4) fp64 = (a, b, tx, ty) as pws_motion_fit_scaled writes it: row k maps a position of frame k, relative to the frame centre
+ *   ((w-1)/2, (h-1)/2) and in frame pixels, to frame k-1: p' = [[a, -b], [b, a]] p + (tx, ty).  Row 0 is not read.
+ * sharpness: (n) int64, S as above.     radius: R = 1 .. 15.
+ * maps:      (n, 2R+1, 6) fp64, row-major 2 x 3: maps[t, R+k] takes a centred position of frame t to frame t+k.  Column R is the identity.
+ *   Both chains are walked OUTWARD from t, one step per column, C_j = step_j o C_{j-1} with C_0 the identity: to the past step_j = motion[t-j+1]
+ *   (so that C_j = motion[t-j+1] o ... o motion[t]); to the future step_j = motion[t+j]^-1 = (ia, ib, -(ia tx + ib ty); -ib, ia, ib tx - ia ty)
+ *   with d = a a + b b, ia = a / d, ib = b / d.  A composition is l = s0 c0 + s1 c3, ..., the translation (s0 c2 + s1 c5) + s2; every product
+ *   and every sum is rounded once, in this order.
+ * A chain stops at the scene's ends, and at the first step whose motion row is not finite or whose hypot(a, b) lies outside [0.5, 2]: from
+ *   that column outward the map is NaN and the gain 0.  (Smoothing counts such a row as the identity; a donor that is not aligned is worse
+ *   than none.)
+ * gain:      (n, 2R+1) fp32: (float)(1 - (double)S[t] / (double)S[t+k]) where the chain reaches frame t+k and S[t+k] > S[t], else 0; column R is 0.
+ * donors:    (n) int32, the gains of the row that are positive.
+ * One fixed order: the same bits on every run.  n == 1 gives the identity and no donor; n == 0 returns PWS_OK and launches nothing.
+ * PWS_EINVAL: n < 0 or above 2^24, radius outside 1 .. 15, a NULL pointer, motion / sharpness / maps not 8-byte aligned, gain / donors not
+ * 4-byte aligned.  The outputs must not overlap the inputs.  Two launches. */
+int pws_deblur_plan(const double *motion, const long long *sharpness, int n, int radius, double *maps, float *gain, int *donors,
+                    pws_stream_t stream);
+
+/* The deblurring blend.  frames: n consecutive SOURCE frames; maps (stop - start, 2R+1, 6) fp64 and gain (stop - start, 2R+1) fp32: the plan's
+ * rows of frames [start, stop); out: stop - start frames of the frames' layout, not overlapping frames.  Every read is of `frames`, so calls
+ * over [start, stop) pieces of a clip that is padded by R frames give the bytes of one call.  Per sample position p = (x, y) of frame t:
+ *   acc = own sample(s), wsum = 1; then k = -R .. -1, 1 .. R in this order, only where gain[t, k] > 0 and 0 <= t+k < n:
+ *   q = maps[t, k] (p - c) + c with c = ((w-1)/2, (h-1)/2), in fp64 as qx = (m0 dx + (m1 dy + m2)) + cx, qy = (m3 dx + (m4 dy + m5)) + cy, each
+ *     product and sum rounded once; each coordinate is then rounded ONCE to fp32.  The donor counts only if 0 <= qx <= w-1 and
+ *     0 <= qy <= h-1 on those fp32 values (NaN: no donor).
+ *   The donor frame is sampled bilinearly in fp32 at x0 = clamp(floor(qx), 0, w-2), lx = qx - x0 (y alike): taps that hold one value give it.
+ *   weight = gain s / (s + |I_q - I_0|), I the sample itself (planes) or (29 c0 + 150 c1 + 77 c2) / 256 of the own resp. the interpolated
+ *     channels (3-byte pixels); s = sensitivity in 8-bit gray levels, times 4 for 16-bit planes (10-bit samples).
+ *   acc += weight sample, wsum += weight.
+ * The output is acc / wsum rounded to the NEAREST integer (ties to even) and clamped to the sample range 0 .. 255 resp. 0 .. 1023: a blend
+ * of frames that truncated would come out half a level darker than the frames beside it that have no donor.
+ *   pws_deblur_u8:        (n, h, w, 3) bytes; the three channels are blended with one weight.
+ *   pws_deblur_plane_u8:  frames of `rows` rows of w bytes whose first h rows are the plane to blend: a packed YUV frame with its packed rows,
+ *     whose LUMA is blended and whose chroma rows are copied from the frame's own source.  w % 4 == 0.
+ *   pws_deblur_plane_u16: the same for 16-bit words; layout 0: the sample is word >> 6 and is written back << 6, 1: min(word, 1023).
+ * A frame without a donor (no positive gain inside [0, n)) is copied word for word.  h, w >= 2.  start == stop returns PWS_OK and launches
+ * nothing.  PWS_EINVAL: a bad shape or range, radius outside 1 .. 15, a sensitivity that is not finite and positive, w % 4 != 0 (planes),
+ * rows < h, rows w (3 h w for pixels) >= 2^31, n above 65535, a NULL pointer, maps not 8-byte or gain not 4-byte aligned, frames / out not 4-byte
+ * (u8 planes) resp. 8-byte (u16 planes) aligned.  One launch. */
+int pws_deblur_u8(const unsigned char *frames_hwc, const double *maps, const float *gain, unsigned char *out, int n, int start, int stop,
+                  int radius, int h, int w, double sensitivity, pws_stream_t stream);
+int pws_deblur_plane_u8(const unsigned char *frames, const double *maps, const float *gain, unsigned char *out, int n, int start, int stop,
+                        int radius, int rows, int h, int w, double sensitivity, pws_stream_t stream);
+int pws_deblur_plane_u16(const unsigned short *frames, const double *maps, const float *gain, unsigned short *out, int n, int start, int stop,
+                         int radius, int rows, int h, int w, int layout, double sensitivity, pws_stream_t stream);
+
 /* Adam (no weight decay / amsgrad) on a flat fp32 buffer, in place; step counts from 1. */
 int pws_adam_step(float *p, const float *g, float *m, float *v, size_t count, float lr, float beta1,
                   float beta2, float eps, int step, pws_stream_t stream);

@@ -547,6 +547,82 @@ def edge_borders_(warped, source, field, edge, pixel_format="bgr24", swap_rb=Fal
     return warped
 
 
+DEBLUR_MAX_RADIUS = 15   # frames: the generator's own window of +-15 frames at period 30, and mosaic_borders_' reach
+
+
+def _check_deblur(radius, sensitivity, what, zero_ok=False):
+    """(R, s): ``radius`` as an int in 1 .. 15 (or 0 .. 15) and ``sensitivity`` as a finite positive float; ValueError otherwise (NaN included)."""
+    try:
+        r = int(radius)
+        whole = not isinstance(radius, bool) and r == radius
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole or not (0 if zero_ok else 1) <= r <= DEBLUR_MAX_RADIUS:
+        raise ValueError("%s: the deblur radius must be a whole number of frames in %d .. %d, got %r" % (what, 0 if zero_ok else 1, DEBLUR_MAX_RADIUS, radius))
+    try:
+        s = float(sensitivity)
+    except (TypeError, ValueError):
+        raise ValueError("%s: the deblur sensitivity must be a number of gray levels, got %r" % (what, sensitivity)) from None
+    if not (0.0 < s < float("inf")) or s > 3.0e38:
+        raise ValueError("%s: the deblur sensitivity must be finite and positive, got %r" % (what, sensitivity))
+    return r, s
+
+
+def deblur_frames(frames, maps, gain, start=0, stop=None, pixel_format="bgr24", sensitivity=4.0, out=None):
+    """Deblurring for the integer pixel formats (OpenCV videostab's ``WeightingDeblurer`` with bilinear donors; csrc/deblur.hip;
+    include/pwstable.h pws_deblur_u8 has the definition in full): ``frames``, n consecutive SOURCE frames of one clip (``keep_borders_``'
+    shapes and formats), and the plan's rows for frames ``[start, stop)`` (``stop=None``: n) -- ``maps`` (stop - start, 2R+1, 6) float64 and
+    ``gain`` (stop - start, 2R+1) float32 as ``stream.deblur_plan`` returns them, on the device.  Returns the stop - start deblurred frames, in
+    a fresh tensor or in ``out`` (same layout, not overlapping ``frames``).  Per sample position p of frame t: the frame's own sample with
+    weight 1, and for k = -R .. -1, 1 .. R with ``gain[t, k] > 0`` and frame t+k inside [0, n), the donor frame sampled bilinearly (fp32) at
+    ``q = maps[t, k] (p - centre) + centre`` -- fp64, rounded once to fp32, used only where 0 <= qx <= W-1 and 0 <= qy <= H-1 -- with weight
+    ``gain * s / (s + |I_q - I_0|)``: s = ``sensitivity`` in 8-bit gray levels (times 4 for the 10-bit formats), I the sample for YUV and
+    (29 B + 150 G + 77 R) / 256 for BGR, whose three channels share the weight.  The weighted mean is rounded to the nearest integer and
+    clamped to the sample range (P010 / P210 words are written back ``<< 6``).  Packed YUV frames have their LUMA blended and their chroma
+    planes copied: blur detail lives in luma.  A frame without donors is a copy.  Every read is of ``frames``, so chunked calls over a clip
+    padded by R frames give the bytes of one call (``mosaic_borders_``' property).
+    The sensitivity guards against donors that do not show the same thing -- parallax, moving objects, a motion fit that is off: a donor
+    s gray levels away gets half its gain.  The default 4.0 is a judgement that no footage here can fit, like ``zoom_speed``: OpenCV's 0.1
+    lends almost nothing on the synthetic clip of tests/test_deblur_ref_cpu.py.  One launch.
+    ValueError: float frames, host tensors, shapes or dtypes that do not fit, a range outside 0 <= start <= stop <= n, R outside 1 .. 15, a
+    sensitivity that is not finite and positive."""
+    if not isinstance(frames, torch.Tensor) or frames.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError("deblur_frames: frames must be uint8 or uint16 (the integer pixel formats), got %s" % (getattr(frames, "dtype", type(frames)),))
+    fmt = lookup_format(pixel_format) or _packed_format(pixel_format, torch.uint8)   # (an unknown format is a ValueError)
+    if fmt.hwc and (frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3):
+        raise ValueError("deblur_frames: bgr24 frames must be uint8 (T,H,W,3), got %s %s" % (frames.dtype, tuple(frames.shape)))
+    n, h, w = fmt.frame_shape(frames)   # (packed frames: a tensor of the other depth's dtype is a ValueError)
+    start, stop = int(start), n if stop is None else int(stop)
+    if not 0 <= start <= stop <= n:
+        raise ValueError("deblur_frames: the range must satisfy 0 <= start <= stop <= %d, got [%d, %d)" % (n, start, stop))
+    m = stop - start
+    if (not isinstance(maps, torch.Tensor) or maps.dtype != torch.float64 or maps.dim() != 3 or maps.shape[0] != m or maps.shape[2] != 6
+            or maps.shape[1] % 2 != 1):
+        raise ValueError("deblur_frames: maps must be (%d, 2R+1, 6) float64, got %s %s" % (m, getattr(maps, "dtype", type(maps)), tuple(getattr(maps, "shape", ()))))
+    k = maps.shape[1]
+    if not isinstance(gain, torch.Tensor) or gain.dtype != torch.float32 or tuple(gain.shape) != (m, k):
+        raise ValueError("deblur_frames: gain must be (%d, %d) float32, got %s %s" % (m, k, getattr(gain, "dtype", type(gain)), tuple(getattr(gain, "shape", ()))))
+    radius, s = _check_deblur((k - 1) // 2, sensitivity, "deblur_frames")
+    if h < 2 or w < 2:
+        raise ValueError("deblur_frames: frames must be at least 2 x 2 (the bilinear taps), got %d x %d" % (w, h))
+    if not (frames.is_cuda and maps.is_cuda and gain.is_cuda):
+        raise ValueError("deblur_frames: frames, maps and gain must be on the device (there is no CPU path)")
+    if out is None:
+        out = torch.empty((m,) + tuple(frames.shape[1:]), dtype=frames.dtype, device=frames.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != frames.dtype or tuple(out.shape) != (m,) + tuple(frames.shape[1:]) or not out.is_cuda
+          or not out.is_contiguous()):
+        raise ValueError("deblur_frames: out must be a contiguous %s tensor %s on the device" % (frames.dtype, (m,) + tuple(frames.shape[1:])))
+    frames, maps, gain = frames.contiguous(), maps.contiguous(), gain.contiguous()
+    head = (A.ptr(frames), A.ptr(maps), A.ptr(gain), A.ptr(out), n, start, stop, radius)
+    if fmt.hwc:
+        A.check(A.lib().pws_deblur_u8(*head, h, w, s, A.current_stream()), "pws_deblur_u8")
+    elif fmt.dtype == torch.uint8:
+        A.check(A.lib().pws_deblur_plane_u8(*head, frames.shape[1], h, w, s, A.current_stream()), "pws_deblur_plane_u8")
+    else:
+        A.check(A.lib().pws_deblur_plane_u16(*head, frames.shape[1], h, w, fmt.layout, s, A.current_stream()), "pws_deblur_plane_u16")
+    return out
+
+
 def _zoom_windows(windows, n, frame_hw, what="zoom_fields"):
     """``windows`` -- one (x0, x1, y0, y1) or (n, 4) of them, a sequence or a tensor on either side -- as n tuples of floats; ValueError unless
     every one satisfies 0 <= x0 < x1 <= W0 and 0 <= y0 < y1 <= H0 (source-pixel EDGE coordinates: pixel k covers [k, k + 1))."""

@@ -277,6 +277,13 @@ SIGNATURES = {
     "pws_path_levels": (_I, [_P, _I, _I, _P, _P]),
     "pws_field_reach": (_I, [_P, _I, _I, _I, _P, _I, _P, _D, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "pws_path_limit": (_I, [_P, _P, _I, _I, _D, _P, _P, _P, _P]),
+    "pws_frame_sharpness_u8": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "pws_plane_sharpness_u8": (_I, [_P, _S, _I, _I, _I, _P, _P]),
+    "pws_plane_sharpness_u16": (_I, [_P, _S, _I, _I, _I, _I, _P, _P]),
+    "pws_deblur_plan": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
+    "pws_deblur_u8": (_I, [_P, _P, _P, _P] + [_I] * 6 + [_D, _P]),
+    "pws_deblur_plane_u8": (_I, [_P, _P, _P, _P] + [_I] * 7 + [_D, _P]),
+    "pws_deblur_plane_u16": (_I, [_P, _P, _P, _P] + [_I] * 8 + [_D, _P]),
     "pws_field_zoom": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "pws_field_rigid": (_I, [_P, _I, _I, _I, _P, _F, _I, _I, _P, _P, _P, _P]),
     "pws_field_wobble": (_I, [_P, _I, _I, _I, _P, _D, _I, _I, _P, _P, _P, _P]),

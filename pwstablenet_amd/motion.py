@@ -162,6 +162,68 @@ def shutter_rates(motion, scene_cuts=None):
     return rates
 
 
+def frame_sharpness(frames, pixel_format="bgr24", frames_are_rgb=False, out=None):
+    """How sharp each frame is, for deblurring (csrc/deblur.hip; include/pwstable.h pws_frame_sharpness_u8 has the definition): ``frames`` in
+    any integer ``pixel_format`` (``functional.keep_borders_``' shapes), on the device.  ``S[t]`` is the sum over the interior pixels of
+    ``(I[y,x+1] - I[y,x-1])^2 + (I[y+1,x] - I[y-1,x])^2`` with the integer intensity I = ``(29 B + 150 G + 77 R + 128) >> 8`` for "bgr24"
+    (``frames_are_rgb`` swaps the 29 and the 77), the Y plane for the packed YUV formats -- P010 / P210 words ``>> 6``, I010 / I210 / I410
+    words clamped to 1023.  Measured on the frames themselves: on the 256 x 256 window planes a 5-tap blur shows as a ratio of 0.90, here as
+    0.33.  Returns (T,) int64 on the device (``out``: a contiguous (T,) int64 device tensor to fill), no synchronisation.  Exact integer
+    arithmetic: the same bits on every run.  ValueError: float frames, host tensors, a shape that does not fit, frames below 3 x 3."""
+    if not isinstance(frames, torch.Tensor) or frames.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError("frame_sharpness: frames must be uint8 or uint16 (the integer pixel formats), got %s" % (getattr(frames, "dtype", type(frames)),))
+    fmt = PF.lookup_format(pixel_format) or PF._packed_format(pixel_format, torch.uint8)   # (an unknown format is a ValueError)
+    if fmt.hwc and (frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3):
+        raise ValueError("frame_sharpness: bgr24 frames must be uint8 (T,H,W,3), got %s %s" % (frames.dtype, tuple(frames.shape)))
+    n, h, w = fmt.frame_shape(frames)   # (packed frames: a tensor of the other depth's dtype is a ValueError)
+    if h < 3 or w < 3:
+        raise ValueError("frame_sharpness: frames must be at least 3 x 3 (the interior), got %d x %d" % (w, h))
+    if not frames.is_cuda:
+        raise ValueError("frame_sharpness: frames must be on the device (there is no CPU path)")
+    if out is None:
+        out = torch.empty((n,), device=frames.device, dtype=torch.int64)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (n,) or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("frame_sharpness: out must be a contiguous (%d,) int64 tensor on the device" % n)
+    frames = frames.contiguous()
+    if fmt.hwc:
+        A.check(A.lib().pws_frame_sharpness_u8(A.ptr(frames), n, h, w, int(bool(frames_are_rgb)), A.ptr(out), A.current_stream()), "pws_frame_sharpness_u8")
+    elif fmt.dtype == torch.uint8:
+        A.check(A.lib().pws_plane_sharpness_u8(A.ptr(frames), frames.shape[1] * w, n, h, w, A.ptr(out), A.current_stream()), "pws_plane_sharpness_u8")
+    else:
+        A.check(A.lib().pws_plane_sharpness_u16(A.ptr(frames), frames.shape[1] * w, n, h, w, fmt.layout, A.ptr(out), A.current_stream()),
+                "pws_plane_sharpness_u16")
+    return out
+
+
+def deblur_plan(motion, sharpness, radius, scene_cuts=None):
+    """Which neighbours lend a frame detail, and where (csrc/deblur.hip; include/pwstable.h pws_deblur_plan has the definition): ``motion``
+    (T, 4) float64 on the device as ``global_motion(..., pixel_scale=(W / 256, H / 256))`` returns it -- row k maps frame k to frame k-1, in
+    frame pixels about the frame centre -- ``sharpness`` (T,) int64 (``frame_sharpness``) and ``radius`` R in 1 .. 15.  Returns
+    ``maps`` (T, 2R+1, 6) float64 -- ``maps[t, R+k]``, row-major 2 x 3, takes a centred position of frame t to frame t+k: the chain of the
+    per-pair similarities, resp. of their inverses, walked outward from t; the centre column is the identity -- ``gain`` (T, 2R+1) float32,
+    ``1 - S[t] / S[t+k]`` where frame t+k is sharper and 0 elsewhere, and ``donors`` (T,) int32, the positive gains per frame: what
+    ``functional.deblur_frames`` takes.  A chain stops at the scene's ends (``scene_cuts`` as for ``smooth_path``) and at the first pair whose
+    motion is not finite or whose scale lies outside [0.5, 2]: from there outward the map is NaN and the gain 0 -- a donor that is not
+    aligned is worse than none.  On the device, no synchronisation; two launches per scene, on slices; the same bits on every run.
+    One global similarity per pair: parallax and moving objects are not aligned, only down-weighted by ``deblur_frames``' sensitivity.
+    ValueError: tensors other than these, on the device; a radius outside 1 .. 15; bad cuts."""
+    _check_motion(motion, "deblur_plan")
+    T = motion.shape[0]
+    if (not isinstance(sharpness, torch.Tensor) or not sharpness.is_cuda or sharpness.dtype != torch.int64 or tuple(sharpness.shape) != (T,)):
+        raise ValueError("deblur_plan: sharpness must be a (%d,) int64 tensor on the device" % T)
+    radius, _ = PF._check_deblur(radius, 1.0, "deblur_plan")
+    motion, sharpness = motion.contiguous(), sharpness.contiguous()
+    cuts = _cut_list(scene_cuts, T, "deblur_plan")
+    k = 2 * radius + 1
+    maps = torch.empty((T, k, 6), device=motion.device, dtype=torch.float64)
+    gain = torch.empty((T, k), device=motion.device, dtype=torch.float32)
+    donors = torch.empty((T,), device=motion.device, dtype=torch.int32)
+    for a, b in (_scenes(T, cuts) if T else []):
+        A.check(A.lib().pws_deblur_plan(A.ptr(motion[a:b]), A.ptr(sharpness[a:b]), b - a, radius, A.ptr(maps[a:b]), A.ptr(gain[a:b]),
+                                        A.ptr(donors[a:b]), A.current_stream()), "pws_deblur_plan")
+    return maps, gain, donors
+
+
 def estimate_rolling_shutter(motion, mv, sad, activity, plane_hw, radius=16, min_activity=2000, pixel_scale=None, scene_cuts=None,
                              frame_height=None, return_terms=False):
     """The rolling-shutter share r of a clip, estimated from what ``global_motion(..., return_blocks=True)`` measured on it

@@ -24,8 +24,8 @@ from .frameio import (_area_resize_yuv, _crop, _frames_shape, _output_resize, _w
                       area_half, area_resize, area_resize_yuv, area_resize_yuv16, window_planes, window_planes_yuv, window_planes_yuv16)
 from .framing import (_bounds_rows, _centred_window, _check_lattice, _field_homography, _has_lattice, auto_crop_window,  # noqa: F401
                       field_homography, zoom_schedule, zoom_window)
-from .motion import (_check_limit, _check_max_se, _check_shutter, _check_sigma, block_motion, estimate_rolling_shutter,  # noqa: F401
-                     global_motion, limit_path, limit_rectangle, scene_scores, shutter_rates, smooth_path, stability_scores)
+from .motion import (_check_limit, _check_max_se, _check_shutter, _check_sigma, block_motion, deblur_plan, estimate_rolling_shutter,  # noqa: F401
+                     frame_sharpness, global_motion, limit_path, limit_rectangle, scene_scores, shutter_rates, smooth_path, stability_scores)
 from .scenes import _check_cuts, _cut_rule, _scenes, find_scene_cuts  # noqa: F401
 
 
@@ -71,7 +71,8 @@ def _hand_over(warped, dest, lane, down):
 
 class StreamPlan(collections.namedtuple("StreamPlan", "fmt h w oh ow T n_all halo_left halo_right chunk chunks in_flight on_host half_size_output "
                                         "frames_are_rgb crop zmode zwin zoom_speed zoom_min two_pass mosaic radius keep rigid edge metrics lattice "
-                                        "smooth shutter max_se wobble max_crop limit_levels limit_relax detect cuts scene_threshold scene_min_len")):
+                                        "smooth shutter max_se wobble max_crop limit_levels limit_relax detect cuts scene_threshold scene_min_len deblur "
+                                        "deblur_sensitivity")):
     """Everything that run_video decides from its arguments and the stabiliser's options before it touches the device (VideoStabilizer._plan):
     the format record ``fmt``; the source ``h`` x ``w`` and the output ``oh`` x ``ow`` before the crop; the ``T`` frames to stabilise of the
     ``n_all`` given, the halos, ``chunk`` and the ``chunks`` [(start, stop)] in the index space of the frames (the first / last chunk carry
@@ -79,7 +80,8 @@ class StreamPlan(collections.namedtuple("StreamPlan", "fmt h w oh ow T n_all hal
     or "auto"; ``zmode``: None, "fixed" (``zwin``, the one window), "auto" or "adaptive" (``zoom_speed``, ``zoom_min``); ``two_pass``: pass 1
     keeps fields and bounds, the host decides, pass 2 warps; ``mosaic`` and its ``radius``, ``keep``, ``rigid``, the ``edge`` mode,
     ``metrics``, ``lattice`` (the frame holds the homography fit's); ``smooth`` (sigma, 0: off), ``shutter`` (a float or "auto") and ``max_se``, ``wobble`` (sigma, 0: off), ``max_crop`` (None: off) with ``limit_levels`` and the resolved ``limit_relax``; ``detect``
-    (scene_cuts="auto") with its thresholds, and ``cuts``, the checked list the call starts from."""
+    (scene_cuts="auto") with its thresholds, and ``cuts``, the checked list the call starts from; ``deblur`` (the radius, 0: off) and
+    ``deblur_sensitivity``."""
     __slots__ = ()
 
 
@@ -106,8 +108,15 @@ def _windows(gray_padded, start, count, period):
 class VideoStabilizer:
     def __init__(self, netG, batch=32, period=30, device=None, swap_rb=False, interpolation="bilinear", borders="black", rigidity=0.0,
                  mosaic_radius=8, edge="pad", metrics=False, smooth=0.0, rolling_shutter=0.0, wobble=0.0, max_crop=None, limit_levels=16,
-                 limit_relax=None, shutter_max_se=0.02):
+                 limit_relax=None, shutter_max_se=0.02, deblur=0, deblur_sensitivity=4.0):
         self.net = netG
+        # run_video lends every SOURCE frame detail from the sharper frames of its scene within `deblur` frames, 1 .. 15, aligned by the clip's
+        # global motion, in front of the untouched warp (functional.deblur_frames; OpenCV videostab's order): shake blurs some frames and
+        # leaves their neighbours sharp, and once the shake is gone the sharpness pulses.  deblur_sensitivity, in 8-bit gray levels: a donor
+        # that far from the frame's own sample gets half its gain; 4.0 is a judgement that no footage here can fit, like zoom_speed.
+        # 0: no launch, no allocation, every path as it was
+        self.deblur, self.deblur_sensitivity = PF._check_deblur(deblur, deblur_sensitivity, "VideoStabilizer", zero_ok=True)
+        self.deblur_sharpness = self.deblur_donors = None   # deblur > 0, of the last run_video, on the device: (T,) int64 / (T,) int32
         # run_video low-passes the NON-RIGID part of the clip's fields along time: each field minus its fitted homography, under a Gaussian of
         # `wobble` frames, in (0, 5] (functional.wobble_fields).  The generator regresses every field from that frame's own window, and the
         # local part of consecutive fields shimmers; rigidity removes that part altogether, this keeps it and steadies it.  0: no launch, no
@@ -612,6 +621,22 @@ class VideoStabilizer:
         ``self.smooth_correction_unlimited`` (T, 6), what ``smooth_path`` returned; ``self.smooth_correction`` is then the limited D.  It
         bounds the correction and nothing else -- not the generator's own field -- and works with every pixel_format, interpolation,
         edge, crop, zoom, rigidity, wobble, rolling_shutter, in_flight, scene_cuts and metrics.  ValueError: max_crop without smooth > 0.
+        VideoStabilizer(deblur=R, deblur_sensitivity=4.0), R in 1 .. 15 frames: deblurring (OpenCV videostab's ``WeightingDeblurer``).  Shake
+        blurs some frames and leaves their neighbours sharp; once the shake is gone the sharpness pulses.  Every SOURCE frame borrows detail
+        from the sharper frames of its scene within R frames, in front of the untouched warp.  The call takes the two-pass route, also
+        without a crop, zoom, smooth or wobble.  Pass 1: the upload stream also computes ``frame_sharpness`` of each uploaded chunk, beside
+        its window planes.  Between the passes, on the caller's stream: ``global_motion(input planes, pixel_scale=(W / 256, H / 256))`` --
+        the INPUT's own motion, whatever the fields do -- then ``deblur_plan`` under the call's cuts.  Pass 2 prefetches frames
+        [s - R, e + R) of each chunk, clipped to the clip (host frames are uploaded again with the overlap, device frames are read in place),
+        deblurs the chunk into a buffer of its own (``functional.deblur_frames``: every read is of the original frames, so chunks give the
+        bytes of one call over the clip), and everything behind reads that buffer as its source: zoom, warp, edge pass, metrics planes,
+        resize and crop.  Packed YUV frames have their luma deblurred and their chroma left alone.  Left on the device, no synchronisation,
+        None at deblur = 0, which takes no new path: ``self.deblur_sharpness`` (T,) int64 -- of the SOURCE frames -- and ``self.deblur_donors``
+        (T,) int32, the neighbours each frame borrowed from.  One global similarity per pair: parallax and moving objects are guarded by the
+        sensitivity term alone; sensor noise raises every frame's sharpness alike and shrinks the gains; nothing was validated on real
+        footage.  Every integer pixel_format, interpolation, edge, crop, zoom, rigidity, wobble, smooth, max_crop, scene_cuts (also "auto"),
+        in_flight and metrics works as without it.  ValueError: halos, borders="keep" or "mosaic" (no second pass), float frames, R outside
+        0 .. 15, a sensitivity that is not finite and positive.  ``run()`` does not take it.
         Returns (T, H, W, 3) -- or (T, H/2, W/2, 3) / (T, height, width, 3), or the crop window of it -- uint8 on the inputs' side; for YUV
         (T, oh * 3 // 2, ow) of the output (or crop window) size oh x ow."""
         plan = self._plan(frames, chunk, half_size_output, frames_are_rgb, halo_left, halo_right, crop, output_size, in_flight, pixel_format,
@@ -738,7 +763,15 @@ class VideoStabilizer:
             if not second_pass:
                 raise ValueError("run_video: wobble > 0 warps in a second pass, which borders=\"%s\" does not have yet" % self.borders)
             _check_lattice(h, w, "wobble > 0")
-        two_pass = auto or zmode in ("auto", "adaptive") or smoothing or wob > 0.0   # pass 1: fields and bounds; the host's decision; pass 2: the warp
+        deblur, dsens = PF._check_deblur(self.deblur, self.deblur_sensitivity, "run_video", zero_ok=True)   # (the attributes can be set after construction)
+        if deblur > 0:
+            if halos:
+                raise ValueError("run_video: deblur > 0 needs the whole clip (a shard cannot see its neighbours' sharpness or the scene's motion)")
+            if not second_pass:
+                raise ValueError("run_video: deblur > 0 reads the source in a second pass, which borders=\"%s\" does not have yet" % self.borders)
+            _check_integer_frames(frames, "run_video", "deblur=%d" % deblur)
+        # pass 1: fields and bounds; the host's decision; pass 2: the warp
+        two_pass = auto or zmode in ("auto", "adaptive") or smoothing or wob > 0.0 or deblur > 0
         detect = isinstance(scene_cuts, str)
         if detect and scene_cuts != "auto":
             raise ValueError("scene_cuts must be None, \"auto\" or a sorted sequence of frame indices, got %r" % (scene_cuts,))
@@ -751,7 +784,7 @@ class VideoStabilizer:
         return StreamPlan(fmt, h, w, oh, ow, T, n_all, halo_left, halo_right, chunk, chunks, max(1, int(in_flight)) if T > 0 else 1, not frames.is_cuda,
                           bool(half_size_output), bool(frames_are_rgb), window, zmode, zwin, zoom_speed, zoom_min, bool(two_pass), mosaic, radius,
                           self.borders == "keep", rigid, self.edge, metrics, _has_lattice(h, w), self.smooth, rs, max_se, wob, max_crop, limit_levels,
-                          limit_relax, detect, cuts, scene_threshold, scene_min_len)
+                          limit_relax, detect, cuts, scene_threshold, scene_min_len, deblur, dsens)
 
     def _reset(self, plan):
         """What the previous run_video left goes, in one place, once the plan stands: every result is None until this call sets it."""
@@ -763,6 +796,7 @@ class VideoStabilizer:
         self.shutter_rates = self.shutter_estimate = self.rolling_shutter_used = None
         self.limit_strength = self.limit_need = self.limit_uncovered = self.smooth_correction_unlimited = None
         self.wobble_removed = self.wobble_unfit = None
+        self.deblur_sharpness = self.deblur_donors = None
         self.scene_cuts = list(plan.cuts)   # scene_cuts="auto" extends it chunk by chunk
         if plan.detect:
             self.scene_wait_s = 0.0   # host time spent waiting for scores (tools/scene_cuts_bench.py)
@@ -886,6 +920,8 @@ class _Call:
             self.fields = torch.empty((T, 256, 256, 2), device=dev, dtype=torch.float32)
             self.hom = torch.empty((T, 9), device=dev, dtype=torch.float64)
             self.bounds = torch.empty((T, 4), device=dev, dtype=torch.float32)
+        if p.deblur > 0:   # (no halos: the frames given are the T core frames)
+            self.sharp = torch.empty((T,), device=dev, dtype=torch.int64)
         self.up.wait_stream(compute)   # gray_all was allocated on the compute stream
         self.pend = None   # borders="mosaic": the chunk that waits for its successor -- (warped, fields, cs, ce, buf, valid frames of the head pad)
         if p.mosaic:
@@ -902,6 +938,8 @@ class _Call:
         with torch.cuda.stream(self.up):
             buf = self.frames[s:e].to(self.vs.device, non_blocking=True) if p.on_host else self.frames[s:e]
             _window_planes(buf, p.fmt, 256, self.gray_all[s:e], "run_video", p.frames_are_rgb)
+            if p.deblur > 0:   # beside the planes, from the same uploaded frames
+                frame_sharpness(buf, p.fmt.name, p.frames_are_rgb, out=self.sharp[s:e])
             ev = torch.cuda.Event()
             ev.record(self.up)
             if p.detect:   # same stream: ordered behind the planes (and behind the previous chunk's, whose last plane it reads)
@@ -958,8 +996,8 @@ class _Call:
         vs, p = self.vs, self.plan
         fields, hom = self.fields[cs:ce], self.hom[cs:ce]
         vs._fields(gray, hl, hr, fields, sc)
-        if not p.smooth > 0.0 or p.rigid or p.wobble > 0.0:   # (smoothing fits the fields it composes, between the passes; the blend and the
-            #                                                     wobble filter need the raw fit)
+        if (not p.smooth > 0.0 or p.rigid or p.wobble > 0.0) and p.lattice:   # (smoothing fits the fields it composes, between the passes; the
+            # blend and the wobble filter need the raw fit; deblurring alone takes the two passes at any size and needs no fit)
             _field_homography(fields, p.h, p.w, hom, self.bounds[cs:ce])
         if p.rigid:   # the kept fields, in place; the bounds stay the raw fit's
             PF._field_rigid(fields, hom, (p.h, p.w), vs.rigidity, fields, self.rres[cs:ce], self.runf[cs:ce])
@@ -1054,12 +1092,17 @@ class _Call:
 
     def between_passes(self):
         """Every lane has joined the caller's stream: the kept fields (after rigidity) are complete, and so is the cut list.  On that stream,
-        in this order: wobble, the measurement, the "auto" shutter estimate and its one host read, smooth_path, shutter_rates, limit_path,
+        in this order: the deblurring plan (from the input's planes and sharpness alone), wobble, the measurement, the "auto" shutter estimate and its one host read, smooth_path, shutter_rates, limit_path,
         the composition and refit per chunk, the zoom windows, the automatic crop and the output's allocation."""
         vs, p, dev = self.vs, self.plan, self.vs.device
         h, w, T = p.h, p.w, p.T
         cuts = self.cuts or None
         rs = p.shutter
+        if p.deblur > 0:   # the INPUT's own motion, in frame pixels: deblurring acts on the source frames, whatever the fields do with them
+            vs.deblur_sharpness = self.sharp
+            dmotion, _ = global_motion(self.gray_all, pixel_scale=(w / 256.0, h / 256.0))
+            self.dmaps, self.dgain, vs.deblur_donors = deblur_plan(dmotion, self.sharp, p.deblur, scene_cuts=cuts)
+            del dmotion
         if p.wobble > 0.0:
             self.fields, vs.wobble_removed, vs.wobble_unfit = PF.wobble_fields(self.fields, self.hom, (h, w), p.wobble, scene_cuts=cuts, return_stats=True)
             if not p.smooth > 0.0:   # bounds, crop and zoom decisions and the report describe the field that warps (smoothing fits what it composes)
@@ -1119,15 +1162,23 @@ class _Call:
             self.out = self.alloc_out()
 
     def pass2(self):
-        """[zoom +] warp + output resize + crop with the kept fields; chunk k+1 uploads while chunk k computes"""
+        """[deblur +] [zoom +] warp + output resize + crop with the kept fields; chunk k+1 uploads while chunk k computes"""
         vs, p = self.vs, self.plan
-        nxt = _prefetch(self.frames, p.chunks[0][0], p.chunks[0][1], self.up, vs.device)
+        R = p.deblur   # deblurring reads frames [s - R, e + R) of each chunk, clipped to the clip: host frames go up again with the overlap
+        span = [(max(0, s - R), min(p.T, e + R)) for s, e in p.chunks]
+        nxt = _prefetch(self.frames, span[0][0], span[0][1], self.up, vs.device)
         for c, (s, e) in enumerate(p.chunks):
             buf, ev = nxt
             if c + 1 < len(p.chunks):
-                nxt = _prefetch(self.frames, p.chunks[c + 1][0], p.chunks[c + 1][1], self.up, vs.device)
+                nxt = _prefetch(self.frames, span[c + 1][0], span[c + 1][1], self.up, vs.device)
             if ev is not None:
                 self.compute.wait_event(ev)
+            if R > 0:   # into a buffer of its own, which everything behind reads as the chunk's source
+                lo = span[c][0]
+                sharp = PF.deblur_frames(buf, self.dmaps[s:e], self.dgain[s:e], s - lo, e - lo, p.fmt.name, p.deblur_sensitivity)
+                if p.on_host:
+                    buf.record_stream(self.compute)
+                buf = sharp
             fld = self.fields[s:e]
             if p.zmode is not None:
                 fld = PF._field_zoom(fld, self.zcoef[s:e], (p.h, p.w), vs.align_corners, vs.interpolation, torch.empty_like(fld), self.zunc[s:e])
