@@ -51,6 +51,7 @@
  *   pws_field_rigid               the warp field blended towards its fitted homography: rigid warp mode (no counterpart in the reference)
  *   pws_field_wobble              the warp fields' non-rigid part low-passed along time: wobble suppression (no counterpart in the reference)
  *   pws_motion_fit_scaled / pws_path_smooth / pws_field_compose  path smoothing: the measured camera path, low-passed, folded into the warp fields (no counterpart in the reference)
+ *   pws_l1_path / pws_l1_path_workspace  the L1-optimal camera path in pws_path_smooth's place: static, linear and parabolic pieces inside a box (no counterpart in the reference)
  *   pws_shutter_rates / pws_field_compose_rows  rolling-shutter correction: per-frame camera rates, and the composition with a correction per row (no counterpart in the reference)
  *   pws_shutter_terms / pws_shutter_estimate  rolling-shutter estimate: the readout share r from the block vectors smoothing has measured (no counterpart in the reference)
  *   pws_path_levels / pws_field_reach / pws_path_limit  crop-bounded smoothing: per frame the share of its correction that keeps a window covered (no counterpart in the reference)
@@ -708,6 +709,58 @@ int pws_motion_fit_scaled(const short *mv, const int *sad, const int *activity, 
  * PWS_OK and launches nothing.  PWS_EINVAL: n < 0 or above 2^24, sigma outside (0, 256] (NaN included), a NULL pointer, a pointer that is
  * not 8-byte aligned.  motion, path and d must not overlap.  One launch of one workgroup (the scan is sequential). */
 int pws_path_smooth(const double *motion, int n, double sigma, double *path, double *d, pws_stream_t stream);
+
+/* The L1-optimal camera path (csrc/path_l1.hip; Grundmann, Kwatra, Essa, "Auto-directed video stabilization with robust L1 optimal camera
+ * paths", CVPR 2011; OpenCV videostab's LpMotionStabilizer; no counterpart in the reference): pws_path_smooth with another path model.  ONE
+ * scene of n frames; all fp64, in DEVICE memory except `bound` and `weights`, which are read on the host; no synchronisation.
+ * motion, path: as for pws_path_smooth -- the same scan (csrc/path_pose.h), the same rule for a row that is not finite, the same bits.
+ * bound:   4 half-widths b > 0 of the box |P^ - P| <= b, per component (lambda, theta, cx, cy).  stream.optimal_path forms them from
+ *   reach = c in (0, 0.5], the share of an H x W frame per axis that the path may move away from the measured one:
+ *   b = (-log(1 - c), c min(H, W) / max(H, W), c W / 2, c H / 2).  Each half-width alone spends the whole share; their combination is no
+ *   coverage guarantee (pws_path_limit is the coverage rule).  The default c = 0.1 is a judgement that no footage here can fit.
+ * weights: (w1, w2, w3), each finite and > 0; the paper's (10, 1, 100) are the default of stream.optimal_path.
+ * Problem, per component, the four independent: with x = (P^ - P) / b and q = P / b,
+ *     minimise  w1 |D1 (x + q)|_1 + w2 |D2 (x + q)|_1 + w3 |D3 (x + q)|_1   subject to  -1 <= x <= 1,
+ *   D_k the k-th forward difference, n - k rows: (D1 y)[j] = y[j+1] - y[j], (D2 y)[j] = (y[j] - 2 y[j+1]) + y[j+2],
+ *   (D3 y)[j] = ((y[j+3] - 3 y[j+2]) + 3 y[j+1]) - y[j].  The minimiser is made of static, constant-velocity and constant-acceleration
+ *   pieces.  n <= 3: P^ = P, D is the identity (1, 0, 0, 0, 1, 0) exactly, info = (0, 0, 0, 1).
+ * Solver: the LP with slack variables e_k >= |D_k (x + q)|, m = 8 n - 12 constraints  e_k -+ D_k (x + q) >= 0, 1 -+ x >= 0, by a primal-dual
+ *   interior-point method.  Every constraint keeps its slack s > 0 and its multiplier l > 0 as state.
+ *   Start: x = 0, e_k = |D_k q| + 1, s+ = e_k - D_k q, s- = e_k + D_k q, s = 1 for the box, every l = 1 / s.
+ *   Per step: eta = s . l, f = sum_k w_k sum_j e_k[j], the dual residual r = (sum_k D_k^T (l+_k - l-_k) + lU - lL; w_k - l+_k - l-_k).
+ *   Stop, converged, when eta <= 1e-9 max(1, f) and |r|_2 <= 1e-9 max(1, max w); stop after 64 steps.  Otherwise t = 10 m / max(eta, 1e-9
+ *   max(1, f)) -- 10 m / eta until the gap's criterion is met, held from there on, see below -- and with
+ *   g = l / s and v = 1 / (t s) per constraint, G = g+ + g-, be = (v+ + v-) - w_k:  the slacks' elimination leaves the SPD band
+ *     (sum_k D_k^T Theta_k D_k + diag(gU + gL)) dx = (vL - vU) - sum_k D_k^T ((v+ - v-) + (g- - g+) be / G),   Theta = 4 g+ g- / G,
+ *   three sub-diagonals wide, solved by LDL^T without pivoting; then a = D_k dx, de = (be + (g+ - g-) a) / G, ds+ = de - a, ds- = de + a,
+ *   dl = (v - l) - g ds for every constraint (dsU = -dx, dsL = dx).  The step is alpha = min(1, 0.99 min over ds < 0 of s / -ds and over
+ *   dl < 0 of l / -dl) on x, e, s and l alike: every iterate is strictly feasible.
+ *   Skipped pivots: where the optimum is not unique (a static path anywhere inside the box) the band becomes singular to working precision
+ *   as the iteration converges, and a pivot falls below the rounding of its own sum.  A pivot D_i that is not above 2^-44 A_ii is replaced
+ *   by 1e128, which leaves dx_i = 0 for that step (S. Wright, "Modified Cholesky factorizations in interior-point algorithms for linear
+ *   programming", SIAM J. Optim. 9, 1999).  The case on record: a constant path, n = 40, stops unconverged at eta = 1.5e-5 after 11 steps
+ *   without the rule and converges in 16 with it; the cases with a unique optimum never meet it.
+ *   Held t: while t grows with every step the band's conditioning (1e14 and more) keeps |r|_2 at a rounding floor, which at n = 200 and
+ *   w = 100 is 1e-7 .. 3e-7, the criterion's own size: a random walk plus pan plus sine of 200 frames in a box of 20 px then stops after 40
+ *   steps, or runs out of its 64, as the order of the sums falls.  A step at the t that met the gap's criterion only centres; its dx tends
+ *   to 0 and the rounding with it, and |r|_2 falls to 1e-9 and below in one or two steps (that case: 32 steps in every order).
+ *   On record: a shaky pan of 2 048 frames leaves two components at 64 steps, eta = 2e-5 .. 6e-5, converged = 0: short steps, a valid path
+ *   within 2e-6 of the optimum.  No residual backtracking is built: it shortens steps and would not help there.
+ *   Breakdown: a pivot or a step that is not finite ends the iteration, and the last iterate stands -- a valid path, since every iterate
+ *   is feasible.  x is clamped to [-1, 1] at the end, and P^ - P = b x: |P^ - P| <= b holds exactly.
+ * d:      (n, 6) = D[k] = C_k^-1 o C^_k as for pws_path_smooth, from P and P^ - P.
+ * info:   (4, 4): per component (Newton steps taken, the final eta, the final f, converged 1 / 0).
+ * workspace: pws_l1_path_workspace(n) bytes (144 doubles per frame: P^ - P, and per component the solver's state), 8-byte aligned.  Its
+ *   contents on return are not defined.
+ * Every sum -- eta, f, |r|^2 -- is taken in one fixed order (thread i mod 256 adds its frames in ascending order, then the 256 partial sums
+ * are halved), every band entry sums its at most 9 terms in a fixed order, the step length is a min: the same bits on every run, no
+ * atomics.  n == 0 returns PWS_OK and launches nothing.  PWS_EINVAL: n < 0 or above 65 536 (the band solve is sequential: one lane), a
+ * bound or weight that is not finite and > 0, a NULL pointer, a pointer that is not 8-byte aligned, a workspace that is too small.  motion,
+ * path, d, info and workspace must not overlap.  Three launches: the scan on one lane, the solver (one workgroup of 256 threads per
+ * component), D over frames. */
+size_t pws_l1_path_workspace(int n);
+int pws_l1_path(const double *motion, int n, const double *bound, const double *weights, double *path, double *d, double *info,
+                void *workspace, size_t workspace_bytes, pws_stream_t stream);
 
 /* Field composition (csrc/field_compose.hip; no counterpart in the reference): a per-frame affine correction of the OUTPUT frame folded
  * into the warp field; the warp that follows is untouched and still resamples the source once.

@@ -12,9 +12,9 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libpwstable_hip.so")
 SOURCES = ["abi.cpp", "netg_layers.cpp", "netg_forward.cpp", "netg_backward.cpp", "netg_pack.hip", "pack.hip", "conv_dispatch.hip", "conv_mfma.hip", "conv_bf16.hip", "conv_ring.hip", "conv_ring_f32.hip", "conv_first.hip", "conv_first_wino.hip", "conv_wgrad.hip", "wgrad_bf16.hip", "wgrad_ring.hip", "conv_wino.hip", "conv_wring.hip", "conv_skinny.hip", "conv_skinny16.hip", "head.hip", "head_bwd.hip", "grid_sample.hip", "warp_bicubic.hip", "border_keep.hip", "border_mosaic.hip", "border_edge.hip",
-           "adam.hip", "objective.hip", "pool.hip", "frameio.hip", "bnorm.hip", "homography.hip", "scene.hip", "field_zoom.hip", "field_rigid.hip", "field_wobble.hip", "motion.hip", "path_smooth.hip", "field_compose.hip", "field_reach.hip", "path_limit.hip", "shutter_estimate.hip", "deblur.hip"]
+           "adam.hip", "objective.hip", "pool.hip", "frameio.hip", "bnorm.hip", "homography.hip", "scene.hip", "field_zoom.hip", "field_rigid.hip", "field_wobble.hip", "motion.hip", "path_smooth.hip", "path_l1.hip", "field_compose.hip", "field_reach.hip", "path_limit.hip", "shutter_estimate.hip", "deblur.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-HEADERS = ["common.h", "warp_common.h", "border_lane.h", "field_lattice.h", "rigid_position.h", "compose_node.h", "motion_blocks.h", "conv_common.h", "experiments.h", "netg_pack.h", "netg_layers.h", "netg_exec.h", os.path.join("..", "..", "include", "pwstable.h")]
+HEADERS = ["common.h", "warp_common.h", "border_lane.h", "field_lattice.h", "rigid_position.h", "compose_node.h", "path_pose.h", "motion_blocks.h", "conv_common.h", "experiments.h", "netg_pack.h", "netg_layers.h", "netg_exec.h", os.path.join("..", "..", "include", "pwstable.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 

@@ -10,6 +10,7 @@
 // One workgroup, one launch: lane 0 walks the scan (strictly sequential; a scene is thousands of frames at most), then the workgroup's
 // threads take the frames in turn; the Gaussian's Re + 1 weights are in LDS.  Every sum has one fixed order: the same bits on every run.
 #include "common.h"
+#include "path_pose.h"
 
 namespace pws {
 namespace {
@@ -17,10 +18,6 @@ namespace {
 constexpr int PS_THREADS = 256, PS_RMAX = 768;   // Re <= ceil(3 * 256)
 
 #pragma clang fp contract(off)   // every product and every sum rounded once, as the float64 restatement does
-
-__device__ __forceinline__ bool finite4(const double *v) {
-    return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]) && isfinite(v[3]);
-}
 
 // P*(j), component c: P inside the scene, its odd reflection about the first / last frame outside (Re <= n-1 keeps both inside)
 __device__ __forceinline__ double path_at(const double *path, int n, int j, int c) {
@@ -37,22 +34,7 @@ __global__ void __launch_bounds__(PS_THREADS) path_smooth_kernel(const double *_
         const double r = (double)k / sigma;
         g[k] = exp(-0.5 * (r * r));
     }
-    if (tid == 0) {
-        double lam = 0.0, th = 0.0, cx = 0.0, cy = 0.0;
-        path[0] = 0.0, path[1] = 0.0, path[2] = 0.0, path[3] = 0.0;
-        for (int k = 1; k < n; ++k) {
-            const double *m = motion + (size_t)k * 4;
-            const bool ok = finite4(m);
-            const double a = ok ? m[0] : 1.0, b = ok ? m[1] : 0.0, tx = ok ? m[2] : 0.0, ty = ok ? m[3] : 0.0;
-            const double s = exp(lam), c = cos(th), sn = sin(th);
-            cx = cx + s * (c * tx - sn * ty);
-            cy = cy + s * (sn * tx + c * ty);
-            lam = lam + log(hypot(a, b));
-            th = th + atan2(b, a);
-            double *p = path + (size_t)k * 4;
-            p[0] = lam, p[1] = th, p[2] = cx, p[3] = cy;
-        }
-    }
+    if (tid == 0) pose_scan(motion, n, path);   // (path_pose.h: shared with the L1-optimal path)
     __syncthreads();   // (the path is in global memory: written by this workgroup, read by this workgroup)
     for (int k = tid; k < n; k += PS_THREADS) {
         double acc[4] = {0.0, 0.0, 0.0, 0.0}, wsum = 0.0;
@@ -63,12 +45,7 @@ __global__ void __launch_bounds__(PS_THREADS) path_smooth_kernel(const double *_
             wsum = wsum + w;
         }
         const double *p = path + (size_t)k * 4;
-        const double lam = p[0], th = p[1];
-        const double dlam = acc[0] / wsum - lam, dth = acc[1] / wsum - th, ux = acc[2] / wsum - p[2], uy = acc[3] / wsum - p[3];
-        const double s = exp(dlam), e = exp(-lam), c = cos(th), sn = sin(th);
-        double *o = d + (size_t)k * 6;
-        o[0] = s * cos(dth), o[1] = 0.0 - s * sin(dth), o[2] = e * (c * ux + sn * uy);
-        o[3] = s * sin(dth), o[4] = s * cos(dth), o[5] = e * (c * uy - sn * ux);
+        pose_correction(p, acc[0] / wsum - p[0], acc[1] / wsum - p[1], acc[2] / wsum - p[2], acc[3] / wsum - p[3], d + (size_t)k * 6);
     }
 }
 

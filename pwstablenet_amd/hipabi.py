@@ -269,6 +269,8 @@ SIGNATURES = {
     "pws_motion_fit": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "pws_motion_fit_scaled": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _D, _D, _P, _P, _P]),
     "pws_path_smooth": (_I, [_P, _I, _D, _P, _P, _P]),
+    "pws_l1_path_workspace": (_S, [_I]),
+    "pws_l1_path": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _S, _P]),
     "pws_field_compose": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "pws_shutter_rates": (_I, [_P, _I, _P, _P]),
     "pws_field_compose_rows": (_I, [_P, _I, _I, _I, _P, _P, _D, _P, _I, _I, _I, _I, _P, _P]),

@@ -1,5 +1,6 @@
 """Camera motion of a clip: scene scores, block matching and the similarity fit, the smoothed path, shutter rates and estimate, the crop
 budget and the stability metric."""
+import ctypes
 import math
 
 import torch
@@ -142,6 +143,78 @@ def smooth_path(motion, sigma, scene_cuts=None):
     for a, b in (_scenes(T, cuts) if T else []):
         A.check(A.lib().pws_path_smooth(A.ptr(motion[a:b]), b - a, sigma, A.ptr(path[a:b]), A.ptr(d[a:b]), A.current_stream()), "pws_path_smooth")
     return d, path
+
+
+L1_REACH, L1_WEIGHTS = 0.1, (10.0, 1.0, 100.0)
+
+
+def _check_l1(reach, weights, what):
+    """(reach, weights) of the L1-optimal path checked: ``reach`` a float in (0, 0.5], ``weights`` three positive finite floats; ValueError
+    otherwise (NaN included)."""
+    try:
+        c = float(reach)
+    except (TypeError, ValueError):
+        raise ValueError("%s: reach must be a share of the frame in (0, 0.5], got %r" % (what, reach)) from None
+    if not 0.0 < c <= 0.5:   # (False for NaN)
+        raise ValueError("%s: reach must lie in (0, 0.5], got %r" % (what, reach))
+    try:
+        w = tuple(float(v) for v in weights)
+    except (TypeError, ValueError):
+        raise ValueError("%s: weights must be three positive finite numbers (w1, w2, w3), got %r" % (what, weights)) from None
+    if len(w) != 3 or not all(0.0 < v < math.inf for v in w):
+        raise ValueError("%s: weights must be three positive finite numbers (w1, w2, w3), got %r" % (what, weights))
+    return c, w
+
+
+def _l1_bounds(reach, frame_hw, what):
+    """The box's half-widths (log scale, angle, x, y) for ``reach`` = c of an H x W frame: (-log(1 - c), c min(H, W) / max(H, W), c W / 2,
+    c H / 2) -- each alone moves a frame's rim by the share c of the frame; ValueError for a frame that is not two integers >= 2."""
+    try:
+        h, w = (int(v) for v in frame_hw)
+    except (TypeError, ValueError):
+        raise ValueError("%s: frame_hw must be (H, W), got %r" % (what, frame_hw)) from None
+    if h < 2 or w < 2:
+        raise ValueError("%s: the frame must be at least 2 x 2 pixels, got %d x %d" % (what, w, h))
+    return (-math.log(1.0 - reach), reach * min(h, w) / max(h, w), reach * w / 2.0, reach * h / 2.0)
+
+
+def optimal_path(motion, frame_hw, reach=L1_REACH, weights=L1_WEIGHTS, scene_cuts=None, return_info=False):
+    """The L1-optimal camera path (Grundmann, Kwatra, Essa, CVPR 2011; OpenCV videostab's LpMotionStabilizer) in ``smooth_path``'s place
+    (csrc/path_l1.hip; include/pwstable.h pws_l1_path has the definition): ``motion`` (T, 4) float64 on the device as for ``smooth_path``,
+    ``frame_hw`` = (H, W) of the frame whose pixels ``motion`` is in.  Per scene (``scene_cuts`` as for ``smooth_path``) the measured pose P
+    = (log scale, angle, cx, cy) is ``smooth_path``'s, bit for bit; per component the path P^ inside the box |P^ - P| <= b minimises
+    w1 |D1 P^|_1 + w2 |D2 P^|_1 + w3 |D3 P^|_1 (D_k: the k-th forward difference; the components in units of their b), so that it is made of
+    static, constant-velocity and constant-acceleration pieces; D[k] = C_k^-1 o C^_k as for ``smooth_path``.  ``reach`` = c in (0, 0.5]
+    is the share of the frame, per axis, that the path may move away from the measured one: b = (-log(1 - c), c min(H, W) / max(H, W),
+    c W / 2, c H / 2).  Each half-width alone spends the whole share; together they are no coverage guarantee -- ``limit_path`` is.  The
+    default 0.1, like the paper's weights (10, 1, 100), is a judgement that no footage here can fit.  The LP is solved on the device by a
+    primal-dual interior-point method, at most 64 Newton steps; a scene of 3 frames or fewer keeps its path (D is the identity).
+    Returns (D (T, 6), path (T, 4)) float64 on the device -- ``path`` is the MEASURED path -- [, info (scenes, 4, 4): per scene and
+    component (Newton steps, the final gap s . l, the final scaled objective, converged 1 / 0)]; no synchronisation; three launches per
+    scene, on slices, and one workspace allocation of 1 152 bytes per frame of the longest scene.  Fixed order: the same bits on every run.
+    ValueError: a tensor that is not (T, 4) float64 on the device, reach outside (0, 0.5], weights that are not three positive finite
+    numbers, bad cuts, a frame_hw that is not two integers >= 2, a scene above 65 536 frames."""
+    _check_motion(motion, "optimal_path")
+    reach, weights = _check_l1(reach, weights, "optimal_path")
+    bound = _l1_bounds(reach, frame_hw, "optimal_path")
+    motion = motion.contiguous()
+    T = motion.shape[0]
+    cuts = _cut_list(scene_cuts, T, "optimal_path")
+    scenes = list(_scenes(T, cuts)) if T else []
+    longest = max((b - a for a, b in scenes), default=0)
+    if longest > 65536:
+        raise ValueError("optimal_path: a scene of %d frames, at most 65536 (the solver's band solve is sequential)" % longest)
+    d = torch.empty((T, 6), device=motion.device, dtype=torch.float64)
+    path = torch.empty((T, 4), device=motion.device, dtype=torch.float64)
+    info = torch.empty((len(scenes), 4, 4), device=motion.device, dtype=torch.float64)
+    L = A.lib()
+    nbytes = int(L.pws_l1_path_workspace(longest))
+    ws = torch.empty((nbytes // 8,), device=motion.device, dtype=torch.float64)   # (stream-ordered: one scene after the other uses it)
+    cb, cw = (ctypes.c_double * 4)(*bound), (ctypes.c_double * 3)(*weights)
+    for i, (a, b) in enumerate(scenes):
+        A.check(L.pws_l1_path(A.ptr(motion[a:b]), b - a, cb, cw, A.ptr(path[a:b]), A.ptr(d[a:b]), A.ptr(info[i]), A.ptr(ws), nbytes,
+                              A.current_stream()), "pws_l1_path")
+    return (d, path, info) if return_info else (d, path)
 
 
 def shutter_rates(motion, scene_cuts=None):

@@ -24,8 +24,9 @@ from .frameio import (_area_resize_yuv, _crop, _frames_shape, _output_resize, _w
                       area_half, area_resize, area_resize_yuv, area_resize_yuv16, window_planes, window_planes_yuv, window_planes_yuv16)
 from .framing import (_bounds_rows, _centred_window, _check_lattice, _field_homography, _has_lattice, auto_crop_window,  # noqa: F401
                       field_homography, zoom_schedule, zoom_window)
-from .motion import (_check_limit, _check_max_se, _check_shutter, _check_sigma, block_motion, deblur_plan, estimate_rolling_shutter,  # noqa: F401
-                     frame_sharpness, global_motion, limit_path, limit_rectangle, scene_scores, shutter_rates, smooth_path, stability_scores)
+from .motion import (L1_REACH, L1_WEIGHTS, _check_l1, _check_limit, _check_max_se, _check_shutter, _check_sigma, block_motion, deblur_plan,  # noqa: F401
+                     estimate_rolling_shutter, frame_sharpness, global_motion, limit_path, limit_rectangle, optimal_path, scene_scores,
+                     shutter_rates, smooth_path, stability_scores)
 from .scenes import _check_cuts, _cut_rule, _scenes, find_scene_cuts  # noqa: F401
 
 
@@ -72,7 +73,7 @@ def _hand_over(warped, dest, lane, down):
 class StreamPlan(collections.namedtuple("StreamPlan", "fmt h w oh ow T n_all halo_left halo_right chunk chunks in_flight on_host half_size_output "
                                         "frames_are_rgb crop zmode zwin zoom_speed zoom_min two_pass mosaic radius keep rigid edge metrics lattice "
                                         "smooth shutter max_se wobble max_crop limit_levels limit_relax detect cuts scene_threshold scene_min_len deblur "
-                                        "deblur_sensitivity")):
+                                        "deblur_sensitivity path_model l1_reach l1_weights")):
     """Everything that run_video decides from its arguments and the stabiliser's options before it touches the device (VideoStabilizer._plan):
     the format record ``fmt``; the source ``h`` x ``w`` and the output ``oh`` x ``ow`` before the crop; the ``T`` frames to stabilise of the
     ``n_all`` given, the halos, ``chunk`` and the ``chunks`` [(start, stop)] in the index space of the frames (the first / last chunk carry
@@ -81,7 +82,8 @@ class StreamPlan(collections.namedtuple("StreamPlan", "fmt h w oh ow T n_all hal
     keeps fields and bounds, the host decides, pass 2 warps; ``mosaic`` and its ``radius``, ``keep``, ``rigid``, the ``edge`` mode,
     ``metrics``, ``lattice`` (the frame holds the homography fit's); ``smooth`` (sigma, 0: off), ``shutter`` (a float or "auto") and ``max_se``, ``wobble`` (sigma, 0: off), ``max_crop`` (None: off) with ``limit_levels`` and the resolved ``limit_relax``; ``detect``
     (scene_cuts="auto") with its thresholds, and ``cuts``, the checked list the call starts from; ``deblur`` (the radius, 0: off) and
-    ``deblur_sensitivity``."""
+    ``deblur_sensitivity``; ``path_model``: None (no smoothing), "gaussian" (``smooth`` is its sigma) or "l1" (``smooth`` is 0.0) with
+    ``l1_reach`` and ``l1_weights``."""
     __slots__ = ()
 
 
@@ -108,7 +110,7 @@ def _windows(gray_padded, start, count, period):
 class VideoStabilizer:
     def __init__(self, netG, batch=32, period=30, device=None, swap_rb=False, interpolation="bilinear", borders="black", rigidity=0.0,
                  mosaic_radius=8, edge="pad", metrics=False, smooth=0.0, rolling_shutter=0.0, wobble=0.0, max_crop=None, limit_levels=16,
-                 limit_relax=None, shutter_max_se=0.02, deblur=0, deblur_sensitivity=4.0):
+                 limit_relax=None, shutter_max_se=0.02, deblur=0, deblur_sensitivity=4.0, l1_reach=L1_REACH, l1_weights=L1_WEIGHTS):
         self.net = netG
         # run_video lends every SOURCE frame detail from the sharper frames of its scene within `deblur` frames, 1 .. 15, aligned by the clip's
         # global motion, in front of the untouched warp (functional.deblur_frames; OpenCV videostab's order): shake blurs some frames and
@@ -127,7 +129,13 @@ class VideoStabilizer:
         # run_video folds the shake that the fields LEAVE in the clip back into them: the global motion of the planes as the kept fields warp
         # them is measured, the camera path low-passed with a Gaussian of `smooth` frames (smooth_path) and every frame's correction composed
         # into its field (functional.compose_fields) before the one warp.  0: no launch, no allocation, every path as it was
-        self.smooth = _check_sigma(smooth, "VideoStabilizer", zero_ok=True)
+        # smooth="l1": the path model is the L1-optimal path instead (optimal_path: static, constant-velocity and constant-acceleration pieces
+        # inside a box of l1_reach of the frame per axis around the measured path, weights l1_weights on the three differences' L1 norms);
+        # everything that needs smooth > 0 takes "l1" as smoothing on.  0.1 and the paper's (10, 1, 100) are judgements that no footage here
+        # can fit, like zoom_speed
+        self.smooth = "l1" if isinstance(smooth, str) and smooth == "l1" else _check_sigma(smooth, "VideoStabilizer", zero_ok=True)
+        self.l1_reach, self.l1_weights = _check_l1(l1_reach, l1_weights, "VideoStabilizer")
+        self.smooth_l1_info = None   # smooth="l1", of the last run_video, on the device: (scenes, 4, 4) float64, optimal_path's info
         self.smooth_motion = self.smooth_inliers = None       # smooth > 0, of the last run_video, on the device: (T, 4) float64 / (T,) int32, the
         self.smooth_path = self.smooth_correction = None      # motion the fields left (frame pixels); (T, 4) its path, (T, 6) the corrections D;
         self.smooth_uncovered = None                          # (T,) int32, the composed fields' nodes that sample outside the source
@@ -152,8 +160,10 @@ class VideoStabilizer:
         # as much of its correction as keeps the centred window of the fraction 1 - max_crop covered by the source (limit_path: the share is
         # searched on limit_levels + 1 grid levels, on the fields themselves) and the share changes by at most limit_relax per frame.
         # limit_relax=None: 1 / ceil(3 smooth), the strength recovers from 0 to 1 over the Gaussian's own reach -- a judgement that no
-        # footage here can fit, like zoom_speed.  None: no launch, no allocation, every path as it was
-        self.max_crop, self.limit_levels, relax = _check_limit(max_crop, limit_levels, limit_relax, self.smooth, "VideoStabilizer")
+        # footage here can fit, like zoom_speed; under smooth="l1", which has no sigma, 1 / (period // 2): over the generator's own reach,
+        # a judgement of the same kind.  None: no launch, no allocation, every path as it was
+        self.max_crop, self.limit_levels, relax = _check_limit(max_crop, limit_levels, limit_relax, 0.0 if self.smooth == "l1" else self.smooth,
+                                                               "VideoStabilizer")
         self.limit_relax = None if limit_relax is None else relax   # (None is resolved against the call's smooth in run_video)
         if self.max_crop is not None and self.smooth == 0.0:
             raise ValueError("VideoStabilizer: max_crop=%r needs smooth > 0 (it bounds the correction that smoothing composes)" % (max_crop,))
@@ -576,6 +586,16 @@ class VideoStabilizer:
         source).  A pair no similarity could be fitted to counts as no motion.  Every pixel_format, interpolation, edge, crop, zoom,
         rigidity, in_flight and scene_cuts works as without it.  ValueError: halos (a shard cannot see the scene's path), borders="keep" or
         "mosaic" (they have no second pass).
+        VideoStabilizer(smooth="l1", l1_reach=0.1, l1_weights=(10.0, 1.0, 100.0)): the same route with the L1-optimal path (Grundmann, Kwatra,
+        Essa, CVPR 2011; OpenCV videostab's LpMotionStabilizer) as the path model: ``optimal_path`` stands where ``smooth_path`` stands, on the
+        same measured motion and cuts, and nothing else changes.  A Gaussian turns a hand-held "static" shot into a slow drift and bounds
+        nothing; this path is exactly static, constant-velocity or constant-acceleration piece by piece, and it stays inside a box of
+        l1_reach of the frame per axis around the measured path -- per component: the box is no coverage guarantee, max_crop stays that
+        rule.  Everything that needs smooth > 0 takes "l1" as smoothing on: rolling_shutter, fixed and "auto", max_crop (limit_relax=None
+        is 1 / (period // 2) here, the generator's own reach: a judgement), the halo and borders errors.  ``self.smooth_l1_info`` (scenes,
+        4, 4) float64 -- per scene and component: Newton steps, final gap, final objective, converged -- is left on the device; None
+        otherwise.  Reach and weights are judgements that no footage here can fit; similarity motion measured on the 256 x 256 planes, as
+        before.  ValueError: l1_reach outside (0, 0.5], l1_weights that are not three positive finite numbers, a scene above 65 536 frames.
         VideoStabilizer(smooth=sigma, rolling_shutter=r), r != 0: rolling-shutter correction inside the same composition.  r in [-1, 1] is the
         share of the frame interval that the readout from the top row to the bottom row takes (negative: bottom to top).  ``shutter_rates``
         of the measured motion, under the call's cuts, gives every frame's forward and backward velocity; ``compose_fields(rates=,
@@ -743,12 +763,15 @@ class VideoStabilizer:
                     raise ValueError("zoom: the fraction of the frame must lie in (0, 1], got %r" % (zoom,))
                 zmode = "fixed"
                 zwin = _centred_window(zk, h, w)
-        smoothing = self.smooth > 0.0
+        path_model = "l1" if self.smooth == "l1" else "gaussian" if self.smooth > 0.0 else None
+        smoothing, sigma = path_model is not None, 0.0 if path_model == "l1" else self.smooth
+        l1_reach, l1_weights = _check_l1(self.l1_reach, self.l1_weights, "run_video")   # (the attributes can be set after construction)
         rs = _check_shutter(self.rolling_shutter, "run_video")   # (the attributes can be set after construction)
         max_se = _check_max_se(self.shutter_max_se, "run_video")
         if rs != 0.0 and not smoothing:
             raise ValueError("run_video: rolling_shutter=%r needs smooth > 0" % (self.rolling_shutter,))
-        max_crop, limit_levels, limit_relax = _check_limit(self.max_crop, self.limit_levels, self.limit_relax, self.smooth, "run_video")
+        relax = 1.0 / max(1, half) if path_model == "l1" and self.limit_relax is None else self.limit_relax   # (no sigma: the generator's reach)
+        max_crop, limit_levels, limit_relax = _check_limit(self.max_crop, self.limit_levels, relax, sigma, "run_video")
         if max_crop is not None and not smoothing:   # (the attributes can be set after construction)
             raise ValueError("run_video: max_crop=%r needs smooth > 0" % (self.max_crop,))
         if smoothing:
@@ -783,8 +806,8 @@ class VideoStabilizer:
                        for s in range(halo_left, halo_left + T, chunk)) if T > 0 else ()
         return StreamPlan(fmt, h, w, oh, ow, T, n_all, halo_left, halo_right, chunk, chunks, max(1, int(in_flight)) if T > 0 else 1, not frames.is_cuda,
                           bool(half_size_output), bool(frames_are_rgb), window, zmode, zwin, zoom_speed, zoom_min, bool(two_pass), mosaic, radius,
-                          self.borders == "keep", rigid, self.edge, metrics, _has_lattice(h, w), self.smooth, rs, max_se, wob, max_crop, limit_levels,
-                          limit_relax, detect, cuts, scene_threshold, scene_min_len, deblur, dsens)
+                          self.borders == "keep", rigid, self.edge, metrics, _has_lattice(h, w), sigma, rs, max_se, wob, max_crop, limit_levels,
+                          limit_relax, detect, cuts, scene_threshold, scene_min_len, deblur, dsens, path_model, l1_reach, l1_weights)
 
     def _reset(self, plan):
         """What the previous run_video left goes, in one place, once the plan stands: every result is None until this call sets it."""
@@ -793,6 +816,7 @@ class VideoStabilizer:
         self.mosaic_unfilled = None
         self.motion_in = self.motion_out = self.motion_inliers_in = self.motion_inliers_out = self._report = None
         self.smooth_motion = self.smooth_inliers = self.smooth_path = self.smooth_correction = self.smooth_uncovered = None
+        self.smooth_l1_info = None
         self.shutter_rates = self.shutter_estimate = self.rolling_shutter_used = None
         self.limit_strength = self.limit_need = self.limit_uncovered = self.smooth_correction_unlimited = None
         self.wobble_removed = self.wobble_unfit = None
@@ -996,7 +1020,7 @@ class _Call:
         vs, p = self.vs, self.plan
         fields, hom = self.fields[cs:ce], self.hom[cs:ce]
         vs._fields(gray, hl, hr, fields, sc)
-        if (not p.smooth > 0.0 or p.rigid or p.wobble > 0.0) and p.lattice:   # (smoothing fits the fields it composes, between the passes; the
+        if (p.path_model is None or p.rigid or p.wobble > 0.0) and p.lattice:   # (smoothing fits the fields it composes, between the passes; the
             # blend and the wobble filter need the raw fit; deblurring alone takes the two passes at any size and needs no fit)
             _field_homography(fields, p.h, p.w, hom, self.bounds[cs:ce])
         if p.rigid:   # the kept fields, in place; the bounds stay the raw fit's
@@ -1105,10 +1129,10 @@ class _Call:
             del dmotion
         if p.wobble > 0.0:
             self.fields, vs.wobble_removed, vs.wobble_unfit = PF.wobble_fields(self.fields, self.hom, (h, w), p.wobble, scene_cuts=cuts, return_stats=True)
-            if not p.smooth > 0.0:   # bounds, crop and zoom decisions and the report describe the field that warps (smoothing fits what it composes)
+            if p.path_model is None:   # bounds, crop and zoom decisions and the report describe the field that warps (smoothing fits what it composes)
                 _field_homography(self.fields, h, w, self.hom, self.bounds)
         fields = self.fields
-        if p.smooth > 0.0:   # ... and it measures the filtered fields
+        if p.path_model is not None:   # ... and it measures the filtered fields
             scale = (w / 256.0, h / 256.0)   # frame pixels per plane pixel
             seen = PF.grid_sample(self.gray_all.unsqueeze(1), fields, align_corners=vs.align_corners).squeeze(1)   # the planes as the fields warp them
             if rs == "auto":   # the blocks behind the fit are kept for the estimate: the same launches, the same motion
@@ -1122,7 +1146,11 @@ class _Call:
             else:
                 vs.smooth_motion, vs.smooth_inliers = global_motion(seen, pixel_scale=scale)
             del seen
-            vs.smooth_correction, vs.smooth_path = smooth_path(vs.smooth_motion, p.smooth, scene_cuts=cuts)
+            if p.path_model == "l1":
+                vs.smooth_correction, vs.smooth_path, vs.smooth_l1_info = optimal_path(vs.smooth_motion, (h, w), p.l1_reach, p.l1_weights,
+                                                                                       scene_cuts=cuts, return_info=True)
+            else:
+                vs.smooth_correction, vs.smooth_path = smooth_path(vs.smooth_motion, p.smooth, scene_cuts=cuts)
             vs.smooth_uncovered = torch.empty((T,), device=dev, dtype=torch.int32)
             if rs != 0.0:   # the velocity at every frame, from the same measured motion and under the same cuts
                 vs.shutter_rates = shutter_rates(vs.smooth_motion, scene_cuts=cuts)
