@@ -561,7 +561,9 @@ int pws_border_edge_yuv_u16(unsigned short *frames, const unsigned short *source
  * (.992,.992), (.992,-1) mapped through it (|w| <= FLT_EPSILON -> 0, as cv2.perspectiveTransform) give the frame's bounds in source
  * pixels.  m_out[n,9] fp64 row-major; bounds_out[n,4] = top, bottom, left, right; pts_out[n,400,2] = p1 (may be NULL).  Samples
  * without spread, a normal matrix that is not positive definite or a result that is not finite give NaN M and bounds.
- * h0 >= 300 and w0 >= 600 (the lattice must fit); field and pts_out 8-byte aligned. */
+ * h0 >= 300 and w0 >= 600 (the lattice must fit); any fh, fw >= 1; n == 0 returns PWS_OK and launches nothing.  PWS_EINVAL: n < 0,
+ * fh or fw < 1, a frame too small for the lattice, NULL field / m_out / bounds_out, field, pts_out or m_out not 8-byte aligned,
+ * bounds_out not 4-byte aligned. */
 int pws_field_homography(const float *field, int n, int fh, int fw, int h0, int w0, double *m_out, float *bounds_out, float *pts_out,
                          pws_stream_t stream);
 

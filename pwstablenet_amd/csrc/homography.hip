@@ -261,6 +261,8 @@ extern "C" int pws_field_homography(const float *field, int n, int fh, int fw, i
     PWS_REQUIRE(field && m_out && bounds_out, "pws_field_homography: NULL pointer");
     PWS_REQUIRE((reinterpret_cast<size_t>(field) & 7) == 0 && (reinterpret_cast<size_t>(pts_out) & 7) == 0,
                 "pws_field_homography: field and pts_out must be 8-byte aligned");
+    PWS_REQUIRE((reinterpret_cast<size_t>(m_out) & 7) == 0 && (reinterpret_cast<size_t>(bounds_out) & 3) == 0,
+                "pws_field_homography: m_out must be 8-byte aligned and bounds_out 4-byte aligned");
     // the resize's source scale, as pws_upsample_bilinear_ac / the fused warps compute it
     const float ry = (float)(fh - 1) / (float)(h0 - 1), rx = (float)(fw - 1) / (float)(w0 - 1);
     ProfScope prof(KID_FIELD_HOMOGRAPHY, (double)n * (HG_MAX_ITERS + 1) * HG_PTS * 2 * HG_SUMS * 2, (double)n * HG_PTS * 4 * 8,
